@@ -131,6 +131,42 @@ def cpu_baseline(seconds=15.0, reference_nn=False):
     return out
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs DIR: each array as DIR/<name>.npy, float32 / float64 kept as they are and integers converted exactly (float32
+    below 2**24, else float64), at most DUMP_LIMIT_BYTES in all: two builds run with the same arguments compare output for output."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    out = {}
+    for k, v in arrays.items():
+        v = np.asarray(v)
+        if v.dtype not in (np.float32, np.float64):
+            v = v.astype(np.float32 if v.size == 0 or np.abs(v.astype(np.float64)).max() < 2 ** 24 else np.float64)
+        out[k] = np.ascontiguousarray(v)
+    total = sum(v.nbytes for v in out.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit("--dump-outputs: %d bytes of outputs, more than the %d allowed" % (total, DUMP_LIMIT_BYTES))
+    for k, v in out.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v)
+
+
+def trainer_outputs(t, minibatch):
+    """What a caller of the training step receives after it: online and target parameters (fp32 on the device, so float32 is
+    exact), the games' state, the loss and (Q(s,a), y) of the last minibatch, the step counters."""
+    import numpy as np
+    from cn_chess_ai_amd import _capi
+    w, b = (x.astype(np.float32) for x in t.dqn.get_params(_capi.NET_ONLINE))
+    tw, tb = (x.astype(np.float32) for x in t.dqn.get_params(_capi.NET_TARGET))
+    boards, meta = t.env.get_state()
+    q, y = t.dqn.last_td_values(minibatch)
+    c = t.counters()
+    return {"online_weights": w, "online_biases": b, "target_weights": tw, "target_biases": tb, "boards": boards, "meta": meta,
+            "td_q": q, "td_target": y, "loss": np.array([t.dqn.last_loss()]),
+            "counters": np.array([c["env_steps"], c["updates"], c["episodes"]], dtype=np.float64)}
+
+
 _PROFILE_SET = {}
 
 
@@ -213,6 +249,10 @@ def env_only(args, xq, tstream):
     ms = a.elapsed_time(b) / args.steps
     bytes_per = args.games * (2 * (48 + 16))                     # board + meta read and written; no Q row, no replay record
     c = env.counters()
+    if args.dump_outputs:
+        import numpy as np
+        boards, meta = env.get_state()
+        dump_outputs(args.dump_outputs, {"boards": boards, "meta": meta, "counters": np.array([c[k] for k in sorted(c)])})
     print(json.dumps({"metric": "env-only steps/s, uniform-random policy", "value": args.games / (ms * 1e-3), "unit": "env steps/s",
                       "games": args.games, "steps": args.steps, "us_per_launch": ms * 1e3,
                       "algorithmic_GBps": bytes_per / (ms * 1e-3) / 1e9, "episodes_finished": c["episodes"]}), flush=True)
@@ -448,7 +488,12 @@ def main():
                          "saturation) and a greedy-vs-random match at the end; prints ONE JSON line of its own (profiles/*_sustain.json)")
     ap.add_argument("--no-overlap", action="store_true",
                     help="queue collect and learn on one stream (collect -> learn -> apply) instead of running collect beside learn_grads")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (parameters, game states, loss, TD values, counters) "
+                         "as DIR/<name>.npy; rank 0 only")
     args = ap.parse_args()
+    if args.dump_outputs and args.sustain > 0:
+        raise SystemExit("--dump-outputs applies to the timed steps; --sustain has none")
     if args.cpu_worker > 0:                      # child of cpu_all_cores(): CPU only, never touches the GPU
         print(json.dumps(cpu_train_loop(args.cpu_worker)), flush=True)
         return
@@ -651,6 +696,8 @@ def main():
     t.dqn.kernel_stats(enable=live_mode)
     elapsed, host_enqueue, samples = timed(args.steps)
     stats = {s["name"]: s for s in t.dqn.kernel_stats(enable=0)}
+    if args.dump_outputs and rank == 0:      # before the variant legs below train the same trainer further
+        dump_outputs(args.dump_outputs, trainer_outputs(t, minibatch))
     c1 = t.counters()
     comm_info = comm.info() if comm is not None else None
     # the other TD rule on the same trainer, same steady state, timed the same way (reported beside the headline)

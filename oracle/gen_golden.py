@@ -76,6 +76,9 @@ def main():
     rb, rbits, rq, rres = run_rulemat(0xFACE, 24)
     np.savez_compressed(os.path.join(GOLD, "ref_rulemat.npz"), board=rb, rule_bits=rbits, query=rq, query_result=rres)
     print("rulemat positions:", len(rb), "queries true:", int(rres.sum()), "of", rres.size)
+    live = run_trace(12345, 6)               # the run tests/test_oracle_golden.py::test_live_cross_check_against_reference_binary repeats
+    save_trace("ref_trace_live.npz", live)
+    print("live trace records:", len(live))
     rec = run_trace(0x5EED, 20)
     def flat(field, nfield):
         n = rec[nfield].astype(np.int64)

@@ -99,3 +99,27 @@ def test_bench_cpu_baseline_leg():
     assert out.returncode == 0, out.stderr[-1000:]
     steps, episodes, el = json.loads(out.stdout.strip().splitlines()[-1])
     assert steps > 0 and episodes >= 1 and 0.5 < el < 30
+
+
+def test_bench_dump_outputs_are_the_last_timed_step_and_repeat(tmp_path):
+    """--dump-outputs DIR: what the last timed step computed, as float32 / float64 .npy files within 64 MiB; the same arguments
+    give the same outputs, and the counters say that exactly `--repeats` x `--steps` updates were timed."""
+    import numpy as np
+    args = ("--games", "2048", "--no-cpu-baseline", "--no-chain", "--no-variants", "--no-facade", "--settle-steps", "10", "--repeats", "2")
+    dumps = []
+    for k in range(2):
+        d = tmp_path / str(k)
+        line = _bench(*args, "--dump-outputs", str(d))
+        assert line["steps"] == 4
+        dumps.append({f[:-4]: np.load(str(d / f)) for f in sorted(os.listdir(d))})
+    a, b = dumps
+    assert set(a) == {"online_weights", "online_biases", "target_weights", "target_biases", "boards", "meta", "td_q", "td_target",
+                      "loss", "counters"}
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    for k, v in a.items():
+        assert v.dtype in (np.float32, np.float64), k
+        assert np.array_equal(v, b[k]), k                       # same arguments, same inputs, same outputs
+    assert a["boards"].shape == (2048, 90) and a["td_q"].shape == (2048,) and np.isfinite(a["td_q"]).all()
+    assert a["online_weights"].size == 1260 * 256 + 256 * 256 + 256 * 8100
+    env_steps, updates, _ = a["counters"]
+    assert updates == 2 + 10 + 8 + 2 * 4                        # warm-up, settle, back-to-live and the 2 x 4 timed steps: nothing after

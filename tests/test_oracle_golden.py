@@ -1,6 +1,6 @@
 """Pins oracle/xq_oracle.c to the REAL reference rules engine (not gpu).
 
-tests/golden/ref_trace.npz and ref_validmat.npz hold OUTPUTS of /root/reference/src/chessboard.cpp compiled
+tests/golden/ref_trace*.npz and ref_validmat.npz hold OUTPUTS of /root/reference/src/chessboard.cpp compiled
 unmodified (oracle/ref/ref_driver.cpp + oracle/gen_golden.py).  Known answers quoted from SURVEY.md pin the
 chessai.cpp / dqn.cu restatements that cannot be executed here.
 """
@@ -201,16 +201,30 @@ def test_philox_known_answers():
         [0xd16cfe09, 0x94fdcceb, 0x5001e420, 0x24126ea1]
 
 
-@pytest.mark.skipif(not os.path.exists(xo.REF_BIN), reason="real-reference binary only exists in the authoring container")
-def test_live_cross_check_against_reference_binary(tmp_path):
-    import subprocess
-    out = tmp_path / "t.bin"
-    subprocess.check_call([xo.REF_BIN, "trace", "12345", "6", str(out)])
-    rec = np.fromfile(str(out), dtype=xo.REF_RECORD)
+def test_live_cross_check_against_reference_binary(golden_dir, tmp_path):
+    """`xqref trace 12345 6` of the real reference: its output is stored in ref_trace_live.npz (oracle/gen_golden.py); where
+    oracle/_ref/xqref was built, the binary is run again and must still produce exactly that output."""
+    t = np.load(os.path.join(golden_dir, "ref_trace_live.npz"))
+    n = len(t["moveCount"])
+    assert n > 1000
+    if os.path.exists(xo.REF_BIN):
+        import subprocess
+        out = tmp_path / "t.bin"
+        subprocess.check_call([xo.REF_BIN, "trace", "12345", "6", str(out)])
+        rec = np.fromfile(str(out), dtype=xo.REF_RECORD)
+        assert len(rec) == n
+        for k in ("board", "moveCount", "player", "redScore", "blackScore", "over", "winner", "valid", "captured"):
+            assert np.array_equal(rec[k], t[k]), k
+        assert np.array_equal(np.stack([rec["fr"], rec["fc"], rec["tr"], rec["tc"]], axis=1), t["move"])
+        for i in range(n):
+            for key, nkey in (("red", "nRed"), ("black", "nBlack")):
+                assert np.array_equal(rec[key][i, :rec[nkey][i]], t[key][t[key + "_off"][i]:t[key + "_off"][i + 1]]), (i, key)
     L = xo.lib()
-    for r in rec:
-        b = xo.board_from(r["board"], r["moveCount"], r["player"], r["redScore"], r["blackScore"])
-        for colour, key, nkey in ((0, "red", "nRed"), (1, "black", "nBlack")):
+    for i in range(n):
+        b = _board(t, i)
+        for colour, key in ((0, "red"), (1, "black")):
+            want = t[key][t[key + "_off"][i]:t[key + "_off"][i + 1]]
             got, cnt = xo.all_valid_actions(b, colour)
-            assert cnt == r[nkey] and np.array_equal(got, r[key][:cnt])
-        assert L.xqo_move_piece(C.byref(b), int(r["fr"]), int(r["fc"]), int(r["tr"]), int(r["tc"])) == r["captured"]
+            assert cnt == len(want) and np.array_equal(got, want), (i, key)
+        fr, fc, tr, tc = (int(x) for x in t["move"][i])
+        assert L.xqo_move_piece(C.byref(b), fr, fc, tr, tc) == t["captured"][i], i
