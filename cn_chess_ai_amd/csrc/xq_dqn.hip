@@ -26,7 +26,9 @@
 
 #include <algorithm>
 #include <cmath>
+#include <mutex>
 #include <random>
+#include <unordered_map>
 
 namespace xq { struct TailArgs; }
 struct xq_dqn {
@@ -58,7 +60,6 @@ struct xq_dqn {
     uint16_t* sel_acts_bf[XQ_MAX_LAYERS] = {nullptr};
     uint16_t* deltas_bf[XQ_MAX_LAYERS] = {nullptr};    // XQ_PRECISION_BF16_FULL: the hidden deltas rounded to bf16 (operands of the backward products)
     int cap_bf = 0, sel_cap_bf = 0, cap_dbf = 0;
-    bool bg_ready = false;                             // dynamic-LDS attribute of the gemm_bf16_kernel instances set
     float* t2acts[2] = {nullptr, nullptr};             // third forward chain of a Double-DQN step (s' on the target net)
     int cap_t2 = 0;
     int* partial_idx = nullptr;  int cap_idx = 0;      // row index of each column-max partial (Double DQN)
@@ -101,7 +102,6 @@ struct xq_dqn {
     // (xq_dqn_td_grads never touches the others), so the shadow of rows >= 96 and slots [4], [5] are kept from step to step:
     unsigned* scr_wmax = nullptr;
     int scr_static_net = -1;                    // net whose rows >= 96 the shadow holds (-1: none — the next step converts everything)
-    bool scr_new_kernel_ready = false;          // dynamic-LDS attribute of screen_top2_kernel set
     unsigned long long* scr_stats = nullptr;    // [refine blocks][2] running totals per block: candidate (sample, group) pairs, pairs recomputed as whole groups
     int scr_stat_blocks = 0;                    // blocks the array (and its pinned copy) has room for
     unsigned long long scr_carry[2] = {0, 0};   // totals of an array that was replaced by a larger one
@@ -280,15 +280,24 @@ static int launch_gemm(xq_dqn* d, GemmArgs g, int splits, const char* name, int*
 }
 #define XQ_GEMM(expr) XQ_TRY(expr)
 
-// gemm_dma_kernel (xq_gemm_dma.hip.h): (128 TI) x (64 TJ) tiles, up to 144 KB of dynamic LDS (attribute set once per instance)
+// A kernel's dynamic-LDS limit raised to `bytes` the first time it is asked for, per kernel address (every template instance has its own)
+static int ensure_max_dynamic_lds(const void* kernel, int bytes) {
+    static std::mutex m;
+    static std::unordered_map<const void*, int> granted;
+    std::lock_guard<std::mutex> lock(m);
+    int& have = granted[kernel];
+    if (have >= bytes) return XQ_OK;
+    XQ_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+    have = bytes;
+    return XQ_OK;
+}
+template <class F> static int ensure_max_dynamic_lds(F* kernel, int bytes) { return ensure_max_dynamic_lds(reinterpret_cast<const void*>(kernel), bytes); }
+
+// gemm_dma_kernel (xq_gemm_dma.hip.h): (128 TI) x (64 TJ) tiles, up to 144 KB of dynamic LDS
 template <int DT, int AL, int BL, int EPI, int TI, int TJ>
 static int launch_dma_gemm(xq_dqn* d, const Bf16GemmArgs& g, int gz, const char* name) {
-    static bool ready = false;
     constexpr int lds = bg_lds_bytes(TI, TJ);
-    if (!ready) {
-        XQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_dma_kernel<DT, AL, BL, EPI, TI, TJ>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        ready = true;
-    }
+    XQ_TRY(ensure_max_dynamic_lds(gemm_dma_kernel<DT, AL, BL, EPI, TI, TJ>, lds));
     const int groups = g.groups > 1 ? g.groups : 1;
     const double es = DT == DT_F32 ? 4.0 : 2.0;
     ProfScope ps(d, name, 2.0 * g.M * g.N * (double)g.K * groups, es * groups * ((double)g.M * g.K + (double)g.N * g.K + 2.0 * g.M * g.N));
@@ -1023,11 +1032,7 @@ static int l0_gradient(xq_dqn* d, int n, float* dst) {
             d->tail_lds = std::max(d->tail_lds, shmem);
         } else {
             ProfScope ps(d, "l0_grad_segsum", fl, by);
-            static bool granted = false;
-            if (!granted) {
-                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(l0_grad_mfma_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
-                granted = true;
-            }
+            XQ_TRY(ensure_max_dynamic_lds(l0_grad_mfma_kernel<0>, 64 * 1024));
             hipLaunchKernelGGL(l0_grad_mfma_kernel<0>, dim3(H / kL0mCols, 4, nchunks), dim3(256), shmem, d->cur, d->l0_sel, d->l0_planes, plane_stride,
                                kpad, H, chunk, out);
             XQ_HIP(hipGetLastError());
@@ -1064,11 +1069,10 @@ static int l0_gradient(xq_dqn* d, int n, float* dst) {
 }
 
 static int sgd_apply(xq_dqn* d, SegTable t, double alpha) {
-    static const bool vec_ok4 = [] { const char* e = getenv("XQ_SGD_SCALAR"); return !(e && e[0] == '1'); }();
     long long mx = 0;
     for (int i = 0; i < t.nseg; ++i) {
         const uintptr_t bits = (uintptr_t)t.dst[i] | (uintptr_t)t.src[i] | ((uintptr_t)t.dst_bf[i] << 1);   // the bf16 shadow: 8-byte pieces
-        t.vec4[i] = vec_ok4 && (bits & 15) == 0 && (t.len[i] & 3) == 0 && (t.nslabs[i] <= 0 || (t.stride[i] & 3) == 0);
+        t.vec4[i] = (bits & 15) == 0 && (t.len[i] & 3) == 0 && (t.nslabs[i] <= 0 || (t.stride[i] & 3) == 0);
         mx = std::max(mx, t.vec4[i] ? t.len[i] / 4 : t.len[i]);
     }
     const unsigned bx = (unsigned)std::max<long long>(1, std::min<long long>((mx + 255) / 256, 1024));
@@ -1552,18 +1556,11 @@ static int tail_launch(xq_dqn* d, bool last, const char* name) {
     const long long total = (long long)T.n_l0 + T.n_grad + T.n_delta + T.n_out + T.n_colsum + T.n_sel;
     if (total <= 0) return XQ_OK;
     ProfScope ps(d, name, d->tail_flops, d->tail_bytes, true);      // one launch: timed by its own start / stop events
-    auto launch = [&](auto kern) {
-        static size_t granted = 48 * 1024;            // per instantiation
-        if (d->tail_lds > granted) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
-            granted = 64 * 1024;
-        }
-        hipExtLaunchKernelGGL(kern, dim3((unsigned)total), dim3(256), d->tail_lds, d->cur, ps.start(), ps.stop(), 0, T);
-    };
-    if (last && T.l0_planes != nullptr) launch(td_tail_kernel<TAIL_L0 | TAIL_GRAD | TAIL_OUT | TAIL_COLSUM, true>);
-    else if (last) launch(td_tail_kernel<TAIL_L0 | TAIL_GRAD | TAIL_OUT | TAIL_COLSUM>);
-    else if (T.n_sel) launch(td_tail_kernel<TAIL_GRAD | TAIL_DELTA | TAIL_OUT | TAIL_SEL>);
-    else launch(td_tail_kernel<TAIL_GRAD | TAIL_DELTA | TAIL_OUT>);
+    const auto kern = last ? (T.l0_planes != nullptr ? td_tail_kernel<TAIL_L0 | TAIL_GRAD | TAIL_OUT | TAIL_COLSUM, true>
+                                                     : td_tail_kernel<TAIL_L0 | TAIL_GRAD | TAIL_OUT | TAIL_COLSUM>)
+                           : (T.n_sel ? td_tail_kernel<TAIL_GRAD | TAIL_DELTA | TAIL_OUT | TAIL_SEL> : td_tail_kernel<TAIL_GRAD | TAIL_DELTA | TAIL_OUT>);
+    if (d->tail_lds > 48 * 1024) XQ_TRY(ensure_max_dynamic_lds(kern, 64 * 1024));
+    hipExtLaunchKernelGGL(kern, dim3((unsigned)total), dim3(256), d->tail_lds, d->cur, ps.start(), ps.stop(), 0, T);
     XQ_HIP(hipGetLastError());
     return XQ_OK;
 }
@@ -1660,8 +1657,7 @@ static int tail_gradients_impl(xq_dqn* d, int n, float* const* outs, float* G, i
     // two hidden layers: the one weight-gradient product runs beside the layer-0 sums (L2-bound) rather than beside the delta product
     // (both MFMA-bound, and the select chain's Q head is on the chip at that time): 0.2065 against 0.2086 ms per step of the headline
     // bench; three hidden layers (bench --config 4): no difference, kept beside the delta products
-    static const bool grad_early = getenv("XQ_TAIL_GRAD_EARLY") != nullptr;     // A/B switch (tools/ab_env.sh)
-    const bool defer_grad = nl == 3 && !grad_early;
+    const bool defer_grad = nl == 3;
     int waiting = -1;
     for (int l = nl - 3; l >= 0; --l) {
         tail_begin(d);
@@ -1695,6 +1691,275 @@ static int tail_gradients_impl(xq_dqn* d, int n, float* const* outs, float* G, i
     return tail_launch(d, true, "td_tail_l0");
 }
 
+// ---- one TD step (td_grads_impl): the stages below, in the order the step runs them -----------------------------------------------
+
+// What the stages of one step share: its inputs, and the shapes and views decided once at its top.
+struct TdStep {
+    const int32_t* action_to; const float* reward; const uint8_t* done; SlotSrc slots; const PerOpts* per;
+    int n, mode, sel_net, nl, Hl, NO; bool dbl, bf;
+    bool big_tiles;              // the max pass's product on 128-row tiles
+    int n_partial;               // partial maxima per sample of the max pass's tile kernels
+    size_t bias_lds;             // the whole output bias in the persistent column-max kernel's LDS
+    float* outs[XQ_MAX_LAYERS]; uint16_t* outs_bf[XQ_MAX_LAYERS];        // s on the online net (kept for the backward pass)
+    float* touts[XQ_MAX_LAYERS]; uint16_t* touts_bf[XQ_MAX_LAYERS];      // s' on the selecting net
+    float* t2outs[XQ_MAX_LAYERS]; uint16_t* t2outs_bf[XQ_MAX_LAYERS];    // s' on the target net (Double DQN)
+    const float* view; long long view_ld; int view_kmax;                 // the online weights that carry the output delta down a layer
+};
+
+// The screening guard of a step that asks for the screened max pass.  The counters queued at one check boundary are evaluated at the NEXT
+// one (32 screened steps later: the copy finished long ago, the wait returns at once) — the step at which a fallback begins is a function
+// of the step count alone, never of how far the host runs ahead of the device.  *screened: whether this step screens.
+static int screen_guard_tick(xq_dqn* d, int n, bool* screened) {
+    XQ_TRY(ensure_screen_capacity(d, n));
+    if (d->scr_guard_pending && d->scr_host_steps % kScreenCheckEvery == 0 && d->scr_host_steps != d->scr_guard_queued_at) {
+        XQ_HIP(hipEventSynchronize(d->scr_guard_ev));
+        d->scr_guard_pending = false;
+        unsigned long long h[2];
+        screen_stat_sums_of(d, d->scr_guard_host, h);
+        const double ds = (double)(d->scr_guard_samples - d->scr_seen[0]);
+        if (ds > 0 && ((double)(h[0] - d->scr_seen[1]) > kScreenMaxPairs * ds || (double)(h[1] - d->scr_seen[2]) > kScreenMaxWhole * ds)) {
+            d->scr_hold = kScreenHoldSteps;
+            d->scr_fallbacks += 1;
+        }
+        if (ds > 0) {                                // whole groups per sample over the window, with hysteresis
+            const double share = (double)(h[1] - d->scr_seen[2]) / ds;
+            if (share > 0.25) d->scr_stage_whole = true; else if (share < 0.10) d->scr_stage_whole = false;
+        }
+        d->scr_seen[0] = d->scr_guard_samples; d->scr_seen[1] = h[0]; d->scr_seen[2] = h[1];
+    }
+    *screened = d->scr_hold == 0;
+    if (d->scr_hold > 0) --d->scr_hold;
+    return XQ_OK;
+}
+
+// bf16 copy + largest row norm / |bias| of the selecting net's output-layer weights.  Only rows 0..95 change under the TD rule: while
+// `scr_static_net` says that rows >= 96 of the shadow (and their maxima, slots [4], [5]) still belong to this net, the shadow pass converts
+// three blocks of 32 rows instead of 254; everything is converted again after set_params / load_model / update_target / a dense
+// backpropagate / a change of the selecting net.  The maxima of rows 0..95 land in the slots of this step's parity, which the refine kernel
+// of the previous screened step zeroed.
+static int screen_shadow_job(xq_dqn* d, int sel_net, int parity, ShadowJob* shadow) {
+    const int NO = d->nout(), nl = d->nl;
+    const bool full = d->scr_static_net != sel_net;
+    if (full) XQ_HIP(hipMemsetAsync(d->scr_wmax + 4, 0, 2 * sizeof(unsigned), d->cur));     // (the maxima of rows >= 96 start again)
+    memset(shadow, 0, sizeof *shadow);
+    shadow->W = d->wl(sel_net, nl - 1); shadow->bias = d->bl(sel_net, nl - 1); shadow->NO = NO; shadow->K = d->hlast(); shadow->Wb = d->scr_wb;
+    shadow->w_dyn = d->scr_wmax + parity; shadow->b_dyn = d->scr_wmax + 2 + parity;
+    shadow->w_stat = d->scr_wmax + 4; shadow->b_stat = d->scr_wmax + 5;
+    shadow->nblocks = full ? (NO + kShadowRows - 1) / kShadowRows : std::min((int)kShadowDynBlocks, (NO + kShadowRows - 1) / kShadowRows);
+    d->scr_static_net = sel_net;
+    return XQ_OK;
+}
+
+// screen_top2_kernel (xq_screen.hip.h) in mode SCR_TOP2 / SCR_ARG / SCR_MAX for a 256- or 512-wide last hidden layer
+static int launch_screen(xq_dqn* d, const ScreenArgs& a, int mode, hipEvent_t start, hipEvent_t stop) {
+    using ScreenKernel = void (*)(ScreenArgs);
+    static const ScreenKernel kerns[3][2] = {{screen_top2_kernel<1, 2, SCR_TOP2>, screen_top2_kernel<2, 1, SCR_TOP2>},
+                                             {screen_top2_kernel<1, 2, SCR_ARG>, screen_top2_kernel<2, 1, SCR_ARG>},
+                                             {screen_top2_kernel<1, 2, SCR_MAX>, screen_top2_kernel<2, 1, SCR_MAX>}};
+    const ScreenKernel kern = kerns[mode][a.K == 256 ? 0 : 1];
+    XQ_TRY(ensure_max_dynamic_lds(kern, 160 * 1024));
+    hipExtLaunchKernelGGL(kern, dim3(a.panels * a.ranges), dim3(512), screen_lds_bytes(a), d->cur, start, stop, 0, a);
+    XQ_HIP(hipGetLastError());
+    return XQ_OK;
+}
+
+// gemm_colmax_persistent_kernel (xq_gemm.hip.h) over `total` tiles of 128 x 128: 2 blocks per CU walk the tile list with the prefetch
+// running across tile boundaries, the second half of the grid its own half of the tiles at static priority (see the kernel).  Sets the
+// walk's fields of g (zeroed, with g.M, g.K and g.bias set) and returns the grid.
+static int colmax_persistent_grid(const xq_dqn* d, GemmArgs& g, int tiles_m, int total) {
+    g.a_vec = g.b_vec = 1; g.k_chunk = g.K;
+    g.bias_padded = ((((uintptr_t)g.bias) % 16 == 0) && (g.M % 4) == 0) ? 1 : 0;     // wide bias preload
+    const int grid = std::min(total, 2 * d->ncu);
+    if (grid >= 2 && (grid & 1) == 0 && total >= 4 * grid) {
+        g.prio_split = grid / 2;
+        g.prio_tiles = (total / 2) / tiles_m * tiles_m;
+        if (g.prio_tiles <= 0 || g.prio_tiles >= total) { g.prio_split = 0; g.prio_tiles = 0; }
+    }
+    return grid;
+}
+
+// Screened max_a' Q(s', a') of an fp32 net: the bf16 screening product (screen_top2_kernel for the widths it is built for,
+// the persistent tile kernel's CM_TOP2 mode otherwise), the exact fp32 refine of the candidates it leaves, and every kScreenCheckEvery
+// steps the copy of the guard's counters.  *td_fused: the refine kernel did td_delta_kernel's work too.
+static int qmax_screened(xq_dqn* d, const TdStep& s, bool scr_new, int parity, bool* td_fused) {
+    const int n = s.n, NO = s.NO, Hl = s.Hl, nl = s.nl;
+    const float *W = d->wl(s.sel_net, nl - 1), *bias = d->bl(s.sel_net, nl - 1);
+    const int tiles_m = (NO + 127) / 128, total = tiles_m * ((n + 127) / 128);
+    // 32-row lane groups: the tile kernel writes all 4 per 128-row tile, screen_top2_kernel only those of 64-row chunks with real rows
+    const int G = scr_new ? 2 * ((NO + 63) / 64) : 4 * tiles_m;
+    long long ldp = n;
+    int scr_ranges = 0, scr_gpr = 0;
+    if (scr_new) {
+        ScreenArgs a; memset(&a, 0, sizeof a);
+        a.W = d->scr_wb; a.A = d->scr_ab; a.a_frag = 1; a.bias = bias;
+        a.P1 = d->scr_p1; a.P2 = d->scr_p2; a.R = d->scr_R; a.na = d->scr_na;
+        screen_geometry(NO, n, Hl, d->ncu, a);
+        ldp = a.ldp = screen_padded_samples(n, Hl);
+        scr_ranges = a.ranges; scr_gpr = 2 * a.cpr;
+        // (bracketed by its own start / stop events: the live figure is the kernel's duration as rocprofv3 reports it)
+        ProfScope ps(d, "gemm_qmax_screen", 2.0 * NO * (double)n * Hl, 2.0 * ((double)NO * Hl + (double)n * Hl) + 8.0 * G * n, true);
+        XQ_TRY(launch_screen(d, a, SCR_TOP2, ps.start(), ps.stop()));
+    } else {
+        GemmArgs g; memset(&g, 0, sizeof g);
+        g.M = NO; g.N = n;
+        g.K = Hl / 2; g.lda = g.ldb = Hl / 2;
+        g.A = reinterpret_cast<const float*>(d->scr_wb); g.B = reinterpret_cast<const float*>(d->scr_ab);
+        g.bias = bias;
+        g.partial = d->scr_p1; g.partial2 = d->scr_p2;
+        const int grid = colmax_persistent_grid(d, g, tiles_m, total);
+        ProfScope ps(d, "gemm_qmax_screen", 2.0 * g.M * g.N * Hl, 2.0 * ((double)g.M * Hl + (double)g.N * Hl) + 8.0 * G * g.N);
+        hipLaunchKernelGGL((gemm_colmax_persistent_kernel<2, 2, DT_BF16, CM_TOP2>), dim3(grid), dim3(256), s.bias_lds, d->cur, g, tiles_m, total);
+        XQ_HIP(hipGetLastError());
+    }
+    // (the select chain of the trainer started in front of the screening pass.  Behind the refine kernel instead — which would then have
+    // the chip to itself, 17 instead of 27-34 us — the select chain ends after the gradients and the step waits for it: 0.197 -> 0.207 ms)
+    {
+        ProfScope ps(d, "qmax_refine", 2.0 * n * Hl * 3, 12.0 * G * n + 4.0 * n * Hl, true);      // one launch: its own start / stop events
+        const dim3 grid((n + kRefineSamples - 1) / kRefineSamples);
+        // one block per CU and K = 256: room in LDS for the staged pass of qmax_refine2_kernel (whole groups that many samples ask for)
+        const bool stage = scr_new && Hl == 256 && (int)grid.x <= d->ncu && (d->refine_stage > 0 || (d->refine_stage < 0 && d->scr_stage_whole));
+        const size_t lds = refine_cand_words(G) * sizeof(uint32_t) + refine_wlist_bytes(G) + (stage ? refine_stage_bytes() : 0);
+        const float* a_last = s.touts[nl - 2];
+        if (scr_new) {
+            TdFused T; memset(&T, 0, sizeof T);
+            // the TD target / delta kernel rides in the refine blocks (fp32 net, 256-wide last hidden layer, uniform replay)
+            *td_fused = d->td_tail && Hl == 256 && !s.per && !d->bf16_bwd();
+            if (*td_fused) {
+                const int lt = nl - 2;
+                T.src = s.slots; T.action_to = s.action_to; T.reward = s.reward; T.done = s.done;
+                T.a_s = s.outs[lt]; T.w_out = d->wl(XQ_NET_ONLINE, nl - 1); T.b_out = d->bl(XQ_NET_ONLINE, nl - 1);
+                T.view = s.view; T.view_ld = s.view_ld; T.view_kmax = s.view_kmax; T.gamma = (float)d->gamma;
+                T.dtop = d->deltas[lt]; T.dsc = d->dsc; T.act = d->act_mb; T.qsa = d->qsa; T.yv = d->yv; T.lossv = d->lossv;
+            }
+            // whole groups: 2 = the popular ones through LDS when the launch has room for it, 1 = all of them four per round trip
+            const int whole_mode = stage ? 2 : 1;
+            const auto kern = *td_fused ? qmax_refine2_kernel<256, true> : Hl == 256 ? qmax_refine2_kernel<256> : qmax_refine2_kernel<512>;
+            XQ_TRY(ensure_max_dynamic_lds(kern, 152 * 1024));     // the staged pass asks for ~145 KB
+            hipExtLaunchKernelGGL(kern, grid, dim3(256), lds, d->cur, ps.start(), ps.stop(), 0, d->scr_R, scr_ranges, scr_gpr, d->scr_p1, d->scr_p2, G,
+                                  n, ldp, d->scr_na, a_last, Hl, W, bias, NO, d->scr_wmax, parity, d->zmax, d->scr_stats, T, whole_mode);
+        } else {
+            const bool small = G <= 8 * 32;
+            const auto kern = Hl == 256 ? (small ? qmax_refine_kernel<256, 32> : qmax_refine_kernel<256, 64>)
+                            : Hl == 512 ? (small ? qmax_refine_kernel<512, 32> : qmax_refine_kernel<512, 64>)
+                                        : (small ? qmax_refine_kernel<0, 32> : qmax_refine_kernel<0, 64>);
+            hipExtLaunchKernelGGL(kern, grid, dim3(256), lds, d->cur, ps.start(), ps.stop(), 0, d->scr_p1, d->scr_p2, G, n, ldp, a_last, Hl,
+                                  W, bias, NO, d->scr_wmax, parity, d->zmax, d->scr_stats);
+        }
+        XQ_HIP(hipGetLastError());
+    }
+    d->scr_host_steps += 1; d->scr_host_samples += (unsigned long long)n;
+    if (d->scr_host_steps % kScreenCheckEvery == 0 && !d->scr_guard_pending) {
+        XQ_HIP(hipMemcpyAsync(d->scr_guard_host, d->scr_stats, (size_t)2 * d->scr_stat_blocks * sizeof(unsigned long long), hipMemcpyDeviceToHost, d->cur));
+        XQ_HIP(hipEventRecord(d->scr_guard_ev, d->cur));
+        d->scr_guard_pending = true; d->scr_guard_samples = d->scr_host_samples; d->scr_guard_queued_at = d->scr_host_steps;
+    }
+    return XQ_OK;
+}
+
+// Exact max_a' Q(s', a') (+ its row for Double DQN): partial maxima per sample from one of three products — the screen kernel's exact
+// mode (bf16 net), the persistent column-max kernel, launch_gemm's column-max epilogue — folded into kReduceParts values by colmax_reduce.
+static int qmax_exact(xq_dqn* d, const TdStep& s, bool bf_frag, bool gate_early) {
+    const int n = s.n, NO = s.NO, Hl = s.Hl, nl = s.nl;
+    const bool bf = s.bf, dbl = s.dbl;
+    long long part_ld = n;              // row stride of the partial arrays
+    int n_part = s.n_partial;
+    if (bf && (Hl == 256 || Hl == 512) && n >= 1024) {
+        // bf16 Q-net: the same kernel as the screening pass in its exact max / arg-max mode — here the bf16 product IS the net's output
+        // layer, not a screen: per 32-row lane group the largest value (+ its row, first maximum: Double DQN)
+        ScreenArgs a; memset(&a, 0, sizeof a);
+        a.W = d->wl_bf(s.sel_net, nl - 1); a.A = s.touts_bf[nl - 2]; a.a_frag = bf_frag ? 1 : 0; a.bias = d->bl(s.sel_net, nl - 1);
+        a.P1 = d->partial; a.P2 = reinterpret_cast<float*>(d->partial_idx);
+        screen_geometry(NO, n, Hl, d->ncu, a);
+        part_ld = a.ldp = screen_padded_samples(n, Hl);
+        n_part = 2 * a.nchunks;
+        ProfScope ps(d, "gemm_qmax_rowmax", 2.0 * NO * (double)n * Hl, 2.0 * ((double)NO * Hl + (double)n * Hl) + 8.0 * n_part * n, true);
+        XQ_TRY(launch_screen(d, a, dbl ? SCR_ARG : SCR_MAX, ps.start(), ps.stop()));
+    } else {
+        GemmArgs g; memset(&g, 0, sizeof g);
+        g.M = NO; g.N = n;
+        g.K = bf ? Hl / 2 : Hl; g.lda = g.ldb = g.K;        // (bf16 operands: pairs of elements as one fp32 word)
+        g.A = bf ? reinterpret_cast<const float*>(d->wl_bf(s.sel_net, nl - 1)) : d->wl(s.sel_net, nl - 1);
+        g.B = bf ? reinterpret_cast<const float*>(s.touts_bf[nl - 2]) : s.touts[nl - 2];
+        g.bias = d->bl(s.sel_net, nl - 1);
+        g.partial = d->partial;
+        g.partial_idx = dbl ? d->partial_idx : nullptr;
+        // the persistent kernel keeps the whole bias vector in LDS beside its operand tiles (2 blocks per CU must fit)
+        if (s.big_tiles && (g.K % GBK) == 0 && vec_ok(g.A, g.lda) && vec_ok(g.B, g.ldb) && s.bias_lds <= 40 * 1024) {
+            const int tiles_m = (NO + 127) / 128, total = tiles_m * ((n + 127) / 128);
+            const int grid = colmax_persistent_grid(d, g, tiles_m, total);
+            ProfScope ps(d, "gemm_qmax_rowmax", 2.0 * g.M * g.N * Hl, (bf ? 2.0 : 4.0) * ((double)g.M * Hl + (double)g.N * Hl) + 8.0 * tiles_m * g.N);
+            const auto kern = bf ? (dbl ? gemm_colmax_persistent_kernel<2, 2, DT_BF16, CM_ARG> : gemm_colmax_persistent_kernel<2, 2, DT_BF16, CM_MAX>)
+                                 : (dbl ? gemm_colmax_persistent_kernel<2, 2, DT_F32, CM_ARG> : gemm_colmax_persistent_kernel<2, 2, DT_F32, CM_MAX>);
+            hipLaunchKernelGGL(kern, dim3(grid), dim3(256), s.bias_lds, d->cur, g, tiles_m, total);
+            XQ_HIP(hipGetLastError());
+        } else if (bf) XQ_GEMM((launch_gemm<L_KCONTIG, L_KCONTIG, EPI_COLMAX, DT_BF16>(d, g, 1, "gemm_qmax_rowmax")));
+        else XQ_GEMM((launch_gemm<L_KCONTIG, L_KCONTIG, EPI_COLMAX>(d, g, 1, "gemm_qmax_rowmax")));
+    }
+    if (!d->late_gate && !gate_early) XQ_HIP(hipEventRecord(d->ev_qmax, d->stream));
+    {   // the partial maxima of every sample folded into kReduceParts values (+ row indices): coalesced, block-cooperative
+        ProfScope ps(d, "colmax_reduce", (double)n * n_part, (dbl ? 8.0 : 4.0) * n * (n_part + kReduceParts));
+        hipLaunchKernelGGL(colmax_reduce_kernel, dim3((n + 63) / 64, kReduceParts), dim3(256), 0, d->cur, d->partial,
+                           dbl ? d->partial_idx : nullptr, n_part, n, part_ld, d->zmax, d->zidx);
+        XQ_HIP(hipGetLastError());
+    }
+    return XQ_OK;
+}
+
+// Q(s, a), target, the scalar output delta and the delta of the last hidden layer (one launch, no GEMM); zparts = maxima per sample in zmax
+static int td_delta(xq_dqn* d, const TdStep& s, int zparts) {
+    const int n = s.n, nl = s.nl, Hl = s.Hl;
+    const int lt = nl - 2;                                   // last hidden layer
+    ProfScope ps(d, "td_target_delta", 4.0 * n * Hl, (double)n * (Hl * 16 + s.n_partial * 4));
+    TdExtra X; memset(&X, 0, sizeof X);
+    X.nout = s.NO;
+    if (s.dbl) {
+        X.double_dqn = 1; X.partial_idx = d->zidx;
+        X.bout_t = d->bl(XQ_NET_TARGET, nl - 1);
+        if (s.bf) { X.wout_t_bf = d->wl_bf(XQ_NET_TARGET, nl - 1); X.alast_t_bf = s.t2outs_bf[lt]; }
+        else { X.wout_t = d->wl(XQ_NET_TARGET, nl - 1); X.alast_t = s.t2outs[lt]; }
+    }
+    if (s.bf) X.wout_bf = d->wl_bf(XQ_NET_ONLINE, nl - 1);
+    if (d->bf16_bwd()) X.dtop_bf = d->deltas_bf[lt];
+    if (const PerOpts* per = s.per) {
+        X.is_w = per->is_w; X.is_wmax = per->is_wmax; X.prio = per->prio; X.pmax_live = per->pmax_live;
+        X.per_eps = per->eps; X.per_alpha = per->alpha;
+    }
+    hipLaunchKernelGGL(td_delta_kernel, dim3((n + 3) / 4), dim3(256), 0, d->cur, n, s.slots, s.action_to, s.reward, s.done,
+                       s.outs[lt], Hl, d->wl(XQ_NET_ONLINE, nl - 1), d->bl(XQ_NET_ONLINE, nl - 1), d->zmax, zparts,
+                       (float)d->gamma, s.view, s.view_ld, s.view_kmax, d->deltas[lt], d->dsc, d->act_mb, d->qsa, d->yv, d->lossv, X);
+    XQ_HIP(hipGetLastError());
+    return XQ_OK;
+}
+
+// The gradients outside the fused launches, two chains side by side.  Critical (handle stream): the remaining hidden deltas and the layer-0
+// sums that consume delta_0.  Side stream: the output-layer and hidden weight gradients and the bias column sums, as their deltas exist.
+static int td_gradients_fork(xq_dqn* d, const TdStep& s) {
+    const int n = s.n, nl = s.nl;
+    float* G = d->grads_td;
+    XQ_HIP(hipEventRecord(d->ev_fork, d->stream));
+    XQ_HIP(hipStreamWaitEvent(d->side, d->ev_fork, 0));
+    if (nl >= 3) XQ_TRY(hidden_deltas(d, n, d->deltas[nl - 2], d->L[nl - 1], d->L[nl - 1], s.mode, nl - 3));
+    XQ_HIP(hipEventRecord(d->ev_delta, d->stream));
+    // data-parallel step: the gradient buffer is all-reduced in two buckets, each ON THE STREAM OF ITS PRODUCER right behind it — no
+    // communicator stream, no event of its own.  RCCL runs the collectives of one communicator in issue order, so the side bucket (hidden +
+    // output-layer weights, all biases: ready first) is issued first and the layer-0 bucket (the last thing computed, the only exposed one)
+    // second; every rank issues in this order.  Without a communicator the layer-0 sums are issued first.
+    const size_t n0 = (size_t)d->L[0] * d->L[1];
+    if (!d->comm) XQ_TRY(l0_gradient(d, n, G + d->g_w0));
+    d->cur = d->side;
+    const int rc = side_gradients(d, n, s.outs, G);
+    d->cur = d->stream;
+    if (rc != XQ_OK) return rc;
+    if (d->comm) XQ_TRY(comm_allreduce_on(d->comm, G + n0, d->n_grads_td - n0, d->side));
+    XQ_HIP(hipEventRecord(d->ev_join, d->side));
+    if (d->comm) {
+        XQ_TRY(l0_gradient(d, n, G + d->g_w0));
+        XQ_TRY(comm_allreduce_on(d->comm, G, n0, d->stream));
+    }
+    XQ_HIP(hipStreamWaitEvent(d->stream, d->ev_join, 0));
+    return XQ_OK;
+}
+
 static int td_grads_impl(xq_dqn* d, const uint32_t* boards, const uint32_t* next_boards, const int32_t* action_to,
                          const float* reward, const uint8_t* done, SlotSrc slots, int n, int td_net, int mode, const PerOpts* per) {
     if (!d || !boards || !next_boards || !action_to || !reward || !done || n <= 0)
@@ -1716,328 +1981,61 @@ static int td_grads_impl(xq_dqn* d, const uint32_t* boards, const uint32_t* next
     XQ_TRY(ensure_ext_capacity(d, n, dbl));
     const int nl = d->nl, Hl = d->hlast(), NO = d->nout();
     if (bf && (Hl & 1)) return fail(XQ_ERR_INVALID_ARGUMENT, "bf16 Q-net needs even layer widths");
-    // 1. the forward chains in the same launches (one gather grid, grouped hidden GEMMs): s on the online net with the
-    //    activations kept for the backward pass, s' on the net that selects (online, or target for XQ_TD_TARGET_NET) and,
-    //    for Double DQN, s' on the target net that evaluates
-    const int sel_net = td_net == XQ_TD_TARGET_NET ? XQ_NET_TARGET : XQ_NET_ONLINE;
-    float* outs[XQ_MAX_LAYERS]; uint16_t* outs_bf[XQ_MAX_LAYERS];
-    float* touts[XQ_MAX_LAYERS]; uint16_t* touts_bf[XQ_MAX_LAYERS];
-    float* t2outs[XQ_MAX_LAYERS]; uint16_t* t2outs_bf[XQ_MAX_LAYERS];
+    TdStep s;
+    s.action_to = action_to; s.reward = reward; s.done = done; s.slots = slots; s.per = per;
+    s.n = n; s.mode = mode; s.nl = nl; s.Hl = Hl; s.NO = NO; s.dbl = dbl; s.bf = bf; s.sel_net = td_net == XQ_TD_TARGET_NET ? XQ_NET_TARGET : XQ_NET_ONLINE;
     for (int l = 0; l + 1 < nl; ++l) {
-        outs[l] = d->acts[l]; outs_bf[l] = d->acts_bf[l];
-        touts[l] = bf ? nullptr : d->tacts[l & 1]; touts_bf[l] = d->tacts_bf[l & 1];
-        t2outs[l] = bf ? nullptr : d->t2acts[l & 1]; t2outs_bf[l] = d->t2acts_bf[l & 1];
+        s.outs[l] = d->acts[l]; s.outs_bf[l] = d->acts_bf[l];
+        s.touts[l] = bf ? nullptr : d->tacts[l & 1]; s.touts_bf[l] = d->tacts_bf[l & 1];
+        s.t2outs[l] = bf ? nullptr : d->t2acts[l & 1]; s.t2outs_bf[l] = d->t2acts_bf[l & 1];
     }
-    // launched transposed (rows = output neurons, columns = samples): the max over the 8100 outputs then runs over
+    // the max pass is launched transposed (rows = output neurons, columns = samples): the max over the 8100 outputs then runs over
     // accumulator registers inside one lane instead of across the 32 lanes of a row
-    const bool big_tiles = (long long)((NO + 127) / 128) * ((n + 127) / 128) >= 512;
-    const int n_partial = 2 * (big_tiles ? (NO + 127) / 128 : (NO + 63) / 64);
-    const size_t bias_lds_all = (size_t)((NO + 127) / 128) * 128 * sizeof(float);
-    const bool want_screen = d->qmax_mode == XQ_QMAX_SCREENED && !bf && !dbl && big_tiles && (Hl % 64) == 0 && Hl <= 1024 &&
-                          bias_lds_all <= 40 * 1024 && (NO + 127) / 128 * 4 <= 8 * kRefineMaxPerThread;
-    bool screened = want_screen;
-    bool td_fused = false;             // td_delta_kernel's work done inside the refine kernel (below)
-    if (screened) {
-        XQ_TRY(ensure_screen_capacity(d, n));
-        // the counters queued at one check boundary are evaluated at the NEXT one (32 screened steps later: the copy finished long
-        // ago, the wait returns at once) — the step at which a fallback begins is a function of the step count alone, never of how
-        // far the host runs ahead of the device
-        if (d->scr_guard_pending && d->scr_host_steps % kScreenCheckEvery == 0 && d->scr_host_steps != d->scr_guard_queued_at) {
-            XQ_HIP(hipEventSynchronize(d->scr_guard_ev));
-            d->scr_guard_pending = false;
-            unsigned long long h[2];
-            screen_stat_sums_of(d, d->scr_guard_host, h);
-            const double ds = (double)(d->scr_guard_samples - d->scr_seen[0]);
-            if (ds > 0 && ((double)(h[0] - d->scr_seen[1]) > kScreenMaxPairs * ds || (double)(h[1] - d->scr_seen[2]) > kScreenMaxWhole * ds)) {
-                d->scr_hold = kScreenHoldSteps;
-                d->scr_fallbacks += 1;
-            }
-            if (ds > 0) {                                // whole groups per sample over the window, with hysteresis
-                const double share = (double)(h[1] - d->scr_seen[2]) / ds;
-                if (share > 0.25) d->scr_stage_whole = true; else if (share < 0.10) d->scr_stage_whole = false;
-            }
-            d->scr_seen[0] = d->scr_guard_samples; d->scr_seen[1] = h[0]; d->scr_seen[2] = h[1];
-        }
-        if (d->scr_hold > 0) { --d->scr_hold; screened = false; }
-    }
-    // bf16 copy + largest row norm / |bias| of the selecting net's output-layer weights.  Only rows 0..95 change under the TD rule:
-    // while `scr_static_net` says that rows >= 96 of the shadow (and their maxima, slots [4], [5]) still belong to this net, the
-    // shadow pass converts three blocks of 32 rows instead of 254; everything is converted again after set_params / load_model /
-    // update_target / a dense backpropagate / a change of the selecting net.  The maxima of rows 0..95 land in the slots of this
-    // step's parity, which the refine kernel of the previous screened step zeroed.
+    s.big_tiles = (long long)((NO + 127) / 128) * ((n + 127) / 128) >= 512;
+    s.n_partial = 2 * (s.big_tiles ? (NO + 127) / 128 : (NO + 63) / 64);
+    s.bias_lds = (size_t)((NO + 127) / 128) * 128 * sizeof(float);
+    s.view = d->wrest(XQ_NET_ONLINE) + (d->wo[nl - 1] - d->wo[1]);
+    s.view_ld = mode == XQ_BACKPROP_REFERENCE ? d->L[nl - 2] : d->L[nl - 1]; s.view_kmax = mode == XQ_BACKPROP_REFERENCE ? d->L[nl - 1] : NO;
+    const bool want_screen = d->qmax_mode == XQ_QMAX_SCREENED && !bf && !dbl && s.big_tiles && (Hl % 64) == 0 && Hl <= 1024 &&
+                             s.bias_lds <= 40 * 1024 && (NO + 127) / 128 * 4 <= 8 * kRefineMaxPerThread;
+    bool screened = false;
+    if (want_screen) XQ_TRY(screen_guard_tick(d, n, &screened));
     const int parity = (int)(d->scr_host_steps & 1);
     // screen_top2_kernel (xq_screen.hip.h) for the widths it is built for; the persistent tile kernel's CM_TOP2 mode otherwise
     const bool scr_new = screened && (Hl == 256 || Hl == 512);
-    ShadowJob shadow; memset(&shadow, 0, sizeof shadow);
-    if (screened) {
-        const bool full = d->scr_static_net != sel_net;
-        if (full) XQ_HIP(hipMemsetAsync(d->scr_wmax + 4, 0, 2 * sizeof(unsigned), d->cur));
-        shadow.W = d->wl(sel_net, nl - 1); shadow.bias = d->bl(sel_net, nl - 1); shadow.NO = NO; shadow.K = Hl; shadow.Wb = d->scr_wb;
-        shadow.w_dyn = d->scr_wmax + parity; shadow.b_dyn = d->scr_wmax + 2 + parity;
-        shadow.w_stat = d->scr_wmax + 4; shadow.b_stat = d->scr_wmax + 5;
-        shadow.nblocks = full ? (NO + kShadowRows - 1) / kShadowRows : std::min((int)kShadowDynBlocks, (NO + kShadowRows - 1) / kShadowRows);
-        d->scr_static_net = sel_net;
-    }
-    // bf16 net: the s' chain's last activations feed only the max / arg-max pass; when both that pass and the forward product run on
-    // their own loops (whole tiles), the product writes them in fragment order
+    ShadowJob shadow;
+    if (screened) XQ_TRY(screen_shadow_job(d, s.sel_net, parity, &shadow));
+    // 1. the forward chains in the same launches (one gather grid, grouped hidden GEMMs): s on the online net with the activations kept
+    //    for the backward pass, s' on the net that selects (online, or target for XQ_TD_TARGET_NET) and, for Double DQN, s' on the target
+    //    net that evaluates.  bf16 net: the s' chain's last activations feed only the max / arg-max pass; when both that pass and the
+    //    forward product run on their own loops (whole tiles), the product writes them in fragment order
     const bool bf_frag = bf && nl >= 3 && (Hl == 256 || Hl == 512) && n >= 1024 && (n % kBgBM) == 0 && (d->L[nl - 2] % kBgBK) == 0;
-    ChainJob jobs[3] = {{XQ_NET_ONLINE, boards, outs, outs_bf, d->gboards, nullptr, false},
-                        {sel_net, next_boards, touts, touts_bf, nullptr, screened ? d->scr_ab : nullptr, scr_new || bf_frag},
-                        {XQ_NET_TARGET, next_boards, t2outs, t2outs_bf, nullptr, nullptr, false}};
+    ChainJob jobs[3] = {{XQ_NET_ONLINE, boards, s.outs, s.outs_bf, d->gboards, nullptr, false},
+                        {s.sel_net, next_boards, s.touts, s.touts_bf, nullptr, screened ? d->scr_ab : nullptr, scr_new || bf_frag},
+                        {XQ_NET_TARGET, next_boards, s.t2outs, s.t2outs_bf, nullptr, nullptr, false}};
+    // The select chain of the trainer starts at the end of the forward product (its stop event, when chain_boards can take it) when
+    // max_a' Q(s',a') runs on the bf16 matrix pipe (screening pass of an fp32 net, or the output layer of a bf16 net): its layer-0 gather
+    // (L2-bound) then runs beside the screening pass (matrix-pipe-bound) and is gone when the refine kernel — a chain of dependent memory
+    // round trips that the gather doubles in length — starts.  Same-box A/B, round 4 (3 x 300 steps per leg): behind the screening pass
+    // 0.1946-0.1969 ms, here 0.1888-0.1937; behind the layer-0 gather of this step 0.1886-0.1896 against 0.1914-0.1921; at the very top of
+    // the step no difference; --config 4 / 5 -0.3 % / -0.9 %.  The product's stop event rather than a marker behind it: 0.1740 -> 0.1728 ms.
+    // The full fp32 product keeps the chip to itself: there the chain starts behind it (qmax_exact).
     const bool gate_early = (screened || bf) && !d->late_gate;
-    // (same-box A/B, 3 x 3 x 300 steps: 0.1740 -> 0.1728 ms; XQ_FORK_STOP_EVENT=0 records a marker instead)
-    static const bool stop_event_fork = [] { const char* e = getenv("XQ_FORK_STOP_EVENT"); return !(e && e[0] == '0'); }();
-    d->fwd_stop_ev = (gate_early && stop_event_fork) ? d->ev_qmax : nullptr;
+    d->fwd_stop_ev = gate_early ? d->ev_qmax : nullptr;
     const int chain_rc = chain_boards(d, jobs, dbl ? 3 : 2, slots, n, screened ? &shadow : nullptr);
-    const bool fork_recorded = gate_early && stop_event_fork && d->fwd_stop_ev == nullptr;
+    const bool fork_pending = d->fwd_stop_ev != nullptr;            // chain_boards did not take the stop event: a marker instead
     d->fwd_stop_ev = nullptr;
     XQ_TRY(chain_rc);
-    // The select chain of the trainer starts HERE when max_a' Q(s',a') runs on the bf16 matrix pipe (screening pass of an fp32 net, or
-    // the output layer of a bf16 net): its layer-0 gather (L2-bound) then runs beside the screening pass (matrix-pipe-bound) and
-    // is gone when the refine kernel — a chain of dependent memory round trips that the gather doubles in length — starts.  Same-box
-    // A/B, round 4 (3 x 300 steps per leg): behind the screening pass 0.1946-0.1969 ms, here 0.1888-0.1937; behind the layer-0 gather of
-    // this step 0.1886-0.1896 against 0.1914-0.1921; at the very top of the step no difference; --config 4 / 5 -0.3 % / -0.9 %.
-    // The full fp32 product keeps the chip to itself: there the chain starts behind it (below).
-    if (gate_early && !fork_recorded) XQ_HIP(hipEventRecord(d->ev_qmax, d->stream));
-    int zparts = kReduceParts;
-    if (screened) {
-        const int tiles_m = (NO + 127) / 128, total = tiles_m * ((n + 127) / 128);
-        // 32-row lane groups: the tile kernel writes all 4 per 128-row tile, screen_top2_kernel only those of 64-row chunks with real rows
-        const int G = scr_new ? 2 * ((NO + 63) / 64) : 4 * tiles_m;
-        long long ldp = n;
-        int scr_ranges = 0, scr_gpr = 0;
-        if (scr_new) {
-            ScreenArgs a; memset(&a, 0, sizeof a);
-            a.W = d->scr_wb; a.A = d->scr_ab; a.a_frag = 1; a.bias = d->bl(sel_net, nl - 1);
-            a.P1 = d->scr_p1; a.P2 = d->scr_p2; a.R = d->scr_R; a.na = d->scr_na;
-            screen_geometry(NO, n, Hl, d->ncu, a);
-            a.ldp = screen_padded_samples(n, Hl);
-            ldp = a.ldp;
-            scr_ranges = a.ranges; scr_gpr = 2 * a.cpr;
-            const size_t lds = screen_lds_bytes(a);
-            if (!d->scr_new_kernel_ready) {
-                XQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(screen_top2_kernel<1, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-                XQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(screen_top2_kernel<2, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-                d->scr_new_kernel_ready = true;
-            }
-            // (bracketed by its own start / stop events: the live figure is the kernel's duration as rocprofv3 reports it)
-            ProfScope ps(d, "gemm_qmax_screen", 2.0 * NO * (double)n * Hl, 2.0 * ((double)NO * Hl + (double)n * Hl) + 8.0 * G * n, true);
-            if (Hl == 256) hipExtLaunchKernelGGL((screen_top2_kernel<1, 2>), dim3(a.panels * a.ranges), dim3(512), lds, d->cur, ps.start(), ps.stop(), 0, a);
-            else hipExtLaunchKernelGGL((screen_top2_kernel<2, 1>), dim3(a.panels * a.ranges), dim3(512), lds, d->cur, ps.start(), ps.stop(), 0, a);
-            XQ_HIP(hipGetLastError());
-        } else {
-            GemmArgs g; memset(&g, 0, sizeof g);
-            g.M = NO; g.N = n;
-            g.K = Hl / 2; g.lda = g.ldb = Hl / 2;
-            g.A = reinterpret_cast<const float*>(d->scr_wb);
-            g.B = reinterpret_cast<const float*>(d->scr_ab);
-            g.bias = d->bl(sel_net, nl - 1);
-            g.partial = d->scr_p1; g.partial2 = d->scr_p2;
-            g.a_vec = g.b_vec = 1; g.k_chunk = g.K;
-            g.bias_padded = ((((uintptr_t)g.bias) % 16 == 0) && (NO % 4) == 0) ? 1 : 0;
-            const int grid = std::min(total, 2 * d->ncu);
-            if (grid >= 2 && (grid & 1) == 0 && total >= 4 * grid) {
-                g.prio_split = grid / 2;
-                g.prio_tiles = (total / 2) / tiles_m * tiles_m;
-                if (g.prio_tiles <= 0 || g.prio_tiles >= total) { g.prio_split = 0; g.prio_tiles = 0; }
-            }
-            ProfScope ps(d, "gemm_qmax_screen", 2.0 * g.M * g.N * Hl, 2.0 * ((double)g.M * Hl + (double)g.N * Hl) + 8.0 * G * g.N);
-            hipLaunchKernelGGL((gemm_colmax_persistent_kernel<2, 2, DT_BF16, CM_TOP2>), dim3(grid), dim3(256), bias_lds_all, d->cur, g, tiles_m, total);
-            XQ_HIP(hipGetLastError());
-        }
-        // (the select chain of the trainer started in front of the screening pass, above.  Behind the refine kernel instead — which would
-        // then have the chip to itself, 17 instead of 27-34 us — the select chain ends after the gradients and the step waits for
-        // it: 0.197 -> 0.207 ms)
-        {
-            ProfScope ps(d, "qmax_refine", 2.0 * n * Hl * 3, 12.0 * G * n + 4.0 * n * Hl, true);      // one launch: its own start / stop events
-            const dim3 grid((n + kRefineSamples - 1) / kRefineSamples);
-            // one block per CU and K = 256: room in LDS for the staged pass of qmax_refine2_kernel (whole groups that many samples ask for)
-            const bool stage = scr_new && Hl == 256 && (int)grid.x <= d->ncu && (d->refine_stage > 0 || (d->refine_stage < 0 && d->scr_stage_whole));
-            const size_t lds = refine_cand_words((int)G) * sizeof(uint32_t) + refine_wlist_bytes((int)G) + (stage ? refine_stage_bytes() : 0);
-            auto launch = [&](auto kern) {
-                hipExtLaunchKernelGGL(kern, grid, dim3(256), lds, d->cur, ps.start(), ps.stop(), 0, d->scr_p1, d->scr_p2, G, n, ldp, touts[nl - 2], Hl,
-                                      d->wl(sel_net, nl - 1), d->bl(sel_net, nl - 1), NO, d->scr_wmax, parity, d->zmax, d->scr_stats);
-            };
-            const bool small = G <= 8 * 32;
-            if (scr_new) {
-                TdFused T; memset(&T, 0, sizeof T);
-                // the TD target / delta kernel rides in the refine blocks (fp32 net, 256-wide last hidden layer, uniform replay)
-                td_fused = d->td_tail && Hl == 256 && !per && !d->bf16_bwd();
-                if (td_fused) {
-                    const int lt = nl - 2;
-                    T.src = slots; T.action_to = action_to; T.reward = reward; T.done = done;
-                    T.a_s = outs[lt]; T.w_out = d->wl(XQ_NET_ONLINE, nl - 1); T.b_out = d->bl(XQ_NET_ONLINE, nl - 1);
-                    T.view = d->wrest(XQ_NET_ONLINE) + (d->wo[lt + 1] - d->wo[1]);
-                    T.view_ld = (mode == XQ_BACKPROP_REFERENCE) ? d->L[lt] : d->L[lt + 1];
-                    T.view_kmax = (mode == XQ_BACKPROP_REFERENCE) ? d->L[lt + 1] : NO;
-                    T.gamma = (float)d->gamma;
-                    T.dtop = d->deltas[lt]; T.dsc = d->dsc; T.act = d->act_mb; T.qsa = d->qsa; T.yv = d->yv; T.lossv = d->lossv;
-                }
-                // whole groups of qmax_refine2_kernel: 2 = the popular ones through LDS when the launch has room for it, 1 = all of them four per
-                // round trip from global memory (XQ_REFINE_WHOLE=1: A/B knob, same bits)
-                static const bool whole_staged = [] { const char* e = getenv("XQ_REFINE_WHOLE"); return !(e && e[0] == '1'); }();
-                const int whole_mode = (whole_staged && stage) ? 2 : 1;
-                auto launch2 = [&](auto kern) {
-                    static bool granted = false;          // per instantiation: the staged pass asks for ~145 KB of dynamic LDS
-                    if (!granted) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024); granted = true; }
-                    hipExtLaunchKernelGGL(kern, grid, dim3(256), lds, d->cur, ps.start(), ps.stop(), 0, d->scr_R, scr_ranges, scr_gpr, d->scr_p1, d->scr_p2, G, n,
-                                          ldp, d->scr_na, touts[nl - 2], Hl, d->wl(sel_net, nl - 1), d->bl(sel_net, nl - 1), NO, d->scr_wmax, parity, d->zmax,
-                                          d->scr_stats, T, whole_mode);
-                };
-                if (td_fused) launch2(qmax_refine2_kernel<256, true>);
-                else if (Hl == 256) launch2(qmax_refine2_kernel<256>); else launch2(qmax_refine2_kernel<512>);
-            } else
-            if (Hl == 256) { if (small) launch(qmax_refine_kernel<256, 32>); else launch(qmax_refine_kernel<256, 64>); }
-            else if (Hl == 512) { if (small) launch(qmax_refine_kernel<512, 32>); else launch(qmax_refine_kernel<512, 64>); }
-            else { if (small) launch(qmax_refine_kernel<0, 32>); else launch(qmax_refine_kernel<0, 64>); }
-            XQ_HIP(hipGetLastError());
-        }
-        d->scr_host_steps += 1; d->scr_host_samples += (unsigned long long)n;
-        if (d->scr_host_steps % kScreenCheckEvery == 0 && !d->scr_guard_pending) {
-            XQ_HIP(hipMemcpyAsync(d->scr_guard_host, d->scr_stats, (size_t)2 * d->scr_stat_blocks * sizeof(unsigned long long), hipMemcpyDeviceToHost, d->cur));
-            XQ_HIP(hipEventRecord(d->scr_guard_ev, d->cur));
-            d->scr_guard_pending = true;
-            d->scr_guard_samples = d->scr_host_samples;
-            d->scr_guard_queued_at = d->scr_host_steps;
-        }
-        zparts = 1;
-    } else {
-    long long part_ld = n;              // row stride of the partial arrays
-    int n_part = n_partial;
-    if (bf && (Hl == 256 || Hl == 512) && n >= 1024) {
-        // bf16 Q-net: the same kernel as the screening pass (xq_screen.hip.h) in its exact max / arg-max mode — here the bf16 product
-        // IS the net's output layer, not a screen: per 32-row lane group the largest value (+ its row, first maximum: Double DQN)
-        ScreenArgs a; memset(&a, 0, sizeof a);
-        a.W = d->wl_bf(sel_net, nl - 1); a.A = touts_bf[nl - 2]; a.a_frag = bf_frag ? 1 : 0; a.bias = d->bl(sel_net, nl - 1);
-        a.P1 = d->partial; a.P2 = reinterpret_cast<float*>(d->partial_idx);
-        screen_geometry(NO, n, Hl, d->ncu, a);
-        a.ldp = screen_padded_samples(n, Hl);
-        part_ld = a.ldp; n_part = 2 * a.nchunks;
-        const size_t lds = screen_lds_bytes(a);
-        hipEvent_t ev0 = nullptr, ev1 = nullptr;     // (the launch's own start / stop events when it is being timed)
-        auto launch = [&](auto kern) {
-            static bool ready = false;       // per instantiation
-            if (!ready) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); ready = true; }
-            hipExtLaunchKernelGGL(kern, dim3(a.panels * a.ranges), dim3(512), lds, d->cur, ev0, ev1, 0, a);
-        };
-        ProfScope ps(d, "gemm_qmax_rowmax", 2.0 * NO * (double)n * Hl, 2.0 * ((double)NO * Hl + (double)n * Hl) + 8.0 * n_part * n, true);
-        ev0 = ps.start(); ev1 = ps.stop();
-        if (Hl == 256) { if (dbl) launch(screen_top2_kernel<1, 2, SCR_ARG>); else launch(screen_top2_kernel<1, 2, SCR_MAX>); }
-        else { if (dbl) launch(screen_top2_kernel<2, 1, SCR_ARG>); else launch(screen_top2_kernel<2, 1, SCR_MAX>); }
-        XQ_HIP(hipGetLastError());
-    } else {
-        GemmArgs g; memset(&g, 0, sizeof g);
-        g.M = NO; g.N = n;
-        if (bf) {
-            g.K = Hl / 2; g.lda = g.ldb = Hl / 2;
-            g.A = reinterpret_cast<const float*>(d->wl_bf(sel_net, nl - 1));
-            g.B = reinterpret_cast<const float*>(touts_bf[nl - 2]);
-        } else {
-            g.K = Hl; g.lda = g.ldb = Hl;
-            g.A = d->wl(sel_net, nl - 1);
-            g.B = touts[nl - 2];
-        }
-        g.bias = d->bl(sel_net, nl - 1);
-        g.partial = d->partial;
-        g.partial_idx = dbl ? d->partial_idx : nullptr;
-        // the persistent kernel keeps the whole bias vector in LDS beside its operand tiles (2 blocks per CU must fit)
-        const size_t bias_lds = (size_t)((NO + 127) / 128) * 128 * sizeof(float);
-        if (big_tiles && (g.K % GBK) == 0 && vec_ok(g.A, g.lda) && vec_ok(g.B, g.ldb) && bias_lds <= 40 * 1024) {
-            // persistent form: 2 blocks per CU walk the tile list with the prefetch running across tile boundaries
-            const int tiles_m = (NO + 127) / 128, total = tiles_m * ((n + 127) / 128);
-            const int ncu = d->ncu;
-            g.a_vec = g.b_vec = 1; g.k_chunk = g.K;
-            g.bias_padded = ((((uintptr_t)g.bias) % 16 == 0) && (NO % 4) == 0) ? 1 : 0;     // wide bias preload
-            const int grid = std::min(total, 2 * ncu);
-            // static priority for the second half of the grid (see the kernel): each half walks its own half of the tiles
-            g.prio_split = 0; g.prio_tiles = 0;
-            if (grid >= 2 && (grid & 1) == 0 && total >= 4 * grid) {
-                g.prio_split = grid / 2;
-                g.prio_tiles = (total / 2) / tiles_m * tiles_m;
-                if (g.prio_tiles <= 0 || g.prio_tiles >= total) { g.prio_split = 0; g.prio_tiles = 0; }
-            }
-            ProfScope ps(d, "gemm_qmax_rowmax", 2.0 * g.M * g.N * Hl, (bf ? 2.0 : 4.0) * ((double)g.M * Hl + (double)g.N * Hl) + 8.0 * tiles_m * g.N);
-            if (bf && dbl) hipLaunchKernelGGL((gemm_colmax_persistent_kernel<2, 2, DT_BF16, CM_ARG>), dim3(grid), dim3(256), bias_lds, d->cur, g, tiles_m, total);
-            else if (bf) hipLaunchKernelGGL((gemm_colmax_persistent_kernel<2, 2, DT_BF16, CM_MAX>), dim3(grid), dim3(256), bias_lds, d->cur, g, tiles_m, total);
-            else if (dbl) hipLaunchKernelGGL((gemm_colmax_persistent_kernel<2, 2, DT_F32, CM_ARG>), dim3(grid), dim3(256), bias_lds, d->cur, g, tiles_m, total);
-            else hipLaunchKernelGGL((gemm_colmax_persistent_kernel<2, 2, DT_F32, CM_MAX>), dim3(grid), dim3(256), bias_lds, d->cur, g, tiles_m, total);
-            XQ_HIP(hipGetLastError());
-        } else if (bf) {
-            XQ_GEMM((launch_gemm<L_KCONTIG, L_KCONTIG, EPI_COLMAX, DT_BF16>(d, g, 1, "gemm_qmax_rowmax")));
-        } else {
-            XQ_GEMM((launch_gemm<L_KCONTIG, L_KCONTIG, EPI_COLMAX>(d, g, 1, "gemm_qmax_rowmax")));
-        }
-    }
-    if (!d->late_gate && !gate_early) XQ_HIP(hipEventRecord(d->ev_qmax, d->stream));
-    {   // the partial maxima of every sample folded into kReduceParts values (+ row indices): coalesced, block-cooperative
-        ProfScope ps(d, "colmax_reduce", (double)n * n_part, (dbl ? 8.0 : 4.0) * n * (n_part + kReduceParts));
-        hipLaunchKernelGGL(colmax_reduce_kernel, dim3((n + 63) / 64, kReduceParts), dim3(256), 0, d->cur, d->partial,
-                           dbl ? d->partial_idx : nullptr, n_part, n, part_ld, d->zmax, d->zidx);
-        XQ_HIP(hipGetLastError());
-    }
-    }   // !screened
-    // 3. Q(s, a), target, the scalar output delta and the delta of the last hidden layer (one launch, no GEMM)
-    if (!td_fused) {
-        const int lt = nl - 2;                               // last hidden layer
-        const float* view = d->wrest(XQ_NET_ONLINE) + (d->wo[lt + 1] - d->wo[1]);
-        const long long view_ld = (mode == XQ_BACKPROP_REFERENCE) ? d->L[lt] : d->L[lt + 1];
-        const int view_kmax = (mode == XQ_BACKPROP_REFERENCE) ? d->L[lt + 1] : NO;
-        ProfScope ps(d, "td_target_delta", 4.0 * n * Hl, (double)n * (Hl * 16 + n_partial * 4));
-        TdExtra X; memset(&X, 0, sizeof X);
-        X.nout = NO;
-        if (dbl) {
-            X.double_dqn = 1; X.partial_idx = d->zidx;
-            X.bout_t = d->bl(XQ_NET_TARGET, nl - 1);
-            if (bf) { X.wout_t_bf = d->wl_bf(XQ_NET_TARGET, nl - 1); X.alast_t_bf = t2outs_bf[nl - 2]; }
-            else { X.wout_t = d->wl(XQ_NET_TARGET, nl - 1); X.alast_t = t2outs[nl - 2]; }
-        }
-        if (bf) X.wout_bf = d->wl_bf(XQ_NET_ONLINE, nl - 1);
-        if (d->bf16_bwd()) X.dtop_bf = d->deltas_bf[lt];
-        if (per) {
-            X.is_w = per->is_w; X.is_wmax = per->is_wmax; X.prio = per->prio; X.pmax_live = per->pmax_live;
-            X.per_eps = per->eps; X.per_alpha = per->alpha;
-        }
-        hipLaunchKernelGGL(td_delta_kernel, dim3((n + 3) / 4), dim3(256), 0, d->cur, n, slots, action_to, reward, done,
-                           outs[nl - 2], Hl, d->wl(XQ_NET_ONLINE, nl - 1), d->bl(XQ_NET_ONLINE, nl - 1), d->zmax, zparts,
-                           (float)d->gamma, view, view_ld, view_kmax, d->deltas[lt], d->dsc, d->act_mb, d->qsa, d->yv, d->lossv, X);
-        XQ_HIP(hipGetLastError());
-    }
+    if (fork_pending) XQ_HIP(hipEventRecord(d->ev_qmax, d->stream));
+    // 2. max_a' Q(s', a'); 3. the TD delta, unless the refine kernel did it
+    bool td_fused = false;
+    if (screened) XQ_TRY(qmax_screened(d, s, scr_new, parity, &td_fused));
+    else XQ_TRY(qmax_exact(d, s, bf_frag, gate_early));
+    if (!td_fused) XQ_TRY(td_delta(d, s, screened ? 1 : kReduceParts));
     d->last_n = n;
-    // From here two chains run side by side.  Critical (handle stream): the remaining hidden deltas (GEMMs) and the
-    // layer-0 segmented sum that consumes delta_0.  Side stream: everything that only needs what td_delta_kernel wrote —
-    // the output-layer gradient, the top hidden layer's gradient GEMM — and, once the deltas exist, the lower gradient
-    // GEMMs and the bias column sums.
-    float* G = d->grads_td;
-    if (tail_eligible(d, n)) return tail_gradients(d, n, outs, G, mode);
-    XQ_HIP(hipEventRecord(d->ev_fork, d->stream));
-    XQ_HIP(hipStreamWaitEvent(d->side, d->ev_fork, 0));
-    if (nl >= 3) XQ_TRY(hidden_deltas(d, n, d->deltas[nl - 2], d->L[nl - 1], d->L[nl - 1], mode, nl - 3));
-    XQ_HIP(hipEventRecord(d->ev_delta, d->stream));
-    const size_t n0 = (size_t)d->L[0] * d->L[1];
-    if (d->comm) {
-        // data-parallel step: the gradient buffer is all-reduced in two buckets, each ON THE STREAM OF ITS PRODUCER right behind
-        // it — no communicator stream, no event of its own.  RCCL runs the collectives of one communicator in issue order, so
-        // the side bucket (hidden + output-layer weights, all biases: ready first) is issued first and the layer-0 bucket
-        // (the last thing computed, the only exposed one) second; every rank issues in this order.
-        d->cur = d->side;
-        int rc = side_gradients(d, n, outs, G);
-        d->cur = d->stream;
-        if (rc != XQ_OK) return rc;
-        XQ_TRY(comm_allreduce_on(d->comm, G + n0, d->n_grads_td - n0, d->side));
-        XQ_HIP(hipEventRecord(d->ev_join, d->side));
-        XQ_TRY(l0_gradient(d, n, G + d->g_w0));
-        XQ_TRY(comm_allreduce_on(d->comm, G, n0, d->stream));
-        XQ_HIP(hipStreamWaitEvent(d->stream, d->ev_join, 0));
-        return XQ_OK;
-    }
-    XQ_TRY(l0_gradient(d, n, G + d->g_w0));
-    d->cur = d->side;
-    const int rc = side_gradients(d, n, outs, G);
-    d->cur = d->stream;
-    if (rc != XQ_OK) return rc;
-    XQ_HIP(hipEventRecord(d->ev_join, d->side));
-    XQ_HIP(hipStreamWaitEvent(d->stream, d->ev_join, 0));
-    return XQ_OK;
+    // 4. the gradients
+    if (tail_eligible(d, n)) return tail_gradients(d, n, s.outs, d->grads_td, mode);
+    return td_gradients_fork(d, s);
 }
 
 // The late start of the select chain (beside the all-reduce instead of beside the gradient kernels) costs a step ~41 us when the

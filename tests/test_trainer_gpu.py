@@ -451,14 +451,14 @@ def test_bench_composition_against_the_oracle_directly(xq):
 
 
 def test_timing_knobs_do_not_change_a_bit(xq):
-    """INTEGRATION.md lists the environment variables the library reads as A/B knobs for TIMING (event flags, the fork as a stop event, the SGD
-    kernel's load width, the screening pass's block -> XCD map, the weight-gradient product's launch): six updates of the bench's schedule at 2048
-    games give the same weights, boards, Q(s,a) and targets, bit for bit, under each of them.  One child process per setting (read once per process)."""
+    """INTEGRATION.md lists the environment variable the library reads as an A/B knob for TIMING (the event flags): six updates of the bench's
+    schedule at 2048 games give the same weights, boards, Q(s,a) and targets, bit for bit, under each setting.  One child process per setting
+    (read once per process)."""
     import subprocess
     import sys
     probe = os.path.join(os.path.dirname(os.path.abspath(__file__)), "knob_probe.py")
     got = {}
-    for knob in ("", "XQ_EVENT_SYSFENCE=1", "XQ_FORK_STOP_EVENT=0", "XQ_SGD_SCALAR=1", "XQ_SCREEN_XCD=0", "XQ_SCREEN_XCD=1", "XQ_TAIL_GRAD_EARLY=1", "XQ_REFINE_WHOLE=1"):
+    for knob in ("", "XQ_EVENT_SYSFENCE=1"):
         env = dict(os.environ)
         if knob:
             k, v = knob.split("=")

@@ -125,7 +125,7 @@ int main(int argc, char** argv) {
         { ScreenArgs x = a; CK(hipMalloc(&x.R, (size_t)a.ranges * npad * 4)); CK(hipMalloc(&x.na, (size_t)npad * 4));
           timeit("+ per-range maxima and activation norms (what the library runs)", [&] { launch_new<1, 2, 0>(x, 0); }); }
         { ScreenArgs x = a; x.A = dA; x.a_frag = 0; timeit("row-major activations", [&] { launch_new<1, 2, 0>(x, 0); }); }
-        { ScreenArgs x = a; x.xcd_rows = 1; timeit("full kernel, XCD = row ranges", [&] { launch_new<1, 2, 0>(x, 0); }); }
+        { ScreenArgs x = a; x.xcd_rows = 0; timeit("full kernel, XCD = sample panels", [&] { launch_new<1, 2, 0>(x, 0); }); }
         timeit("TIMING ONLY: two v_mfma_f32_16x16x32_bf16 per 32x32x16 (same pipe cycles, meaningless values)", [&] { launch_new<1, 2, 16>(a, 0); });
         timeit("full kernel again", [&] { launch_new<1, 2, 0>(a, 0); });
         timeit("TIMING ONLY: 16x16x32 again", [&] { launch_new<1, 2, 16>(a, 0); });
@@ -136,7 +136,7 @@ int main(int argc, char** argv) {
         timeit("no fold, no activation loads, no DMA", [&] { launch_new<1, 2, 7>(a, 0); });
         {   // in-kernel clocks: s_memtime (shader cycles) against s_memrealtime (100 MHz), prologue and loop, median over the blocks
             unsigned long long* dbg; CK(hipMalloc(&dbg, 256 * 8 * 8)); CK(hipMemset(dbg, 0, 256 * 8 * 8));
-            for (int mode = 1; mode >= 0; --mode) {
+            for (int mode : {a.xcd_rows, 0}) {
             ScreenArgs c = a; c.dbg = dbg; c.xcd_rows = mode;
             for (int i = 0; i < 30; ++i) launch_new<1, 2, 8>(c, 0);
             CK(hipDeviceSynchronize());

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """The step and the refine kernel in the screen's WHOLE-GROUP regime (seed 4: 0.8 whole groups per sample after 2500 updates; tools/whole_seed_scan.py).
-usage: [XQ_REFINE_WHOLE=1] python tools/whole_probe.py [seed]      (1 = every whole group from global memory, four per round trip)"""
+usage: python tools/whole_probe.py [seed]"""
 import ctypes as C, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -23,8 +23,7 @@ steps(2500)
 t.dqn.kernel_filter(["qmax_refine"]); t.dqn.kernel_stats(enable=3)
 s0 = t.dqn.qmax_stats(); t0 = time.perf_counter(); steps(300); dt = time.perf_counter() - t0; s1 = t.dqn.qmax_stats()
 smp = max(s1[1] - s0[1], 1)
-mode = os.environ.get("XQ_REFINE_WHOLE", "2 (default)")
 if True:
     k = [x for x in t.dqn.kernel_stats(enable=0) if x["name"] == "qmax_refine"][0]
-    print("seed %d XQ_REFINE_WHOLE=%s: %.4f ms per step, %.2f whole groups per sample, refine kernel %.1f us" %
-          (seed, mode, 1e3 * dt / 300, (s1[3] - s0[3]) / smp, 1e3 * k["ms"] / max(k["launches"], 1)), flush=True)
+    print("seed %d: %.4f ms per step, %.2f whole groups per sample, refine kernel %.1f us" %
+          (seed, 1e3 * dt / 300, (s1[3] - s0[3]) / smp, 1e3 * k["ms"] / max(k["launches"], 1)), flush=True)
