@@ -62,7 +62,14 @@ class TrainerConfig(C.Structure):
                 ("precision", C.c_int)]
 
 
+class ArenaGame(C.Structure):
+    _fields_ = [("cause", C.c_uint8), ("winner", C.c_uint8), ("a_result", C.c_int8), ("a_is_red", C.c_uint8),
+                ("plies", C.c_uint16), ("red_score", C.c_int16), ("black_score", C.c_int16), ("reserved", C.c_uint16)]
+
+
 assert C.sizeof(StepResult) == 24 and C.sizeof(EpisodeRecord) == 16
+assert C.sizeof(ArenaGame) == 12
+ARENA_LIVE, ARENA_GENERAL_CAPTURED, ARENA_NO_LEGAL_MOVE, ARENA_MOVE_CAP, ARENA_OPENING = 0, 1, 2, 3, 4
 
 _vp, _i, _u32, _u64, _d = C.c_void_p, C.c_int, C.c_uint32, C.c_uint64, C.c_double
 _pi, _pd, _pf = C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_float)
@@ -180,6 +187,15 @@ PROTOTYPES = {
     "xq_trainer_learn_apply": [_vp, _i],
     "xq_trainer_step": [_vp, _i],
     "xq_trainer_counters": [_vp, _pu64, _pu64, _pu64],
+    "xq_arena_create": [_i, _u64, _u32, _vp, _pvp],
+    "xq_arena_destroy": [_vp],
+    "xq_arena_reset": [_vp, _i],
+    "xq_arena_ply_q_dev": [_vp, _vp, _i, _d, _d],
+    "xq_arena_run": [_vp, _vp, _vp, _d, _d, _i, _pi],
+    "xq_arena_results": [_vp, C.POINTER(ArenaGame)],
+    "xq_arena_live": [_vp, _pi],
+    "xq_arena_env": [_vp, _pvp],
+    "xq_arena_last_step": [_vp, C.POINTER(StepResult)],
 }
 _RESTYPES = {"xq_last_error": C.c_char_p, "xq_env_boards_dev": C.c_void_p, "xq_env_meta_dev": C.c_void_p}
 

@@ -187,6 +187,7 @@ Profiler* dqn_profiler(xq_dqn* d) { return &d->prof; }
 int dqn_fused_apply(const xq_dqn* d) { return d->fused_apply ? 1 : 0; }
 xq_comm* dqn_comm(const xq_dqn* d) { return d->comm; }
 hipStream_t dqn_stream(xq_dqn* d) { return d->stream; }
+void dqn_shape(const xq_dqn* d, int* n_in, int* n_out) { *n_in = d->L[0]; *n_out = d->nout(); }
 hipEvent_t dqn_qmax_event(xq_dqn* d) { return d->ev_qmax; }
 uint64_t dqn_params_version(const xq_dqn* d) { return d->params_version; }
 

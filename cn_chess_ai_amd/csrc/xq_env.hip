@@ -13,7 +13,7 @@
 
 namespace xq {
 
-enum { MODE_LEGAL = 0, MODE_STEP = 1, MODE_SELFPLAY = 2 };
+enum { MODE_LEGAL = 0, MODE_STEP = 1, MODE_SELFPLAY = 2, MODE_ARENA = 3 };
 
 struct EnvParams {
     uint32_t* boards;
@@ -42,6 +42,13 @@ struct EnvParams {
     xq_episode_record* ep_ring;
     int ep_cap;
     unsigned long long* ep_head;
+    // MODE_ARENA (xq_arena.hip, DESIGN.md §4 "Arena"): games [0, pairs) have player A as Red, [pairs, 2 pairs) as Black.  Per half of the
+    // games (h = g >= pairs): the epsilon threshold and whether q90 holds that half's Q rows (0: uniform-random player)
+    int arena_pairs, arena_opening;
+    uint32_t arena_eps[2];
+    int arena_has_q[2];
+    xq_arena_game* arena_rec;
+    int* arena_live;
 };
 
 __constant__ uint32_t c_start_words[kBoardWords];
@@ -53,7 +60,8 @@ __constant__ uint32_t c_start_words[kBoardWords];
 // (chessboard.cpp:286-320) need no scan of the 90 squares: score(mover) = own score - other score, a general dies only by capture,
 // and the first general in index order is Red's while it lives.
 enum : uint32_t { META_TRACKED = 1u << 17, META_RED_GENERAL = 1u << 18, META_BLACK_GENERAL = 1u << 19,
-                  META_START = META_TRACKED | META_RED_GENERAL | META_BLACK_GENERAL };
+                  META_START = META_TRACKED | META_RED_GENERAL | META_BLACK_GENERAL,
+                  META_FROZEN = 1u << 20 };     // MODE_ARENA: the game has ended and is never stepped again
 constexpr int kSideMaterial = 1000 + 2 * 20 + 2 * 20 + 2 * 40 + 2 * 90 + 2 * 45 + 5 * 10;      // 1480, chessboard.h:23-31
 
 template <int MODE>
@@ -98,6 +106,18 @@ __global__ __launch_bounds__(256) void env_kernel(EnvParams P) {
     }
     m.x = __builtin_amdgcn_readfirstlane(m.x); m.y = __builtin_amdgcn_readfirstlane(m.y);
     m.z = __builtin_amdgcn_readfirstlane(m.z); m.w = __builtin_amdgcn_readfirstlane(m.w);
+    // arena: a finished game is frozen — its wave stops here, before the Q row is even requested; the half the game lies in picks the
+    // player (and so the epsilon and whether there is a Q row at all); the opening plies are uniform-random on the PAIR's stream
+    const int arena_half = MODE == MODE_ARENA && g >= P.arena_pairs ? 1 : 0;
+    const bool arena_opening = MODE == MODE_ARENA && (int)m.z < P.arena_opening;
+    if (MODE == MODE_ARENA) {
+        if (!active || (m.x & META_FROZEN)) return;
+        if (!arena_opening && P.arena_has_q[arena_half]) {
+            const float* qrow = P.q90 + (size_t)g * P.q_stride;
+            qpre[0][0] = qrow[lane];
+            qpre[1][0] = qrow[64 + (lane < 26 ? lane : 0)];
+        }
+    }
     unpack_to_slab(word, S.sq);
     wave_sync();
 
@@ -125,13 +145,16 @@ __global__ __launch_bounds__(256) void env_kernel(EnvParams P) {
     bool have_action = false, valid = false, explored = false;
     const int mover = player;
 
-    if (MODE == MODE_SELFPLAY) {
+    if (MODE == MODE_SELFPLAY || MODE == MODE_ARENA) {
         n_moves = gen_all_actions(S, player);                       // chessai.cpp:98
         wave_sync();
         if (n_moves > 0) {
-            const Philox4 r = philox4x32_10(plies, 0u, P.first_game_id + (uint32_t)g, 0u, P.seed_lo, P.seed_hi);
-            const bool have_q = P.q90 != nullptr || P.q_slabs != nullptr;
-            explored = !have_q || (r.v[0] < P.eps_u32);             // dqn.cpp:30-31
+            const uint32_t stream_id = arena_opening ? (uint32_t)(g - arena_half * P.arena_pairs) : (uint32_t)g;   // twins share the opening
+            const Philox4 r = philox4x32_10(plies, 0u, P.first_game_id + stream_id, 0u, P.seed_lo, P.seed_hi);
+            const bool have_q = MODE == MODE_ARENA ? (!arena_opening && P.arena_has_q[arena_half] != 0)
+                                                   : (P.q90 != nullptr || P.q_slabs != nullptr);
+            const uint32_t eps_u32 = MODE == MODE_ARENA ? P.arena_eps[arena_half] : P.eps_u32;
+            explored = !have_q || (r.v[0] < eps_u32);               // dqn.cpp:30-31
             int idx;
             if (explored) {
                 idx = (int)(r.v[1] % (uint32_t)n_moves);            // dqn.cpp:33
@@ -249,13 +272,13 @@ __global__ __launch_bounds__(256) void env_kernel(EnvParams P) {
         winner_now = st.first_general_color;
     }
     const bool over = move_count >= 200 || !red_general || !black_general;         // chessboard.cpp:286-309
-    const bool no_action = (MODE == MODE_SELFPLAY) && !have_action;                 // chessai.cpp:100-103
+    const bool no_action = (MODE == MODE_SELFPLAY || MODE == MODE_ARENA) && !have_action;     // chessai.cpp:100-103
     const bool done = over || no_action || (move_count + 1 >= 200);
     const bool terminated = over || no_action;
     // the episode ENDS on the ply that made it terminal; a rejected move on an already finished board (the facade's
     // checkGameOver() probe, a retried step) reports `terminated` but changes nothing: no stats, no episode record, no reset
-    const bool ended_now = terminated && (MODE == MODE_SELFPLAY || valid);
-    const bool do_reset = ended_now && (MODE == MODE_SELFPLAY || P.auto_reset != 0);
+    const bool ended_now = terminated && (MODE == MODE_SELFPLAY || MODE == MODE_ARENA || valid);
+    const bool do_reset = MODE != MODE_ARENA && ended_now && (MODE == MODE_SELFPLAY || P.auto_reset != 0);
     const int winner = terminated ? winner_now : C_NONE;
 
     const uint32_t next_word = pack_from_slab(S.sq);               // s' = board after the move, before any reset
@@ -296,7 +319,7 @@ __global__ __launch_bounds__(256) void env_kernel(EnvParams P) {
     }
 
     const bool policy_q = P.q90 != nullptr || P.q_slabs != nullptr;
-    if ((captured != 0 || ended_now || (explored && policy_q)) && lane == 0) {
+    if (MODE != MODE_ARENA && (captured != 0 || ended_now || (explored && policy_q)) && lane == 0) {
         uint4 s = P.stats[g];
         if (ended_now && winner == C_RED) s.x += 1;
         if (ended_now && winner == C_BLACK) s.y += 1;
@@ -317,6 +340,27 @@ __global__ __launch_bounds__(256) void env_kernel(EnvParams P) {
         e.winner = (uint8_t)winner;
         e.reserved = no_action ? 1 : 0;
         P.ep_ring[h % (unsigned long long)P.ep_cap] = e;
+    }
+    if (MODE == MODE_ARENA && ended_now) {                          // the game's record; the board stays as the last ply left it
+        if (lane == 0) {
+            const int a_side = arena_half == 0 ? C_RED : C_BLACK;
+            xq_arena_game rec;
+            int res;
+            if (!red_general || !black_general) { rec.cause = XQ_ARENA_GENERAL_CAPTURED; res = winner_now == a_side ? 1 : -1; }   // the captor wins
+            else if (no_action) { rec.cause = XQ_ARENA_NO_LEGAL_MOVE; res = mover == a_side ? -1 : 1; }   // the side to move loses
+            else { rec.cause = XQ_ARENA_MOVE_CAP; res = 0; }                                                // the 200-ply cap: a draw
+            if (arena_opening) { rec.cause = XQ_ARENA_OPENING; res = 0; }                                   // reported, never scored
+            rec.winner = (uint8_t)winner;
+            rec.a_result = (int8_t)res;
+            rec.a_is_red = arena_half == 0 ? 1 : 0;
+            rec.plies = (uint16_t)move_count;
+            rec.red_score = (int16_t)red;
+            rec.black_score = (int16_t)black;
+            rec.reserved = 0;
+            P.arena_rec[g] = rec;
+            atomicSub(P.arena_live, 1);
+        }
+        flags |= META_FROZEN;
     }
     if (do_reset) {                                                 // board->reset(), chessai.cpp:90
         out_word = lane < kBoardWords ? c_start_words[lane] : 0u;
@@ -442,6 +486,24 @@ int env_selfplay_launch(xq_env* e, const float* q90_dev, int q_stride, uint32_t 
         replay->size = std::min(replay->dev.capacity, replay->size + e->n);
         replay->total += (uint64_t)e->n;
     }
+    return XQ_OK;
+}
+
+// One arena ply (xq_arena.hip): q90_dev = [n][q_stride] rows of the halves whose has_q is set; nothing else of the env is touched
+int env_arena_launch(xq_env* e, const float* q90_dev, int q_stride, int pairs, int opening, const uint32_t eps_u32[2], const int has_q[2],
+                     xq_arena_game* records_dev, int* live_dev, xq_step_result* results_dev) {
+    EnvParams P = base_params(e);
+    P.ep_ring = nullptr;                  // no episode records, no stats, no replay: an arena game ends once and stays as it ended
+    P.q90 = q90_dev;
+    P.q_stride = q_stride;
+    P.results = results_dev;
+    P.arena_pairs = pairs;
+    P.arena_opening = opening;
+    for (int h = 0; h < 2; ++h) { P.arena_eps[h] = eps_u32[h]; P.arena_has_q[h] = has_q[h] && q90_dev != nullptr; }
+    P.arena_rec = records_dev;
+    P.arena_live = live_dev;
+    hipLaunchKernelGGL(env_kernel<MODE_ARENA>, dim3((e->n + 3) / 4), dim3(256), 0, e->stream, P);
+    XQ_HIP(hipGetLastError());
     return XQ_OK;
 }
 

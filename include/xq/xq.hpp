@@ -9,7 +9,9 @@
 // this header only marshals arguments (and keeps a host copy of the 90 board bytes for getPieceAt()).
 #pragma once
 
+#include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <ctime>
@@ -351,6 +353,81 @@ private:
     int rank_, world_;
 };
 
+// ---- Arena (build's own, DESIGN.md §4 "Arena"): A against B over `pairs` pairs of games on the GPU ----------------------------------------
+struct ArenaSummary {
+    int games = 0, pairs = 0, wins = 0, draws = 0, losses = 0, scoredGames = 0, scoredPairs = 0;
+    int causes[5] = {0, 0, 0, 0, 0};                    // by XQ_ARENA_* cause
+    double score = 0, ciLow = 0, ciHigh = 0, elo = 0;   // s = (W + D/2) / N; 95 % interval from the pair scores; -400 log10(1/s - 1)
+};
+// The summary of cn_chess_ai_amd/arena.py summarize(), from the records: games that ended inside the opening (and live ones) are not
+// scored; the interval uses the variance of the pair scores (twins are correlated); the Elo is clamped at s = 0 and 1.
+inline ArenaSummary summarizeArena(const std::vector<xq_arena_game>& r, int pairs) {
+    ArenaSummary s;
+    s.games = (int)r.size(); s.pairs = pairs;
+    auto scored = [&](size_t g) { return r[g].cause != XQ_ARENA_LIVE && r[g].cause != XQ_ARENA_OPENING; };
+    for (size_t g = 0; g < r.size(); ++g) {
+        if (r[g].cause < 5) s.causes[r[g].cause] += 1;
+        if (!scored(g)) continue;
+        if (r[g].a_result > 0) s.wins += 1; else if (r[g].a_result < 0) s.losses += 1; else s.draws += 1;
+    }
+    const int n = s.wins + s.draws + s.losses;
+    s.scoredGames = n;
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    if (n == 0) { s.score = s.ciLow = s.ciHigh = s.elo = nan; return s; }
+    s.score = (s.wins + 0.5 * s.draws) / n;
+    std::vector<double> ps;
+    for (int p = 0; p < pairs; ++p)
+        if (scored((size_t)p) && scored((size_t)(p + pairs)))
+            ps.push_back(((r[(size_t)p].a_result + 1) / 2.0 + (r[(size_t)(p + pairs)].a_result + 1) / 2.0) / 2.0);
+    s.scoredPairs = (int)ps.size();
+    double half = std::numeric_limits<double>::infinity();
+    if (ps.size() > 1) {
+        double mean = 0, var = 0;
+        for (double v : ps) mean += v;
+        mean /= (double)ps.size();
+        for (double v : ps) var += (v - mean) * (v - mean);
+        var /= (double)(ps.size() - 1);
+        half = 1.96 * std::sqrt(var / (double)ps.size());
+    }
+    s.ciLow = std::max(0.0, s.score - half);
+    s.ciHigh = std::min(1.0, s.score + half);
+    const double sc = std::min(std::max(s.score, 0.5 / n), 1.0 - 0.5 / n);
+    s.elo = -400.0 * std::log10(1.0 / sc - 1.0);
+    return s;
+}
+
+class Arena {
+public:
+    explicit Arena(int pairs, uint64_t seed = 1, uint32_t firstGameId = 0, int openingPlies = 8) : pairs_(pairs) {
+        check(xq_arena_create(pairs, seed, firstGameId, nullptr, &h_));
+        reset(openingPlies);
+    }
+    ~Arena() { xq_arena_destroy(h_); }
+    Arena(const Arena&) = delete;
+    Arena& operator=(const Arena&) = delete;
+
+    void reset(int openingPlies = 8) { check(xq_arena_reset(h_, openingPlies)); }
+    // a / b: borrowed networks (nullptr = uniform-random play); plays every game to its end.  Returns the plies played.
+    int run(const DQN* a, const DQN* b, double epsA = 0.0, double epsB = 0.0, int maxPlies = 0) {
+        int n = 0;
+        check(xq_arena_run(h_, a ? a->handle() : nullptr, b ? b->handle() : nullptr, epsA, epsB, maxPlies, &n));
+        return n;
+    }
+    std::vector<xq_arena_game> results() {
+        std::vector<xq_arena_game> r((size_t)2 * pairs_);
+        check(xq_arena_results(h_, r.data()));
+        return r;
+    }
+    int live() { int n = 0; check(xq_arena_live(h_, &n)); return n; }
+    ArenaSummary summary() { return summarizeArena(results(), pairs_); }
+    int pairs() const { return pairs_; }
+    xq_arena* handle() const { return h_; }
+
+private:
+    xq_arena* h_ = nullptr;
+    int pairs_ = 0;
+};
+
 // ---- ChessAI, chessai.h:17-56 ---------------------------------------------------------------------------------------
 class ChessAI {
 public:
@@ -375,6 +452,21 @@ public:
     }
     void loadModel(const std::string& filename) {
         if (dqn) dqn->loadModel(filename); else std::fprintf(stderr, "DQN is not initialized. Cannot load model.\n");
+    }
+
+    // Playing strength (build's own): this AI's network as player A against the model in opponentModelFile (same topology; "random" =
+    // uniform-random play) over `pairs` pairs of games on the GPU, greedy unless epsilons are given.  Returns A's summary.
+    ArenaSummary evaluateAgainst(const std::string& opponentModelFile, int pairs, uint64_t seed = 1, int openingPlies = 8,
+                                 double epsSelf = 0.0, double epsOpponent = 0.0) {
+        if (!dqn) throw std::invalid_argument("DQN is not initialized. Cannot evaluate.");
+        std::unique_ptr<DQN> opponent;
+        if (opponentModelFile != "random") {
+            opponent = std::make_unique<DQN>(dqn->layerSizes(), 0.001, 0.99, 1);
+            opponent->loadModel(opponentModelFile);
+        }
+        Arena arena(pairs, seed, 0, openingPlies);
+        arena.run(dqn.get(), opponent.get(), epsSelf, epsOpponent);
+        return arena.summary();
     }
 
     // chessai.cpp:29-83 — epsilon stays 0.1 at play time; 10 re-validated attempts, then a random valid action

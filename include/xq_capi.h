@@ -444,6 +444,57 @@ int xq_dqn_exchange_calibration(const xq_dqn* d, int* calibrated, double* allred
 int xq_allreduce_grads(xq_dqn* d, xq_comm* comm);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * xq_arena — playing strength: player A against player B over n_pairs PAIRS of games, all 2 n_pairs games at once
+ * (no upstream analogue beyond ChessAI::getAIMove, chessai.cpp:29-83, one game and one net at a time; DESIGN.md §4 "Arena").
+ *   seats    : games [0, n_pairs) have A as Red, games [n_pairs, 2 n_pairs) have A as Black; game g and g + n_pairs are twins;
+ *   opening  : the first opening_plies plies are uniform-random on the PAIR's Philox stream (ctr = {ply, 0, first_game_id + g mod
+ *              n_pairs, 0}), so twins play the same opening with the seats swapped; then game g draws on its own id first_game_id + g;
+ *   moves    : each player moves like xq_env_selfplay_step (epsilon-greedy over q[action.to] of the legal list, first maximum wins,
+ *              same Philox draws) with an epsilon of its own; a NULL player always takes the uniform-random branch;
+ *   end      : a game stops on the ply that ends it (a general captured, no legal action for the side to move, the 200-move cap,
+ *              chessboard.cpp:286-309) and stays frozen — no reset, no replay write — with its record written on that ply.
+ * A player handle is borrowed: the arena runs its forwards through xq_dqn_forward_boards_dev on the handle's stream (no kept
+ * layer-0 sums, no TD-step state, no kernel statistics), so a training run that lends its network gets the same bits afterwards.
+ * ---------------------------------------------------------------------------------------------------------- */
+typedef struct xq_arena xq_arena;
+enum {
+    XQ_ARENA_LIVE = 0,              /* still playing */
+    XQ_ARENA_GENERAL_CAPTURED = 1,  /* the side that captured the general wins */
+    XQ_ARENA_NO_LEGAL_MOVE = 2,     /* build-defined: the side to move with no legal action loses (upstream just ends the episode) */
+    XQ_ARENA_MOVE_CAP = 3,          /* the 200-move cap: a draw here (getWinner() says Red, which would reward the Red seat) */
+    XQ_ARENA_OPENING = 4            /* ended inside the random opening: reported, never scored (its twin ended the same way) */
+};
+typedef struct {
+    uint8_t cause;                  /* XQ_ARENA_* */
+    uint8_t winner;                 /* getWinner() on the final board (chessboard.cpp:312-320), 2 while live */
+    int8_t a_result;                /* +1 A won, 0 draw / opening / live, -1 A lost */
+    uint8_t a_is_red;
+    uint16_t plies;                 /* getMoveCount() of the final board */
+    int16_t red_score, black_score; /* getRedScore() / getBlackScore() of the final board */
+    uint16_t reserved;
+} xq_arena_game;
+/* n_pairs > 0 pairs (2 n_pairs games, one xq_env of its own on hip_stream, NULL = its own stream); seed and first_game_id key the
+ * Philox streams as for xq_env_create.  The arena starts reset with the default opening of 8 plies. */
+int xq_arena_create(int n_pairs, uint64_t seed, uint32_t first_game_id, void* hip_stream, xq_arena** out);
+int xq_arena_destroy(xq_arena* a);
+/* Every game back to the start position, every record live, 0 <= opening_plies <= 200 random plies to come. */
+int xq_arena_reset(xq_arena* a, int opening_plies);
+/* One ply with caller-supplied Q rows: q_dev = [2 n_pairs] rows of q_stride >= 90 floats (tanh Q of outputs 0..89) on the arena's
+ * device, ordered behind the arena's stream by the caller (NULL = both players random); eps_a / eps_b in [0, 1] are the players'
+ * epsilons.  A's rows are read from the half where A is to move.  INVALID_ARGUMENT once no game is live. */
+int xq_arena_ply_q_dev(xq_arena* a, const float* q_dev, int q_stride, double eps_a, double eps_b);
+/* Plays until no game is live or max_plies plies (<= 0: no limit) have been played by this call; *plies_played (optional) = how many.
+ * dqn_a / dqn_b: a network with layer_sizes[0] == 1260 and >= 90 outputs, or NULL for uniform-random play; dqn_a == dqn_b is allowed,
+ * and so are handles on different streams (ordered by events).  eps_a, eps_b in [0, 1]. */
+int xq_arena_run(xq_arena* a, xq_dqn* dqn_a, xq_dqn* dqn_b, double eps_a, double eps_b, int max_plies, int* plies_played);
+/* [2 n_pairs] records (live games report their current plies and scores). */
+int xq_arena_results(xq_arena* a, xq_arena_game* records_host);
+int xq_arena_live(xq_arena* a, int* n_live);
+int xq_arena_env(xq_arena* a, xq_env** env);                 /* the arena's games (get_state etc.); owned by the arena */
+/* The per-game xq_step_result of the last ply (a move trace for tests); defined for the games that were live before that ply. */
+int xq_arena_last_step(xq_arena* a, xq_step_result* results_host);
+
+/* ------------------------------------------------------------------------------------------------------------
  * xq_trainer — the ChessAI::train() loop (chessai.cpp:85-170) for n_games boards at once, on device.
  *   collect : Q(s)[0..89] for every game -> xq_env_selfplay_step -> transitions into the replay ring
  *   learn   : sample minibatch -> xq_dqn_td_grads  [caller may all-reduce xq_dqn_grad_buffer] -> apply
