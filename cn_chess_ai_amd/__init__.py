@@ -7,7 +7,7 @@ from . import _capi
 from ._capi import XqError
 from .vecenv import VecEnv, ReplayBuffer, StepResult, START_BOARD, eps_to_u32
 from .dqn import DQN, Trainer, TrainerConfig
-from .arena import Arena
+from .arena import Arena, Search
 
-__all__ = ["VecEnv", "ReplayBuffer", "DQN", "Trainer", "TrainerConfig", "Arena", "XqError", "StepResult", "START_BOARD",
+__all__ = ["VecEnv", "ReplayBuffer", "DQN", "Trainer", "TrainerConfig", "Arena", "Search", "XqError", "StepResult", "START_BOARD",
            "eps_to_u32"]

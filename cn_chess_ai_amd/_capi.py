@@ -70,6 +70,12 @@ class ArenaGame(C.Structure):
 assert C.sizeof(StepResult) == 24 and C.sizeof(EpisodeRecord) == 16
 assert C.sizeof(ArenaGame) == 12
 ARENA_LIVE, ARENA_GENERAL_CAPTURED, ARENA_NO_LEGAL_MOVE, ARENA_MOVE_CAP, ARENA_OPENING = 0, 1, 2, 3, 4
+PLAYER_RANDOM, PLAYER_NET, PLAYER_SEARCH = 0, 1, 2
+SEARCH_MATE = 1000000
+
+
+class ArenaPlayer(C.Structure):
+    _fields_ = [("kind", C.c_int), ("dqn", C.c_void_p), ("depth", C.c_int), ("eps", C.c_double)]
 
 _vp, _i, _u32, _u64, _d = C.c_void_p, C.c_int, C.c_uint32, C.c_uint64, C.c_double
 _pi, _pd, _pf = C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_float)
@@ -107,6 +113,8 @@ PROTOTYPES = {
     "xq_env_get_state": [_vp, _i, _i, _pu8, _pi],
     "xq_env_legal_moves": [_vp, _i, _pu16, _pi],
     "xq_env_legal_moves_dev": [_vp, _i, _vp, _vp],
+    "xq_env_search": [_vp, _i, _pi, _pi, _pi],
+    "xq_env_search_dev": [_vp, _i, _vp, _vp, _vp],
     "xq_env_valid_matrix": [_vp, _i, _pu8],
     "xq_env_get_winner": [_vp, _i, _i, _pu8],
     "xq_env_rule_matrix": [_vp, _i, _pu8],
@@ -192,6 +200,7 @@ PROTOTYPES = {
     "xq_arena_reset": [_vp, _i],
     "xq_arena_ply_q_dev": [_vp, _vp, _i, _d, _d],
     "xq_arena_run": [_vp, _vp, _vp, _d, _d, _i, _pi],
+    "xq_arena_run_players": [_vp, C.POINTER(ArenaPlayer), C.POINTER(ArenaPlayer), _i, _pi],
     "xq_arena_results": [_vp, C.POINTER(ArenaGame)],
     "xq_arena_live": [_vp, _pi],
     "xq_arena_env": [_vp, _pvp],

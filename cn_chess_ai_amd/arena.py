@@ -1,8 +1,8 @@
 """Arena — player A against player B over P pairs of games, all 2P games at once on the GPU (include/xq_capi.h, xq_arena).
 
 Games [0, P) have A as Red, games [P, 2P) have A as Black; twins g and g + P play the same random opening with the seats
-swapped (DESIGN.md §4 "Arena").  A player is a DQN or None (uniform-random play).  The summary is computed here, on the host,
-from the per-game records.
+swapped (DESIGN.md §4 "Arena").  A player is a DQN, a Search (the fixed material search of DESIGN.md §4 "Search player") or None
+(uniform-random play).  The summary is computed here, on the host, from the per-game records.
 """
 import ctypes as C
 import math
@@ -44,6 +44,28 @@ def summarize(records, n_pairs):
     return out
 
 
+class Search:
+    """The material search player: a full-width negamax of `depth` (1, 2 or 3) plies, exploring with probability eps."""
+
+    def __init__(self, depth, eps=0.0):
+        if int(depth) != depth or not 1 <= depth <= 3:
+            raise ValueError(f"Search depth must be 1, 2 or 3 (got {depth!r})")
+        if not 0.0 <= float(eps) <= 1.0:
+            raise ValueError(f"Search eps must be in [0, 1] (got {eps!r})")
+        self.depth, self.eps = int(depth), float(eps)
+
+    def __repr__(self):
+        return f"Search({self.depth}, eps={self.eps})"
+
+
+def _player(p, eps):
+    if p is None:
+        return _capi.ArenaPlayer(_capi.PLAYER_RANDOM, None, 0, 0.0)
+    if isinstance(p, Search):
+        return _capi.ArenaPlayer(_capi.PLAYER_SEARCH, None, p.depth, p.eps)
+    return _capi.ArenaPlayer(_capi.PLAYER_NET, p.handle, 0, float(eps))
+
+
 class Arena:
     def __init__(self, n_pairs, seed=0x5EED, first_game_id=0, stream=None, opening_plies=8):
         self.n_pairs = int(n_pairs)
@@ -81,8 +103,13 @@ class Arena:
         call("xq_arena_ply_q_dev", self._h, q_dev, int(q_stride), float(eps_a), float(eps_b))
 
     def run(self, dqn_a, dqn_b, eps_a=0.0, eps_b=0.0, max_plies=0):
-        """Plays until every game has ended (or max_plies plies); dqn_* = DQN or None (uniform random).  -> plies played."""
+        """Plays until every game has ended (or max_plies plies); dqn_* = DQN, Search or None (uniform random).  eps_a / eps_b are
+        the networks' exploration (a Search carries its own).  -> plies played."""
         n = C.c_int32()
+        if isinstance(dqn_a, Search) or isinstance(dqn_b, Search):
+            pa, pb = _player(dqn_a, eps_a), _player(dqn_b, eps_b)
+            call("xq_arena_run_players", self._h, C.byref(pa), C.byref(pb), int(max_plies), C.byref(n))
+            return n.value
         call("xq_arena_run", self._h, dqn_a.handle if dqn_a is not None else None,
              dqn_b.handle if dqn_b is not None else None, float(eps_a), float(eps_b), int(max_plies), C.byref(n))
         return n.value

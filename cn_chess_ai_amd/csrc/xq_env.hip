@@ -49,6 +49,10 @@ struct EnvParams {
     int arena_has_q[2];
     xq_arena_game* arena_rec;
     int* arena_live;
+    // ... or, where arena_pick_on[h] is set, the half's greedy move is arena_pick[g], an index into the generated list (the search
+    // player, xq_search.hip); the epsilon draw stays the kernel's own
+    const int16_t* arena_pick;
+    int arena_pick_on[2];
 };
 
 __constant__ uint32_t c_start_words[kBoardWords];
@@ -61,7 +65,7 @@ __constant__ uint32_t c_start_words[kBoardWords];
 // and the first general in index order is Red's while it lives.
 enum : uint32_t { META_TRACKED = 1u << 17, META_RED_GENERAL = 1u << 18, META_BLACK_GENERAL = 1u << 19,
                   META_START = META_TRACKED | META_RED_GENERAL | META_BLACK_GENERAL,
-                  META_FROZEN = 1u << 20 };     // MODE_ARENA: the game has ended and is never stepped again
+                  META_FROZEN = kMetaFrozen };     // MODE_ARENA: the game has ended and is never stepped again
 constexpr int kSideMaterial = 1000 + 2 * 20 + 2 * 20 + 2 * 40 + 2 * 90 + 2 * 45 + 5 * 10;      // 1480, chessboard.h:23-31
 
 template <int MODE>
@@ -151,13 +155,16 @@ __global__ __launch_bounds__(256) void env_kernel(EnvParams P) {
         if (n_moves > 0) {
             const uint32_t stream_id = arena_opening ? (uint32_t)(g - arena_half * P.arena_pairs) : (uint32_t)g;   // twins share the opening
             const Philox4 r = philox4x32_10(plies, 0u, P.first_game_id + stream_id, 0u, P.seed_lo, P.seed_hi);
-            const bool have_q = MODE == MODE_ARENA ? (!arena_opening && P.arena_has_q[arena_half] != 0)
+            const bool have_q = MODE == MODE_ARENA ? (!arena_opening && (P.arena_has_q[arena_half] != 0 || P.arena_pick_on[arena_half] != 0))
                                                    : (P.q90 != nullptr || P.q_slabs != nullptr);
             const uint32_t eps_u32 = MODE == MODE_ARENA ? P.arena_eps[arena_half] : P.eps_u32;
             explored = !have_q || (r.v[0] < eps_u32);               // dqn.cpp:30-31
             int idx;
             if (explored) {
                 idx = (int)(r.v[1] % (uint32_t)n_moves);            // dqn.cpp:33
+            } else if (MODE == MODE_ARENA && P.arena_pick_on[arena_half]) {
+                const int p = P.arena_pick[g];
+                idx = (unsigned)p < (unsigned)n_moves ? p : 0;
             } else {
                 if (q_from_slabs) {
                     auto q_pre = [&](int e) {                                        // q_head_finish_kernel's association, on the
@@ -489,9 +496,10 @@ int env_selfplay_launch(xq_env* e, const float* q90_dev, int q_stride, uint32_t 
     return XQ_OK;
 }
 
-// One arena ply (xq_arena.hip): q90_dev = [n][q_stride] rows of the halves whose has_q is set; nothing else of the env is touched
+// One arena ply (xq_arena.hip): q90_dev = [n][q_stride] rows of the halves whose has_q is set, pick_dev = [n] move indices of the halves
+// whose pick_on is set; nothing else of the env is touched
 int env_arena_launch(xq_env* e, const float* q90_dev, int q_stride, int pairs, int opening, const uint32_t eps_u32[2], const int has_q[2],
-                     xq_arena_game* records_dev, int* live_dev, xq_step_result* results_dev) {
+                     xq_arena_game* records_dev, int* live_dev, xq_step_result* results_dev, const int16_t* pick_dev, const int pick_on[2]) {
     EnvParams P = base_params(e);
     P.ep_ring = nullptr;                  // no episode records, no stats, no replay: an arena game ends once and stays as it ended
     P.q90 = q90_dev;
@@ -499,7 +507,12 @@ int env_arena_launch(xq_env* e, const float* q90_dev, int q_stride, int pairs, i
     P.results = results_dev;
     P.arena_pairs = pairs;
     P.arena_opening = opening;
-    for (int h = 0; h < 2; ++h) { P.arena_eps[h] = eps_u32[h]; P.arena_has_q[h] = has_q[h] && q90_dev != nullptr; }
+    for (int h = 0; h < 2; ++h) {
+        P.arena_eps[h] = eps_u32[h];
+        P.arena_pick_on[h] = pick_on[h] && pick_dev != nullptr;
+        P.arena_has_q[h] = has_q[h] && q90_dev != nullptr && !P.arena_pick_on[h];
+    }
+    P.arena_pick = pick_dev;
     P.arena_rec = records_dev;
     P.arena_live = live_dev;
     hipLaunchKernelGGL(env_kernel<MODE_ARENA>, dim3((e->n + 3) / 4), dim3(256), 0, e->stream, P);

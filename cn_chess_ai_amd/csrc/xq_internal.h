@@ -253,7 +253,10 @@ int env_selfplay_launch(xq_env* env, const float* q90_dev, int q_stride, uint32_
                         xq_replay* replay, hipStream_t on = nullptr, const QSource* qs = nullptr, hipEvent_t ev_start = nullptr,
                         hipEvent_t ev_stop = nullptr);      // ev_*: the kernel's own start / stop events (profiler, kernel-exact timing)
 int env_arena_launch(xq_env* env, const float* q90_dev, int q_stride, int pairs, int opening, const uint32_t eps_u32[2],
-                     const int has_q[2], xq_arena_game* records_dev, int* live_dev, xq_step_result* results_dev);   // xq_arena.hip
+                     const int has_q[2], xq_arena_game* records_dev, int* live_dev, xq_step_result* results_dev,
+                     const int16_t* pick_dev, const int pick_on[2]);   // xq_arena.hip
 void dqn_shape(const xq_dqn* d, int* n_in, int* n_out);    // layer_sizes[0], outputs
+int search_pick_launch(xq_env* env, int depth, int first, int count, int pairs, uint32_t eps_u32, int16_t* pick_dev);   // xq_search.hip
+constexpr uint32_t kMetaFrozen = 1u << 20;                  // meta.x flag of a finished arena game (xq_env.hip META_FROZEN)
 inline int round_up(int a, int b) { return (a + b - 1) / b * b; }
 }  // namespace xq

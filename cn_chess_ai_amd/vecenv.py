@@ -205,6 +205,16 @@ class VecEnv:
         call("xq_env_legal_moves", self._h, int(player), _ptr(codes, C.c_uint16), _ptr(counts, C.c_int32))
         return codes, counts
 
+    def search_values(self, depth):
+        """Material search of every game for its side to move (DESIGN.md §4 "Search player"), depth 1..3 ->
+        (values [n][128] int32 root value of each legal move in list order, INT32_MIN past the count; counts [n]; best [n] index of
+        the first best move, -1 without a move)"""
+        values = np.zeros((self.n_games, _capi.MAX_MOVES), dtype=np.int32)
+        counts = np.zeros(self.n_games, dtype=np.int32)
+        best = np.zeros(self.n_games, dtype=np.int32)
+        call("xq_env_search", self._h, int(depth), _ptr(values, C.c_int32), _ptr(counts, C.c_int32), _ptr(best, C.c_int32))
+        return values, counts, best
+
     def valid_matrix(self, game):
         m = np.zeros(8100, dtype=np.uint8)
         call("xq_env_valid_matrix", self._h, int(game), _ptr(m, C.c_uint8))

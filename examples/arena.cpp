@@ -1,11 +1,13 @@
-// examples/arena.cpp — did the network get stronger?  Player A (a reference-format model file) against player B (another model file, or
-// `random` for uniform-random play) over PAIRS pairs of games on the GPU (xq::Arena, DESIGN.md §4 "Arena"); prints A's summary.
+// examples/arena.cpp — did the network get stronger?  Player A (a reference-format model file) against player B (another model file,
+// `random` for uniform-random play, or `search1` / `search2` / `search3` for the fixed material search of that depth, DESIGN.md §4
+// "Search player") over PAIRS pairs of games on the GPU (xq::Arena, DESIGN.md §4 "Arena"); prints A's summary.
 //
 //   g++ -std=c++17 -O2 examples/arena.cpp -Iinclude -Lcn_chess_ai_amd -lxqhip -Wl,-rpath,$PWD/cn_chess_ai_amd -o arena
 //   ./arena model_after_2000_games.bin model_after_100_games.bin [pairs] [options]
 //   ./arena model.bin random 4096
+//   ./arena model.bin search2 4096
 //
-// A may be `random` too.  The topology of each model is read from the file itself (the layer sizes DQN::saveModel writes after the
+// A may be `random` or a search too.  The topology of each model is read from the file itself (the layer sizes DQN::saveModel writes after the
 // parameters, dqn.cpp:133-140).  options:
 //   --seed S        Philox key of the games (default 1)
 //   --opening K     uniform-random opening plies, shared by the two games of a pair (default 8)
@@ -19,6 +21,11 @@
 #include <vector>
 
 #include "xq/xq.hpp"
+
+// `search1` .. `search3`: the depth of the search player, 0 for any other name
+static int search_depth(const std::string& name) {
+    return name.size() == 7 && name.compare(0, 6, "search") == 0 && name[6] >= '1' && name[6] <= '3' ? name[6] - '0' : 0;
+}
 
 // layer sizes of a reference-format model file: [weights f64][biases f64][count u64 BE][count x u32 BE]
 static std::vector<int> model_layer_sizes(const std::string& path) {
@@ -42,10 +49,16 @@ static std::vector<int> model_layer_sizes(const std::string& path) {
 }
 
 static std::unique_ptr<xq::DQN> load_player(const std::string& path) {
-    if (path == "random") return nullptr;
+    if (path == "random" || search_depth(path) > 0) return nullptr;
     auto d = std::make_unique<xq::DQN>(model_layer_sizes(path), 0.001, 0.99, 1);
     d->loadModel(path);
     return d;
+}
+
+static xq::Player as_player(const std::string& name, const xq::DQN* net, double eps) {
+    if (net) return xq::Player::net(*net, eps);
+    if (search_depth(name) > 0) return xq::Player::search(search_depth(name), eps);
+    return xq::Player::random();
 }
 
 int main(int argc, char** argv) {
@@ -64,7 +77,7 @@ int main(int argc, char** argv) {
         else pos.push_back(argv[i]);
     }
     if (pos.size() < 2) {
-        std::fprintf(stderr, "usage: %s MODEL_A|random MODEL_B|random [pairs] [--seed S] [--opening K] [--eps-a E] [--eps-b E] [--json]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s MODEL_A|random|searchD MODEL_B|random|searchD [pairs] [--seed S] [--opening K] [--eps-a E] [--eps-b E] [--json]\n", argv[0]);
         return 2;
     }
     const int pairs = pos.size() > 2 ? std::atoi(pos[2].c_str()) : 1024;
@@ -73,7 +86,7 @@ int main(int argc, char** argv) {
         auto b = load_player(pos[1]);
         xq::Arena arena(pairs, seed, 0, opening);
         const auto t0 = std::chrono::steady_clock::now();
-        const int plies = arena.run(a.get(), b.get(), eps_a, eps_b);
+        const int plies = arena.run(as_player(pos[0], a.get(), eps_a), as_player(pos[1], b.get(), eps_b));
         const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         const xq::ArenaSummary s = arena.summary();
         if (json) {

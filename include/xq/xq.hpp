@@ -321,6 +321,15 @@ public:
         check(xq_env_step(h_, actions.data(), autoReset ? 1 : 0, r.data()));
         return r;
     }
+    // material search of every game for its side to move, depth 1..3 (DESIGN.md §4 "Search player"): values[g*128 + k] = root value of
+    // move k of legalMoves(-1) (INT32_MIN past counts[g]), best[g] = index of the first best move (-1 without a move)
+    struct SearchResult { std::vector<int32_t> values, counts, best; };
+    SearchResult search(int depth) {
+        SearchResult r;
+        r.values.resize((size_t)n_ * XQ_MAX_MOVES); r.counts.resize((size_t)n_); r.best.resize((size_t)n_);
+        check(xq_env_search(h_, depth, r.values.data(), r.counts.data(), r.best.data()));
+        return r;
+    }
     xq_env* handle() const { return h_; }
 private:
     xq_env* h_ = nullptr;
@@ -396,6 +405,21 @@ inline ArenaSummary summarizeArena(const std::vector<xq_arena_game>& r, int pair
     return s;
 }
 
+// One side of an arena: uniform-random play, a borrowed network, or the fixed material search of depth 1..3 (DESIGN.md §4 "Search player")
+class Player {
+public:
+    static Player random() { return Player(XQ_PLAYER_RANDOM, nullptr, 0, 0.0); }
+    static Player net(const DQN& d, double eps = 0.0) { return Player(XQ_PLAYER_NET, d.handle(), 0, eps); }
+    static Player search(int depth, double eps = 0.0) {
+        if (depth < 1 || depth > 3) throw std::invalid_argument("search depth must be 1, 2 or 3");
+        return Player(XQ_PLAYER_SEARCH, nullptr, depth, eps);
+    }
+    const xq_arena_player& spec() const { return p_; }
+private:
+    Player(int kind, xq_dqn* d, int depth, double eps) { p_.kind = kind; p_.dqn = d; p_.depth = depth; p_.eps = eps; }
+    xq_arena_player p_;
+};
+
 class Arena {
 public:
     explicit Arena(int pairs, uint64_t seed = 1, uint32_t firstGameId = 0, int openingPlies = 8) : pairs_(pairs) {
@@ -411,6 +435,11 @@ public:
     int run(const DQN* a, const DQN* b, double epsA = 0.0, double epsB = 0.0, int maxPlies = 0) {
         int n = 0;
         check(xq_arena_run(h_, a ? a->handle() : nullptr, b ? b->handle() : nullptr, epsA, epsB, maxPlies, &n));
+        return n;
+    }
+    int run(const Player& a, const Player& b, int maxPlies = 0) {
+        int n = 0;
+        check(xq_arena_run_players(h_, &a.spec(), &b.spec(), maxPlies, &n));
         return n;
     }
     std::vector<xq_arena_game> results() {
@@ -466,6 +495,14 @@ public:
         }
         Arena arena(pairs, seed, 0, openingPlies);
         arena.run(dqn.get(), opponent.get(), epsSelf, epsOpponent);
+        return arena.summary();
+    }
+    // ... against the fixed material search of depth 1..3 (Player::search), a reference whose strength does not move between runs
+    ArenaSummary evaluateAgainst(int searchDepth, int pairs, uint64_t seed = 1, int openingPlies = 8, double epsSelf = 0.0,
+                                 double epsOpponent = 0.0) {
+        if (!dqn) throw std::invalid_argument("DQN is not initialized. Cannot evaluate.");
+        Arena arena(pairs, seed, 0, openingPlies);
+        arena.run(Player::net(*dqn, epsSelf), Player::search(searchDepth, epsOpponent));
         return arena.summary();
     }
 

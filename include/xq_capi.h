@@ -130,6 +130,14 @@ int xq_env_get_state(xq_env* env, int first, int n, uint8_t* boards90_host, int3
  * codes: [n_games][128] u16 action codes, counts: [n_games]. */
 int xq_env_legal_moves(xq_env* env, int player, uint16_t* codes_host, int32_t* counts_host);
 int xq_env_legal_moves_dev(xq_env* env, int player, uint16_t* codes_dev, int32_t* counts_dev);
+/* Material search of every game for its side to move (build-defined, DESIGN.md §4 "Search player"): a full-width negamax of
+ * depth 1, 2 or 3 plies over the xq_env_legal_moves list, int32 values in material points, XQ_SEARCH_MATE - k for a general
+ * captured k plies from the root.  values: [n_games][128] root value of each move in list order (INT32_MIN past the count),
+ * counts: [n_games] move counts, best: [n_games] index of the first best move (-1 without a move).  Any other depth:
+ * INVALID_ARGUMENT.  The _dev form writes device buffers on the env's stream and does not synchronise. */
+enum { XQ_SEARCH_MATE = 1000000 };
+int xq_env_search(xq_env* env, int depth, int32_t* values_host, int32_t* counts_host, int32_t* best_host);
+int xq_env_search_dev(xq_env* env, int depth, int32_t* values_dev, int32_t* counts_dev, int32_t* best_dev);
 /* ChessBoard::getWinner() (chessboard.cpp:312-320) for games first..first+n-1: colour of the first general in index order
  * (so Red while both are alive), 2 if none. */
 int xq_env_get_winner(xq_env* env, int first, int n, uint8_t* winners_host);
@@ -487,6 +495,20 @@ int xq_arena_ply_q_dev(xq_arena* a, const float* q_dev, int q_stride, double eps
  * dqn_a / dqn_b: a network with layer_sizes[0] == 1260 and >= 90 outputs, or NULL for uniform-random play; dqn_a == dqn_b is allowed,
  * and so are handles on different streams (ordered by events).  eps_a, eps_b in [0, 1]. */
 int xq_arena_run(xq_arena* a, xq_dqn* dqn_a, xq_dqn* dqn_b, double eps_a, double eps_b, int max_plies, int* plies_played);
+/* A player of xq_arena_run_players.  kind XQ_PLAYER_RANDOM: uniform-random play (dqn, depth, eps unused); XQ_PLAYER_NET: the borrowed
+ * network dqn (as for xq_arena_run) with exploration eps; XQ_PLAYER_SEARCH: the material search of xq_env_search at depth 1..3 with
+ * exploration eps — greedy plies take one of the best root moves, ties broken uniformly on the PAIR's Philox stream (ctr = {ply, 0,
+ * first_game_id + g mod n_pairs, 3}), so twins break ties alike and a search player against itself at eps = 0 scores exactly 0.5. */
+enum { XQ_PLAYER_RANDOM = 0, XQ_PLAYER_NET = 1, XQ_PLAYER_SEARCH = 2 };
+typedef struct {
+    int kind;                       /* XQ_PLAYER_* */
+    xq_dqn* dqn;                    /* XQ_PLAYER_NET: the network (layer_sizes[0] == 1260, >= 90 outputs) */
+    int depth;                      /* XQ_PLAYER_SEARCH: 1, 2 or 3 */
+    double eps;                     /* XQ_PLAYER_NET / XQ_PLAYER_SEARCH: exploration in [0, 1] */
+} xq_arena_player;
+/* xq_arena_run with any two players (NULL = XQ_PLAYER_RANDOM).  An invalid kind, depth or eps, or a NULL dqn for XQ_PLAYER_NET:
+ * INVALID_ARGUMENT.  The search runs on the arena's stream, one launch per ply and searching half, over the live games only. */
+int xq_arena_run_players(xq_arena* a, const xq_arena_player* pa, const xq_arena_player* pb, int max_plies, int* plies_played);
 /* [2 n_pairs] records (live games report their current plies and scores). */
 int xq_arena_results(xq_arena* a, xq_arena_game* records_host);
 int xq_arena_live(xq_arena* a, int* n_live);
