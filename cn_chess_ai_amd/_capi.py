@@ -190,6 +190,8 @@ PROTOTYPES = {
     "xq_trainer_replay": [_vp, _pvp],
     "xq_trainer_random_plies": [_vp, _i],
     "xq_trainer_set_td_net": [_vp, _i],
+    "xq_trainer_set_opponent": [_vp, C.POINTER(ArenaPlayer)],
+    "xq_trainer_versus_results": [_vp, _pu64],
     "xq_trainer_collect": [_vp],
     "xq_trainer_learn_grads": [_vp],
     "xq_trainer_learn_apply": [_vp, _i],

@@ -13,7 +13,7 @@
 
 namespace xq {
 
-enum { MODE_LEGAL = 0, MODE_STEP = 1, MODE_SELFPLAY = 2, MODE_ARENA = 3 };
+enum { MODE_LEGAL = 0, MODE_STEP = 1, MODE_SELFPLAY = 2, MODE_ARENA = 3, MODE_VERSUS = 4 };
 
 struct EnvParams {
     uint32_t* boards;
@@ -53,6 +53,13 @@ struct EnvParams {
     // player, xq_search.hip); the epsilon draw stays the kernel's own
     const int16_t* arena_pick;
     int arena_pick_on[2];
+    // MODE_VERSUS (xq_trainer.hip, DESIGN.md §4 "Versus training"): the learner plays Black in game g iff (first_game_id + g) & 1.
+    // vs_phase 0: the opponent's pre-move, 1: the learner's half-ply (Q from q90 / q_slabs, epsilon eps_u32), 2: the opponent's reply.
+    // In phases 0 and 2 the opponent picks from vs_pick (search), from the rows of q90 (a network) or uniformly (neither), with
+    // epsilon eps_u32.  All three phases write the transition of slot rp_write_base + g; vs_counts[g] = learner wins, draws, losses, ended
+    int vs_phase;
+    const int16_t* vs_pick;
+    uint4* vs_counts;
 };
 
 __constant__ uint32_t c_start_words[kBoardWords];
@@ -65,7 +72,8 @@ __constant__ uint32_t c_start_words[kBoardWords];
 // and the first general in index order is Red's while it lives.
 enum : uint32_t { META_TRACKED = 1u << 17, META_RED_GENERAL = 1u << 18, META_BLACK_GENERAL = 1u << 19,
                   META_START = META_TRACKED | META_RED_GENERAL | META_BLACK_GENERAL,
-                  META_FROZEN = kMetaFrozen };     // MODE_ARENA: the game has ended and is never stepped again
+                  META_FROZEN = kMetaFrozen,       // MODE_ARENA: the game has ended and is never stepped again
+                  META_VS_DONE = kMetaVsDone };    // MODE_VERSUS: this collect's slot is written, the game sits out the later phases
 constexpr int kSideMaterial = 1000 + 2 * 20 + 2 * 20 + 2 * 40 + 2 * 90 + 2 * 45 + 5 * 10;      // 1480, chessboard.h:23-31
 
 template <int MODE>
@@ -87,7 +95,7 @@ __global__ __launch_bounds__(256) void env_kernel(EnvParams P) {
     // (last hidden width <= 512), two outputs per lane (lane, 64 + lane < 90).
     float qpre[2][8];
     float qbias[2] = {0.f, 0.f};
-    const bool q_from_slabs = MODE == MODE_SELFPLAY && P.q_slabs != nullptr && P.q_nslabs <= 8;
+    const bool q_from_slabs = (MODE == MODE_SELFPLAY || MODE == MODE_VERSUS) && P.q_slabs != nullptr && P.q_nslabs <= 8;
     if (active) {
         if (lane < kBoardWords) word = P.boards[(size_t)g * kBoardWords + lane];
         m = P.meta[g];
@@ -102,7 +110,7 @@ __global__ __launch_bounds__(256) void env_kernel(EnvParams P) {
             }
             qbias[0] = P.q_bias[lane];
             qbias[1] = P.q_bias[64 + (lane < 26 ? lane : 0)];
-        } else if (MODE == MODE_SELFPLAY && P.q90 != nullptr) {
+        } else if ((MODE == MODE_SELFPLAY || MODE == MODE_VERSUS) && P.q90 != nullptr) {
             const float* qrow = P.q90 + (size_t)g * P.q_stride;
             qpre[0][0] = qrow[lane];
             qpre[1][0] = qrow[64 + (lane < 26 ? lane : 0)];
@@ -120,6 +128,17 @@ __global__ __launch_bounds__(256) void env_kernel(EnvParams P) {
             const float* qrow = P.q90 + (size_t)g * P.q_stride;
             qpre[0][0] = qrow[lane];
             qpre[1][0] = qrow[64 + (lane < 26 ? lane : 0)];
+        }
+    }
+    // versus: the pre-move only where the opponent is to move; a game whose slot an earlier phase of this collect wrote sits out the
+    // rest of it (the reply phase clears the mark)
+    const int vs_learner = MODE == MODE_VERSUS ? (int)((P.first_game_id + (uint32_t)g) & 1u) : 0;
+    if (MODE == MODE_VERSUS) {
+        if (!active) return;
+        if (P.vs_phase == 0 && (int)((m.x >> 16) & 1u) == vs_learner) return;
+        if (m.x & META_VS_DONE) {
+            if (P.vs_phase == 2 && lane == 0) P.meta[g] = make_uint4(m.x & ~(uint32_t)META_VS_DONE, m.y, m.z, m.w);
+            return;
         }
     }
     unpack_to_slab(word, S.sq);
@@ -149,14 +168,14 @@ __global__ __launch_bounds__(256) void env_kernel(EnvParams P) {
     bool have_action = false, valid = false, explored = false;
     const int mover = player;
 
-    if (MODE == MODE_SELFPLAY || MODE == MODE_ARENA) {
+    if (MODE == MODE_SELFPLAY || MODE == MODE_ARENA || MODE == MODE_VERSUS) {
         n_moves = gen_all_actions(S, player);                       // chessai.cpp:98
         wave_sync();
         if (n_moves > 0) {
             const uint32_t stream_id = arena_opening ? (uint32_t)(g - arena_half * P.arena_pairs) : (uint32_t)g;   // twins share the opening
             const Philox4 r = philox4x32_10(plies, 0u, P.first_game_id + stream_id, 0u, P.seed_lo, P.seed_hi);
             const bool have_q = MODE == MODE_ARENA ? (!arena_opening && (P.arena_has_q[arena_half] != 0 || P.arena_pick_on[arena_half] != 0))
-                                                   : (P.q90 != nullptr || P.q_slabs != nullptr);
+                                                   : (P.q90 != nullptr || P.q_slabs != nullptr || (MODE == MODE_VERSUS && P.vs_pick != nullptr));
             const uint32_t eps_u32 = MODE == MODE_ARENA ? P.arena_eps[arena_half] : P.eps_u32;
             explored = !have_q || (r.v[0] < eps_u32);               // dqn.cpp:30-31
             int idx;
@@ -164,6 +183,9 @@ __global__ __launch_bounds__(256) void env_kernel(EnvParams P) {
                 idx = (int)(r.v[1] % (uint32_t)n_moves);            // dqn.cpp:33
             } else if (MODE == MODE_ARENA && P.arena_pick_on[arena_half]) {
                 const int p = P.arena_pick[g];
+                idx = (unsigned)p < (unsigned)n_moves ? p : 0;
+            } else if (MODE == MODE_VERSUS && P.vs_pick != nullptr) {           // the opponent's search pick
+                const int p = P.vs_pick[g];
                 idx = (unsigned)p < (unsigned)n_moves ? p : 0;
             } else {
                 if (q_from_slabs) {
@@ -260,10 +282,12 @@ __global__ __launch_bounds__(256) void env_kernel(EnvParams P) {
     }
 
     // ---- reward, terminal test (chessai.cpp:115-119) ------------------------------------------------------------
+    // versus: evaluateBoard from the learner's side, whoever moved (DESIGN.md §4 "Versus training")
+    const int rside = MODE == MODE_VERSUS ? vs_learner : mover;
     int reward, winner_now;
     bool red_general, black_general;
     if (flags & META_TRACKED) {          // no board scan: see META_TRACKED
-        const int score = mover == C_RED ? red - black : black - red;      // (1480 - lost own) - (1480 - lost enemy)
+        const int score = rside == C_RED ? red - black : black - red;      // (1480 - lost own) - (1480 - lost enemy)
         {
 #pragma clang fp contract(off)
             const double pen = __dmul_rn((double)move_count, 0.1);         // `score -= moveCount * 0.1` on an int, chessai.cpp:342
@@ -273,19 +297,19 @@ __global__ __launch_bounds__(256) void env_kernel(EnvParams P) {
         black_general = (flags & META_BLACK_GENERAL) != 0;
         winner_now = red_general ? C_RED : (black_general ? C_BLACK : C_NONE);
     } else {
-        reward = evaluate_board_wave(S.sq, mover, move_count);
+        reward = evaluate_board_wave(S.sq, rside, move_count);
         const BoardStatus st = board_status_wave(S.sq);
         red_general = st.red_general; black_general = st.black_general;
         winner_now = st.first_general_color;
     }
     const bool over = move_count >= 200 || !red_general || !black_general;         // chessboard.cpp:286-309
-    const bool no_action = (MODE == MODE_SELFPLAY || MODE == MODE_ARENA) && !have_action;     // chessai.cpp:100-103
+    const bool no_action = (MODE == MODE_SELFPLAY || MODE == MODE_ARENA || MODE == MODE_VERSUS) && !have_action;     // chessai.cpp:100-103
     const bool done = over || no_action || (move_count + 1 >= 200);
     const bool terminated = over || no_action;
     // the episode ENDS on the ply that made it terminal; a rejected move on an already finished board (the facade's
     // checkGameOver() probe, a retried step) reports `terminated` but changes nothing: no stats, no episode record, no reset
-    const bool ended_now = terminated && (MODE == MODE_SELFPLAY || MODE == MODE_ARENA || valid);
-    const bool do_reset = MODE != MODE_ARENA && ended_now && (MODE == MODE_SELFPLAY || P.auto_reset != 0);
+    const bool ended_now = terminated && (MODE == MODE_SELFPLAY || MODE == MODE_ARENA || MODE == MODE_VERSUS || valid);
+    const bool do_reset = MODE != MODE_ARENA && ended_now && (MODE == MODE_SELFPLAY || MODE == MODE_VERSUS || P.auto_reset != 0);
     const int winner = terminated ? winner_now : C_NONE;
 
     const uint32_t next_word = pack_from_slab(S.sq);               // s' = board after the move, before any reset
@@ -325,7 +349,40 @@ __global__ __launch_bounds__(256) void env_kernel(EnvParams P) {
         }
     }
 
-    const bool policy_q = P.q90 != nullptr || P.q_slabs != nullptr;
+    if (MODE == MODE_VERSUS && P.rp.capacity > 0) {
+        int slot = P.rp_write_base + g;
+        slot -= (slot >= P.rp.capacity) ? P.rp.capacity : 0;
+        const int ph = P.vs_phase;
+        // (a) writes the slot only when the game ended there: an empty transition, s = s' = the board the opponent's half-ply left.
+        // (b) writes s and the learner's `to`, and the rest too when the game ended there.  (c) writes s', reward and done.
+        const bool s_now = ph == 1 || (ph == 0 && ended_now);
+        const bool s2_now = ph == 2 || ended_now;
+        if (lane < kBoardWords) {
+            if (s_now) P.rp.boards[(size_t)slot * kBoardWords + lane] = ph == 0 ? next_word : word;
+            if (s2_now) P.rp.next_boards[(size_t)slot * kBoardWords + lane] = next_word;
+        }
+        if (lane == 0) {
+            const bool learner_moved = ph == 2 || (ph == 1 && have_action);
+            if (ph == 0 && ended_now) P.rp.action_to[slot] = -1;
+            if (ph == 1) P.rp.action_to[slot] = have_action ? to : -1;
+            if (s2_now) {
+                P.rp.reward[slot] = ph == 0 ? 0.f : (float)reward;
+                P.rp.done[slot] = ph == 0 || done ? 1 : 0;
+                if (P.rp.prio != nullptr) P.rp.prio[slot] = learner_moved ? __uint_as_float(*P.rp.pmax_snap) : 0.f;
+            }
+        }
+    }
+    if (MODE == MODE_VERSUS && ended_now && lane == 0) {            // the outcome from the learner's side, by the arena's rules
+        uint4 c = P.vs_counts[g];
+        if (!red_general || !black_general) { if (winner_now == vs_learner) c.x += 1; else c.z += 1; }   // the captor wins
+        else if (no_action) { if (mover == vs_learner) c.z += 1; else c.x += 1; }                        // the side to move loses
+        else c.y += 1;                                                                                   // the 200-move cap
+        c.w += 1;
+        P.vs_counts[g] = c;
+    }
+
+    // versus: the learner's exploration only
+    const bool policy_q = (P.q90 != nullptr || P.q_slabs != nullptr) && (MODE != MODE_VERSUS || P.vs_phase == 1);
     if (MODE != MODE_ARENA && (captured != 0 || ended_now || (explored && policy_q)) && lane == 0) {
         uint4 s = P.stats[g];
         if (ended_now && winner == C_RED) s.x += 1;
@@ -375,6 +432,7 @@ __global__ __launch_bounds__(256) void env_kernel(EnvParams P) {
         flags = META_START;
         episodes += 1;
     }
+    if (MODE == MODE_VERSUS && ended_now && P.vs_phase != 2) flags |= META_VS_DONE;
     if (lane < kBoardWords) P.boards[(size_t)g * kBoardWords + lane] = out_word;
     if (lane == 0)
         P.meta[g] = make_uint4((uint32_t)move_count | ((uint32_t)player << 16) | flags, (uint32_t)red | ((uint32_t)black << 16),
@@ -516,6 +574,33 @@ int env_arena_launch(xq_env* e, const float* q90_dev, int q_stride, int pairs, i
     P.arena_rec = records_dev;
     P.arena_live = live_dev;
     hipLaunchKernelGGL(env_kernel<MODE_ARENA>, dim3((e->n + 3) / 4), dim3(256), 0, e->stream, P);
+    XQ_HIP(hipGetLastError());
+    return XQ_OK;
+}
+
+// One phase of a versus collect (xq_trainer.hip): phase 1 = the learner's half-ply on q90_dev / qs with eps_u32; phases 0 and 2 = the
+// opponent's, on its search picks (pick_dev), its Q rows (q90_dev) or uniform-random (neither) with its eps_u32.  The transitions go to
+// the ring slots from replay->write_pos; the caller advances the ring once the collect's last phase is queued.
+int env_versus_launch(xq_env* e, int phase, const float* q90_dev, int q_stride, const QSource* qs, uint32_t eps_u32, const int16_t* pick_dev,
+                      uint4* counts_dev, xq_replay* replay, hipStream_t on) {
+    if (phase < 0 || phase > 2 || replay == nullptr || counts_dev == nullptr) return fail(XQ_ERR_INVALID_ARGUMENT, "env_versus_launch: bad argument");
+    if (replay->dev.capacity < e->n) return fail(XQ_ERR_INVALID_ARGUMENT, "replay capacity %d < n_games %d", replay->dev.capacity, e->n);
+    EnvParams P = base_params(e);
+    P.q90 = q90_dev;
+    P.q_stride = q_stride;
+    if (phase == 1 && qs && qs->slabs) {
+        if (qs->nslabs < 2 || (qs->nslabs & 1)) return fail(XQ_ERR_INVALID_ARGUMENT, "select head slabs: even count >= 2");
+        P.q90 = nullptr; P.q_slabs = qs->slabs; P.q_slab_stride = qs->slab_stride; P.q_nslabs = qs->nslabs; P.q_bias = qs->bias;
+    }
+    P.eps_u32 = eps_u32;
+    P.rp = replay->dev;
+    P.rp_write_base = replay->write_pos;
+    P.vs_phase = phase;
+    P.vs_pick = phase == 1 ? nullptr : pick_dev;
+    P.vs_counts = counts_dev;
+    hipStream_t s = on ? on : e->stream;
+    if (phase == 0) XQ_TRY(replay_writer_begin(replay, s));
+    hipLaunchKernelGGL(env_kernel<MODE_VERSUS>, dim3((e->n + 3) / 4), dim3(256), 0, s, P);
     XQ_HIP(hipGetLastError());
     return XQ_OK;
 }

@@ -258,5 +258,11 @@ int env_arena_launch(xq_env* env, const float* q90_dev, int q_stride, int pairs,
 void dqn_shape(const xq_dqn* d, int* n_in, int* n_out);    // layer_sizes[0], outputs
 int search_pick_launch(xq_env* env, int depth, int first, int count, int pairs, uint32_t eps_u32, int16_t* pick_dev);   // xq_search.hip
 constexpr uint32_t kMetaFrozen = 1u << 20;                  // meta.x flag of a finished arena game (xq_env.hip META_FROZEN)
+constexpr uint32_t kMetaVsDone = 1u << 21;                  // meta.x flag: the game's versus slot of this collect is written (META_VS_DONE)
+// versus training (xq_trainer_set_opponent): one phase of the collect, see env_versus_launch in xq_env.hip
+int env_versus_launch(xq_env* env, int phase, const float* q90_dev, int q_stride, const QSource* qs, uint32_t eps_u32,
+                      const int16_t* pick_dev, uint4* counts_dev, xq_replay* replay, hipStream_t on);
+// the search player's picks of the games where the opponent of the learner is to move (xq_search.hip), on stream s
+int search_versus_launch(xq_env* env, int depth, uint32_t eps_u32, int16_t* pick_dev, hipStream_t s);
 inline int round_up(int a, int b) { return (a + b - 1) / b * b; }
 }  // namespace xq

@@ -108,7 +108,9 @@ __device__ int negamax2(WaveSlab& A, WaveSlab& B, int side, int k) {
     return best;
 }
 
-template <int DEPTH, bool PICK>
+// SEATED (versus training, PICK only): a block searches only where the learner's opponent is to move — the learner plays Black in game g
+// iff (first_game_id + g) & 1 — and the game's versus slot of this collect is not written yet (kMetaVsDone)
+template <int DEPTH, bool PICK, bool SEATED = false>
 __global__ __launch_bounds__(256) void search_kernel(SearchParams P) {
     __shared__ WaveSlab slabs[kWaves][DEPTH == 3 ? 2 : 1];
     __shared__ int32_t root_val[kMaxMoves];
@@ -121,6 +123,7 @@ __global__ __launch_bounds__(256) void search_kernel(SearchParams P) {
     m.x = __builtin_amdgcn_readfirstlane(m.x);
     m.z = __builtin_amdgcn_readfirstlane(m.z);
     if (PICK && (m.x & kMetaFrozen)) return;                       // (block-uniform: every wave reads the same meta)
+    if (SEATED && (((m.x >> 16) & 1u) == ((P.first_game_id + (uint32_t)g) & 1u) || (m.x & kMetaVsDone))) return;
     const int side = (int)((m.x >> 16) & 1u);
     const uint32_t plies = m.z;
     const uint32_t word = lane < kBoardWords ? P.boards[(size_t)g * kBoardWords + lane] : 0u;
@@ -189,20 +192,20 @@ __global__ __launch_bounds__(256) void search_kernel(SearchParams P) {
     if (lane == 0) P.pick[g] = (int16_t)idx;
 }
 
-template <int DEPTH, bool PICK>
+template <int DEPTH, bool PICK, bool SEATED = false>
 int launch_depth(const SearchParams& P, int n_boards, hipStream_t s) {
-    hipLaunchKernelGGL((search_kernel<DEPTH, PICK>), dim3(n_boards), dim3(64 * kWaves), 0, s, P);
+    hipLaunchKernelGGL((search_kernel<DEPTH, PICK, SEATED>), dim3(n_boards), dim3(64 * kWaves), 0, s, P);
     XQ_HIP(hipGetLastError());
     return XQ_OK;
 }
 
-template <bool PICK>
+template <bool PICK, bool SEATED = false>
 int launch(const SearchParams& P, int depth, int n_boards, hipStream_t s) {
     if (n_boards <= 0) return XQ_OK;
     switch (depth) {
-        case 1: return launch_depth<1, PICK>(P, n_boards, s);
-        case 2: return launch_depth<2, PICK>(P, n_boards, s);
-        case 3: return launch_depth<3, PICK>(P, n_boards, s);
+        case 1: return launch_depth<1, PICK, SEATED>(P, n_boards, s);
+        case 2: return launch_depth<2, PICK, SEATED>(P, n_boards, s);
+        case 3: return launch_depth<3, PICK, SEATED>(P, n_boards, s);
         default: return fail(XQ_ERR_INVALID_ARGUMENT, "search depth must be 1, 2 or 3 (got %d)", depth);
     }
 }
@@ -228,6 +231,16 @@ int search_pick_launch(xq_env* e, int depth, int first, int count, int pairs, ui
     P.eps_u32 = eps_u32;
     P.pairs = pairs;
     return launch<true>(P, depth, count, e->stream);
+}
+
+// Versus pick for every game of e where the learner's opponent is to move, on stream s: ties are broken on the game's own stream
+// (ctr {plies, 0, first_game_id + g, 3}: no twin), the epsilon draw is the env kernel's
+int search_versus_launch(xq_env* e, int depth, uint32_t eps_u32, int16_t* pick_dev, hipStream_t s) {
+    SearchParams P = base(e, 0);
+    P.pick = pick_dev;
+    P.eps_u32 = eps_u32;
+    P.pairs = INT_MAX;
+    return launch<true, true>(P, depth, e->n, s);
 }
 
 }  // namespace xq

@@ -375,6 +375,31 @@ class Trainer:
     def set_td_net(self, td_net):
         call("xq_trainer_set_td_net", self._h, int(td_net))
 
+    def set_opponent(self, opponent):
+        """Train against a fixed opponent from the next collect on (DESIGN.md §4 "Versus training"): None = self-play (the default),
+        "random" = uniform-random play, an arena.Search(depth, eps) = the material search, (DQN, eps) = a borrowed network.  The
+        learner plays Black in game g iff (first_game_id + g) is odd.  Call between iterations."""
+        from .arena import Search
+        if opponent is None:
+            call("xq_trainer_set_opponent", self._h, None)
+            return
+        if isinstance(opponent, str) and opponent == "random":
+            p = _capi.ArenaPlayer(_capi.PLAYER_RANDOM, None, 0, 0.0)
+        elif isinstance(opponent, Search):
+            p = _capi.ArenaPlayer(_capi.PLAYER_SEARCH, None, opponent.depth, opponent.eps)
+        elif isinstance(opponent, tuple) and len(opponent) == 2 and isinstance(opponent[0], DQN):
+            p = _capi.ArenaPlayer(_capi.PLAYER_NET, opponent[0].handle, 0, float(opponent[1]))
+        else:
+            raise TypeError(f"set_opponent: expected None, 'random', Search(depth, eps) or (DQN, eps), got {opponent!r}")
+        call("xq_trainer_set_opponent", self._h, C.byref(p))
+
+    def versus_results(self):
+        """The learner's games against the opponent since set_opponent: wins, draws, losses, games ended and the score (W + D/2) / N."""
+        out = (C.c_uint64 * 4)()
+        call("xq_trainer_versus_results", self._h, out)
+        w, d, l, n = (int(v) for v in out)
+        return dict(wins=w, draws=d, losses=l, games=n, score=(w + 0.5 * d) / n if n else float("nan"))
+
     def collect(self):
         call("xq_trainer_collect", self._h)
 

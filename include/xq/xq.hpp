@@ -578,6 +578,8 @@ public:
     // chessai.cpp:85-170.  parallelGames == 1: the reference's sequential loop (trainEpisode() x numEpisodes).
     // parallelGames > 1 (default 8192): the batched device loop (xq_trainer) until numEpisodes episodes finished.
     void train(int numEpisodes) {
+        if (parallelGames_ <= 1 && opponent_)
+            throw std::logic_error("ChessAI::train: an opponent (setOpponent) needs the batched loop (setParallelGames(n > 1))");
         initializeDQN();
         if (parallelGames_ <= 1) {
             for (int e = 0; e < numEpisodes; ++e) {
@@ -634,13 +636,19 @@ public:
     void setLayer0Derive(bool on) { l0Derive_ = on; }
     // uniform-random plies played in every game before the batched loop starts (spreads the games over all phases; 0 = from the opening)
     void setPrefillRandomPlies(int n) { prefillPlies_ = n; }
+    // Versus training (DESIGN.md §4 "Versus training"): the batched train() plays a fixed opponent instead of itself — Player::random(),
+    // Player::search(depth, eps) or Player::net(dqn, eps) (a network that must outlive train()); the learner plays Black in every
+    // other game.  clearOpponent() returns to self-play.  The sequential loop (parallelGames == 1) has no opponent: train() throws.
+    void setOpponent(const Player& p) { opponent_.reset(new Player(p)); }
+    void clearOpponent() { opponent_.reset(); }
     // what the last batched train() did: plies played by this process, updates, episodes finished, wall seconds of the loop
     // (from the first iteration queued to the last one finished, model saves included)
     // screenedSteps / guardFallbacks: TD steps that found max_a' Q(s',a') by exact screening, and how often the screen's guard sent a run of
     // 512 steps to the full fp32 product instead (a net whose outputs lie within the bf16 bound of each other — typical of some fresh nets)
     struct TrainStats { uint64_t envSteps = 0, updates = 0, episodes = 0; double seconds = 0; uint64_t screenedSteps = 0, guardFallbacks = 0;
-                        double candidateGroupsPerSample = 0, wholeGroupsPerSample = 0; };   // (sample, 32-output group) pairs the screen left for fp32
+                        double candidateGroupsPerSample = 0, wholeGroupsPerSample = 0;      // (sample, 32-output group) pairs the screen left for fp32
                                                                                            // re-evaluation per sample; those re-evaluated as whole groups
+                        uint64_t versus[4] = {0, 0, 0, 0}; };   // with an opponent: the learner's wins, draws, losses, games ended
     TrainStats lastTrainStats() const { return stats_; }
     // data-parallel train(): this process is rank comm->rank() of comm->world(); its batched games take the id range
     // [rank * parallelGames, (rank + 1) * parallelGames) and every update all-reduces the gradients over RCCL (nullptr = off)
@@ -694,6 +702,7 @@ private:
         check(xq_dqn_set_l0_derive(td, l0Derive_ ? 1 : 0));
         if (comm_) check(xq_trainer_set_comm(t, comm_->handle()));
         if (prefillPlies_ > 0) check(xq_trainer_random_plies(t, prefillPlies_));
+        if (opponent_) check(xq_trainer_set_opponent(t, &opponent_->spec()));
         std::vector<xq_episode_record> rec(4096);
         // Every rank must run the same number of iterations (each carries a collective): the loop ends when the episodes
         // finished on ALL ranks together reach numEpisodes per rank; a rank reports at most its own numEpisodes.
@@ -730,6 +739,7 @@ private:
         uint64_t eps = 0;
         check(xq_trainer_counters(t, &stats_.envSteps, &stats_.updates, &eps));
         stats_.episodes = eps;
+        if (opponent_) check(xq_trainer_versus_results(t, stats_.versus));
         {
             uint64_t q[4] = {0, 0, 0, 0}; int hold = 0;
             check(xq_dqn_qmax_stats(td, q));
@@ -754,6 +764,7 @@ private:
     int saveInterval_ = 100, savedMark_ = 0;
     bool l0Derive_ = false;
     int prefillPlies_ = 0;
+    std::unique_ptr<Player> opponent_;
     TrainStats stats_;
     Comm* comm_ = nullptr;
     uint64_t batchSeed_ = 0;

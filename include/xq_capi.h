@@ -37,6 +37,8 @@
  *   xq_dqn_apply_grads / set_params / load_model / update_target
  *     -> xq_dqn_forward* / select_q_dev / td_grads*               parameters                        one handle, one stream: stream order
  *     -> xq_trainer_collect (collect stream of overlap_collect)   parameters                        library: XQ_ORDER_TRAINER_PARAMS
+ *   opponent net (xq_trainer_set_opponent) -> xq_trainer_collect  its Q rows of the trainer's boards   library: events (the forward on
+ *                                                                 (and the boards it reads)           the net's stream waits for the env)
  *   xq_dqn_select_q_dev / forward_boards_dev -> xq_env_selfplay_step   q90_dev (raw pointer)        CALLER: xq_stream_wait_stream(env stream, Q-net stream)
  *   xq_env_*step* -> xq_dqn_select_q_dev / forward_boards_dev / td_grads(boards_dev)  boards (raw pointer)   CALLER: xq_stream_wait_stream(Q-net stream, env stream)
  *   xq_env_selfplay_step(results_dev) / legal_moves_dev -> anything    raw pointers                 CALLER
@@ -563,6 +565,17 @@ int xq_trainer_random_plies(xq_trainer* t, int n_plies);
 /* Which rule gives the TD target from the next learn step on: XQ_TD_ONLINE_NET (ChessAI::train, chessai.cpp:126), XQ_TD_TARGET_NET
  * (DQN::train, dqn.cpp:166) or XQ_TD_DOUBLE.  Call between iterations. */
 int xq_trainer_set_td_net(xq_trainer* t, int td_net);
+/* Versus training (DESIGN.md §4 "Versus training"): from the next collect on, the learner plays against a fixed opponent instead of
+ * itself — uniform-random play, the material search (depth 1..3, eps) or a borrowed network (eps; layer_sizes[0] == 1260, >= 90
+ * outputs, not the trainer's own).  The learner plays Black in game g iff (first_game_id + g) & 1.  A collect still writes one
+ * transition per game, from one learner decision to the next: the opponent moves first where it is to move (a game it ends there gives
+ * an empty slot), then the learner, then the opponent's reply; reward = evaluateBoard(learner, moveCount) at s'.  The borrowed network's
+ * forwards run on its own stream (ordered by events), keep no layer-0 sums and touch no TD-step state.  NULL returns to self-play.
+ * Call between iterations.  A bad kind, depth or eps, a NULL dqn for XQ_PLAYER_NET or a network of the wrong shape: INVALID_ARGUMENT. */
+int xq_trainer_set_opponent(xq_trainer* t, const xq_arena_player* opp);
+/* Learner wins, draws, losses and games ended since the last xq_trainer_set_opponent (the arena's rules: the captor of a general wins,
+ * the side without a legal move loses, the 200-move cap is a draw). */
+int xq_trainer_versus_results(xq_trainer* t, uint64_t out[4]);
 int xq_trainer_collect(xq_trainer* t);                       /* one ply in every game */
 int xq_trainer_learn_grads(xq_trainer* t);                   /* sample + gradients into the grad buffer */
 int xq_trainer_learn_apply(xq_trainer* t, int world_size);   /* SGD apply (+ target sync bookkeeping) */
