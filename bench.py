@@ -15,9 +15,14 @@ runs its own 8192 games (game ids rank*8192..) and the gradient buffer is all-re
 
 Rank 0 prints ONE JSON line.  `roofline` prices the dominant kernel with HIP events recorded around each of its launches inside
 the timed region: by default (`--qmax screened`) the 8100 x 8192 x 256 bf16-MFMA screening pass of max_a' Q(s',a') (its fp32
-re-evaluation kernel follows it), with `--qmax full` the fp32-MFMA column-max GEMM, which the default run
-also times as `variant_qmax_full_fp32_product` (own roofline inside).  `roofline_env` does the same for the fused self-play step
-kernel (HBM-bound).  `cpu_baseline` times the CPU port of ChessAI::train (oracle) on a bounded sample.
+re-evaluation kernel follows it), with `--qmax full` the fp32-MFMA column-max GEMM.  `roofline_env` does the
+same for the fused self-play step kernel (HBM-bound).
+
+A plain run does only what the headline needs: set-up, warm-up, the per-kernel leg (it picks the kernels bracketed inside the
+timed region, and its steps lead up to the timed ones), the timed steps, --dump-outputs, the line.  `--full` adds the legs that
+take runs of their own after the timed steps: the other TD net and the full fp32 product (`variant_td_*`,
+`variant_qmax_full_fp32_product`), the isolated kernel times, the torch.distributed exchange calibration, the C++ facade process
+(`facade`) and the CPU port of ChessAI::train on a bounded sample (`cpu_baseline`).
 """
 import argparse
 import ctypes as C
@@ -431,10 +436,13 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the legs the headline does not need: variants (other TD net, full fp32 product), "
+                         "isolated kernel times, the torch.distributed exchange calibration, the C++ facade and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline leg")
     ap.add_argument("--reference-nn", action="store_true",
-                    help="cpu_baseline also times the reference's own NN runtime on this GPU (oracle/_ref/xqref_nn time; off by default: upstream's "
-                         "backpropagate reads device memory it has released, which the default bench does not need to run)")
+                    help="--full: cpu_baseline also times the reference's own NN runtime on this GPU (oracle/_ref/xqref_nn time; off by default: "
+                         "upstream's backpropagate reads device memory it has released, which the default bench does not need to run)")
     ap.add_argument("--cpu-worker", type=float, default=0.0, help=argparse.SUPPRESS)   # one instance of cpu_all_cores()
     ap.add_argument("--profile-all", action="store_true", help="bracket every kernel with HIP events (diagnostic)")
     ap.add_argument("--games", type=int, default=N_GAMES, help="games per GPU (default = BASELINE's 8192; other values are diagnostic)")
@@ -470,7 +478,7 @@ def main():
                     help="A/B: the gradient kernels of the TD step one by one on two streams instead of the fused launches (xq_dqn_set_td_tail)")
     ap.add_argument("--l0-grad", choices=("mfma", "segmented"), default="mfma",
                     help="A/B: layer-0 weight gradient as segmented sums (library default) or on the bf16 matrix pipe (exact 3-term split)")
-    ap.add_argument("--no-variants", action="store_true", help="skip the variant legs (other TD net, full fp32 product): A/B runs")
+    ap.add_argument("--no-variants", action="store_true", help="--full: skip the variant legs (other TD net, full fp32 product)")
     ap.add_argument("--repeats", type=int, default=5,
                     help="the timed region (exactly --steps steps, barrier + synchronize on both sides) is run this many times back to "
                          "back; ms_per_step / value are the MEDIAN repetition, all of them are listed in ms_per_step_samples")
@@ -481,7 +489,7 @@ def main():
                          "cannot be created on every rank")
     ap.add_argument("--no-chain", action="store_true", help="skip the per-kernel leg (roofline_chain): A/B runs")
     ap.add_argument("--chain-steps", type=int, default=10, help="untimed steps per kernel in the per-kernel leg (one bracketed kernel at a time)")
-    ap.add_argument("--no-facade", action="store_true", help="skip the C++ facade leg (examples/train_selfplay through xq::ChessAI::train)")
+    ap.add_argument("--no-facade", action="store_true", help="--full: skip the C++ facade leg (examples/train_selfplay through xq::ChessAI::train)")
     ap.add_argument("--facade-episodes", type=int, default=400000, help="episodes the facade leg trains for (~1.5 s of GPU at 8192 games)")
     ap.add_argument("--sustain", type=int, default=0,
                     help="sustained-run mode: N updates of the headline loop with checkpoints (step time, screening statistics, loss, "
@@ -634,7 +642,8 @@ def main():
     # (a bracket costs its stream ~6-10 us, so bracketing everything at once — --profile-all — stretches the step by a third; one
     # kernel at a time leaves the co-scheduling of the two chains as it is in the timed region).  Names: 3 steps with every bracket
     # on; then `--chain-steps` steps per name.  The kernel with the largest share of the step becomes `roofline` and is the one
-    # bracketed (every 4th launch) inside the timed region.
+    # bracketed (every 4th launch) inside the timed region.  So this leg runs without --full too: it decides what the timed region
+    # brackets, and its steps train the net the timed steps start from.
     chain = {}
     if not args.no_chain and not args.profile_all:
         t.dqn.kernel_stats(enable=2)
@@ -700,15 +709,15 @@ def main():
         dump_outputs(args.dump_outputs, trainer_outputs(t, minibatch))
     c1 = t.counters()
     comm_info = comm.info() if comm is not None else None
-    # the other TD rule on the same trainer, same steady state, timed the same way (reported beside the headline)
+    # --full: the other TD rule on the same trainer, same steady state, timed the same way (reported beside the headline)
     other, el_other = None, None
-    if args.config == 2 and args.td_net in ("online", "target") and not args.no_variants:
+    if args.full and args.config == 2 and args.td_net in ("online", "target") and not args.no_variants:
         other = "target" if args.td_net == "online" else "online"
         t.set_td_net(td_code[other])
         one_step()
         el_other, _, _ = timed(args.steps)
         t.set_td_net(td_code[args.td_net])
-    # the same loop with the full fp32 column-max product in place of the exact screen (bracketed the same way)
+    # --full: the same loop with the full fp32 column-max product in place of the exact screen (bracketed the same way)
     qmax_info, full_variant = None, None
     screened_live = "gemm_qmax_screen" in stats
     if args.qmax == "screened":
@@ -718,7 +727,7 @@ def main():
                              "rigorous error bound (DESIGN.md section 4)",
                      "candidate_groups_per_sample": (st[2] - qstat0[2]) / max(st[1] - qstat0[1], 1),
                      "whole_groups_per_sample": (st[3] - qstat0[3]) / max(st[1] - qstat0[1], 1)}
-        if screened_live and world == 1 and not args.no_variants:
+        if args.full and screened_live and world == 1 and not args.no_variants:
             t.dqn.set_qmax_mode(_capi.QMAX_FULL)
             one_step()
             t.dqn.kernel_stats(enable=3 if args.bracket_all else 4)
@@ -733,7 +742,7 @@ def main():
     _, legal_counts = t.env.legal_moves(-1)
     rp_size, rp_cap, rp_total = t.replay.stats()
     iso = {}
-    if not args.no_overlap and world == 1 and args.config == 2:
+    if args.full and not args.no_overlap and world == 1 and args.config == 2:
         # the same two kernels with nothing beside them (device-wide sync between collect and learn), outside the timed region:
         # in the overlapped loop the env kernel shares the chip with the TD step, so its live duration is not its own
         t.dqn.kernel_stats(enable=3)
@@ -754,7 +763,7 @@ def main():
             print(f"replicas identical on {world} ranks: {digest.tolist()}", file=sys.stderr)
 
     torch_exchange_calibration = None
-    if comm is None and grads is not None and not args.independent:
+    if args.full and comm is None and grads is not None and not args.independent:
         # the torch.distributed path (gloo rehearsal / fallback): the same measurement the library makes behind the C ABI, on every rank
         # (a collective), AFTER the replicas were compared — it sums the gradient buffer into itself
         ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -1025,7 +1034,7 @@ def main():
         if args.profile_all:
             line["kernels"] = {k: {"ms_per_launch": v["ms"] / max(v["launches"], 1), "launches": v["launches"]}
                                for k, v in stats.items()}
-        if world == 1 and not args.no_facade and args.config == 2 and n_games == CFG["games"]:
+        if args.full and world == 1 and not args.no_facade and args.config == 2 and n_games == CFG["games"]:
             # the trainer of this process is idle now (everything synchronised); the facade process gets the GPU to itself
             f = facade_leg(n_games, LAYERS, max(REPLAY, n_games), minibatch, args.facade_episodes, not args.no_derive, args.prefill_plies)
             if "env_steps_per_s" in f:
@@ -1034,7 +1043,7 @@ def main():
                              "ctypes loop above; its clock starts with an EMPTY ring and includes the ring fill, the episode drains (one device "
                              "synchronisation per 64 iterations) and a gameCompleted callback per episode")
             line["facade"] = f
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 line["cpu_baseline"] = cpu_baseline(15.0 if args.config == 2 else 6.0, args.reference_nn)
             except Exception as e:           # never lose the measured line to the reporting leg

@@ -1,5 +1,6 @@
 """bench.py keeps its contract on every configuration it offers (`pytest -m gpu`): one JSON line with the driver's keys, the roofline
-and cpu_baseline objects, and the steady-state fields — run at reduced size so that the three runs take seconds."""
+objects and the steady-state fields (with --full also the variant, facade and CPU legs) — run at reduced size so that the runs take
+seconds."""
 import json
 import os
 import subprocess
@@ -22,7 +23,7 @@ def _bench(*extra):
 
 @pytest.mark.parametrize("config,games,dtype", [(2, 2048, "f32"), (4, 2048, "f32"), (5, 2048, "bf16")])
 def test_bench_line_contract(config, games, dtype):
-    d = _bench("--config", str(config), "--games", str(games), "--no-cpu-baseline", "--chain-steps", "4")
+    d = _bench("--full", "--config", str(config), "--games", str(games), "--no-cpu-baseline", "--chain-steps", "4")
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype",
               "data", "config", "roofline"):
         assert k in d, k
@@ -69,9 +70,21 @@ def test_bench_line_contract(config, games, dtype):
         assert "variant_td_target" in d and d["variant_td_target"]["value"] > 0
 
 
+def test_bench_plain_run_leaves_the_extra_legs_to_full():
+    """Without --full the line carries the headline and what the timed region and the per-kernel leg measured, nothing that takes
+    runs of its own after the timed steps: no variants, no isolated kernel times, no CPU baseline."""
+    d = _bench("--games", "2048", "--chain-steps", "4")
+    for k in ("metric", "value", "unit", "ms_per_step", "higher_is_better", "dtype", "roofline", "roofline_qmax", "roofline_chain"):
+        assert k in d, k
+    assert d["steps"] == 4 and d["warmup"] == 2 and d["value"] > 0 and len(d["ms_per_step_samples"]) == 5
+    for k in ("variant_td_target", "variant_qmax_full_fp32_product", "facade", "cpu_baseline"):
+        assert k not in d, k
+    assert "isolated_avg_launch_ms" not in d["roofline_qmax"] and "isolated_avg_launch_ms" not in d.get("roofline_env", {})
+
+
 def test_bench_facade_leg_runs_the_cpp_entry_point():
     """`facade`: examples/train_selfplay (xq::ChessAI::train with setReplay) as a process of its own at the headline's size."""
-    d = _bench("--no-cpu-baseline", "--no-chain", "--no-variants", "--facade-episodes", "30000", "--settle-steps", "10")
+    d = _bench("--full", "--no-cpu-baseline", "--no-chain", "--no-variants", "--facade-episodes", "30000", "--settle-steps", "10")
     f = d["facade"]
     assert "error" not in f, f
     assert f["parallel_games"] == 8192 and f["replay_capacity"] == 1 << 20 and f["minibatch"] == 8192

@@ -192,7 +192,7 @@ def test_two_rank_rehearsal_on_one_gpu():
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2",
-                          "--check-replicas", "--no-cpu-baseline"],
+                          "--check-replicas", "--full", "--no-cpu-baseline"],
                          capture_output=True, text=True, env=env, cwd=root, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     assert "replicas identical on 2 ranks" in out.stderr

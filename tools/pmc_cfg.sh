@@ -7,4 +7,4 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/pmc_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --pmc "$@" --output-format csv -d $OUT -- python3 $ROOT/bench.py --config $CFG --steps 12 --warmup 4 --no-cpu-baseline > $OUT/bench.json 2> $OUT/err.txt
+rocprofv3 --pmc "$@" --output-format csv -d $OUT -- python3 $ROOT/bench.py --full --config $CFG --steps 12 --warmup 4 --no-cpu-baseline > $OUT/bench.json 2> $OUT/err.txt
