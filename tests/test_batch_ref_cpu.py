@@ -1,0 +1,200 @@
+"""tests/batch_ref.py, the batched fp64 TD-step reference of the full-size GPU checks: equal to the scalar oracle on every combination
+it defines, and its comparator tight enough to reject the bugs full-size batches can hide (a dropped chunk or sample, a ragged tail,
+the other backprop mode)."""
+import os
+
+import numpy as np
+import pytest
+
+import batch_ref as br
+import xqoracle as xo
+from test_dqn_gpu import transitions, valid_indices
+
+REF_NET = [1260, 128, 8100]
+CFG2_NET = [1260, 256, 256, 8100]
+CFG4_NET = [1260, 512, 512, 512, 8100]
+SMALL_NET = [40, 24, 24, 56]
+
+
+@pytest.fixture(scope="module")
+def trace(golden_dir):
+    return np.load(os.path.join(golden_dir, "ref_trace.npz"))
+
+
+def _params(sizes, seed):
+    w, _ = xo.init_weights(sizes, seed)
+    b = np.random.default_rng(seed + 100).uniform(-0.05, 0.05, size=xo.nn_counts(sizes)[1])
+    return w * 4.0, b                     # wider pre-activations: hidden deltas well away from zero
+
+
+def _batch(trace, sizes, n, seed):
+    S, A, R, D, S2 = transitions(trace, valid_indices(trace, n, seed=seed))
+    R = (R / 1000.0).astype(np.float32)
+    if sizes[0] != 1260:                  # dense inputs for the small net; actions below its width
+        rng = np.random.default_rng(seed)
+        S, S2 = rng.uniform(-1, 1, (n, sizes[0])), rng.uniform(-1, 1, (n, sizes[0]))
+        A = (A % sizes[-1]).astype(np.int32)
+    return S, A, R, D, S2
+
+
+def _x(s):
+    return xo.state_repr(xo.board_from(s)) if s.dtype == np.uint8 else np.asarray(s, np.float64)
+
+
+def _close(got, want, what):
+    scale = max(np.abs(want).max(), 1e-300)
+    assert np.abs(got - want).max() <= 1e-12 * scale, (what, float(np.abs(got - want).max() / scale))
+
+
+@pytest.mark.parametrize("sizes", [REF_NET, CFG2_NET, CFG4_NET, SMALL_NET], ids=["ref", "cfg2", "cfg4", "small"])
+@pytest.mark.parametrize("mode", [0, 1])
+def test_batched_reference_equals_the_oracle(trace, sizes, mode):
+    """Q, y, a*, the activations and every gradient element against xo.ext_td_accum for TD rules 0 / 1 / 2, precisions 0 / 1 / 2,
+    with and without importance weights; and against xo.td_target + xo.nn_accum_grad where that is defined (rule 0, fp32, no weights)."""
+    n = 32 if sizes != CFG4_NET else 12
+    S, A, R, D, S2 = _batch(trace, sizes, n, seed=3)
+    assert D.any() and not D.all()
+    w, b = _params(sizes, 5)
+    wt, bt = _params(sizes, 6)
+    wts = np.random.default_rng(1).uniform(0.1, 1.0, n)
+    xs, x2s = [_x(s) for s in S], [_x(s) for s in S2]
+    for prec in (0, 1, 2):
+        for rule in (0, 1, 2):
+            weighted = [False, True] if sizes != CFG4_NET else [(rule + prec) % 2 == 1]
+            for use_w in weighted:
+                net, f, bk, u = br.td_step(sizes, w, b, S, S2, A, R, D, 0.99, rule, mode, prec, wts if use_w else None, wt, bt)
+                gw, gb = br.flat_grads(net, u)
+                ow, ob = np.zeros_like(w), np.zeros_like(b)
+                q, y, star = np.empty(n), np.empty(n), np.empty(n, np.int64)
+                for i in range(n):
+                    q[i], y[i], star[i] = xo.ext_td_accum(sizes, w, b, wt, bt, xs[i], x2s[i], int(A[i]), float(R[i]), int(D[i]), 0.99,
+                                                          rule, mode, prec, float(wts[i]) if use_w else 1.0, ow, ob)
+                key = (prec, rule, use_w)
+                _close(f.q, q, ("q",) + key); _close(f.y, y, ("y",) + key)
+                assert np.array_equal(f.astar, star), key
+                _close(gw, ow, ("gw",) + key); _close(gb, ob, ("gb",) + key)
+                for l in range(net.nl):                 # every layer's block on its own scale as well
+                    blk = slice(net.wo[l], net.wo[l] + sizes[l] * sizes[l + 1])
+                    _close(gw[blk], ow[blk], ("gw", l) + key)
+                if rule == 2:
+                    for i in np.nonzero(~f.D)[0]:
+                        assert np.abs(f.cand_y[i] - y[i]).min() <= 1e-12
+                if rule == 0 and not use_w:
+                    acts, z = xo.ext_forward(sizes, w, b, xs[0], bf16=prec > 0)
+                    _close(np.concatenate([a[0] for a in f.acts]), acts, ("acts",) + key)
+                    _close(np.tanh(z[A[0]]), f.q[0], ("z",) + key)
+                if rule == 0 and prec == 0 and not use_w:
+                    nw, nb = np.zeros_like(w), np.zeros_like(b)
+                    for i in range(n):
+                        tq = xo.td_target(sizes, w, b, xs[i], x2s[i], int(A[i]), float(R[i]), int(D[i]), 0.99)
+                        assert xo.nn_accum_grad(sizes, w, b, xs[i], tq, mode, nw, nb) == 0
+                        assert abs(tq[A[i]] - f.y[i]) <= 1e-12 * max(1.0, abs(f.y[i]))
+                    _close(gw, nw, ("nn gw", mode)); _close(gb, nb, ("nn gb", mode))
+                assert abs(br.loss(f) - 0.5 * np.sum((q - y) ** 2)) <= 1e-12 * max(br.loss(f), 1e-300)
+
+
+def test_undefined_topology_is_an_error_in_both():
+    sizes = [40, 16, 32, 56]                    # mode 0 reads delta_{l+1} past its end (the oracle's -1)
+    w, b = _params(sizes, 2)
+    x = np.random.default_rng(0).uniform(-1, 1, (3, 40))
+    gw, gb = np.zeros_like(w), np.zeros_like(b)
+    assert xo.nn_accum_grad(sizes, w, b, x[0], np.zeros(56), 0, gw, gb) == -1
+    net = br.Net(sizes, w, b)
+    f = br.forward(net, x, x, [1, 2, 3], [0.0, 0.0, 0.0], [0, 0, 1], 0.99, 0)
+    with pytest.raises(br.UndefinedTopology):
+        br.backward(net, f, 0)
+    br.backward(net, f, 1)
+
+
+def test_bf16_round_matches_the_oracle():
+    rng = np.random.default_rng(0)
+    v = np.concatenate([rng.standard_normal(3000) * 10.0 ** rng.integers(-30, 30, 3000), [0.0, -0.0, np.inf, -np.inf, np.nan, 3.3895314e38,
+                        1.0 + 2.0 ** -8, 1.0 + 3 * 2.0 ** -8, 1.0 + 2.0 ** -9]]).astype(np.float32)
+    want = np.array([xo.lib().xqo_bf16_round(float(x)) for x in v], np.float32)
+    got = br.bf16_round(v).astype(np.float32)
+    assert np.array_equal(got.view(np.uint32), want.view(np.uint32))
+
+
+# ------------------------------------------------------------------------------------------------ negative controls
+def _full_batch(trace, n, seed):
+    """n transitions of the reference trace drawn with replacement (rewards /100), every 9th terminal"""
+    S, A, R, D, S2 = transitions(trace, valid_indices(trace, 600, seed=seed))
+    pick = np.random.default_rng(seed).integers(0, len(S), n)
+    D = D[pick].copy()
+    D[::9] = 1
+    return S[pick], A[pick], (R[pick] * 10.0 / 1000.0).astype(np.float32), D, S2[pick]
+
+
+def _worst(net, u_ref, gw, gb, lr, scale, prec):
+    """max err / bound when a device had computed the gradient (gw, gb) and stored the result in fp32"""
+    new_w = (net.w - lr * scale * gw).astype(np.float32).astype(np.float64)
+    new_b = (net.b - lr * scale * gb).astype(np.float32).astype(np.float64)
+    return br.update_ratios(net, u_ref, new_w, new_b, lr, scale, prec)
+
+
+def _controls(net, f, bk, prec, lr, scale, chunk, ragged, extra=()):
+    n = f.n
+    u = br.accumulate(net, f, bk, prec)
+    gw, gb = br.flat_grads(net, u)
+    ok = _worst(net, u, gw, gb, lr, scale, prec)
+    assert max(ok.values()) <= 0.5, ok                                 # the reference passes its own bound: only its fp32 store rounds
+    variants = {}
+    m = np.ones(n, bool); m[chunk:2 * chunk] = False
+    variants["one chunk missing"] = br.accumulate(net, f, bk, prec, mask=m)
+    lone = int(np.nonzero(~f.D)[0][-1])
+    m = np.ones(n, bool); m[lone] = False
+    variants["one sample missing"] = br.accumulate(net, f, bk, prec, mask=m)
+    if ragged:
+        nr = n - 37                                                    # ragged n; its last n mod 64 samples dropped
+        keep = np.arange(n) < nr
+        u_r = br.accumulate(net, f, bk, prec, mask=keep)
+        variants["ragged tail missing"] = (u_r, br.accumulate(net, f, bk, prec, mask=np.arange(n) < nr - nr % 64))
+    variants["other backprop mode"] = br.accumulate(net, f, br.backward(net, f, 1 - bk.mode, prec, bk.weights), prec)
+    variants.update(extra)
+    seen = {}
+    for name, v in variants.items():
+        ref = u
+        if isinstance(v, tuple):
+            ref, v = v
+        r = _worst(net, ref, *br.flat_grads(net, v), lr, scale, prec)
+        seen[name] = max(r.values())
+        if name == "one sample missing":
+            # visible in the W0 columns of its board, and in fp32 in the output row of its action as well (the bf16 modes' output
+            # layer carries the bf16 forward's Q error in its budget)
+            assert r["w0"] >= 4.0 and (prec != 0 or r[f"w{net.nl - 1}"] >= 4.0), (name, r)
+    return seen
+
+
+def test_comparator_rejects_full_size_bugs_fp32(trace):
+    """CFG2, n = 8192, fp32, online rule, mode 0 (the bench headline's arithmetic)."""
+    sizes, n, lr, scale = CFG2_NET, 8192, 1.0, 16.0 / 8192
+    S, A, R, D, S2 = _full_batch(trace, n, seed=11)
+    w, b = _params(sizes, 7)
+    w, b = w.astype(np.float32).astype(np.float64), b.astype(np.float32).astype(np.float64)
+    net = br.Net(sizes, w, b)
+    f = br.forward(net, S, S2, A, R, D, 0.99, 0)
+    bk = br.backward(net, f, 0)
+    bk.mode = 0
+    seen = _controls(net, f, bk, 0, lr, scale, 1024, ragged=True)
+    assert min(seen.values()) >= 4.0, seen
+
+
+def test_comparator_rejects_full_size_bugs_bf16_full(trace):
+    """CFG4, n = 16384, bf16 everywhere (precision 2), Double DQN, importance weights (config 5's arithmetic)."""
+    sizes, n, lr, scale, prec = CFG4_NET, 16384, 1.0, 16.0 / 16384, 2
+    S, A, R, D, S2 = _full_batch(trace, n, seed=12)
+    w, b = _params(sizes, 8)
+    wt, bt = _params(sizes, 9)
+    w, b = w.astype(np.float32).astype(np.float64), b.astype(np.float32).astype(np.float64)
+    wts = np.random.default_rng(2).uniform(0.2, 1.0, n)
+    net = br.Net(sizes, w, b, prec)
+    tnet = br.Net(sizes, wt, bt, prec)
+    f = br.forward(net, S, S2, A, R, D, 0.99, 2, prec, target=tnet)
+    bk = br.backward(net, f, 0, prec, wts)
+    bk.mode = 0
+    # the fp32 forward (no bf16 rounding) under the same backward
+    net32 = br.Net(sizes, w, b, 0)
+    f32 = br.forward(net32, S, S2, A, R, D, 0.99, 2, prec, target=br.Net(sizes, wt, bt, 0))
+    u32 = br.accumulate(net32, f32, br.backward(net32, f32, 0, prec, wts), prec)
+    seen = _controls(net, f, bk, prec, lr, scale, 2048, ragged=False, extra={"fp32 forward": u32})
+    assert min(seen.values()) >= 4.0, seen

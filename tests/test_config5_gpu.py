@@ -69,7 +69,7 @@ def test_double_dqn_td_update_matches_oracle(xq, trace, sizes, mode, n):
 
 def test_double_dqn_persistent_argmax_kernel(xq, trace):
     """n = 1100 samples: the persistent column-ARG-max GEMM (128x128 tiles, 2 blocks per CU) instead of the plain kernel.
-    y must be the target net's value at the online net's first maximum (near-ties within 2e-6 of the maximum accepted)."""
+    y must be the target net's value at the online net's first maximum (near-ties within 2e-6 of the maximum accepted), every sample."""
     sizes, n = CFG2_NET, 1100
     idx = valid_indices(trace, n, seed=9)
     S, A, R, D, S2 = transitions(trace, idx)
@@ -79,7 +79,7 @@ def test_double_dqn_persistent_argmax_kernel(xq, trace):
     R = R / 1000.0
     qsa, y = d.td_update(S, S2, A, R, D, td_net=xq._capi.TD_DOUBLE, mode=0, learning_rate=0.0, grad_scale=1.0)
     exact = 0
-    for i in range(0, n, 7):
+    for i in range(n):
         if D[i]:
             assert abs(y[i] - R[i]) < 1e-6
             continue
@@ -91,7 +91,7 @@ def test_double_dqn_persistent_argmax_kernel(xq, trace):
         ys = R[i] + 0.99 * np.tanh(zt[cand])
         assert np.abs(ys - y[i]).min() < QTOL, i
         exact += abs(R[i] + 0.99 * np.tanh(zt[star]) - y[i]) < QTOL
-    assert exact > 100
+    assert exact > 700                                    # was > 100 of every 7th sample
     d.close()
 
 

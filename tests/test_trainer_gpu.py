@@ -377,7 +377,8 @@ def test_bench_composition_against_the_oracle_directly(xq):
     """the 8192-wide loop EXACTLY as bench.py configures it — 1 M-slot ring filled to capacity, collect overlapped on its
     own stream, exact screening of max_a' Q(s',a'), layer 0 of s' derived, TD target inside the refine blocks, fused tail launches, slab
     sums inside the SGD kernel — checked against the fp64 oracle itself, not through another HIP path: Q(s,a) and y of 64 transitions
-    of the last minibatch, and the update of one output row + bias (every sample of that action, ~90 backward passes in fp64).
+    of the last minibatch, and the update of one output row + bias (every sample of that action, ~90 backward passes in fp64); then
+    Q(s,a), y of all n samples and every parameter against the batched fp64 reference (tests/batch_ref.py).
     The minibatch is re-derived on the host from the trainer's documented Philox stream and sampling window."""
     from cn_chess_ai_amd import _capi
     from test_dqn_gpu import QTOL, PTOL
@@ -447,6 +448,16 @@ def test_bench_composition_against_the_oracle_directly(xq):
     assert np.abs(w3[row] - want_w).max() < PTOL and abs(b3[512 + a_star] - want_b) < PTOL
     # ... and the step was not a no-op on that row
     assert np.abs(w3[row] - w2[row]).max() > 0
+    # Q(s,a) and y of all n samples and the whole parameter set after the third update, against the batched fp64 reference
+    import batch_ref as br
+    for i in range(n):
+        transition(i)
+    S, A, R, D, S2 = (np.array([trans[i][k] for i in range(n)]) for k in range(5))
+    net = br.Net(CFG2_NET, w2, b2)
+    f = br.forward(net, S, S2, A, R, D, 0.99, 0)
+    br.check_q_y(f, qsa, y, br.PRECISION_F32)
+    u = br.accumulate(net, f, br.backward(net, f, 0))
+    br.check_update(net, u, f, w3, b3, lr, 1.0 / n, br.PRECISION_F32)
     t.close()
 
 
