@@ -58,7 +58,8 @@ class Search:
         return f"Search({self.depth}, eps={self.eps})"
 
 
-def _player(p, eps):
+def player(p, eps=0.0):
+    """The _capi.ArenaPlayer of None (uniform-random play), a Search, or a DQN that explores with eps."""
     if p is None:
         return _capi.ArenaPlayer(_capi.PLAYER_RANDOM, None, 0, 0.0)
     if isinstance(p, Search):
@@ -107,7 +108,7 @@ class Arena:
         the networks' exploration (a Search carries its own).  -> plies played."""
         n = C.c_int32()
         if isinstance(dqn_a, Search) or isinstance(dqn_b, Search):
-            pa, pb = _player(dqn_a, eps_a), _player(dqn_b, eps_b)
+            pa, pb = player(dqn_a, eps_a), player(dqn_b, eps_b)
             call("xq_arena_run_players", self._h, C.byref(pa), C.byref(pb), int(max_plies), C.byref(n))
             return n.value
         call("xq_arena_run", self._h, dqn_a.handle if dqn_a is not None else None,

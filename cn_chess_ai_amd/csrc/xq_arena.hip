@@ -1,12 +1,12 @@
-// xq_arena.hip — head-to-head evaluation: player A against player B over P pairs of games, all 2P games on one device.
+// xq_arena.hip — head-to-head evaluation: player A against player B over P pairs of games, all 2P games on one device;
+// and xq::CheckedPlayer, "someone who moves on an env", for the arena's two sides and the trainer's opponent (xq_trainer.hip): make_player
+// holds the validation of an xq_arena_player, borrowed_forward the one way a lent network is run.
 //
-// Per ply: the Q rows of each half of the games through the network of the player that moves there (xq_dqn_forward_boards_dev on that
-// network's stream, ordered by events) or that half's search picks (search_kernel, xq_search.hip, on the arena's stream), then one
-// env_kernel<MODE_ARENA> launch (xq_env.hip) that plays the ply, freezes the games it ends and writes their records.  The networks are
-// borrowed: the forwards keep no layer-0 sums, touch no TD-step state and are not counted by the handle's kernel statistics.
+// Per ply: the Q rows of each half of the games through the network of the player that moves there (borrowed_forward, on that network's
+// stream, ordered by events) or that half's search picks (search_kernel, xq_search.hip, on the arena's stream), then one
+// env_kernel<MODE_ARENA> launch (xq_env.hip) that plays the ply, freezes the games it ends and writes their records.
 #include "xq_internal.h"
 
-#include <algorithm>
 #include <cmath>
 #include <vector>
 
@@ -26,9 +26,51 @@ struct xq_arena {
     hipEvent_t ev_env = nullptr, ev_q[2] = {nullptr, nullptr};
 };
 
-namespace {
+namespace xq {
 
-uint32_t eps_u32(double eps) { return (uint32_t)std::min(std::max(eps, 0.0) * 4294967296.0, 4294967295.0); }
+int make_player(const xq_arena_player* in, const char* who, CheckedPlayer* out) {
+    *out = CheckedPlayer();
+    if (!in || in->kind == XQ_PLAYER_RANDOM) return XQ_OK;
+    const xq_arena_player& x = *in;
+    if (x.kind != XQ_PLAYER_NET && x.kind != XQ_PLAYER_SEARCH) return fail(XQ_ERR_INVALID_ARGUMENT, "%s has an unknown kind %d", who, x.kind);
+    if (!(x.eps >= 0.0 && x.eps <= 1.0)) return fail(XQ_ERR_INVALID_ARGUMENT, "%s epsilon must be in [0, 1]", who);
+    out->kind = x.kind;
+    out->eps_u32 = eps_to_u32(x.eps);
+    if (x.kind == XQ_PLAYER_SEARCH) {
+        if (x.depth < 1 || x.depth > 3) return fail(XQ_ERR_INVALID_ARGUMENT, "%s search depth must be 1, 2 or 3 (got %d)", who, x.depth);
+        out->depth = x.depth;
+        return XQ_OK;
+    }
+    if (!x.dqn) return fail(XQ_ERR_INVALID_ARGUMENT, "%s is a network player without a network", who);
+    int nin = 0, nout = 0;
+    dqn_shape(x.dqn, &nin, &nout);
+    if (nin != kStateSize || nout < 90)
+        return fail(XQ_ERR_INVALID_ARGUMENT, "%s needs layer_sizes[0] == 1260 and >= 90 outputs (got %d -> %d)", who, nin, nout);
+    out->net = x.dqn;
+    out->n_out = std::min(nout, 96);
+    return XQ_OK;
+}
+
+int borrowed_forward(xq_dqn* d, const uint32_t* boards_dev, int n, int n_out, float* q_rows_dev, hipStream_t s, hipEvent_t ev_env,
+                     hipEvent_t ev_q) {
+    hipStream_t ds = dqn_stream(d);
+    if (ds != s) XQ_HIP(hipStreamWaitEvent(ds, ev_env, 0));
+    Profiler* prof = dqn_profiler(d);
+    const bool was = prof->enabled;
+    prof->enabled = false;                   // not the handle's work
+    const int rc = xq_dqn_forward_boards_dev(d, XQ_NET_ONLINE, boards_dev, n, n_out, q_rows_dev, 96);
+    prof->enabled = was;
+    XQ_TRY(rc);
+    if (ds != s) {
+        XQ_HIP(hipEventRecord(ev_q, ds));
+        XQ_HIP(hipStreamWaitEvent(s, ev_q, 0));
+    }
+    return XQ_OK;
+}
+
+}  // namespace xq
+
+namespace {
 
 int read_live(xq_arena* a, int* n) {
     XQ_HIP(hipMemcpyAsync(a->live_host, a->live, sizeof(int), hipMemcpyDeviceToHost, a->env->stream));
@@ -40,80 +82,43 @@ int read_live(xq_arena* a, int* n) {
 // the mover of half h (0: A is Red there) at the arena's current ply: Red moves on even plies
 int mover_of_half(const xq_arena* a, int h) { return ((a->ply & 1) ^ h) == 0 ? 0 : 1; }   // 0 = A, 1 = B
 
-int launch_ply(xq_arena* a, const float* q, int q_stride, const double eps[2], const bool has_q[2], const int depth[2] = nullptr) {
+// one ply of players pl on the Q rows q of the halves a network player moves in (its own, or the caller's: xq_arena_ply_q_dev)
+int launch_ply(xq_arena* a, const float* q, int q_stride, const CheckedPlayer pl[2]) {
     uint32_t e[2];
     int hq[2], pick_on[2];
     for (int h = 0; h < 2; ++h) {
-        const int p = mover_of_half(a, h);
-        e[h] = eps_u32(eps[p]);
-        hq[h] = has_q[p] ? 1 : 0;
-        pick_on[h] = depth && depth[p] > 0 && a->ply >= a->opening ? 1 : 0;
+        const CheckedPlayer& p = pl[mover_of_half(a, h)];
+        e[h] = p.eps_u32;
+        hq[h] = p.kind == XQ_PLAYER_NET ? 1 : 0;
+        pick_on[h] = p.kind == XQ_PLAYER_SEARCH && a->ply >= a->opening ? 1 : 0;
         if (pick_on[h])      // the searching half's picks, on the arena's stream right ahead of the ply (frozen games are skipped)
-            XQ_TRY(search_pick_launch(a->env, depth[p], h * a->pairs, a->pairs, a->pairs, e[h], a->pick));
+            XQ_TRY(search_pick_launch(a->env, p.depth, h * a->pairs, a->pairs, a->pairs, false, e[h], a->pick, a->env->stream));
     }
     XQ_TRY(env_arena_launch(a->env, q, q_stride, a->pairs, a->opening, e, hq, a->rec, a->live, a->results, a->pick, pick_on));
     a->ply += 1;
     return XQ_OK;
 }
 
-// Q rows of half h through network d, on d's stream, behind the arena's last ply and ahead of its next
-int half_forward(xq_arena* a, xq_dqn* d, int h, int n_out) {
-    hipStream_t s = dqn_stream(d), as = a->env->stream;
-    if (s != as) XQ_HIP(hipStreamWaitEvent(s, a->ev_env, 0));
-    Profiler* prof = dqn_profiler(d);
-    const bool was = prof->enabled;
-    prof->enabled = false;                   // the arena's forwards are not the handle's work: they stay out of its kernel statistics
-    const size_t off = (size_t)h * a->pairs;
-    const int rc = xq_dqn_forward_boards_dev(d, XQ_NET_ONLINE, a->env->boards + off * kBoardWords, a->pairs, n_out, a->q + off * 96, 96);
-    prof->enabled = was;
-    XQ_TRY(rc);
-    if (s != as) {
-        XQ_HIP(hipEventRecord(a->ev_q[h], s));
-        XQ_HIP(hipStreamWaitEvent(as, a->ev_q[h], 0));
-    }
-    return XQ_OK;
-}
-
-// one player of the arena: a network (net), the material search (depth > 0) or uniform-random play (neither)
-struct Policy {
-    xq_dqn* net = nullptr;
-    int depth = 0;
-    double eps = 0.0;
-};
-
-int check_net(xq_dqn* d, int* n_out) {
-    if (!d) return XQ_OK;
-    int nin = 0, nout = 0;
-    dqn_shape(d, &nin, &nout);
-    if (nin != kStateSize || nout < 90)
-        return fail(XQ_ERR_INVALID_ARGUMENT, "xq_arena: a player needs layer_sizes[0] == 1260 and >= 90 outputs (got %d -> %d)", nin, nout);
-    *n_out = std::min(nout, 96);
-    return XQ_OK;
-}
-
 // The play loop of xq_arena_run / xq_arena_run_players: every live game has played a->ply plies, and the 200-move cap ends every game
 // by ply 200; the live counter is read every kCheck plies (a read costs a stream synchronisation)
-int run_policies(xq_arena* a, const Policy pol[2], int max_plies, int* plies_played) {
-    int out[2] = {96, 96};
-    XQ_TRY(check_net(pol[0].net, &out[0]));
-    XQ_TRY(check_net(pol[1].net, &out[1]));
+int run_players(xq_arena* a, const CheckedPlayer pl[2], int max_plies, int* plies_played) {
     int live = 0;
     XQ_TRY(read_live(a, &live));
     if (live == 0) return fail(XQ_ERR_INVALID_ARGUMENT, "xq_arena_run: every game has finished (xq_arena_reset starts over)");
-    const double eps[2] = {pol[0].eps, pol[1].eps};
-    const bool has_q[2] = {pol[0].net != nullptr, pol[1].net != nullptr};
-    const int depth[2] = {pol[0].depth, pol[1].depth};
     int played = 0;
     constexpr int kCheck = 4;
     while (a->ply < 200 && (max_plies <= 0 || played < max_plies) && live > 0) {
         if (a->ply >= a->opening) {
-            XQ_HIP(hipEventRecord(a->ev_env, a->env->stream));
+            XQ_HIP(hipEventRecord(a->ev_env, a->env->stream));      // once per ply, for both halves
             for (int h = 0; h < 2; ++h) {
-                const int p = mover_of_half(a, h);
-                if (pol[p].net) XQ_TRY(half_forward(a, pol[p].net, h, out[p]));
+                const CheckedPlayer& p = pl[mover_of_half(a, h)];
+                const size_t off = (size_t)h * a->pairs;
+                if (p.net)
+                    XQ_TRY(borrowed_forward(p.net, a->env->boards + off * kBoardWords, a->pairs, p.n_out, a->q + off * 96, a->env->stream,
+                                            a->ev_env, a->ev_q[h]));
             }
         }
-        XQ_TRY(launch_ply(a, a->q, 96, eps, has_q, depth));
+        XQ_TRY(launch_ply(a, a->q, 96, pl));
         played += 1;
         if (played % kCheck == 0) XQ_TRY(read_live(a, &live));
     }
@@ -190,40 +195,30 @@ int xq_arena_ply_q_dev(xq_arena* a, const float* q_dev, int q_stride, double eps
     int live = 0;
     XQ_TRY(read_live(a, &live));
     if (live == 0) return fail(XQ_ERR_INVALID_ARGUMENT, "xq_arena_ply_q_dev: every game has finished");
-    const double eps[2] = {eps_a, eps_b};
-    const bool has_q[2] = {q_dev != nullptr, q_dev != nullptr};
-    return launch_ply(a, q_dev, q_stride, eps, has_q);
+    CheckedPlayer pl[2];       // network players whose rows the caller computed
+    pl[0].kind = pl[1].kind = q_dev ? XQ_PLAYER_NET : XQ_PLAYER_RANDOM;
+    pl[0].eps_u32 = eps_to_u32(eps_a);
+    pl[1].eps_u32 = eps_to_u32(eps_b);
+    return launch_ply(a, q_dev, q_stride, pl);
+}
+
+int xq_arena_run_players(xq_arena* a, const xq_arena_player* pa, const xq_arena_player* pb, int max_plies, int* plies_played) {
+    if (!a) return fail(XQ_ERR_INVALID_ARGUMENT, "null arena");
+    CheckedPlayer pl[2];
+    XQ_TRY(make_player(pa, "xq_arena_run_players: player A", &pl[0]));
+    XQ_TRY(make_player(pb, "xq_arena_run_players: player B", &pl[1]));
+    return run_players(a, pl, max_plies, plies_played);
 }
 
 int xq_arena_run(xq_arena* a, xq_dqn* dqn_a, xq_dqn* dqn_b, double eps_a, double eps_b, int max_plies, int* plies_played) {
     if (!a) return fail(XQ_ERR_INVALID_ARGUMENT, "null arena");
     if (!(eps_a >= 0.0 && eps_a <= 1.0 && eps_b >= 0.0 && eps_b <= 1.0)) return fail(XQ_ERR_INVALID_ARGUMENT, "epsilon must be in [0, 1]");
-    Policy pol[2];
-    pol[0].net = dqn_a; pol[0].eps = eps_a;
-    pol[1].net = dqn_b; pol[1].eps = eps_b;
-    return run_policies(a, pol, max_plies, plies_played);
-}
-
-int xq_arena_run_players(xq_arena* a, const xq_arena_player* pa, const xq_arena_player* pb, int max_plies, int* plies_played) {
-    if (!a) return fail(XQ_ERR_INVALID_ARGUMENT, "null arena");
-    Policy pol[2];
-    const xq_arena_player* in[2] = {pa, pb};
-    for (int p = 0; p < 2; ++p) {
-        const char* who = p == 0 ? "player A" : "player B";
-        if (!in[p]) continue;                                       // uniform-random play
-        const xq_arena_player& x = *in[p];
-        if (x.kind == XQ_PLAYER_RANDOM) continue;
-        if (x.kind != XQ_PLAYER_NET && x.kind != XQ_PLAYER_SEARCH)
-            return fail(XQ_ERR_INVALID_ARGUMENT, "xq_arena_run_players: %s has an unknown kind %d", who, x.kind);
-        if (!(x.eps >= 0.0 && x.eps <= 1.0)) return fail(XQ_ERR_INVALID_ARGUMENT, "xq_arena_run_players: %s epsilon must be in [0, 1]", who);
-        if (x.kind == XQ_PLAYER_NET && !x.dqn) return fail(XQ_ERR_INVALID_ARGUMENT, "xq_arena_run_players: %s is a network player without a network", who);
-        if (x.kind == XQ_PLAYER_SEARCH && (x.depth < 1 || x.depth > 3))
-            return fail(XQ_ERR_INVALID_ARGUMENT, "xq_arena_run_players: %s search depth must be 1, 2 or 3 (got %d)", who, x.depth);
-        pol[p].eps = x.eps;
-        if (x.kind == XQ_PLAYER_NET) pol[p].net = x.dqn;
-        else pol[p].depth = x.depth;
-    }
-    return run_policies(a, pol, max_plies, plies_played);
+    const xq_arena_player in[2] = {{dqn_a ? XQ_PLAYER_NET : XQ_PLAYER_RANDOM, dqn_a, 0, eps_a},
+                                   {dqn_b ? XQ_PLAYER_NET : XQ_PLAYER_RANDOM, dqn_b, 0, eps_b}};
+    CheckedPlayer pl[2];
+    XQ_TRY(make_player(&in[0], "xq_arena_run: player A", &pl[0]));
+    XQ_TRY(make_player(&in[1], "xq_arena_run: player B", &pl[1]));
+    return run_players(a, pl, max_plies, plies_played);
 }
 
 int xq_arena_results(xq_arena* a, xq_arena_game* records_host) {

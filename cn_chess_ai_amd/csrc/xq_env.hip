@@ -524,33 +524,39 @@ static EnvParams base_params(xq_env* e) {
     return P;
 }
 
-int env_selfplay_launch(xq_env* e, const float* q90_dev, int q_stride, uint32_t eps_u32, xq_step_result* results_dev,
-                        xq_replay* replay, hipStream_t on, const QSource* qs, hipEvent_t ev_start, hipEvent_t ev_stop) {
-    EnvParams P = base_params(e);
+// The Q values of a launch: finished rows q90_dev, or the k-slabs of the select head (qs && qs->slabs) for the kernel to finish
+static int set_q_source(EnvParams& P, const float* q90_dev, int q_stride, const QSource* qs) {
     P.q90 = q90_dev;
     P.q_stride = q_stride;
     if (qs && qs->slabs) {
         if (qs->nslabs < 2 || (qs->nslabs & 1)) return fail(XQ_ERR_INVALID_ARGUMENT, "select head slabs: even count >= 2");
         P.q90 = nullptr; P.q_slabs = qs->slabs; P.q_slab_stride = qs->slab_stride; P.q_nslabs = qs->nslabs; P.q_bias = qs->bias;
     }
+    return XQ_OK;
+}
+
+// the launch writes one transition per game into the ring, from write_pos on
+static int set_ring(EnvParams& P, const xq_replay* replay) {
+    if (replay->dev.capacity < P.n_games)
+        return fail(XQ_ERR_INVALID_ARGUMENT, "replay capacity %d < n_games %d", replay->dev.capacity, P.n_games);
+    P.rp = replay->dev;
+    P.rp_write_base = replay->write_pos;
+    return XQ_OK;
+}
+
+int env_selfplay_launch(xq_env* e, const float* q90_dev, int q_stride, uint32_t eps_u32, xq_step_result* results_dev,
+                        xq_replay* replay, hipStream_t on, const QSource* qs, hipEvent_t ev_start, hipEvent_t ev_stop) {
+    EnvParams P = base_params(e);
+    XQ_TRY(set_q_source(P, q90_dev, q_stride, qs));
     P.eps_u32 = eps_u32;
     P.results = results_dev;
-    if (replay != nullptr) {
-        if (replay->dev.capacity < e->n)
-            return fail(XQ_ERR_INVALID_ARGUMENT, "replay capacity %d < n_games %d", replay->dev.capacity, e->n);
-        P.rp = replay->dev;
-        P.rp_write_base = replay->write_pos;
-    }
+    if (replay != nullptr) XQ_TRY(set_ring(P, replay));
     const int blocks = (e->n + 3) / 4;
     if (replay != nullptr) XQ_TRY(replay_writer_begin(replay, on ? on : e->stream));    // (costs nothing when the ring's users share this stream)
     if (ev_start || ev_stop) hipExtLaunchKernelGGL(env_kernel<MODE_SELFPLAY>, dim3(blocks), dim3(256), 0, on ? on : e->stream, ev_start, ev_stop, 0, P);
     else hipLaunchKernelGGL(env_kernel<MODE_SELFPLAY>, dim3(blocks), dim3(256), 0, on ? on : e->stream, P);
     XQ_HIP(hipGetLastError());
-    if (replay != nullptr) {
-        replay->write_pos = (replay->write_pos + e->n) % replay->dev.capacity;
-        replay->size = std::min(replay->dev.capacity, replay->size + e->n);
-        replay->total += (uint64_t)e->n;
-    }
+    if (replay != nullptr) replay_advance(replay, e->n);
     return XQ_OK;
 }
 
@@ -584,17 +590,10 @@ int env_arena_launch(xq_env* e, const float* q90_dev, int q_stride, int pairs, i
 int env_versus_launch(xq_env* e, int phase, const float* q90_dev, int q_stride, const QSource* qs, uint32_t eps_u32, const int16_t* pick_dev,
                       uint4* counts_dev, xq_replay* replay, hipStream_t on) {
     if (phase < 0 || phase > 2 || replay == nullptr || counts_dev == nullptr) return fail(XQ_ERR_INVALID_ARGUMENT, "env_versus_launch: bad argument");
-    if (replay->dev.capacity < e->n) return fail(XQ_ERR_INVALID_ARGUMENT, "replay capacity %d < n_games %d", replay->dev.capacity, e->n);
     EnvParams P = base_params(e);
-    P.q90 = q90_dev;
-    P.q_stride = q_stride;
-    if (phase == 1 && qs && qs->slabs) {
-        if (qs->nslabs < 2 || (qs->nslabs & 1)) return fail(XQ_ERR_INVALID_ARGUMENT, "select head slabs: even count >= 2");
-        P.q90 = nullptr; P.q_slabs = qs->slabs; P.q_slab_stride = qs->slab_stride; P.q_nslabs = qs->nslabs; P.q_bias = qs->bias;
-    }
+    XQ_TRY(set_ring(P, replay));
+    XQ_TRY(set_q_source(P, q90_dev, q_stride, phase == 1 ? qs : nullptr));
     P.eps_u32 = eps_u32;
-    P.rp = replay->dev;
-    P.rp_write_base = replay->write_pos;
     P.vs_phase = phase;
     P.vs_pick = phase == 1 ? nullptr : pick_dev;
     P.vs_counts = counts_dev;

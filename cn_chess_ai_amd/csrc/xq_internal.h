@@ -3,6 +3,7 @@
 
 #include "xq_common.h"
 
+#include <algorithm>
 #include <vector>
 
 namespace xq {
@@ -244,6 +245,7 @@ int replay_sample_implicit(xq_replay* r, int batch, int start = 0, int count = -
 // cross-stream ordering of the ring's users (SharedResource; no-ops on one stream or when the owner orders: xq_replay::caller_orders)
 int replay_consumer_begin(xq_replay* r, hipStream_t consumer, bool listed, bool prioritized);   // a TD step that reads the ring
 int replay_writer_begin(xq_replay* r, hipStream_t writer);                                      // an env step that writes it
+void replay_advance(xq_replay* r, int n);   // n transitions were written (or queued) from write_pos on: moves write_pos, size and total
 // prioritized replay internals used by the trainer (xq_replay.hip)
 int replay_per_rebuild(xq_replay* r, int retire_start, int retire_count, hipStream_t on);
 int replay_per_sample(xq_replay* r, int batch, hipStream_t on);
@@ -256,13 +258,34 @@ int env_arena_launch(xq_env* env, const float* q90_dev, int q_stride, int pairs,
                      const int has_q[2], xq_arena_game* records_dev, int* live_dev, xq_step_result* results_dev,
                      const int16_t* pick_dev, const int pick_on[2]);   // xq_arena.hip
 void dqn_shape(const xq_dqn* d, int* n_in, int* n_out);    // layer_sizes[0], outputs
-int search_pick_launch(xq_env* env, int depth, int first, int count, int pairs, uint32_t eps_u32, int16_t* pick_dev);   // xq_search.hip
 constexpr uint32_t kMetaFrozen = 1u << 20;                  // meta.x flag of a finished arena game (xq_env.hip META_FROZEN)
 constexpr uint32_t kMetaVsDone = 1u << 21;                  // meta.x flag: the game's versus slot of this collect is written (META_VS_DONE)
 // versus training (xq_trainer_set_opponent): one phase of the collect, see env_versus_launch in xq_env.hip
 int env_versus_launch(xq_env* env, int phase, const float* q90_dev, int q_stride, const QSource* qs, uint32_t eps_u32,
                       const int16_t* pick_dev, uint4* counts_dev, xq_replay* replay, hipStream_t on);
-// the search player's picks of the games where the opponent of the learner is to move (xq_search.hip), on stream s
-int search_versus_launch(xq_env* env, int depth, uint32_t eps_u32, int16_t* pick_dev, hipStream_t s);
+// The search player's picks (xq_search.hip) of games [first, first + count) of env, on stream s: pick_dev[g] = an index into game g's
+// move list.  Arena: ties are broken on the stream of the pair (twin g - pairs).  seated (versus training, pairs = INT_MAX): only the
+// games where the learner's opponent is to move, ties on the game's own stream.
+int search_pick_launch(xq_env* env, int depth, int first, int count, int pairs, bool seated, uint32_t eps_u32, int16_t* pick_dev,
+                       hipStream_t s);
+
+// ---- a player that moves on an env: the arena's two sides and the trainer's opponent (defined in xq_arena.hip) ----------------------
+// floor(eps * 2^32), saturated: the threshold the env kernel holds a Philox word against (vecenv.eps_to_u32 is the Python mirror)
+inline uint32_t eps_to_u32(double eps) { return (uint32_t)std::min(std::max(eps, 0.0) * 4294967296.0, 4294967295.0); }
+struct CheckedPlayer {
+    int kind = XQ_PLAYER_RANDOM;
+    xq_dqn* net = nullptr;      // XQ_PLAYER_NET: borrowed
+    int depth = 0;              // XQ_PLAYER_SEARCH: 1..3
+    uint32_t eps_u32 = 0;       // (0 for random play: every move explores anyway)
+    int n_out = 96;             // XQ_PLAYER_NET: the Q columns to compute, min(outputs, 96)
+};
+// in == nullptr: uniform-random play.  `who` opens the message of a rejected player ("xq_arena_run_players: player A")
+int make_player(const xq_arena_player* in, const char* who, CheckedPlayer* out);
+// Q rows [n][96] of n boards through the borrowed network d, on d's own stream: behind ev_env, which the caller has recorded on the
+// consumer stream s behind the env's last launch, and ahead of whatever s queues next (ev_q; neither event is touched when d runs on
+// s).  The forward keeps no layer-0 sums, touches no TD-step state and stays out of the handle's kernel statistics, so a lent network
+// has the same bits afterwards.
+int borrowed_forward(xq_dqn* d, const uint32_t* boards_dev, int n, int n_out, float* q_rows_dev, hipStream_t s, hipEvent_t ev_env,
+                     hipEvent_t ev_q);
 inline int round_up(int a, int b) { return (a + b - 1) / b * b; }
 }  // namespace xq

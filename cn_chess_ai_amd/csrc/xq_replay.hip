@@ -237,6 +237,12 @@ int replay_writer_begin(xq_replay* r, hipStream_t writer) {
     return XQ_OK;
 }
 
+void replay_advance(xq_replay* r, int n) {
+    r->write_pos = (r->write_pos + n) % r->dev.capacity;
+    r->size = std::min(r->dev.capacity, r->size + n);
+    r->total += (uint64_t)n;
+}
+
 int replay_sample_implicit(xq_replay* r, int batch, int start, int count) {
     if (!r || batch <= 0) return fail(XQ_ERR_INVALID_ARGUMENT, "replay_sample_implicit: batch must be > 0");
     if (count < 0) { start = 0; count = r->size; }
@@ -336,9 +342,7 @@ int xq_replay_push_host(xq_replay* r, int n, const uint8_t* boards90, const int3
                                action_to[i] >= 0 ? r->per.scalars + 0 : nullptr, 0.f);
             XQ_HIP(hipGetLastError());
         }
-        r->write_pos = (r->write_pos + 1) % r->dev.capacity;
-        if (r->size < r->dev.capacity) r->size++;
-        r->total++;
+        replay_advance(r, 1);
     }
     if (r->per.enabled) XQ_HIP(hipStreamSynchronize(r->stream));
     return XQ_OK;

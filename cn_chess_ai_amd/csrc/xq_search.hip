@@ -224,23 +224,14 @@ SearchParams base(const xq_env* e, int first) {
 
 }  // namespace
 
-// Arena pick for games [first, first + count) of e, on e's stream (xq_arena.hip): pick_dev[g] = the index into game g's move list
-int search_pick_launch(xq_env* e, int depth, int first, int count, int pairs, uint32_t eps_u32, int16_t* pick_dev) {
+// The search player's picks for games [first, first + count) of e on stream s (xq_internal.h).  seated: ties are broken on the game's
+// own stream (ctr {plies, 0, first_game_id + g, 3}: no twin); the epsilon draw is the env kernel's either way
+int search_pick_launch(xq_env* e, int depth, int first, int count, int pairs, bool seated, uint32_t eps_u32, int16_t* pick_dev, hipStream_t s) {
     SearchParams P = base(e, first);
     P.pick = pick_dev;
     P.eps_u32 = eps_u32;
     P.pairs = pairs;
-    return launch<true>(P, depth, count, e->stream);
-}
-
-// Versus pick for every game of e where the learner's opponent is to move, on stream s: ties are broken on the game's own stream
-// (ctr {plies, 0, first_game_id + g, 3}: no twin), the epsilon draw is the env kernel's
-int search_versus_launch(xq_env* e, int depth, uint32_t eps_u32, int16_t* pick_dev, hipStream_t s) {
-    SearchParams P = base(e, 0);
-    P.pick = pick_dev;
-    P.eps_u32 = eps_u32;
-    P.pairs = INT_MAX;
-    return launch<true, true>(P, depth, e->n, s);
+    return !seated ? launch<true>(P, depth, count, s) : launch<true, true>(P, depth, count, s);
 }
 
 }  // namespace xq

@@ -7,14 +7,17 @@
 //   learn   : sample -> TD gradients (xq_dqn_td_grads) -> [caller all-reduces the gradient buffer over RCCL] -> SGD;
 //   target  : updateTargetNetwork() every target_sync_interval updates (chessai.cpp:140 uses moveCount % 100).
 // With an opponent (xq_trainer_set_opponent, DESIGN.md §4 "Versus training") a collect is the learner's half-ply between two of the
-// opponent's: [its pick] -> env pre-move -> select chain -> env learner half-ply -> [its pick] -> env reply, all on the collect stream; a
-// network opponent's forwards run on its own stream, ordered by events like the arena's.
+// opponent's: [its pick] -> env pre-move -> select chain -> env learner half-ply -> [its pick] -> env reply, all on the collect stream
+// (versus_collect).  The opponent is an xq::CheckedPlayer, validated and run by the code the arena's players use (make_player,
+// borrowed_forward: xq_arena.hip); a network opponent's forwards run on its own stream, ordered by events.
 // No host round trip inside an iteration; everything is queued on one HIP stream — or, with cfg.overlap_collect, collect
 // goes to a second stream: collect(t) and learn_grads(t) both read theta_t, learn_grads(t) samples the ring minus the
 // slots collect(t) is writing, learn_apply(t) joins both before theta_{t+1} is written.  Preferred call order there:
 // learn_grads, collect, learn_apply — collect then starts behind the column-max GEMM (which wants the chip to itself) and
 // runs beside the gradient chain, which is a string of small latency-bound kernels.  collect-first is also accepted.
 #include "xq_internal.h"
+
+#include <climits>
 
 struct xq_trainer {
     xq_trainer_config cfg;
@@ -45,12 +48,10 @@ struct xq_trainer {
     uint64_t params_version = 0;            // dqn_params_version() when ev_params was last recorded: anything that rewrote parameters on the
                                             // handle's stream since (set_params on a bf16 net, an apply_grads of the caller's own) lies
                                             // BEHIND that record, and the select chain must not start in front of it
-    // versus training: the opponent (kind XQ_PLAYER_* as set; vs_on false = self-play), its picks / Q rows of the current phase, and the
-    // per-game outcome counters from the learner's side {wins, draws, losses, ended} since xq_trainer_set_opponent
+    // versus training: the opponent (vs_on false = self-play), its picks / Q rows of the current phase, and the per-game outcome
+    // counters from the learner's side {wins, draws, losses, ended} since xq_trainer_set_opponent
     bool vs_on = false;
-    xq_arena_player vs{};
-    uint32_t vs_eps = 0;
-    int vs_out = 96;
+    xq::CheckedPlayer vs;
     int16_t* vs_pick = nullptr;
     float* vs_q = nullptr;
     uint4* vs_counts = nullptr;
@@ -98,9 +99,7 @@ static int trainer_init(xq_trainer* t, const xq_trainer_config* cfg, void* hip_s
         XQ_TRY(xq_replay_enable_per(t->replay, cfg->per_alpha > 0 ? cfg->per_alpha : 0.6, cfg->per_beta > 0 ? cfg->per_beta : 0.4,
                                     cfg->per_eps > 0 ? cfg->per_eps : 1e-3));
     }
-    const double e = cfg->epsilon < 0 ? 0 : cfg->epsilon;
-    const double v = e * 4294967296.0;
-    t->eps_u32 = v >= 4294967295.0 ? 4294967295u : (uint32_t)v;
+    t->eps_u32 = eps_to_u32(cfg->epsilon);       // (a negative epsilon counts as 0)
     if (cfg->overlap_collect) {
         int lo = 0, hi = 0;
         XQ_HIP(hipDeviceGetStreamPriorityRange(&lo, &hi));        // lo = least urgent: collect has slack until learn_apply,
@@ -154,38 +153,35 @@ static int wait_collects(xq_trainer* t) {
 
 // The opponent's half-ply of a versus collect (phase 0: the pre-move, 2: the reply) on stream s: its picks, then the env launch
 static int versus_opponent(xq_trainer* t, int phase, hipStream_t s) {
+    const CheckedPlayer& o = t->vs;
     const int16_t* pick = nullptr;
     const float* q = nullptr;
-    if (t->vs.kind == XQ_PLAYER_SEARCH) {
-        XQ_TRY(search_versus_launch(t->env, t->vs.depth, t->vs_eps, t->vs_pick, s));
+    if (o.kind == XQ_PLAYER_SEARCH) {
+        XQ_TRY(search_pick_launch(t->env, o.depth, 0, t->env->n, INT_MAX, true, o.eps_u32, t->vs_pick, s));
         pick = t->vs_pick;
-    } else if (t->vs.kind == XQ_PLAYER_NET) {
-        // the borrowed network's forward on its own stream, behind the env's last launch and ahead of the next (as xq_arena.hip): no
-        // layer-0 sums kept, no TD-step state touched, left out of the handle's kernel statistics
-        xq_dqn* d = t->vs.dqn;
-        hipStream_t ds = dqn_stream(d);
-        if (ds != s) {
-            XQ_HIP(hipEventRecord(t->vs_ev_env, s));
-            XQ_HIP(hipStreamWaitEvent(ds, t->vs_ev_env, 0));
-        }
-        Profiler* prof = dqn_profiler(d);
-        const bool was = prof->enabled;
-        prof->enabled = false;
-        const int rc = xq_dqn_forward_boards_dev(d, XQ_NET_ONLINE, t->env->boards, t->env->n, t->vs_out, t->vs_q, 96);
-        prof->enabled = was;
-        XQ_TRY(rc);
-        if (ds != s) {
-            XQ_HIP(hipEventRecord(t->vs_ev_q, ds));
-            XQ_HIP(hipStreamWaitEvent(s, t->vs_ev_q, 0));
-        }
+    } else if (o.kind == XQ_PLAYER_NET) {
+        if (dqn_stream(o.net) != s) XQ_HIP(hipEventRecord(t->vs_ev_env, s));     // behind the env's last launch
+        XQ_TRY(borrowed_forward(o.net, t->env->boards, t->env->n, o.n_out, t->vs_q, s, t->vs_ev_env, t->vs_ev_q));
         q = t->vs_q;
     }
-    return env_versus_launch(t->env, phase, q, 96, nullptr, t->vs_eps, pick, t->vs_counts, t->replay, s);
+    return env_versus_launch(t->env, phase, q, 96, nullptr, o.eps_u32, pick, t->vs_counts, t->replay, s);
+}
+
+// A versus collect on stream s (`on`: the collect stream, if any): pre-move, select chain, learner half-ply, reply; one transition per
+// game, into the ring slots from write_pos, which moves once the last phase is queued
+static int versus_collect(xq_trainer* t, hipStream_t on, hipStream_t s) {
+    float* q90 = nullptr;
+    int stride = 0;
+    QSource qs;
+    XQ_TRY(versus_opponent(t, 0, s));
+    XQ_TRY(dqn_q90_boards(t->dqn, t->env->boards, t->env->n, &q90, &stride, on, &qs));
+    XQ_TRY(env_versus_launch(t->env, 1, q90, stride, &qs, t->eps_u32, nullptr, t->vs_counts, t->replay, s));
+    XQ_TRY(versus_opponent(t, 2, s));
+    replay_advance(t->replay, t->env->n);
+    return XQ_OK;
 }
 
 static int collect_impl(xq_trainer* t) {
-    float* q90 = nullptr;
-    int stride = 0;
     hipStream_t on = nullptr;
     if (t->cstream) {
         on = t->cstream;
@@ -218,34 +214,24 @@ static int collect_impl(xq_trainer* t) {
         }
     }
     hipStream_t s = on ? on : t->stream;
-    QSource qs;
     if (t->cfg.replay_capacity == 0) {           // on-policy: the ring is exactly one batch, refilled every ply
         t->replay->write_pos = 0;
         t->replay->size = 0;
     }
-    if (t->vs_on) {                              // versus: pre-move, select chain, learner half-ply, reply; one transition per game
-        XQ_TRY(versus_opponent(t, 0, s));
+    if (t->vs_on) {
+        XQ_TRY(versus_collect(t, on, s));
+    } else {
+        float* q90 = nullptr;
+        int stride = 0;
+        QSource qs;
         XQ_TRY(dqn_q90_boards(t->dqn, t->env->boards, t->env->n, &q90, &stride, on, &qs));
-        XQ_TRY(env_versus_launch(t->env, 1, q90, stride, &qs, t->eps_u32, nullptr, t->vs_counts, t->replay, s));
-        XQ_TRY(versus_opponent(t, 2, s));
-        xq_replay* r = t->replay;
-        r->write_pos = (r->write_pos + t->env->n) % r->dev.capacity;
-        r->size = std::min(r->dev.capacity, r->size + t->env->n);
-        r->total += (uint64_t)t->env->n;
-        t->env_steps += (uint64_t)t->env->n;
-        if (on) {
-            t->inflight += t->env->n;
-            t->collect_event_stale = true;
-        }
-        return XQ_OK;
+        Profiler* p = dqn_profiler(t->dqn);
+        const int h = p->begin("env_selfplay_step", s, true);       // one kernel: timed by its own start / stop events
+        XQ_TRY(env_selfplay_launch(t->env, q90, stride, t->eps_u32, nullptr, t->replay, on, &qs, h >= 0 ? p->recs[h].a : nullptr,
+                                   h >= 0 ? p->recs[h].b : nullptr));
+        // algorithmic HBM bytes per game and ply: board+meta in/out (2*(48+16)), Q row 360, transition 48+48+4+4+1
+        p->end(h, s, 0.0, (double)t->env->n * (2.0 * (48 + 16) + 360 + 105));
     }
-    XQ_TRY(dqn_q90_boards(t->dqn, t->env->boards, t->env->n, &q90, &stride, on, &qs));
-    Profiler* p = dqn_profiler(t->dqn);
-    const int h = p->begin("env_selfplay_step", s, true);       // one kernel: timed by its own start / stop events
-    XQ_TRY(env_selfplay_launch(t->env, q90, stride, t->eps_u32, nullptr, t->replay, on, &qs, h >= 0 ? p->recs[h].a : nullptr,
-                               h >= 0 ? p->recs[h].b : nullptr));
-    // algorithmic HBM bytes per game and ply: board+meta in/out (2*(48+16)), Q row 360, transition 48+48+4+4+1
-    p->end(h, s, 0.0, (double)t->env->n * (2.0 * (48 + 16) + 360 + 105));
     t->env_steps += (uint64_t)t->env->n;
     if (on) {
         t->inflight += t->env->n;
@@ -277,24 +263,9 @@ int xq_trainer_set_opponent(xq_trainer* t, const xq_arena_player* opp) {
     if (!t) return fail(XQ_ERR_INVALID_ARGUMENT, "null trainer");
     if (t->grads_queued || t->inflight > 0 || t->prepaid_collects > 0)
         return fail(XQ_ERR_RUNTIME, "xq_trainer_set_opponent: call between iterations (after learn_apply)");
-    if (opp) {
-        const xq_arena_player& x = *opp;
-        if (x.kind != XQ_PLAYER_RANDOM && x.kind != XQ_PLAYER_NET && x.kind != XQ_PLAYER_SEARCH)
-            return fail(XQ_ERR_INVALID_ARGUMENT, "xq_trainer_set_opponent: unknown kind %d", x.kind);
-        if (x.kind != XQ_PLAYER_RANDOM && !(x.eps >= 0.0 && x.eps <= 1.0))
-            return fail(XQ_ERR_INVALID_ARGUMENT, "xq_trainer_set_opponent: epsilon must be in [0, 1]");
-        if (x.kind == XQ_PLAYER_SEARCH && (x.depth < 1 || x.depth > 3))
-            return fail(XQ_ERR_INVALID_ARGUMENT, "xq_trainer_set_opponent: search depth must be 1, 2 or 3 (got %d)", x.depth);
-        if (x.kind == XQ_PLAYER_NET) {
-            if (!x.dqn) return fail(XQ_ERR_INVALID_ARGUMENT, "xq_trainer_set_opponent: a network opponent without a network");
-            if (x.dqn == t->dqn) return fail(XQ_ERR_INVALID_ARGUMENT, "xq_trainer_set_opponent: the opponent is the trainer's own network");
-            int nin = 0, nout = 0;
-            dqn_shape(x.dqn, &nin, &nout);
-            if (nin != kStateSize || nout < 90)
-                return fail(XQ_ERR_INVALID_ARGUMENT, "xq_trainer_set_opponent: the network needs 1260 inputs and >= 90 outputs (got %d -> %d)", nin, nout);
-            t->vs_out = std::min(nout, 96);
-        }
-    }
+    CheckedPlayer vs;
+    XQ_TRY(make_player(opp, "xq_trainer_set_opponent: the opponent", &vs));
+    if (vs.net && vs.net == t->dqn) return fail(XQ_ERR_INVALID_ARGUMENT, "xq_trainer_set_opponent: the opponent is the trainer's own network");
     // the previous collects are finished and nothing of the next one is queued: the buffers below are free
     if (t->cstream) XQ_HIP(hipStreamSynchronize(t->cstream));
     XQ_HIP(hipStreamSynchronize(t->stream));
@@ -309,9 +280,7 @@ int xq_trainer_set_opponent(xq_trainer* t, const xq_arena_player* opp) {
     }
     XQ_HIP(hipMemsetAsync(t->vs_counts, 0, n * sizeof(uint4), t->stream));
     XQ_HIP(hipStreamSynchronize(t->stream));
-    t->vs = *opp;
-    const double e = opp->kind == XQ_PLAYER_RANDOM ? 0.0 : opp->eps;
-    t->vs_eps = (uint32_t)std::min(e * 4294967296.0, 4294967295.0);
+    t->vs = vs;
     t->vs_on = true;
     return XQ_OK;
 }

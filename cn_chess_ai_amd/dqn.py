@@ -10,6 +10,7 @@ import numpy as np
 from . import _capi
 from ._capi import call, KernelStat, KernelSpan, TrainerConfig as _CConfig
 from .vecenv import VecEnv, ReplayBuffer, _ptr
+from .arena import Search, player
 
 REFERENCE_LAYERS = (1260, 128, 8100)     # ChessAI::initializeDQN, chessai.cpp:395-404
 
@@ -379,16 +380,15 @@ class Trainer:
         """Train against a fixed opponent from the next collect on (DESIGN.md §4 "Versus training"): None = self-play (the default),
         "random" = uniform-random play, an arena.Search(depth, eps) = the material search, (DQN, eps) = a borrowed network.  The
         learner plays Black in game g iff (first_game_id + g) is odd.  Call between iterations."""
-        from .arena import Search
         if opponent is None:
             call("xq_trainer_set_opponent", self._h, None)
             return
         if isinstance(opponent, str) and opponent == "random":
-            p = _capi.ArenaPlayer(_capi.PLAYER_RANDOM, None, 0, 0.0)
+            p = player(None)
         elif isinstance(opponent, Search):
-            p = _capi.ArenaPlayer(_capi.PLAYER_SEARCH, None, opponent.depth, opponent.eps)
+            p = player(opponent)
         elif isinstance(opponent, tuple) and len(opponent) == 2 and isinstance(opponent[0], DQN):
-            p = _capi.ArenaPlayer(_capi.PLAYER_NET, opponent[0].handle, 0, float(opponent[1]))
+            p = player(*opponent)
         else:
             raise TypeError(f"set_opponent: expected None, 'random', Search(depth, eps) or (DQN, eps), got {opponent!r}")
         call("xq_trainer_set_opponent", self._h, C.byref(p))
