@@ -81,6 +81,18 @@ inline void pack_board(const uint8_t* sq90, uint32_t words[kBoardWords]) {
         words[w] = v;
     }
 }
+// What makes a host board unacceptable to xq_env_set_state / xq_replay_push_host, or nullptr: a piece code above 14 (code 15 would
+// index one-hot plane 14 of 14), or more than kMaxSidePieces pieces of one colour (gen_all_actions ranks a side's pieces into a
+// 16-entry table and would list the moves of the first 16 only).
+constexpr int kMaxSidePieces = 16;
+inline const char* board_fault(const uint8_t* sq90) {
+    int n[2] = {0, 0};
+    for (int s = 0; s < kSquares; ++s) {
+        if (sq90[s] > 14) return "piece code > 14";
+        if (sq90[s] != 0) n[sq90[s] > 7] += 1;
+    }
+    return (n[0] > kMaxSidePieces || n[1] > kMaxSidePieces) ? "more than 16 pieces of one colour" : nullptr;
+}
 inline void unpack_board(const uint32_t words[kBoardWords], uint8_t* sq90) {
     for (int s = 0; s < kSquares; ++s) sq90[s] = (uint8_t)((words[s >> 3] >> (4 * (s & 7))) & 15u);
 }

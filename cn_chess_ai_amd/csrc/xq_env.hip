@@ -716,8 +716,7 @@ int xq_env_set_state(xq_env* e, int first, int n, const uint8_t* boards90, const
     std::vector<uint32_t> words((size_t)n * kBoardWords);
     std::vector<uint4> meta((size_t)n);
     for (int i = 0; i < n; ++i) {
-        for (int s = 0; s < kSquares; ++s)
-            if (boards90[(size_t)i * 90 + s] > 14) return fail(XQ_ERR_INVALID_ARGUMENT, "piece code > 14");
+        if (const char* why = board_fault(boards90 + (size_t)i * 90)) return fail(XQ_ERR_INVALID_ARGUMENT, "xq_env_set_state: board %d: %s", i, why);
         pack_board(boards90 + (size_t)i * 90, &words[(size_t)i * kBoardWords]);
         uint32_t mc = 0, pl = 0, rs = 0, bs = 0;
         if (meta4) {

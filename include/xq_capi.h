@@ -50,6 +50,10 @@
  *   - square  s = row*9 + col, rows 0..9 (Red home rows 0-4, Red moves +row: chessboard.cpp:12-28), cols 0..8;
  *   - piece code: 0 empty, 1..7 = Red General,Advisor,Elephant,Horse,Chariot,Cannon,Soldier, 8..14 = Black
  *     (PieceType/PieceColor, chessboard.h:8-14; code-1 is the one-hot plane of chessai.cpp:278-282);
+ *   - a board given on the host (xq_env_set_state, xq_replay_push_host) holds codes 0..14 and AT MOST 16 PIECES OF ONE COLOUR, of any
+ *     types on any squares; anything else is XQ_ERR_INVALID_ARGUMENT and nothing is written.  (The move generator ranks a side's
+ *     pieces into a 16-entry table; play from the start position never has more.)  A move list holds XQ_MAX_MOVES = 128 entries: a
+ *     side with more moves — only such arbitrary boards can have them — gets the first 128 in canonical order, count 128;
  *   - action code = from*90 + to  (Action{from,to}, action.h:4-11);
  *   - colours: 0 Red, 1 Black, 2 None (PieceColor, chessboard.h:12-14).
  */
@@ -124,7 +128,8 @@ int xq_env_stream(const xq_env* env, void** hip_stream);      /* the stream the 
 /* ChessBoard::reset() on every game (chessboard.cpp:95-102); also zeroes the RNG counters and episode counts. */
 int xq_env_reset(xq_env* env);
 /* Test/interop access to the state (no upstream analogue: upstream board is private).  boards90: [n][90] piece codes;
- * meta4: [n][4] = moveCount, currentPlayer, redScore, blackScore (chessboard.h:62-77). */
+ * meta4: [n][4] = moveCount, currentPlayer, redScore, blackScore (chessboard.h:62-77).  A board with a code above 14 or with more
+ * than 16 pieces of one colour is rejected (XQ_ERR_INVALID_ARGUMENT, no game changed). */
 int xq_env_set_state(xq_env* env, int first, int n, const uint8_t* boards90_host, const int32_t* meta4_host);
 int xq_env_get_state(xq_env* env, int first, int n, uint8_t* boards90_host, int32_t* meta4_host);
 /* ChessAI::getAllValidActions(player) for every game (chessai.cpp:347-368 over chessboard.cpp:112-283): canonical
@@ -158,7 +163,8 @@ int xq_env_rule_query(xq_env* env, int game, int piece_type, int from_row, int f
 typedef struct {
     int32_t action;      /* action code played, -1 if the side to move had no action (chessai.cpp:100-103) */
     int32_t n_moves;     /* size of the legal list the action was chosen from (0 for xq_env_step) */
-    int32_t reward;      /* evaluateBoard(mover, post-move count), chessai.cpp:311-345 */
+    int32_t reward;      /* evaluateBoard(mover, post-move count), chessai.cpp:311-345; where no move was made (action -1, or a
+                          * rejected move of xq_env_step) it is evaluateBoard(side to move, the unchanged count) of the untouched board */
     uint8_t captured;    /* piece code movePiece() returned (chessboard.cpp:38-64); 0 = none or invalid move */
     uint8_t valid;       /* 0: movePiece() rejected the move — no state change */
     uint8_t done;        /* checkGameOver() || moveCount+1 >= 200 (chessai.cpp:119) */
@@ -209,7 +215,8 @@ int xq_replay_create(int capacity, uint64_t seed, void* hip_stream, xq_replay** 
 int xq_replay_destroy(xq_replay* r);
 int xq_replay_size(xq_replay* r, int* size, int* capacity, uint64_t* total_pushed);
 int xq_replay_stream(const xq_replay* r, void** hip_stream);
-/* push(s, a, r, s', done) for n transitions given as 90-byte boards on the host (tests / interop). */
+/* push(s, a, r, s', done) for n transitions given as 90-byte boards on the host (tests / interop).  Boards as xq_env_set_state:
+ * a code above 14 or more than 16 pieces of one colour in s or s' is XQ_ERR_INVALID_ARGUMENT and nothing is pushed. */
 int xq_replay_push_host(xq_replay* r, int n, const uint8_t* boards90, const int32_t* action_to, const float* reward,
                         const uint8_t* done, const uint8_t* next_boards90);
 /* sample(B): uniform with replacement, Philox(ctr = {draw, 0, sample call #, 1}, key = seed) % size.

@@ -256,6 +256,157 @@ int cmdRuleMat(uint64_t seed, int npos, const char* path) {
     return 0;
 }
 
+// sparse: STEERED play of the unmodified engine, so that games run on into the regions uniform-random play never visits: bare
+// endgames (a side with 16 down to 0 pieces), soldiers of both colours on their far ranks, generals walked round their palaces,
+// and play that goes on after a general has fallen (movePiece allows it; there is no turn check either, so when the side to move
+// has no move the other side moves out of turn).  One policy per game, by game index:
+//   0 hunt     capture whenever possible, never the general while anything else can be done; otherwise step towards the
+//              nearest enemy piece
+//   1 march    push soldiers forward (non-capturing first), then sideways along the far side; otherwise as hunt
+//   2 walk     every other choice moves a general if it can; otherwise as hunt
+//   3 regicide any capture, the general included, and on from there until a side is bare
+// One Record per attempt (same layout as `trace`), games stay below the 200-move cap and each ends with one record whose attempt is
+// off the board (no state change), so record i + 1 of a game is always the state after attempt i.  For a subsample — dense among
+// positions with a side of <= 3 pieces or a soldier on a far rank — MATOUT receives board + the 8100 isValidMove results + the
+// 7 x 8100 results of the public per-piece validators (as `validmat` / `rulemat`; from == to skipped for chariot / cannon).
+int cmdSparse(uint64_t seed, int ngames, const char* path, const char* matpath) {
+    FILE* f = std::fopen(path, "wb");
+    if (!f) { std::perror(path); return 1; }
+    FILE* fm = std::fopen(matpath, "wb");
+    if (!fm) { std::perror(matpath); return 1; }
+    SplitMix64 rng(seed);
+    ChessBoard b;
+    long nrec = 0, nmat = 0;
+    auto rule = [&](int type, int fr, int fc, int tr, int tc) -> bool {
+        switch (type) {
+            case 1: return b.isValidGeneralMove(fr, fc, tr, tc);
+            case 2: return b.isValidAdvisorMove(fr, fc, tr, tc);
+            case 3: return b.isValidElephantMove(fr, fc, tr, tc);
+            case 4: return b.isValidHorseMove(fr, fc, tr, tc);
+            case 5: return b.isValidChariotMove(fr, fc, tr, tc);
+            case 6: return b.isValidCannonMove(fr, fc, tr, tc);
+            default: return b.isValidSoldierMove(fr, fc, tr, tc);
+        }
+    };
+    for (int g = 0; g < ngames; ++g) {
+        b.reset();
+        const int policy = g % 4;
+        int bare = 0;          // records written with a side that has no piece left
+        int turn = 0;
+        while (true) {
+            Record r;
+            snapshot(b, r);
+            if (r.moveCount >= 198) break;
+            int nPieces[2] = {0, 0};
+            bool farSoldier = false;
+            for (int s = 0; s < 90; ++s) {
+                const int c = r.board[s];
+                if (c) ++nPieces[c > 7];
+                if ((c == 7 && s >= 81) || (c == 14 && s < 9)) farSoldier = true;
+            }
+            if (nPieces[0] == 0 || nPieces[1] == 0) { if (++bare > 6) break; }
+            int mover = r.player;                                    // 0 red, 1 black
+            const uint16_t* list = mover == 0 ? r.red : r.black;
+            int n = mover == 0 ? r.nRed : r.nBlack;
+            if (n == 0) { mover ^= 1; list = mover == 0 ? r.red : r.black; n = mover == 0 ? r.nRed : r.nBlack; }   // out of turn
+            if (n == 0) break;
+            if (n > 128) n = 128;
+            // sort the moves into kinds
+            std::vector<int> capOther, capGeneral, quiet, soldierFwd, soldierSide, general;
+            for (int i = 0; i < n; ++i) {
+                const int from = list[i] / 90, to = list[i] % 90;
+                const int p = r.board[from], v = r.board[to];
+                const int type = p > 7 ? p - 7 : p;
+                if (v == 1 || v == 8) capGeneral.push_back(i);
+                else if (v) capOther.push_back(i);
+                else quiet.push_back(i);
+                if (type == 7 && !(v == 1 || v == 8)) {
+                    const int dr = to / 9 - from / 9;
+                    if (dr != 0 && !v) soldierFwd.push_back(i);
+                    if (dr == 0) soldierSide.push_back(i);
+                }
+                if (type == 1 && !(v == 1 || v == 8)) general.push_back(i);
+            }
+            auto any = [&](const std::vector<int>& v) { return v[rng.below((uint32_t)v.size())]; };
+            auto approach = [&]() -> int {                           // the quiet move that ends nearest to an enemy piece
+                if (quiet.empty()) return -1;
+                if (rng.below(4) == 0) return any(quiet);
+                int best = -1, bestD = 1 << 20, ties = 0;
+                for (int i : quiet) {
+                    const int to = list[i] % 90;
+                    int d = 1 << 19;
+                    for (int s = 0; s < 90; ++s) {
+                        const int c = r.board[s];
+                        if (!c || (c > 7) == (mover == 1)) continue;
+                        int dd = std::abs(s / 9 - to / 9) + std::abs(s % 9 - to % 9);
+                        if (c == 1 || c == 8) dd += 6;               // the general last
+                        if (dd < d) d = dd;
+                    }
+                    if (d < bestD) { bestD = d; best = i; ties = 1; }
+                    else if (d == bestD && rng.below((uint32_t)++ties) == 0) best = i;
+                }
+                return best;
+            };
+            auto hunt = [&](bool regicide) -> int {
+                if (regicide && !capGeneral.empty() && rng.below(2) == 0) return any(capGeneral);
+                if (!capOther.empty()) return any(capOther);
+                const int q = approach();
+                if (q >= 0 && !(regicide && !capGeneral.empty())) return q;
+                if (!capGeneral.empty() && (regicide || q < 0 || rng.below(16) == 0)) return any(capGeneral);
+                return q;
+            };
+            int pick = -1;
+            ++turn;
+            if (policy == 1) {
+                if (!soldierFwd.empty() && rng.below(8) != 0) pick = any(soldierFwd);
+                else if (!soldierSide.empty() && rng.below(3) != 0) pick = any(soldierSide);
+                else if (!quiet.empty() && rng.below(4) != 0) pick = any(quiet);
+            } else if (policy == 2) {
+                if ((turn & 2) && !general.empty()) pick = any(general);
+            }
+            if (pick < 0) pick = hunt(policy == 3);
+            int fr, fc, tr, tc;
+            if (rng.below(24) == 0) {                                // an arbitrary, mostly invalid attempt
+                fr = (int)rng.below(12) - 1; fc = (int)rng.below(11) - 1;
+                tr = (int)rng.below(12) - 1; tc = (int)rng.below(11) - 1;
+            } else {
+                const int c = list[pick];
+                fr = (c / 90) / 9; fc = (c / 90) % 9; tr = (c % 90) / 9; tc = (c % 90) % 9;
+            }
+            const bool small = nPieces[0] <= 3 || nPieces[1] <= 3;
+            if (rng.below(small ? 6 : (farSoldier ? 12 : 96)) == 0) {
+                static uint8_t mat[8 * 8100];
+                for (int fsq = 0; fsq < 90; ++fsq)
+                    for (int tsq = 0; tsq < 90; ++tsq) {
+                        mat[fsq * 90 + tsq] = b.isValidMove(fsq / 9, fsq % 9, tsq / 9, tsq % 9);
+                        for (int type = 1; type <= 7; ++type)
+                            mat[type * 8100 + fsq * 90 + tsq] =
+                                (fsq == tsq && (type == 5 || type == 6)) ? 0 : rule(type, fsq / 9, fsq % 9, tsq / 9, tsq % 9);
+                    }
+                std::fwrite(r.board, 1, 90, fm);
+                std::fwrite(mat, 1, sizeof mat, fm);
+                ++nmat;
+            }
+            r.fr = (int8_t)fr; r.fc = (int8_t)fc; r.tr = (int8_t)tr; r.tc = (int8_t)tc;
+            r.valid = b.isValidMove(fr, fc, tr, tc);
+            r.captured = pieceCode(b.movePiece(fr, fc, tr, tc));
+            std::fwrite(&r, sizeof r, 1, f);
+            ++nrec;
+        }
+        Record r;                                                    // closing record: an attempt off the board
+        snapshot(b, r);
+        r.fr = r.fc = r.tr = r.tc = -1;
+        r.valid = b.isValidMove(-1, -1, -1, -1);
+        r.captured = pieceCode(b.movePiece(-1, -1, -1, -1));
+        std::fwrite(&r, sizeof r, 1, f);
+        ++nrec;
+    }
+    std::fclose(f);
+    std::fclose(fm);
+    std::fprintf(stderr, "sparse: %ld records, %ld matrix positions\n", nrec, nmat);
+    return 0;
+}
+
 // bench: env-only random-policy stepping (move-gen for the side to move + movePiece + game-over test),
 // the reference-CPU leg of BASELINE.md §3 C2.  Prints "steps seconds".
 int cmdBench(uint64_t seed, double seconds) {
@@ -291,9 +442,11 @@ int main(int argc, char** argv) {
         return cmdTraceBig(std::strtoull(argv[2], nullptr, 0), std::atoi(argv[3]), argv[4]);
     if (argc >= 5 && !std::strcmp(argv[1], "rulemat"))
         return cmdRuleMat(std::strtoull(argv[2], nullptr, 0), std::atoi(argv[3]), argv[4]);
+    if (argc >= 6 && !std::strcmp(argv[1], "sparse"))
+        return cmdSparse(std::strtoull(argv[2], nullptr, 0), std::atoi(argv[3]), argv[4], argv[5]);
     if (argc >= 4 && !std::strcmp(argv[1], "bench"))
         return cmdBench(std::strtoull(argv[2], nullptr, 0), std::atof(argv[3]));
     if (argc >= 2 && !std::strcmp(argv[1], "recsize")) { std::printf("%zu\n", sizeof(Record)); return 0; }
-    std::fprintf(stderr, "usage: xqref trace SEED NGAMES OUT | tracebig SEED NREC OUT | validmat SEED NPOS OUT | rulemat SEED NPOS OUT | bench SEED SECONDS | recsize\n");
+    std::fprintf(stderr, "usage: xqref trace SEED NGAMES OUT | tracebig SEED NREC OUT | validmat SEED NPOS OUT | rulemat SEED NPOS OUT | sparse SEED NGAMES OUT MATOUT | bench SEED SECONDS | recsize\n");
     return 2;
 }

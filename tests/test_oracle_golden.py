@@ -228,3 +228,114 @@ def test_live_cross_check_against_reference_binary(golden_dir, tmp_path):
             assert cnt == len(want) and np.array_equal(got, want), (i, key)
         fr, fc, tr, tc = (int(x) for x in t["move"][i])
         assert L.xqo_move_piece(C.byref(b), fr, fc, tr, tc) == t["captured"][i], i
+
+
+# ---------------------------------------------------------------- steered play: ref_sparse.npz / ref_sparse_mat.npz
+@pytest.fixture(scope="module")
+def sparse(golden_dir):
+    """ref_sparse.npz: `xqref sparse` — the unmodified engine under steering policies (oracle/ref/ref_driver.cpp cmdSparse: hunt,
+    march, palace walk, regicide, play going on after a general has fallen), deduplicated and thinned by quotas in
+    oracle/gen_golden.py.  Records do not chain; after_board / after_meta hold the engine's state after each attempt.
+    A side WITHOUT A PIECE (and so with an empty list) is reached by valid moves.  A side that still has pieces but no move was
+    not reached by the steering: tests/test_env_gpu.py's hand-built position and class (d) / (a) boards of
+    tests/test_rules_sparse_gpu.py cover it."""
+    return np.load(os.path.join(golden_dir, "ref_sparse.npz"))
+
+
+def _side_counts(boards):
+    return ((boards >= 1) & (boards <= 7)).sum(axis=1), (boards >= 8).sum(axis=1)
+
+
+def test_sparse_fixture_covers_the_thin_regions(sparse, golden_dir):
+    """Conditions on the INPUTS (they decide whether the fixture is accepted), none on any code under test."""
+    b = sparse["board"]
+    nr, nb = _side_counts(b)
+    for k in range(1, 17):                                  # every own-piece count of either colour, both lists recorded
+        assert int((nr == k).sum()) >= 8, ("red", k)
+        assert int((nb == k).sum()) >= 8, ("black", k)
+    assert len(sparse["red_off"]) == len(sparse["black_off"]) == len(b) + 1
+    far_both = (b[:, 81:] == 7).any(axis=1) & (b[:, :9] == 14).any(axis=1)
+    assert int(far_both.sum()) >= 32                        # a soldier of EACH colour on its far rank
+    missing = ~(b == 1).any(axis=1) | ~(b == 8).any(axis=1)
+    assert int(missing.sum()) >= 32
+    n_red, n_black = np.diff(sparse["red_off"]), np.diff(sparse["black_off"])
+    assert int((nr == 0).sum()) >= 4 and int((nb == 0).sum()) >= 4          # a zero-piece side, reached by valid moves
+    assert int((n_red == 0).sum()) >= 4 and int((n_black == 0).sum()) >= 4  # and its zero-length list
+    assert int((sparse["valid"] == 0).sum()) >= 16 and int(np.isin(sparse["captured"], (1, 8)).sum()) >= 8
+    assert len(np.unique(np.concatenate([b, sparse["player"][:, None]], axis=1), axis=0)) == len(b)   # deduplicated
+    m = np.load(os.path.join(golden_dir, "ref_sparse_mat.npz"))
+    mr, mb = _side_counts(m["board"])
+    assert int((np.minimum(mr, mb) <= 3).sum()) >= 16
+    assert int(((m["board"][:, 81:] == 7).any(axis=1) | (m["board"][:, :9] == 14).any(axis=1)).sum()) >= 8
+    for name in ("ref_sparse.npz", "ref_sparse_mat.npz"):
+        assert os.path.getsize(os.path.join(golden_dir, name)) <= os.path.getsize(os.path.join(golden_dir, "ref_trace.npz"))
+
+
+def test_sparse_lists_and_status_match_reference(sparse):
+    L = xo.lib()
+    for i in range(len(sparse["moveCount"])):
+        b = _board(sparse, i)
+        for colour, key in ((0, "red"), (1, "black")):
+            want = sparse[key][sparse[key + "_off"][i]:sparse[key + "_off"][i + 1]]
+            got, cnt = xo.all_valid_actions(b, colour)
+            assert cnt == len(want) and np.array_equal(got, want), (i, key)
+        assert L.xqo_check_game_over(C.byref(b)) == sparse["over"][i], i
+        assert L.xqo_get_winner(C.byref(b)) == sparse["winner"][i], i
+
+
+def test_sparse_move_piece_matches_reference(sparse):
+    L = xo.lib()
+    for i in range(len(sparse["moveCount"])):
+        b = _board(sparse, i)
+        fr, fc, tr, tc = (int(x) for x in sparse["move"][i])
+        assert L.xqo_is_valid_move(C.byref(b), fr, fc, tr, tc) == sparse["valid"][i], i
+        assert L.xqo_move_piece(C.byref(b), fr, fc, tr, tc) == sparse["captured"][i], i
+        assert np.array_equal(b.squares(), sparse["after_board"][i]), i
+        assert (b.moveCount, b.currentPlayer, b.redScore, b.blackScore) == tuple(int(x) for x in sparse["after_meta"][i]), i
+
+
+def test_sparse_matrices_match_reference(golden_dir):
+    """isValidMove and the seven public validators over all 8100 (from, to) pairs, every entry, on the steered positions."""
+    g = np.load(os.path.join(golden_dir, "ref_sparse_mat.npz"))
+    L = xo.lib()
+    for i in range(len(g["board"])):
+        b = xo.board_from(g["board"][i])
+        want = np.unpackbits(g["valid_bits"][i])[:8100]
+        assert np.array_equal(xo.valid_matrix(b), want), i
+        for colour in (0, 1):                               # generator set == validator set, no duplicates
+            codes, cnt = xo.all_valid_actions(b, colour)
+            own = (g["board"][i] > 0) & ((g["board"][i] > 7) == (colour == 1))
+            assert sorted(int(c) for c in codes) == [int(k) for k in np.nonzero(want)[0] if own[k // 90]]
+            assert len(set(codes.tolist())) == cnt
+        rule = np.unpackbits(g["rule_bits"][i])[:7 * 8100].reshape(7, 8100)
+        for t in range(7):
+            for ft in np.concatenate([np.nonzero(rule[t])[0], np.arange(t, 8100, 7)]):   # every true entry + every 7th
+                f, to = divmod(int(ft), 90)
+                r = L.xqo_piece_rule(C.byref(b), t + 1, f // 9, f % 9, to // 9, to % 9)
+                assert max(r, 0) == rule[t, ft], (i, t, f, to)
+
+
+def test_sparse_fixtures_regenerate_where_the_reference_binary_is_built(sparse, golden_dir):
+    """Only where oracle/_ref/xqref exists and was built from this driver (its usage line names the mode) — elsewhere this checks
+    nothing, like the live cross-check above.  There the steered run, thinned by oracle/gen_golden.py, must give every array of
+    ref_sparse.npz and ref_sparse_mat.npz again: boards, meta, lists, attempts, results, after-states and matrices."""
+    import subprocess
+    if not os.path.exists(xo.REF_BIN) or "sparse" not in subprocess.run([xo.REF_BIN], capture_output=True, text=True).stderr:
+        return
+    import gen_golden as gg
+    rec, mboard, mvalid, mrule = gg.run_sparse(gg.SPARSE_SEED, gg.SPARSE_GAMES)
+    keep = gg.select_sparse(rec)
+    after_board, after_meta, mats = gg.sparse_extras(rec, keep, mboard, mvalid, mrule)
+    r = rec[keep]
+    assert len(r) == len(sparse["board"])
+    for k in ("board", "moveCount", "player", "redScore", "blackScore", "over", "winner", "valid", "captured"):
+        assert np.array_equal(r[k], sparse[k]), k
+    assert np.array_equal(np.stack([r["fr"], r["fc"], r["tr"], r["tc"]], axis=1), sparse["move"])
+    assert np.array_equal(after_board, sparse["after_board"]) and np.array_equal(after_meta, sparse["after_meta"])
+    for key, nkey in (("red", "nRed"), ("black", "nBlack")):
+        assert np.array_equal(np.concatenate([[0], np.cumsum(r[nkey])]), sparse[key + "_off"]), key
+        assert np.array_equal(np.concatenate([r[key][i, :r[nkey][i]] for i in range(len(r))]), sparse[key]), key
+    m = np.load(os.path.join(golden_dir, "ref_sparse_mat.npz"))
+    assert sorted(m.files) == sorted(mats)
+    for k in mats:
+        assert np.array_equal(mats[k], m[k]), k
