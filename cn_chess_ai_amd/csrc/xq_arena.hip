@@ -17,12 +17,12 @@ struct xq_arena {
     int opening = 8;
     int ply = 0;                            // plies played since the reset (every live game has played exactly this many)
     xq_env* env = nullptr;                  // 2 * pairs games on the arena's stream
-    float* q = nullptr;                     // [2 pairs][96] Q rows of the ply
-    xq_arena_game* rec = nullptr;           // [2 pairs]
-    int* live = nullptr;                    // device counter of live games
-    int* live_host = nullptr;               // pinned
-    xq_step_result* results = nullptr;      // [2 pairs] the last ply's step results
-    int16_t* pick = nullptr;                // [2 pairs] the search players' move indices of the ply (xq_search.hip)
+    xq::DevBuf<float> q;                    // [2 pairs][96] Q rows of the ply
+    xq::DevBuf<xq_arena_game> rec;          // [2 pairs]
+    xq::DevBuf<int> live;                   // device counter of live games
+    xq::PinnedBuf<int> live_host;
+    xq::DevBuf<xq_step_result> results;     // [2 pairs] the last ply's step results
+    xq::DevBuf<int16_t> pick;               // [2 pairs] the search players' move indices of the ply (xq_search.hip)
     hipEvent_t ev_env = nullptr, ev_q[2] = {nullptr, nullptr};
 };
 
@@ -134,8 +134,6 @@ extern "C" {
 int xq_arena_destroy(xq_arena* a) {
     if (!a) return XQ_OK;
     if (a->env) hipStreamSynchronize(a->env->stream);
-    hipFree(a->q); hipFree(a->rec); hipFree(a->live); hipFree(a->results); hipFree(a->pick);
-    if (a->live_host) hipHostFree(a->live_host);
     if (a->ev_env) hipEventDestroy(a->ev_env);
     for (auto ev : a->ev_q) if (ev) hipEventDestroy(ev);
     xq_env_destroy(a->env);
@@ -147,12 +145,12 @@ static int arena_init(xq_arena* a, int n_pairs, uint64_t seed, uint32_t first_ga
     a->pairs = n_pairs;
     XQ_TRY(xq_env_create(2 * n_pairs, seed, first_game_id, hip_stream, &a->env));
     const size_t n = 2 * (size_t)n_pairs;
-    XQ_HIP(hipMalloc(&a->q, n * 96 * sizeof(float)));
-    XQ_HIP(hipMalloc(&a->rec, n * sizeof(xq_arena_game)));
-    XQ_HIP(hipMalloc(&a->live, sizeof(int)));
-    XQ_HIP(hipMalloc(&a->results, n * sizeof(xq_step_result)));
-    XQ_HIP(hipMalloc(&a->pick, n * sizeof(int16_t)));
-    XQ_HIP(hipHostMalloc(reinterpret_cast<void**>(&a->live_host), sizeof(int), hipHostMallocDefault));
+    XQ_TRY(a->q.alloc(n * 96));
+    XQ_TRY(a->rec.alloc(n));
+    XQ_TRY(a->live.alloc(1));
+    XQ_TRY(a->results.alloc(n));
+    XQ_TRY(a->pick.alloc(n));
+    XQ_TRY(a->live_host.alloc(1));
     XQ_HIP(hipEventCreateWithFlags(&a->ev_env, stream_event_flags()));
     for (auto& ev : a->ev_q) XQ_HIP(hipEventCreateWithFlags(&ev, stream_event_flags()));
     return xq_arena_reset(a, 8);

@@ -61,7 +61,7 @@ struct xq_comm {
     int rank = 0, world = 1;
     hipStream_t stream = nullptr;          // stand-alone collectives only (created on first use); the TD step uses its producers' streams
     uint64_t collectives = 0, floats = 0;  // issued so far (tests, bench)
-    unsigned long long* scalar = nullptr;  // device scratch of xq_comm_sum_u64
+    xq::DevBuf<unsigned long long> scalar; // device scratch of xq_comm_sum_u64
 };
 
 #define XQ_RCCL(call)                                                                                              \
@@ -117,8 +117,8 @@ int xq_comm_create(int rank, int world, const uint8_t* id128, xq_comm** out) {
         delete c;
         return fail(XQ_ERR_RUNTIME, "ncclCommInitRank(rank %d of %d): %s", rank, world, rccl().GetErrorString(r));
     }
-    hipError_t e = hipMalloc(&c->scalar, sizeof(unsigned long long));
-    if (e != hipSuccess) { xq_comm_destroy(c); return fail(XQ_ERR_RUNTIME, "HIP error: %s (xq_comm_create)", hipGetErrorString(e)); }
+    const int rc = c->scalar.alloc(1);
+    if (rc != XQ_OK) { xq_comm_destroy(c); return rc; }
     *out = c;
     return XQ_OK;
 }
@@ -163,7 +163,6 @@ int xq_comm_destroy(xq_comm* c) {
     if (!c) return XQ_OK;
     if (c->stream) hipStreamSynchronize(c->stream);
     if (c->comm) rccl().CommDestroy(c->comm);
-    if (c->scalar) hipFree(c->scalar);
     if (c->stream) hipStreamDestroy(c->stream);
     delete c;
     return XQ_OK;

@@ -48,68 +48,63 @@ struct xq_dqn {
     hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_delta = nullptr;
     hipEvent_t ev_qmax = nullptr;               // recorded behind the column-max GEMM of the last TD step (trainer: collect starts here)
     hipEvent_t fwd_stop_ev = nullptr;           // set: the last grouped forward product of chain_boards completes this event itself (taken = reset)
-    float* params[2] = {nullptr, nullptr};
+    xq::DevBuf<float> params[2];
     uint64_t params_version = 0;                // ++ whenever an operation that rewrites parameters is queued (xq_trainer: is ev_params still current?)
     // bf16 Q-net (xq_dqn_set_precision): bf16 shadow of the WEIGHTS of both nets, same element order as params[] (biases stay fp32);
     // forward kernels read the shadow, the backward pass and the SGD step work on the fp32 master copy and refresh the shadow
     int precision = XQ_PRECISION_F32;
-    uint16_t* params_bf[2] = {nullptr, nullptr};
-    uint16_t* acts_bf[XQ_MAX_LAYERS] = {nullptr};      // bf16 bits of acts[] (acts[] then holds the same, rounded, values in fp32)
-    uint16_t* tacts_bf[2] = {nullptr, nullptr};
-    uint16_t* t2acts_bf[2] = {nullptr, nullptr};
-    uint16_t* sel_acts_bf[XQ_MAX_LAYERS] = {nullptr};
-    uint16_t* deltas_bf[XQ_MAX_LAYERS] = {nullptr};    // XQ_PRECISION_BF16_FULL: the hidden deltas rounded to bf16 (operands of the backward products)
-    int cap_bf = 0, sel_cap_bf = 0, cap_dbf = 0;
-    float* t2acts[2] = {nullptr, nullptr};             // third forward chain of a Double-DQN step (s' on the target net)
-    int cap_t2 = 0;
-    int* partial_idx = nullptr;  int cap_idx = 0;      // row index of each column-max partial (Double DQN)
-    // workspaces sized for `cap` samples
-    int cap = 0;
-    float* acts[XQ_MAX_LAYERS] = {nullptr};     // online hidden activations a_{l+1} = tanh(z_l), l = 0..nl-2
-    float* tacts[2] = {nullptr, nullptr};       // ping-pong chain for s' / inference
-    float* deltas[XQ_MAX_LAYERS] = {nullptr};   // delta_l of hidden layer l
-    float* dsc = nullptr;                       // [cap] the one non-zero output delta of each TD sample
-    int32_t* act_mb = nullptr;                  // [cap] action.to of each TD sample (gathered), -1 = empty slot
-    float* q90 = nullptr;                       // [cap][96]
+    xq::DevBuf<uint16_t> params_bf[2];
+    xq::DevBuf<uint16_t> acts_bf[XQ_MAX_LAYERS];       // bf16 bits of acts[] (acts[] then holds the same, rounded, values in fp32)
+    xq::DevBuf<uint16_t> tacts_bf[2];
+    xq::DevBuf<uint16_t> t2acts_bf[2];
+    xq::DevBuf<uint16_t> sel_acts_bf[XQ_MAX_LAYERS];
+    xq::DevBuf<uint16_t> deltas_bf[XQ_MAX_LAYERS];     // XQ_PRECISION_BF16_FULL: the hidden deltas rounded to bf16 (operands of the backward products)
+    xq::DevBuf<float> t2acts[2];                       // third forward chain of a Double-DQN step (s' on the target net)
+    xq::DevBuf<int> partial_idx;                       // row index of each column-max partial (Double DQN)
+    // workspaces sized for the largest batch seen (ensure_capacity)
+    xq::DevBuf<float> acts[XQ_MAX_LAYERS];      // online hidden activations a_{l+1} = tanh(z_l), l = 0..nl-2
+    xq::DevBuf<float> tacts[2];                 // ping-pong chain for s' / inference
+    xq::DevBuf<float> deltas[XQ_MAX_LAYERS];    // delta_l of hidden layer l
+    xq::DevBuf<float> dsc;                      // [cap] the one non-zero output delta of each TD sample
+    xq::DevBuf<int32_t> act_mb;                 // [cap] action.to of each TD sample (gathered), -1 = empty slot
+    xq::DevBuf<float> q90;                      // [cap][96]
     // second workspace for the action-select chain, so that it can run on its own stream beside a TD step
-    float* sel_acts[XQ_MAX_LAYERS] = {nullptr};
-    float* sel_q90 = nullptr;
-    int sel_cap = 0;
+    xq::DevBuf<float> sel_acts[XQ_MAX_LAYERS];
+    xq::DevBuf<float> sel_q90;
     // layer-0 sums of the select chain kept from ply to ply (xq_dqn_set_l0_derive, fp32 net): while the online weights do not change
     // — the plies of one update — the next ply's sums are the kept ones minus the rows of the squares that changed plus the rows of
     // what stands there now (l0_select_kernel); `boards` / `n` = whose boards the kept state belongs to.  One set per stream the chain
     // runs on — [0] the handle's stream (xq_dqn_select_q_dev), [1] any other (the trainer's collect stream) — like qh_slabs: a query on
     // the handle's stream neither races with collects in flight nor changes what their next ply derives from
     struct SelKeep {
-        float* z1 = nullptr;  uint32_t* prev_boards = nullptr;  int cap = 0;
+        xq::DevBuf<float> z1;  xq::DevBuf<uint32_t> prev_boards;
         bool valid = false;  const uint32_t* boards = nullptr;  int n = 0;
         int calls = 0;  bool pays = false;                // select calls since the last parameter update; the last period had >= 2
     } sel_keep[2];
     void sel_invalidate() { sel_keep[0].valid = sel_keep[1].valid = false; }
-    float* qh_slabs[2] = {nullptr, nullptr};    // k-slabs of the select head (handle stream / any other stream)
-    size_t qh_cap[2] = {0, 0};
+    xq::DevBuf<float> qh_slabs[2];              // k-slabs of the select head (handle stream / any other stream)
     bool small_tiles = false;                   // force 64x64 GEMM tiles (<= 80 VGPRs: fits beside the persistent GEMM)
     bool l0_derive = false;                     // xq_dqn_set_l0_derive: layer-0 sums of s' from those of s (online TD rule, fp32 net)
     // exact screening of max_a' Q(s', a') (xq_dqn_set_qmax_mode): bf16 copies of the output-layer weights and of
     // the last hidden activations of s', the two screening partial arrays, the largest row norm of the weights, counters
     int qmax_mode = XQ_QMAX_FULL;
-    uint16_t* scr_wb = nullptr;                 // [round_up(nout,128)][hlast] (rows >= nout zero)
-    uint16_t* scr_ab = nullptr;  int scr_cap = 0;   // [round_up(cap,512)][hlast]: row-major, or B-fragment order for screen_top2_kernel
-    float* scr_p1 = nullptr; float* scr_p2 = nullptr;   // [4*tiles_m][round_up(cap,512)]
-    float* scr_R = nullptr; float* scr_na = nullptr;    // [chunks][round_up(cap,512)] per-range maxima, [round_up(cap,512)] ||bf16(a)||^2
+    xq::DevBuf<uint16_t> scr_wb;                // [round_up(nout,128)][hlast] (rows >= nout zero)
+    xq::DevBuf<uint16_t> scr_ab;                // [round_up(cap,512)][hlast]: row-major, or B-fragment order for screen_top2_kernel
+    xq::DevBuf<float> scr_p1, scr_p2;           // [4*tiles_m][round_up(cap,512)]
+    xq::DevBuf<float> scr_R, scr_na;            // [chunks][round_up(cap,512)] per-range maxima, [round_up(cap,512)] ||bf16(a)||^2
     // bits of the largest row norm / largest |bias| of the output layer (non-negative floats order like unsigned): [0..1] rows 0..95 by
     // step parity, [2..3] their biases by step parity, [4] rows >= 96, [5] their biases.  Only rows 0..95 change under the TD rule
     // (xq_dqn_td_grads never touches the others), so the shadow of rows >= 96 and slots [4], [5] are kept from step to step:
-    unsigned* scr_wmax = nullptr;
+    xq::DevBuf<unsigned> scr_wmax;
     int scr_static_net = -1;                    // net whose rows >= 96 the shadow holds (-1: none — the next step converts everything)
-    unsigned long long* scr_stats = nullptr;    // [refine blocks][2] running totals per block: candidate (sample, group) pairs, pairs recomputed as whole groups
+    xq::DevBuf<unsigned long long> scr_stats;   // [refine blocks][2] running totals per block: candidate (sample, group) pairs, pairs recomputed as whole groups
     int scr_stat_blocks = 0;                    // blocks the array (and its pinned copy) has room for
     unsigned long long scr_carry[2] = {0, 0};   // totals of an array that was replaced by a larger one
     unsigned long long scr_host_steps = 0, scr_host_samples = 0;
     // guard: every kScreenCheckEvery screened steps the candidate counters are copied back asynchronously and evaluated kScreenCheckEvery
     // steps later; a net that leaves the screen too many candidates (outputs all within the bf16 bound of each other) gets the full
     // product for the next kScreenHoldSteps steps
-    unsigned long long* scr_guard_host = nullptr;      // pinned copy of scr_stats
+    xq::PinnedBuf<unsigned long long> scr_guard_host;  // pinned copy of scr_stats
     hipEvent_t scr_guard_ev = nullptr;
     bool scr_guard_pending = false;
     unsigned long long scr_guard_samples = 0;          // scr_host_samples when the pending copy was queued
@@ -121,22 +116,20 @@ struct xq_dqn {
     unsigned long long scr_seen[3] = {0, 0, 0};        // samples, pairs, whole groups at the last evaluation
     int scr_hold = 0;                                  // > 0: that many TD steps still run the full product
     unsigned long long scr_fallbacks = 0;
-    float* partial = nullptr;                   // row-max partials
-    float* zmax = nullptr;  int* zidx = nullptr;    // [kReduceParts][cap] their reduction per sample (colmax_reduce_kernel)
-    float* qsa = nullptr;
-    float* yv = nullptr;
-    float* lossv = nullptr;
-    uint32_t* gboards = nullptr;                // [cap][12] boards of the current minibatch, gathered
+    xq::DevBuf<float> partial;                  // row-max partials
+    xq::DevBuf<float> zmax;  xq::DevBuf<int> zidx;  // [kReduceParts][cap] their reduction per sample (colmax_reduce_kernel)
+    xq::DevBuf<float> qsa, yv, lossv;
+    xq::DevBuf<uint32_t> gboards;               // [cap][12] boards of the current minibatch, gathered
     int last_n = 0;
     // gradients
-    float* grads_td = nullptr;  size_t n_grads_td = 0;
+    xq::DevBuf<float> grads_td;  size_t n_grads_td = 0;
     size_t g_w0 = 0, g_wh[XQ_MAX_LAYERS] = {0}, g_wout = 0, g_bh[XQ_MAX_LAYERS] = {0}, g_bout = 0;
-    float* grads_full = nullptr;
-    float* slabs = nullptr;  size_t slabs_cap = 0;
-    float* slabs_l0 = nullptr;  size_t slabs_l0_cap = 0;     // layer-0 gradient partials
+    xq::DevBuf<float> grads_full;
+    xq::DevBuf<float> slabs;
+    xq::DevBuf<float> slabs_l0;                 // layer-0 gradient partials
     // layer-0 gradient on the bf16 matrix pipe (xq_l0grad.hip.h): delta_0 as three bf16 planes, transposed [plane][column][sample]
-    uint16_t* l0_planes = nullptr;  size_t l0_planes_cap = 0;
-    uint16_t* l0_sel = nullptr;     size_t l0_sel_cap = 0;       // selector half-words of the minibatch's boards (xq_l0grad.hip.h)
+    xq::DevBuf<uint16_t> l0_planes;
+    xq::DevBuf<uint16_t> l0_sel;                // selector half-words of the minibatch's boards (xq_l0grad.hip.h)
     bool l0_split_done = false;                 // this step's layer-0 delta product wrote the planes in its epilogue
     bool l0_sel_done = false;                   // this step's selector words rode in an earlier fused launch
     bool l0_mfma = true;                        // xq_dqn_set_l0_grad_mode (default since round 5: xq_l0grad.hip.h)
@@ -146,13 +139,11 @@ struct xq_dqn {
     struct PendingSlab { const float* src = nullptr; int nslabs = 0; long long stride = 0; };
     PendingSlab pend_hidden[XQ_MAX_LAYERS], pend_wout, pend_bout;   // same for the hidden / output-layer gradients (fused_apply)
     PendingSlab pend_bh;                        // ... and the hidden biases (rows of column sums, bias_grads)
-    float* bias_work = nullptr;  size_t bias_work_cap = 0;
+    xq::DevBuf<float> bias_work;
     // dense API scratch
-    float* xdense = nullptr;  size_t xdense_cap = 0;
-    float* qfull = nullptr;   size_t qfull_cap = 0;
-    float* tfull = nullptr;   size_t tfull_cap = 0;
-    uint32_t* hb = nullptr;   size_t hb_cap = 0;     // host-batch staging: boards, next boards
-    int32_t* ha = nullptr; float* hr = nullptr; uint8_t* hd = nullptr;
+    xq::DevBuf<float> xdense, qfull, tfull;
+    xq::DevBuf<uint32_t> hb;                    // host-batch staging: boards, next boards
+    xq::DevBuf<int32_t> ha;  xq::DevBuf<float> hr;  xq::DevBuf<uint8_t> hd;
     xq::Profiler prof;
     // fused launches of the TD step's tail (td_tail_kernel): while `tail_open`, the launch helpers of the small fp32 GEMMs, the
     // output-layer / layer-0 segmented sums and the bias column sums append their blocks to `tail` instead of launching
@@ -311,53 +302,35 @@ static int launch_bf16_gemm(xq_dqn* d, const Bf16GemmArgs& g, int gz, const char
     return launch_dma_gemm<DT_BF16, AL, BL, EPI, 2, 2>(d, g, gz, name);
 }
 
-static int ensure_slabs(xq_dqn* d, size_t floats) {
-    if (floats <= d->slabs_cap) return XQ_OK;
-    if (d->slabs) { XQ_HIP(hipStreamSynchronize(d->stream)); XQ_HIP(hipFree(d->slabs)); }
-    XQ_HIP(hipMalloc(&d->slabs, floats * sizeof(float)));
-    d->slabs_cap = floats;
-    return XQ_OK;
-}
-
-static int grow(float** p, size_t* cap, size_t floats, hipStream_t s) {
-    if (floats <= *cap) return XQ_OK;
-    if (*p) { XQ_HIP(hipStreamSynchronize(s)); XQ_HIP(hipFree(*p)); }
-    XQ_HIP(hipMalloc(p, floats * sizeof(float)));
-    *cap = floats;
+// The ensure_* functions: the size arithmetic of a family of workspaces.  Every buffer reserves on its own (DevBuf::reserve: free when
+// it is large enough), so a growth that fails part-way leaves nothing to repair — the next call grows what is still too small.
+// A buffer whose padding is read gets its zeros, on stream s, when it is new.
+template <class T> static int reserve_zeroed(DevBuf<T>& b, size_t count, hipStream_t s) {
+    bool grew = false;
+    XQ_TRY(b.reserve(count, &grew));
+    if (grew) XQ_HIP(hipMemsetAsync(b, 0, count * sizeof(T), s));
     return XQ_OK;
 }
 
 static int ensure_capacity(xq_dqn* d, int n) {
-    if (n <= d->cap) return XQ_OK;
-    XQ_HIP(hipStreamSynchronize(d->stream));
     const size_t cap = (size_t)n;
     int maxh = 0;
     for (int l = 0; l + 1 < d->nl; ++l) maxh = std::max(maxh, d->L[l + 1]);
     for (int l = 0; l + 1 < d->nl; ++l) {
-        if (d->acts[l]) XQ_HIP(hipFree(d->acts[l]));
-        if (d->deltas[l]) XQ_HIP(hipFree(d->deltas[l]));
-        XQ_HIP(hipMalloc(&d->acts[l], cap * d->L[l + 1] * sizeof(float)));
-        XQ_HIP(hipMalloc(&d->deltas[l], cap * d->L[l + 1] * sizeof(float)));
+        XQ_TRY(d->acts[l].reserve(cap * d->L[l + 1]));
+        XQ_TRY(d->deltas[l].reserve(cap * d->L[l + 1]));
     }
-    for (int i = 0; i < 2; ++i) {    // rows padded to a multiple of 128 (whole-tile reads of the persistent GEMM)
-        if (d->tacts[i]) XQ_HIP(hipFree(d->tacts[i]));
-        const size_t rows = (size_t)round_up(n, 128);
-        XQ_HIP(hipMalloc(&d->tacts[i], rows * (size_t)maxh * sizeof(float)));
-        XQ_HIP(hipMemsetAsync(d->tacts[i], 0, rows * (size_t)maxh * sizeof(float), d->stream));
-    }
+    // rows padded to a multiple of 128 (whole-tile reads of the persistent GEMM)
+    for (auto& t : d->tacts) XQ_TRY(reserve_zeroed(t, (size_t)round_up(n, 128) * (size_t)maxh, d->stream));
     const int ntn = (d->nout() + 63) / 64;             // column-max partials: 2 per 64- or 128-row tile
-    float** bufs[] = {&d->q90, &d->partial, &d->qsa, &d->yv, &d->lossv, &d->dsc, reinterpret_cast<float**>(&d->act_mb), &d->zmax,
-                      reinterpret_cast<float**>(&d->zidx)};
+    XQ_TRY(d->q90.reserve(cap * 96));
     // (partials: the sample dimension padded to whole blocks of screen_top2_kernel, which stores every column of its panels)
-    const size_t sizes[] = {cap * 96, (size_t)round_up(n, 512) * (size_t)ntn * 2, cap, cap, cap, cap, cap, cap * kReduceParts, cap * kReduceParts};
-    for (int i = 0; i < 9; ++i) {
-        if (*bufs[i]) XQ_HIP(hipFree(*bufs[i]));
-        XQ_HIP(hipMalloc(bufs[i], sizes[i] * sizeof(float)));
-    }
-    if (d->gboards) XQ_HIP(hipFree(d->gboards));
-    XQ_HIP(hipMalloc(&d->gboards, cap * kBoardWords * sizeof(uint32_t)));
-    d->cap = n;
-    return XQ_OK;
+    XQ_TRY(d->partial.reserve((size_t)round_up(n, 512) * (size_t)ntn * 2));
+    for (DevBuf<float>* b : {&d->qsa, &d->yv, &d->lossv, &d->dsc}) XQ_TRY(b->reserve(cap));
+    XQ_TRY(d->act_mb.reserve(cap));
+    XQ_TRY(d->zmax.reserve(cap * kReduceParts));
+    XQ_TRY(d->zidx.reserve(cap * kReduceParts));
+    return d->gboards.reserve(cap * kBoardWords);
 }
 
 // the extra buffers of the build-defined modes, allocated on first use: bf16 bits of every activation buffer (bf16 Q-net), the
@@ -366,45 +339,19 @@ static int ensure_ext_capacity(xq_dqn* d, int n, bool want_double) {
     int maxh = 0;
     for (int l = 0; l + 1 < d->nl; ++l) maxh = std::max(maxh, d->L[l + 1]);
     const size_t rows = (size_t)round_up(n, 512);      // whole-tile reads of the persistent GEMM (128) / whole panels of screen_top2_kernel (512)
-    if (d->bf16() && n > d->cap_bf) {
-        XQ_HIP(hipDeviceSynchronize());
-        for (int l = 0; l + 1 < d->nl; ++l) {
-            if (d->acts_bf[l]) XQ_HIP(hipFree(d->acts_bf[l]));
-            XQ_HIP(hipMalloc(&d->acts_bf[l], rows * d->L[l + 1] * sizeof(uint16_t)));
-        }
+    if (d->bf16()) {
+        for (int l = 0; l + 1 < d->nl; ++l) XQ_TRY(d->acts_bf[l].reserve(rows * d->L[l + 1]));
         for (int i = 0; i < 2; ++i) {
-            if (d->tacts_bf[i]) XQ_HIP(hipFree(d->tacts_bf[i]));
-            if (d->t2acts_bf[i]) XQ_HIP(hipFree(d->t2acts_bf[i]));
-            XQ_HIP(hipMalloc(&d->tacts_bf[i], rows * (size_t)maxh * sizeof(uint16_t)));
-            XQ_HIP(hipMalloc(&d->t2acts_bf[i], rows * (size_t)maxh * sizeof(uint16_t)));
-            XQ_HIP(hipMemsetAsync(d->tacts_bf[i], 0, rows * (size_t)maxh * sizeof(uint16_t), d->stream));
-            XQ_HIP(hipMemsetAsync(d->t2acts_bf[i], 0, rows * (size_t)maxh * sizeof(uint16_t), d->stream));
+            XQ_TRY(reserve_zeroed(d->tacts_bf[i], rows * (size_t)maxh, d->stream));
+            XQ_TRY(reserve_zeroed(d->t2acts_bf[i], rows * (size_t)maxh, d->stream));
         }
-        d->cap_bf = n;
     }
-    if (d->bf16_bwd() && n > d->cap_dbf) {
-        XQ_HIP(hipDeviceSynchronize());
-        for (int l = 0; l + 1 < d->nl; ++l) {
-            if (d->deltas_bf[l]) XQ_HIP(hipFree(d->deltas_bf[l]));
-            XQ_HIP(hipMalloc(&d->deltas_bf[l], rows * d->L[l + 1] * sizeof(uint16_t)));
-        }
-        d->cap_dbf = n;
-    }
-    if (want_double && n > d->cap_t2) {
-        XQ_HIP(hipDeviceSynchronize());
-        for (int i = 0; i < 2; ++i) {
-            if (d->t2acts[i]) XQ_HIP(hipFree(d->t2acts[i]));
-            XQ_HIP(hipMalloc(&d->t2acts[i], rows * (size_t)maxh * sizeof(float)));
-            XQ_HIP(hipMemsetAsync(d->t2acts[i], 0, rows * (size_t)maxh * sizeof(float), d->stream));
-        }
-        d->cap_t2 = n;
-    }
-    if (want_double && n > d->cap_idx) {
-        XQ_HIP(hipDeviceSynchronize());
-        if (d->partial_idx) XQ_HIP(hipFree(d->partial_idx));
+    if (d->bf16_bwd())
+        for (int l = 0; l + 1 < d->nl; ++l) XQ_TRY(d->deltas_bf[l].reserve(rows * d->L[l + 1]));
+    if (want_double) {
+        for (auto& t : d->t2acts) XQ_TRY(reserve_zeroed(t, rows * (size_t)maxh, d->stream));
         const int ntn = (d->nout() + 63) / 64;
-        XQ_HIP(hipMalloc(&d->partial_idx, (size_t)round_up(n, 512) * (size_t)ntn * 2 * sizeof(int)));
-        d->cap_idx = n;
+        XQ_TRY(d->partial_idx.reserve(rows * (size_t)ntn * 2));
     }
     return XQ_OK;
 }
@@ -413,12 +360,10 @@ static SlotSrc explicit_slots(const int32_t* slots) {
     SlotSrc s; memset(&s, 0, sizeof s); s.slots = slots; return s;
 }
 
-// One forward chain of a launch group: a_1 .. a_{nl-1} of `net` for n packed boards; outs[l] receives a_{l+1} in fp32 (may be
-// nullptr per chain in bf16 mode when only the next layer reads it), outs_bf[l] its bf16 bits (bf16 Q-net only).
 // totals of the per-block candidate counters (synchronises the device)
 static int screen_stat_sums(xq_dqn* d, unsigned long long sums[2]) {
     sums[0] = d->scr_carry[0]; sums[1] = d->scr_carry[1];
-    if (!d->scr_stats) return XQ_OK;
+    if (!d->scr_stat_blocks) return XQ_OK;
     std::vector<unsigned long long> h((size_t)2 * d->scr_stat_blocks);
     XQ_HIP(hipDeviceSynchronize());
     XQ_HIP(hipMemcpy(h.data(), d->scr_stats, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
@@ -433,50 +378,53 @@ static void screen_stat_sums_of(const xq_dqn* d, const unsigned long long* h, un
 static int ensure_screen_capacity(xq_dqn* d, int n) {
     const int NO = d->nout(), Hl = d->hlast();
     const size_t wrows = (size_t)round_up(NO, 128);
-    if (!d->scr_wb) {
-        XQ_HIP(hipMalloc(&d->scr_wb, wrows * Hl * sizeof(uint16_t)));
+    bool grew = false;
+    XQ_TRY(d->scr_wb.reserve(wrows * Hl, &grew));
+    if (grew) {
         XQ_HIP(hipMemset(d->scr_wb, 0, wrows * Hl * sizeof(uint16_t)));
-        XQ_HIP(hipMalloc(&d->scr_wmax, 6 * sizeof(unsigned)));
-        XQ_HIP(hipMemset(d->scr_wmax, 0, 6 * sizeof(unsigned)));
-        XQ_HIP(hipEventCreateWithFlags(&d->scr_guard_ev, hipEventDisableTiming));
         d->scr_static_net = -1;
     }
-    if (n > d->scr_cap) {
-        XQ_HIP(hipDeviceSynchronize());
-        // sample dimension padded to whole blocks of screen_top2_kernel (512): it stores every column of its panels unconditionally
-        const size_t rows = (size_t)round_up(n, 512), G = (size_t)4 * ((NO + 127) / 128);
-        if (d->scr_ab) XQ_HIP(hipFree(d->scr_ab));
-        if (d->scr_p1) XQ_HIP(hipFree(d->scr_p1));
-        if (d->scr_p2) XQ_HIP(hipFree(d->scr_p2));
-        XQ_HIP(hipMalloc(&d->scr_ab, rows * Hl * sizeof(uint16_t)));
-        XQ_HIP(hipMemset(d->scr_ab, 0, rows * Hl * sizeof(uint16_t)));
-        XQ_HIP(hipMalloc(&d->scr_p1, G * rows * sizeof(float)));
-        XQ_HIP(hipMalloc(&d->scr_p2, G * rows * sizeof(float)));
-        if (d->scr_R) XQ_HIP(hipFree(d->scr_R));
-        if (d->scr_na) XQ_HIP(hipFree(d->scr_na));
-        XQ_HIP(hipMalloc(&d->scr_R, (size_t)((NO + 63) / 64) * rows * sizeof(float)));       // at most one range per 64-row chunk
-        XQ_HIP(hipMalloc(&d->scr_na, rows * sizeof(float)));
+    grew = false;
+    XQ_TRY(d->scr_wmax.reserve(6, &grew));
+    if (grew) XQ_HIP(hipMemset(d->scr_wmax, 0, 6 * sizeof(unsigned)));
+    if (!d->scr_guard_ev) XQ_HIP(hipEventCreateWithFlags(&d->scr_guard_ev, hipEventDisableTiming));
+    // sample dimension padded to whole blocks of screen_top2_kernel (512): it stores every column of its panels unconditionally
+    const size_t rows = (size_t)round_up(n, 512), G = (size_t)4 * ((NO + 127) / 128);
+    grew = false;
+    XQ_TRY(d->scr_ab.reserve(rows * Hl, &grew));
+    if (grew) XQ_HIP(hipMemset(d->scr_ab, 0, rows * Hl * sizeof(uint16_t)));
+    XQ_TRY(d->scr_p1.reserve(G * rows, &grew));
+    XQ_TRY(d->scr_p2.reserve(G * rows, &grew));
+    XQ_TRY(d->scr_R.reserve((size_t)((NO + 63) / 64) * rows, &grew));       // at most one range per 64-row chunk
+    XQ_TRY(d->scr_na.reserve(rows, &grew));
+    if (grew)
         if (const char* e = getenv("XQ_DEBUG_PTRS")) if (e[0] == '1')
-            fprintf(stderr, "[xq] screening buffers: P1 %p P2 %p R %p ab %p na %p params %p acts %p\n", (void*)d->scr_p1, (void*)d->scr_p2, (void*)d->scr_R,
-                    (void*)d->scr_ab, (void*)d->scr_na, (void*)d->params[0], (void*)d->tacts[0]);
-        // candidate counters: one pair per refine block (32 samples); the totals of the array it replaces are carried on the host
-        if (d->scr_stats) {
+            fprintf(stderr, "[xq] screening buffers: P1 %p P2 %p R %p ab %p na %p params %p acts %p\n", (void*)d->scr_p1.p, (void*)d->scr_p2.p,
+                    (void*)d->scr_R.p, (void*)d->scr_ab.p, (void*)d->scr_na.p, (void*)d->params[0].p, (void*)d->tacts[0].p);
+    // candidate counters: one pair per refine block (32 samples); the totals of the array it replaces are carried on the host.
+    // scr_stat_blocks is the capacity of the pair (array + pinned copy): 0 while it is being replaced, so that a failure in between
+    // leaves totals that screen_stat_sums still gets right and a pair that the next call allocates again
+    const int blocks = (int)(rows / kRefineSamples);
+    if (blocks > d->scr_stat_blocks) {
+        if (d->scr_stat_blocks) {
             unsigned long long sums[2];
             XQ_TRY(screen_stat_sums(d, sums));
             d->scr_carry[0] = sums[0]; d->scr_carry[1] = sums[1];
-            XQ_HIP(hipFree(d->scr_stats)); XQ_HIP(hipHostFree(d->scr_guard_host));
             d->scr_guard_pending = false;
         }
-        d->scr_stat_blocks = (int)(rows / kRefineSamples);
-        XQ_HIP(hipMalloc(&d->scr_stats, (size_t)2 * d->scr_stat_blocks * sizeof(unsigned long long)));
-        XQ_HIP(hipMemset(d->scr_stats, 0, (size_t)2 * d->scr_stat_blocks * sizeof(unsigned long long)));
-        XQ_HIP(hipHostMalloc(reinterpret_cast<void**>(&d->scr_guard_host), (size_t)2 * d->scr_stat_blocks * sizeof(unsigned long long), hipHostMallocDefault));
-        memset(d->scr_guard_host, 0, (size_t)2 * d->scr_stat_blocks * sizeof(unsigned long long));
-        d->scr_cap = n;
+        d->scr_stat_blocks = 0;
+        XQ_TRY(d->scr_stats.reserve((size_t)2 * blocks));
+        XQ_HIP(hipMemset(d->scr_stats, 0, d->scr_stats.n * sizeof(unsigned long long)));
+        XQ_TRY(d->scr_guard_host.reserve((size_t)2 * blocks));
+        memset(d->scr_guard_host, 0, d->scr_guard_host.n * sizeof(unsigned long long));
+        d->scr_stat_blocks = blocks;
     }
     return XQ_OK;
 }
 
+// One forward chain of a launch group: a_1 .. a_{nl-1} of `net` for n packed boards; outs[l] receives a_{l+1} in fp32 (may be
+// nullptr per chain in bf16 mode when only the next layer reads it), outs_bf[l] its bf16 bits (bf16 Q-net only).
+// Up to three chains run in the same launches: one gather grid with blockIdx.y = chain, grouped GEMMs with blockIdx.z = chain.
 struct ChainJob {
     int net;
     const uint32_t* boards;
@@ -490,7 +438,6 @@ struct ChainJob {
     int sel_keep;               // fp32 net, one chain: 1 = layer 0 through l0_select_kernel (sums kept in sel_state->z1 for the next ply),
                                 //   2 = ... and derived from the sums kept last time
 };
-// Up to three chains run in the same launches: one gather grid with blockIdx.y = chain, grouped GEMMs with blockIdx.z = chain.
 static int chain_boards(xq_dqn* d, const ChainJob* jobs, int njobs, SlotSrc src, int n, const ShadowJob* shadow = nullptr) {
     if (d->L[0] != kStateSize) return fail(XQ_ERR_INVALID_ARGUMENT, "board input needs layer_sizes[0] == 1260 (got %d)", d->L[0]);
     if (njobs < 1 || njobs > kMaxChains) return fail(XQ_ERR_INVALID_ARGUMENT, "1..3 forward chains per launch group");
@@ -499,8 +446,8 @@ static int chain_boards(xq_dqn* d, const ChainJob* jobs, int njobs, SlotSrc src,
         const int H = d->L[1];
         ProfScope ps(d, "l0_forward_gather", 2.0 * n * 32 * H, (double)n * (96 + (jobs[0].sel_keep == 2 ? 4.0 : 32.0) * H * 4 + H * 12), true);
         xq_dqn::SelKeep& K = d->sel_keep[d->cur == d->stream ? 0 : 1];
-        hipExtLaunchKernelGGL(l0_select_kernel, dim3((n + 3) / 4), dim3(256), 0, d->cur, ps.start(), ps.stop(), 0, jobs[0].boards, K.prev_boards, d->w0t(jobs[0].net),
-                           d->bl(jobs[0].net, 0), K.z1, jobs[0].outs[0], n, H, jobs[0].sel_keep == 2 ? 1 : 0);
+        hipExtLaunchKernelGGL(l0_select_kernel, dim3((n + 3) / 4), dim3(256), 0, d->cur, ps.start(), ps.stop(), 0, jobs[0].boards, K.prev_boards.p, d->w0t(jobs[0].net),
+                           d->bl(jobs[0].net, 0), K.z1.p, jobs[0].outs[0], n, H, jobs[0].sel_keep == 2 ? 1 : 0);
         XQ_HIP(hipGetLastError());
     } else
     {
@@ -543,7 +490,7 @@ static int chain_boards(xq_dqn* d, const ChainJob* jobs, int njobs, SlotSrc src,
         g.M = n; g.N = d->L[l + 1];
         g.grouped = njobs > 1 ? njobs : 0;
         if (bf && (n % kBgBM) == 0 && (d->L[l + 1] % kBgBN) == 0 && (d->L[l] % kBgBK) == 0) {
-            // the bf16 loop of its own (xq_gemm_bf16.hip.h): whole 256 x 128 tiles only, the chains as groups of one launch
+            // the bf16 loop of its own (xq_gemm_dma.hip.h): whole 256 x 128 tiles only, the chains as groups of one launch
             Bf16GemmArgs b; memset(&b, 0, sizeof b);
             b.M = n; b.N = d->L[l + 1]; b.K = d->L[l]; b.lda = b.ldb = d->L[l]; b.k_chunk = b.K;
             b.ldc = d->L[l + 1]; b.ldcb = d->L[l + 1];
@@ -625,6 +572,15 @@ static int chain_boards(xq_dqn* d, const ChainJob* jobs, int njobs, SlotSrc src,
     return XQ_OK;
 }
 
+// k-slabs of the select head for the stream the launches go to: the select chain may run on its own stream beside a TD step or a
+// query on the handle's, so each of the two has its own
+static int head_slabs(xq_dqn* d, size_t floats, float** slab) {
+    DevBuf<float>& b = d->qh_slabs[d->cur == d->stream ? 0 : 1];
+    XQ_TRY(b.reserve(floats));
+    *slab = b;
+    return XQ_OK;
+}
+
 // Q head on the first n_out outputs: q[m][0..n_out) = tanh(W_out[0:n_out] a_last + b_out); a_last_bf != nullptr: bf16 operands
 // (weights from the shadow), fp32 result (the output layer is never rounded)
 static int q_head(xq_dqn* d, int net, const float* a_last, int n, int n_out, float* q, int ldq, const char* name,
@@ -654,18 +610,12 @@ static int q_head(xq_dqn* d, int net, const float* a_last, int n, int n_out, flo
         const int nc = round_up(n_out, 4);
         const int nslabs = g.K / 64;
         const size_t need = (size_t)nslabs * n * nc;
-        float** slab = d->cur == d->stream ? &d->qh_slabs[0] : &d->qh_slabs[1];      // the select chain may run on its own stream beside a TD step
-        size_t* cap = d->cur == d->stream ? &d->qh_cap[0] : &d->qh_cap[1];
-        if (need > *cap) {
-            XQ_HIP(hipDeviceSynchronize());
-            if (*slab) XQ_HIP(hipFree(*slab));
-            XQ_HIP(hipMalloc(slab, need * sizeof(float)));
-            *cap = need;
-        }
-        g.C = *slab; g.ldc = nc; g.slab_stride = (long long)n * nc;
+        float* slab = nullptr;
+        XQ_TRY(head_slabs(d, need, &slab));
+        g.C = slab; g.ldc = nc; g.slab_stride = (long long)n * nc;
         XQ_GEMM((launch_gemm<L_KCONTIG, L_KCONTIG, EPI_STORE>(d, g, nslabs, name, nullptr, true)));
         const long long total = (long long)n * n_out;
-        hipLaunchKernelGGL(q_head_finish_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, d->cur, *slab, g.slab_stride, nslabs, n, n_out, nc,
+        hipLaunchKernelGGL(q_head_finish_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, d->cur, slab, g.slab_stride, nslabs, n, n_out, nc,
                            g.bias, q, ldq);
         XQ_HIP(hipGetLastError());
         return XQ_OK;
@@ -676,25 +626,12 @@ static int q_head(xq_dqn* d, int net, const float* a_last, int n, int n_out, flo
 }
 
 static int ensure_select_capacity(xq_dqn* d, int n) {
-    if (n <= d->sel_cap) return XQ_OK;
-    XQ_HIP(hipDeviceSynchronize());
-    for (int l = 0; l + 1 < d->nl; ++l) {
-        if (d->sel_acts[l]) XQ_HIP(hipFree(d->sel_acts[l]));
-        XQ_HIP(hipMalloc(&d->sel_acts[l], (size_t)n * d->L[l + 1] * sizeof(float)));
-    }
-    if (d->sel_q90) XQ_HIP(hipFree(d->sel_q90));
-    XQ_HIP(hipMalloc(&d->sel_q90, (size_t)n * 96 * sizeof(float)));
-    d->sel_cap = n;
-    return XQ_OK;
+    for (int l = 0; l + 1 < d->nl; ++l) XQ_TRY(d->sel_acts[l].reserve((size_t)n * d->L[l + 1]));
+    return d->sel_q90.reserve((size_t)n * 96);
 }
 static int ensure_select_capacity_bf(xq_dqn* d, int n) {
-    if (!d->bf16() || n <= d->sel_cap_bf) return XQ_OK;
-    XQ_HIP(hipDeviceSynchronize());
-    for (int l = 0; l + 1 < d->nl; ++l) {
-        if (d->sel_acts_bf[l]) XQ_HIP(hipFree(d->sel_acts_bf[l]));
-        XQ_HIP(hipMalloc(&d->sel_acts_bf[l], (size_t)round_up(n, 128) * d->L[l + 1] * sizeof(uint16_t)));
-    }
-    d->sel_cap_bf = n;
+    if (!d->bf16()) return XQ_OK;
+    for (int l = 0; l + 1 < d->nl; ++l) XQ_TRY(d->sel_acts_bf[l].reserve((size_t)round_up(n, 128) * d->L[l + 1]));
     return XQ_OK;
 }
 
@@ -727,16 +664,11 @@ int dqn_q90_boards(xq_dqn* d, const uint32_t* boards_dev, int n, float** q90_dev
     xq_dqn::SelKeep& K = d->sel_keep[on ? 1 : 0];
     K.calls += 1;
     bool kept = false;
+    int rc = XQ_OK;
     if (d->l0_derive && !bf && (d->L[1] & 3) == 0 && (K.pays || K.calls >= 2)) {
-        if (n > K.cap) {
-            XQ_HIP(hipDeviceSynchronize());
-            if (K.z1) XQ_HIP(hipFree(K.z1));
-            if (K.prev_boards) XQ_HIP(hipFree(K.prev_boards));
-            K.z1 = nullptr; K.prev_boards = nullptr; K.cap = 0; K.valid = false;
-            XQ_HIP(hipMalloc(&K.z1, (size_t)n * d->L[1] * sizeof(float)));
-            XQ_HIP(hipMalloc(&K.prev_boards, (size_t)n * kBoardWords * sizeof(uint32_t)));
-            K.cap = n;
-        }
+        if ((size_t)n * d->L[1] > K.z1.n) K.valid = false;          // new buffers keep nothing (nor does a growth that fails)
+        rc = K.z1.reserve((size_t)n * d->L[1]);
+        if (rc == XQ_OK) rc = K.prev_boards.reserve((size_t)n * kBoardWords);
         job.sel_keep = (K.valid && K.boards == boards_dev && K.n == n) ? 2 : 1;
         K.valid = false;                   // true again once the launch that keeps the sums has been queued
         kept = true;
@@ -746,33 +678,25 @@ int dqn_q90_boards(xq_dqn* d, const uint32_t* boards_dev, int n, float** q90_dev
     const int Hl = d->hlast();
     const bool ride = !bf && d->nl >= 3 && n >= 2048 && (n & 63) == 0 && (Hl % 128) == 0 && (d->L[d->nl - 2] & 31) == 0 && d->nout() >= 128 &&
                       vec_ok(d->wl(XQ_NET_ONLINE, d->nl - 1), Hl) && vec_ok(d->wl(XQ_NET_ONLINE, d->nl - 2), d->L[d->nl - 2]);
-    int rc = XQ_OK;
-    if (ride) {
+    if (rc == XQ_OK && ride) {
         const int nslabs = Hl / 64;
-        const size_t need = (size_t)nslabs * n * 96;
-        float** slab = d->cur == d->stream ? &d->qh_slabs[0] : &d->qh_slabs[1];
-        size_t* cap = d->cur == d->stream ? &d->qh_cap[0] : &d->qh_cap[1];
-        if (need > *cap) {
-            XQ_HIP(hipDeviceSynchronize());
-            if (*slab) XQ_HIP(hipFree(*slab));
-            XQ_HIP(hipMalloc(slab, need * sizeof(float)));
-            *cap = need;
-        }
-        job.head_slabs = *slab;
+        float* slab = nullptr;
+        rc = head_slabs(d, (size_t)nslabs * n * 96, &slab);
+        job.head_slabs = slab;
         float* keep = outs[d->nl - 2];
         outs[d->nl - 2] = nullptr;                       // nobody else reads the select chain's last activations
-        rc = chain_boards(d, &job, 1, explicit_slots(nullptr), n);
+        if (rc == XQ_OK) rc = chain_boards(d, &job, 1, explicit_slots(nullptr), n);
         outs[d->nl - 2] = keep;
         if (rc == XQ_OK && qs) {                         // the env kernel finishes the values it needs itself
-            qs->slabs = *slab; qs->slab_stride = (long long)n * 96; qs->nslabs = nslabs; qs->bias = d->bl(XQ_NET_ONLINE, d->nl - 1);
+            qs->slabs = slab; qs->slab_stride = (long long)n * 96; qs->nslabs = nslabs; qs->bias = d->bl(XQ_NET_ONLINE, d->nl - 1);
             q = nullptr;
         } else if (rc == XQ_OK) {
             ProfScope ps(d, "gemm_q90_select", (double)n * 96 * nslabs, 4.0 * n * 96 * (nslabs + 1));
-            hipLaunchKernelGGL(q_head_finish_kernel, dim3((unsigned)(((long long)n * 96 + 255) / 256)), dim3(256), 0, d->cur, *slab, (long long)n * 96,
+            hipLaunchKernelGGL(q_head_finish_kernel, dim3((unsigned)(((long long)n * 96 + 255) / 256)), dim3(256), 0, d->cur, slab, (long long)n * 96,
                                nslabs, n, 96, 96, d->bl(XQ_NET_ONLINE, d->nl - 1), q, 96);
             if (hipGetLastError() != hipSuccess) rc = fail(XQ_ERR_RUNTIME, "q_head_finish_kernel launch failed");
         }
-    } else {
+    } else if (rc == XQ_OK) {
     rc = chain_boards(d, &job, 1, explicit_slots(nullptr), n);
     if (rc == XQ_OK) rc = q_head(d, XQ_NET_ONLINE, outs[d->nl - 2], n, 96, q, 96, "gemm_q90_select", bf ? outs_bf[d->nl - 2] : nullptr);
     }
@@ -797,31 +721,18 @@ static int check_reference_topology(const xq_dqn* d) {
     return XQ_OK;
 }
 
-// hidden deltas l = nl-2 .. 0 from the output-side delta `dnext` ([n][ld_next], only the first k_nz columns can be
-// non-zero).  reference mode: delta_l = (dnext[:, :L[l+1]] x View) * (1-a^2), View[i][idx] = Wflat[wo[l+1] + i*L[l] + idx];
-// textbook: View[k][idx] = W_{l+1}[k][idx], k < L[l+2].
 // matrix-pipe form of the layer-0 gradient (xq_dqn_set_l0_grad_mode(1), xq_l0grad.hip.h): taken at these shapes
 static bool l0_mfma_shape(const xq_dqn* d, int n) { return d->l0_mfma && (d->L[1] % 64) == 0 && n >= 256; }
 static int l0_chunk_of(int n) { return n >= 16384 ? 2048 : 1024; }
 static int ensure_l0_mfma(xq_dqn* d, int n) {
     const int H = d->L[1], chunk = l0_chunk_of(n), kpad = (n + chunk - 1) / chunk * chunk;
-    const size_t need = l0m_plane_elems(H, kpad);
-    if (need > d->l0_planes_cap) {
-        if (d->l0_planes) { XQ_HIP(hipDeviceSynchronize()); XQ_HIP(hipFree(d->l0_planes)); }
-        XQ_HIP(hipMalloc(&d->l0_planes, need * sizeof(uint16_t)));
-        XQ_HIP(hipMemsetAsync(d->l0_planes, 0, need * sizeof(uint16_t), d->cur));      // (the slack behind the planes is read, never used)
-        d->l0_planes_cap = need;
-    }
-    const size_t need_sel = l0sel_elems(kpad);
-    if (need_sel > d->l0_sel_cap) {
-        if (d->l0_sel) { XQ_HIP(hipDeviceSynchronize()); XQ_HIP(hipFree(d->l0_sel)); }
-        XQ_HIP(hipMalloc(&d->l0_sel, need_sel * sizeof(uint16_t)));
-        XQ_HIP(hipMemsetAsync(d->l0_sel, 0, need_sel * sizeof(uint16_t), d->cur));
-        d->l0_sel_cap = need_sel;
-    }
-    return XQ_OK;
+    XQ_TRY(reserve_zeroed(d->l0_planes, l0m_plane_elems(H, kpad), d->cur));     // (the slack behind the planes is read, never used)
+    return reserve_zeroed(d->l0_sel, l0sel_elems(kpad), d->cur);
 }
 
+// hidden deltas l = nl-2 .. 0 from the output-side delta `dnext` ([n][ld_next], only the first k_nz columns can be
+// non-zero).  reference mode: delta_l = (dnext[:, :L[l+1]] x View) * (1-a^2), View[i][idx] = Wflat[wo[l+1] + i*L[l] + idx];
+// textbook: View[k][idx] = W_{l+1}[k][idx], k < L[l+2].
 static int hidden_deltas(xq_dqn* d, int n, const float* dnext, int ld_next, int k_nz, int mode, int l_start = -1, int l_stop = 0) {
     const float* up = dnext;
     int ld_up = ld_next, nz = k_nz;
@@ -903,7 +814,7 @@ static int grad_gemm(xq_dqn* d, GemmArgs g, float* dst, const char* name, float*
         Bf16GemmArgs b; memset(&b, 0, sizeof b);
         b.M = g.M; b.N = g.N; b.K = g.K; b.A = a_bf; b.lda = g.lda; b.B = b_bf; b.ldb = g.ldb; b.k_chunk = g.K / splits;
         if (splits > 1) {
-            if (!slabs) { XQ_TRY(ensure_slabs(d, (size_t)splits * (size_t)len)); slabs = d->slabs; }
+            if (!slabs) { XQ_TRY(d->slabs.reserve((size_t)splits * (size_t)len)); slabs = d->slabs; }
             b.C = slabs; b.ldc = g.N; b.slab_stride = len;
         } else { b.C = dst; b.ldc = g.N; }
         XQ_TRY((launch_bf16_gemm<L_MCONTIG, L_MCONTIG, BG_STORE>(d, b, splits, name)));
@@ -919,7 +830,7 @@ static int grad_gemm(xq_dqn* d, GemmArgs g, float* dst, const char* name, float*
     const long long len = (long long)g.M * g.N;
     float* slabs = slab_base;
     if (splits > 1) {
-        if (!slabs) { XQ_TRY(ensure_slabs(d, (size_t)splits * (size_t)len)); slabs = d->slabs; }
+        if (!slabs) { XQ_TRY(d->slabs.reserve((size_t)splits * (size_t)len)); slabs = d->slabs; }
         g.C = slabs; g.ldc = g.N; g.slab_stride = len;
     } else {
         g.C = dst; g.ldc = g.N; g.slab_stride = 0;
@@ -960,11 +871,7 @@ static int bias_grads(xq_dqn* d, BiasJobs& bj, int n, xq_dqn::PendingSlab* defer
     for (int k = 0; k < J.njobs; ++k) { J.poff[k] = off; off += J.C[k]; maxc = std::max(maxc, J.C[k]); }
     J.wld = off;
     off *= J.R;
-    if ((size_t)off > d->bias_work_cap) {
-        if (d->bias_work) { XQ_HIP(hipStreamSynchronize(d->stream)); XQ_HIP(hipFree(d->bias_work)); }
-        XQ_HIP(hipMalloc(&d->bias_work, (size_t)off * sizeof(float)));
-        d->bias_work_cap = (size_t)off;
-    }
+    XQ_TRY(d->bias_work.reserve((size_t)off));
     J.work = d->bias_work;
     if (defer) { defer->src = J.work; defer->nslabs = J.R; defer->stride = J.wld; }
     double tot = 0;
@@ -994,12 +901,7 @@ static int l0_gradient(xq_dqn* d, int n, float* dst) {
     const long long len = (long long)kStateSize * H;
     float* out = dst;
     if (nchunks > 1) {
-        const size_t need = (size_t)nchunks * (size_t)len;
-        if (need > d->slabs_l0_cap) {
-            if (d->slabs_l0) { XQ_HIP(hipDeviceSynchronize()); XQ_HIP(hipFree(d->slabs_l0)); }
-            XQ_HIP(hipMalloc(&d->slabs_l0, need * sizeof(float)));
-            d->slabs_l0_cap = need;
-        }
+        XQ_TRY(d->slabs_l0.reserve((size_t)nchunks * (size_t)len));
         out = d->slabs_l0;
     }
     if (l0_mfma_shape(d, n)) {
@@ -1119,7 +1021,7 @@ int xq_dqn_create(const int* layer_sizes, int n_sizes, double learning_rate, dou
     if (c == 0) return fail(XQ_ERR_NO_DEVICE, "no HIP device: libxqhip has no CPU fallback");
     xq_dqn* d = new xq_dqn();
     const int rc = dqn_init(d, layer_sizes, n_sizes, learning_rate, gamma, seed, hip_stream);
-    if (rc != XQ_OK) { xq_dqn_destroy(d); return rc; }      // a failed allocation must not leak the ones before it
+    if (rc != XQ_OK) { xq_dqn_destroy(d); return rc; }      // whatever it had allocated, created or recorded goes with the handle
     *out = d;
     return XQ_OK;
 }
@@ -1152,12 +1054,12 @@ static int dqn_init(xq_dqn* d, const int* layer_sizes, int n_sizes, double learn
     int widest = 0;
     for (int i = 0; i < n_sizes; ++i) widest = std::max(widest, layer_sizes[i]);
     const size_t pad = (size_t)128 * widest;
-    for (int i = 0; i < 2; ++i) {
-        XQ_HIP(hipMalloc(&d->params[i], (d->nw + d->nb + pad) * sizeof(float)));
-        XQ_HIP(hipMemsetAsync(d->params[i], 0, (d->nw + d->nb + pad) * sizeof(float), d->stream));
+    for (auto& p : d->params) {
+        XQ_TRY(p.alloc(d->nw + d->nb + pad));
+        XQ_HIP(hipMemsetAsync(p, 0, p.n * sizeof(float), d->stream));
     }
     layout_td_grads(d);
-    XQ_HIP(hipMalloc(&d->grads_td, d->n_grads_td * sizeof(float)));
+    XQ_TRY(d->grads_td.alloc(d->n_grads_td));
     XQ_HIP(hipMemsetAsync(d->grads_td, 0, d->n_grads_td * sizeof(float), d->stream));
     // initializeHostWeightsAndBiases (dqn.cu:96-123): U(-0.05, 0.05) in [layer][out][in] order, biases 0
     std::vector<double> w(d->nw), b(d->nb, 0.0);
@@ -1171,32 +1073,19 @@ static int dqn_init(xq_dqn* d, const int* layer_sizes, int n_sizes, double learn
 int xq_dqn_destroy(xq_dqn* d) {
     if (!d) return XQ_OK;
     hipStreamSynchronize(d->stream);
+    if (d->side) hipStreamSynchronize(d->side);
     retire_stream(d->stream);                                // (synchronised above: nothing queued on it is left to wait for — also when the stream is the caller's, which may destroy it next)
-    for (int i = 0; i < 2; ++i) { hipFree(d->params[i]); hipFree(d->tacts[i]); }
-    for (int l = 0; l < XQ_MAX_LAYERS; ++l) { hipFree(d->acts[l]); hipFree(d->deltas[l]); hipFree(d->sel_acts[l]); }
-    hipFree(d->gboards); hipFree(d->dsc); hipFree(d->act_mb); hipFree(d->q90); hipFree(d->sel_q90); for (auto& K : d->sel_keep) { hipFree(K.z1); hipFree(K.prev_boards); } hipFree(d->partial); hipFree(d->zmax); hipFree(d->zidx); hipFree(d->qsa); hipFree(d->yv); hipFree(d->lossv);
-    hipFree(d->grads_td); hipFree(d->grads_full); hipFree(d->slabs); hipFree(d->bias_work); hipFree(d->xdense); hipFree(d->qfull); hipFree(d->tfull);
-    hipFree(d->hb); hipFree(d->ha); hipFree(d->hr); hipFree(d->hd);
+    if (d->side) retire_stream(d->side);
     d->prof.collect();
-    hipFree(d->slabs_l0); hipFree(d->l0_planes); hipFree(d->l0_sel);
-    for (int i = 0; i < 2; ++i) { hipFree(d->params_bf[i]); hipFree(d->tacts_bf[i]); hipFree(d->t2acts_bf[i]); hipFree(d->t2acts[i]); }
-    for (int l = 0; l < XQ_MAX_LAYERS; ++l) { hipFree(d->acts_bf[l]); hipFree(d->sel_acts_bf[l]); }
-    hipFree(d->partial_idx);
-    hipFree(d->qh_slabs[0]); hipFree(d->qh_slabs[1]);
-    for (int l = 0; l < XQ_MAX_LAYERS; ++l) hipFree(d->deltas_bf[l]);
-    if (d->side) { hipStreamSynchronize(d->side); retire_stream(d->side); hipStreamDestroy(d->side); }
+    if (d->side) hipStreamDestroy(d->side);
     delete d->tail;
     if (d->ev_fork) hipEventDestroy(d->ev_fork);
     if (d->ev_join) hipEventDestroy(d->ev_join);
     if (d->ev_delta) hipEventDestroy(d->ev_delta);
     if (d->ev_qmax) hipEventDestroy(d->ev_qmax);
-    for (void* q : {(void*)d->scr_wb, (void*)d->scr_ab, (void*)d->scr_p1, (void*)d->scr_p2, (void*)d->scr_wmax, (void*)d->scr_stats, (void*)d->scr_R,
-                    (void*)d->scr_na})
-        if (q) hipFree(q);
-    if (d->scr_guard_host) hipHostFree(d->scr_guard_host);
     if (d->scr_guard_ev) hipEventDestroy(d->scr_guard_ev);
     if (d->own_stream) hipStreamDestroy(d->stream);
-    delete d;
+    delete d;                                                // the buffers go here: behind the synchronises above
     return XQ_OK;
 }
 
@@ -1325,15 +1214,10 @@ int xq_dqn_set_precision(xq_dqn* d, int precision) {
     if (precision != XQ_PRECISION_F32) {
         for (int l = 1; l <= d->nl - 1; ++l)
             if (d->L[l] & 1) return fail(XQ_ERR_INVALID_ARGUMENT, "bf16 Q-net needs even hidden widths (layer %d has %d)", l, d->L[l]);
-        if (!d->params_bf[0]) {
-            int widest = 0;
-            for (int i = 0; i < d->ns; ++i) widest = std::max(widest, d->L[i]);
-            const size_t pad = (size_t)128 * widest;         // whole-tile reads of the persistent GEMM, like params[]
-            for (int i = 0; i < 2; ++i) {
-                XQ_HIP(hipMalloc(&d->params_bf[i], (d->nw + pad) * sizeof(uint16_t)));
-                XQ_HIP(hipMemsetAsync(d->params_bf[i], 0, (d->nw + pad) * sizeof(uint16_t), d->stream));
-            }
-        }
+        int widest = 0;
+        for (int i = 0; i < d->ns; ++i) widest = std::max(widest, d->L[i]);
+        const size_t pad = (size_t)128 * widest;             // whole-tile reads of the persistent GEMM, like params[]
+        for (auto& p : d->params_bf) XQ_TRY(reserve_zeroed(p, d->nw + pad, d->stream));      // (first call only)
     }
     d->precision = precision;
     d->params_version += 1;
@@ -1364,12 +1248,12 @@ static int chain_dense(xq_dqn* d, int net, const float* x, int n, float* const* 
     return XQ_OK;
 }
 
-static int upload_dense(xq_dqn* d, const double* src, size_t count, float** dev, size_t* cap) {
-    XQ_TRY(grow(dev, cap, count, d->stream));
+static int upload_dense(xq_dqn* d, const double* src, size_t count, DevBuf<float>& dev) {
+    XQ_TRY(dev.reserve(count));
     std::vector<float> tmp(count);
     for (size_t i = 0; i < count; ++i) tmp[i] = (float)src[i];
     XQ_HIP(hipStreamSynchronize(d->stream));
-    XQ_HIP(hipMemcpy(*dev, tmp.data(), count * sizeof(float), hipMemcpyHostToDevice));
+    XQ_HIP(hipMemcpy(dev, tmp.data(), count * sizeof(float), hipMemcpyHostToDevice));
     return XQ_OK;
 }
 
@@ -1377,8 +1261,8 @@ int xq_dqn_forward(xq_dqn* d, int net, const double* states, int n, double* q_ho
     if (!d || !states || !q_host || n <= 0 || net < 0 || net > 1)
         return fail(XQ_ERR_INVALID_ARGUMENT, "Input size does not match network input layer size.");
     XQ_TRY(ensure_capacity(d, n));
-    XQ_TRY(upload_dense(d, states, (size_t)n * d->L[0], &d->xdense, &d->xdense_cap));
-    XQ_TRY(grow(&d->qfull, &d->qfull_cap, (size_t)n * d->nout(), d->stream));
+    XQ_TRY(upload_dense(d, states, (size_t)n * d->L[0], d->xdense));
+    XQ_TRY(d->qfull.reserve((size_t)n * d->nout()));
     float* outs[XQ_MAX_LAYERS];
     for (int l = 0; l + 1 < d->nl; ++l) outs[l] = d->acts[l];
     XQ_TRY(chain_dense(d, net, d->xdense, n, outs));
@@ -1419,10 +1303,10 @@ int xq_dqn_backpropagate(xq_dqn* d, const double* states, const double* targets,
     if (mode == XQ_BACKPROP_REFERENCE) XQ_TRY(check_reference_topology(d));
     XQ_TRY(ensure_capacity(d, n));
     const int NO = d->nout();
-    XQ_TRY(upload_dense(d, states, (size_t)n * d->L[0], &d->xdense, &d->xdense_cap));
-    XQ_TRY(upload_dense(d, targets, (size_t)n * NO, &d->tfull, &d->tfull_cap));
-    XQ_TRY(grow(&d->qfull, &d->qfull_cap, (size_t)n * NO, d->stream));
-    if (!d->grads_full) XQ_HIP(hipMalloc(&d->grads_full, (d->nw + d->nb) * sizeof(float)));
+    XQ_TRY(upload_dense(d, states, (size_t)n * d->L[0], d->xdense));
+    XQ_TRY(upload_dense(d, targets, (size_t)n * NO, d->tfull));
+    XQ_TRY(d->qfull.reserve((size_t)n * NO));
+    XQ_TRY(d->grads_full.reserve(d->nw + d->nb));
     float* outs[XQ_MAX_LAYERS];
     for (int l = 0; l + 1 < d->nl; ++l) outs[l] = d->acts[l];
     XQ_TRY(chain_dense(d, XQ_NET_ONLINE, d->xdense, n, outs));
@@ -1499,7 +1383,7 @@ static int side_gradients(xq_dqn* d, int n, float* const* outs, float* G) {
             const int sp = grad_splits(d, d->L[l + 1], d->L[l], n);
             if (sp > 1) need += (size_t)sp * (size_t)d->L[l + 1] * (size_t)d->L[l];
         }
-        XQ_TRY(ensure_slabs(d, need));
+        XQ_TRY(d->slabs.reserve(need));
         for (int l = 0; l < XQ_MAX_LAYERS; ++l) d->pend_hidden[l] = xq_dqn::PendingSlab();
         d->pend_wout = d->pend_bout = xq_dqn::PendingSlab();
     }
@@ -1508,7 +1392,7 @@ static int side_gradients(xq_dqn* d, int n, float* const* outs, float* G) {
         float* out = dst;
         if (nchunks > 1) {
             if (fused) out = d->slabs + off_out;
-            else { XQ_TRY(ensure_slabs(d, (size_t)nchunks * (size_t)len_out)); out = d->slabs; }
+            else { XQ_TRY(d->slabs.reserve((size_t)nchunks * (size_t)len_out)); out = d->slabs; }
         }
         {
             ProfScope ps(d, "out_grad_segsum", 2.0 * n * Hl, (double)n * (Hl * 4 + 8) + 4.0 * nchunks * len_out);
@@ -1629,7 +1513,7 @@ static int tail_gradients_impl(xq_dqn* d, int n, float* const* outs, float* G, i
         const int sp = grad_splits(d, d->L[l + 1], d->L[l], n);
         if (sp > 1) need += (size_t)sp * (size_t)d->L[l + 1] * (size_t)d->L[l];
     }
-    XQ_TRY(ensure_slabs(d, need));
+    XQ_TRY(d->slabs.reserve(need));
     for (int l = 0; l < XQ_MAX_LAYERS; ++l) d->pend_hidden[l] = xq_dqn::PendingSlab();
     d->pend_wout = d->pend_bout = xq_dqn::PendingSlab();
     const size_t og_lds = (size_t)16 * Hl * sizeof(float) + (size_t)chunk * sizeof(uint16_t);
@@ -1804,7 +1688,7 @@ static int qmax_screened(xq_dqn* d, const TdStep& s, bool scr_new, int parity, b
         GemmArgs g; memset(&g, 0, sizeof g);
         g.M = NO; g.N = n;
         g.K = Hl / 2; g.lda = g.ldb = Hl / 2;
-        g.A = reinterpret_cast<const float*>(d->scr_wb); g.B = reinterpret_cast<const float*>(d->scr_ab);
+        g.A = reinterpret_cast<const float*>(d->scr_wb.p); g.B = reinterpret_cast<const float*>(d->scr_ab.p);
         g.bias = bias;
         g.partial = d->scr_p1; g.partial2 = d->scr_p2;
         const int grid = colmax_persistent_grid(d, g, tiles_m, total);
@@ -1836,15 +1720,15 @@ static int qmax_screened(xq_dqn* d, const TdStep& s, bool scr_new, int parity, b
             const int whole_mode = stage ? 2 : 1;
             const auto kern = *td_fused ? qmax_refine2_kernel<256, true> : Hl == 256 ? qmax_refine2_kernel<256> : qmax_refine2_kernel<512>;
             XQ_TRY(ensure_max_dynamic_lds(kern, 152 * 1024));     // the staged pass asks for ~145 KB
-            hipExtLaunchKernelGGL(kern, grid, dim3(256), lds, d->cur, ps.start(), ps.stop(), 0, d->scr_R, scr_ranges, scr_gpr, d->scr_p1, d->scr_p2, G,
-                                  n, ldp, d->scr_na, a_last, Hl, W, bias, NO, d->scr_wmax, parity, d->zmax, d->scr_stats, T, whole_mode);
+            hipExtLaunchKernelGGL(kern, grid, dim3(256), lds, d->cur, ps.start(), ps.stop(), 0, d->scr_R.p, scr_ranges, scr_gpr, d->scr_p1.p, d->scr_p2.p,
+                                  G, n, ldp, d->scr_na.p, a_last, Hl, W, bias, NO, d->scr_wmax.p, parity, d->zmax.p, d->scr_stats.p, T, whole_mode);
         } else {
             const bool small = G <= 8 * 32;
             const auto kern = Hl == 256 ? (small ? qmax_refine_kernel<256, 32> : qmax_refine_kernel<256, 64>)
                             : Hl == 512 ? (small ? qmax_refine_kernel<512, 32> : qmax_refine_kernel<512, 64>)
                                         : (small ? qmax_refine_kernel<0, 32> : qmax_refine_kernel<0, 64>);
-            hipExtLaunchKernelGGL(kern, grid, dim3(256), lds, d->cur, ps.start(), ps.stop(), 0, d->scr_p1, d->scr_p2, G, n, ldp, a_last, Hl,
-                                  W, bias, NO, d->scr_wmax, parity, d->zmax, d->scr_stats);
+            hipExtLaunchKernelGGL(kern, grid, dim3(256), lds, d->cur, ps.start(), ps.stop(), 0, d->scr_p1.p, d->scr_p2.p, G, n, ldp, a_last, Hl,
+                                  W, bias, NO, d->scr_wmax.p, parity, d->zmax.p, d->scr_stats.p);
         }
         XQ_HIP(hipGetLastError());
     }
@@ -1869,7 +1753,7 @@ static int qmax_exact(xq_dqn* d, const TdStep& s, bool bf_frag, bool gate_early)
         // layer, not a screen: per 32-row lane group the largest value (+ its row, first maximum: Double DQN)
         ScreenArgs a; memset(&a, 0, sizeof a);
         a.W = d->wl_bf(s.sel_net, nl - 1); a.A = s.touts_bf[nl - 2]; a.a_frag = bf_frag ? 1 : 0; a.bias = d->bl(s.sel_net, nl - 1);
-        a.P1 = d->partial; a.P2 = reinterpret_cast<float*>(d->partial_idx);
+        a.P1 = d->partial; a.P2 = reinterpret_cast<float*>(d->partial_idx.p);
         screen_geometry(NO, n, Hl, d->ncu, a);
         part_ld = a.ldp = screen_padded_samples(n, Hl);
         n_part = 2 * a.nchunks;
@@ -2049,8 +1933,8 @@ int xq_dqn_calibrate_exchange(xq_dqn* d, double threshold_us, double* allreduce_
     if (!d->comm) return fail(XQ_ERR_INVALID_ARGUMENT, "xq_dqn_calibrate_exchange: no communicator attached");
     if (d->n_grads_td == 0) layout_td_grads(d);
     // COLLECTIVE: every rank times the same 4 + 20 all-reduces of a scratch buffer of the gradient buffer's size on the handle's stream
-    float* scratch = nullptr;
-    XQ_HIP(hipMalloc(&scratch, d->n_grads_td * sizeof(float)));
+    DevBuf<float> scratch;
+    XQ_TRY(scratch.alloc(d->n_grads_td));
     hipEvent_t e0 = nullptr, e1 = nullptr;
     int rc = XQ_OK;
     float ms = 0.f;
@@ -2068,8 +1952,7 @@ int xq_dqn_calibrate_exchange(xq_dqn* d, double threshold_us, double* allreduce_
     } while (0);
     if (e0) (void)hipEventDestroy(e0);
     if (e1) (void)hipEventDestroy(e1);
-    (void)hipStreamSynchronize(d->stream);
-    (void)hipFree(scratch);
+    (void)hipStreamSynchronize(d->stream);           // (nothing queued reads the scratch buffer when it goes, however this returns)
     if (rc != XQ_OK) return rc;
     // the ranks must agree (a rank that starts its select chain late while its neighbours start early only wastes what the rule
     // saves): the decision is taken on the MEAN over the ranks, in integer nanoseconds so that every rank computes the same number
@@ -2199,15 +2082,10 @@ int xq_dqn_td_update_host(xq_dqn* d, int n, const uint8_t* boards90, const uint8
         return fail(XQ_ERR_INVALID_ARGUMENT, "xq_dqn_td_update_host: bad argument");
     for (size_t i = 0; i < (size_t)n * 90; ++i)       // code 15 would index one-hot plane 14 of 14 in the layer-0 kernels
         if (boards90[i] > 14 || next_boards90[i] > 14) return fail(XQ_ERR_INVALID_ARGUMENT, "piece code > 14");
-    if ((size_t)n > d->hb_cap) {
-        XQ_HIP(hipStreamSynchronize(d->stream));
-        hipFree(d->hb); hipFree(d->ha); hipFree(d->hr); hipFree(d->hd);
-        XQ_HIP(hipMalloc(&d->hb, (size_t)n * 2 * kBoardWords * sizeof(uint32_t)));
-        XQ_HIP(hipMalloc(&d->ha, (size_t)n * sizeof(int32_t)));
-        XQ_HIP(hipMalloc(&d->hr, (size_t)n * sizeof(float)));
-        XQ_HIP(hipMalloc(&d->hd, (size_t)n));
-        d->hb_cap = (size_t)n;
-    }
+    XQ_TRY(d->hb.reserve((size_t)n * 2 * kBoardWords));
+    XQ_TRY(d->ha.reserve((size_t)n));
+    XQ_TRY(d->hr.reserve((size_t)n));
+    XQ_TRY(d->hd.reserve((size_t)n));
     std::vector<uint32_t> w((size_t)n * 2 * kBoardWords);
     for (int i = 0; i < n; ++i) {
         pack_board(boards90 + (size_t)i * 90, &w[(size_t)i * kBoardWords]);

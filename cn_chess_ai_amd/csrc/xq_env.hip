@@ -653,18 +653,18 @@ static int env_init(xq_env* e, int n_games, uint64_t seed, uint32_t first_game_i
     if (hip_stream) e->stream = (hipStream_t)hip_stream;
     else { XQ_HIP(hipStreamCreate(&e->stream)); e->own_stream = true; }
     const size_t n = (size_t)n_games;
-    XQ_HIP(hipMalloc(&e->boards, n * kBoardWords * sizeof(uint32_t)));
-    XQ_HIP(hipMalloc(&e->meta, n * sizeof(uint4)));
-    XQ_HIP(hipMalloc(&e->stats, n * sizeof(uint4)));
-    XQ_HIP(hipMalloc(&e->results, n * sizeof(xq_step_result)));
-    XQ_HIP(hipMalloc(&e->codes, n * kMaxMoves * sizeof(uint16_t)));
-    XQ_HIP(hipMalloc(&e->counts, n * sizeof(int32_t)));
-    XQ_HIP(hipMalloc(&e->actions, n * sizeof(int32_t)));
-    XQ_HIP(hipMalloc(&e->q90, n * 96 * sizeof(float)));
-    XQ_HIP(hipMalloc(&e->validmat, 8 * 8100));        // isValidMove matrix, or the 7 per-piece rule matrices (+ query scratch)
+    XQ_TRY(e->boards.alloc(n * kBoardWords));
+    XQ_TRY(e->meta.alloc(n));
+    XQ_TRY(e->stats.alloc(n));
+    XQ_TRY(e->results.alloc(n));
+    XQ_TRY(e->codes.alloc(n * kMaxMoves));
+    XQ_TRY(e->counts.alloc(n));
+    XQ_TRY(e->actions.alloc(n));
+    XQ_TRY(e->q90.alloc(n * 96));
+    XQ_TRY(e->validmat.alloc(8 * 8100));              // isValidMove matrix, or the 7 per-piece rule matrices (+ query scratch)
     e->ep_cap = std::max(4096, 4 * n_games);
-    XQ_HIP(hipMalloc(&e->ep_ring, (size_t)e->ep_cap * sizeof(xq_episode_record)));
-    XQ_HIP(hipMalloc(&e->ep_head, sizeof(unsigned long long)));
+    XQ_TRY(e->ep_ring.alloc((size_t)e->ep_cap));
+    XQ_TRY(e->ep_head.alloc(1));
     XQ_TRY(upload_start_words(e->stream));
     return xq_env_reset(e);
 }
@@ -685,9 +685,6 @@ int xq_env_destroy(xq_env* e) {
     if (!e) return XQ_OK;
     hipStreamSynchronize(e->stream);
     retire_stream(e->stream);        // synchronised above; unconditional: a caller-owned stream may be destroyed right after this call
-    hipFree(e->boards); hipFree(e->meta); hipFree(e->stats); hipFree(e->results); hipFree(e->codes);
-    hipFree(e->counts); hipFree(e->actions); hipFree(e->q90); hipFree(e->validmat); hipFree(e->ep_ring);
-    hipFree(e->ep_head);
     if (e->own_stream) hipStreamDestroy(e->stream);
     delete e;
     return XQ_OK;
@@ -834,7 +831,7 @@ int xq_env_rule_query(xq_env* e, int game, int piece_type, int fr, int fc, int t
 
 int xq_env_get_winner(xq_env* e, int first, int n, uint8_t* winners_host) {
     if (!e || !winners_host || first < 0 || n <= 0 || first + n > e->n) return fail(XQ_ERR_INVALID_ARGUMENT, "bad game range");
-    uint8_t* out = reinterpret_cast<uint8_t*>(e->counts);          // n bytes of the [n] int32 scratch
+    uint8_t* out = reinterpret_cast<uint8_t*>(e->counts.p);          // n bytes of the [n] int32 scratch
     hipLaunchKernelGGL(winner_kernel, dim3((n + 3) / 4), dim3(256), 0, e->stream, e->boards, first, n, out);
     XQ_HIP(hipGetLastError());
     XQ_HIP(hipMemcpyAsync(winners_host, out, (size_t)n, hipMemcpyDeviceToHost, e->stream));
@@ -916,6 +913,6 @@ int xq_env_counters(xq_env* e, uint64_t c[6]) {
 }
 
 const uint32_t* xq_env_boards_dev(const xq_env* e) { return e ? e->boards : nullptr; }
-const uint32_t* xq_env_meta_dev(const xq_env* e) { return e ? (const uint32_t*)e->meta : nullptr; }
+const uint32_t* xq_env_meta_dev(const xq_env* e) { return e ? (const uint32_t*)e->meta.p : nullptr; }
 
 }  // extern "C"

@@ -49,9 +49,57 @@ struct SharedResource {
 };
 void retire_stream(hipStream_t s);     // after hipStreamSynchronize(s), before hipStreamDestroy(s)
 
+// ---- the one owner of device memory ----------------------------------------------------------------------------------------------
+// DevBuf<T>: n elements of T in device memory (PinnedBuf<T>: in pinned host memory), freed by the destructor — a handle's buffers go
+// with `delete handle`, a local scratch buffer with its scope, whichever way the function returns.  It converts to T* wherever the
+// pointer is read (launch arguments, views such as ReplayDev, arithmetic); `p` names it where no conversion applies.
+// reserve() is the one growth rule of the library: a buffer that is large enough costs no runtime call; one that is not is replaced
+// behind a device-wide synchronise (whatever stream its last reader ran on — the select chain of a handle may be in flight on another
+// stream than the handle's — has finished), the old contents are dropped, the new ones are undefined.  Callers that need zeros queue
+// their own memset when `*grew` says so.  A failed alloc() / reserve() leaves the buffer empty, so a later call starts over.
+struct DeviceMem {
+    static hipError_t get(void** p, size_t bytes) { return hipMalloc(p, bytes); }
+    static hipError_t put(void* p) { return hipFree(p); }
+};
+struct PinnedMem {
+    static hipError_t get(void** p, size_t bytes) { return hipHostMalloc(p, bytes, hipHostMallocDefault); }
+    static hipError_t put(void* p) { return hipHostFree(p); }
+};
+template <class T, class Mem = DeviceMem>
+struct DevBuf {
+    T* p = nullptr;
+    size_t n = 0;                      // elements
+    DevBuf() = default;
+    ~DevBuf() { release(); }
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    operator T*() const { return p; }
+    void release() {
+        if (p) (void)Mem::put(p);
+        p = nullptr; n = 0;
+    }
+    int alloc(size_t count) {          // exactly `count` elements in place of whatever it holds
+        release();
+        void* q = nullptr;
+        const hipError_t e = Mem::get(&q, count * sizeof(T));
+        if (e != hipSuccess) return fail(XQ_ERR_RUNTIME, "HIP error: %s allocating %zu bytes", hipGetErrorString(e), count * sizeof(T));
+        p = static_cast<T*>(q); n = count;
+        return XQ_OK;
+    }
+    int reserve(size_t count, bool* grew = nullptr) {
+        if (count <= n) return XQ_OK;
+        XQ_HIP(hipDeviceSynchronize());
+        XQ_TRY(alloc(count));
+        if (grew) *grew = true;
+        return XQ_OK;
+    }
+};
+template <class T> using PinnedBuf = DevBuf<T, PinnedMem>;
+
 }  // namespace xq
 
-// replay ring in HBM: structure of arrays, states as packed boards (48 B) — never 1260 floats
+// replay ring in HBM: structure of arrays, states as packed boards (48 B) — never 1260 floats.  A plain view, passed to kernels by
+// value; xq_replay owns the memory behind it.
 struct ReplayDev {
     uint32_t* boards = nullptr;       // [capacity][12]
     uint32_t* next_boards = nullptr;  // [capacity][12]
@@ -67,13 +115,16 @@ struct ReplayDev {
 
 struct xq_replay {
     ReplayDev dev;
+    xq::DevBuf<uint32_t> boards, next_boards;     // what `dev` points into
+    xq::DevBuf<int32_t> action_to;
+    xq::DevBuf<float> reward, prio;
+    xq::DevBuf<uint8_t> done;
     int size = 0;
     int write_pos = 0;
     uint64_t total = 0;
     uint64_t seed = 0;
     uint64_t sample_calls = 0;
-    int32_t* slots_dev = nullptr;     // last sample()
-    int slots_cap = 0;
+    xq::DevBuf<int32_t> slots_dev;    // last sample()
     int last_batch = 0;
     bool implicit = false;            // last sample() was "virtual": consumers derive slot i = philox(i, call) % size themselves
     uint32_t implicit_call = 0;
@@ -99,15 +150,15 @@ struct xq_replay {
         bool enabled = false;
         float alpha = 0.6f, beta = 0.4f, eps = 1e-3f;
         int nlv = 0, n[8] = {0}, p[8] = {0};
-        float* leaves = nullptr;          // level 0 as of the last rebuild (copy of dev.prio; the sampler reads this, never the live table)
-        float* upper = nullptr;           // levels 1.. concatenated (padded), root last
+        xq::DevBuf<float> leaves;        // level 0 as of the last rebuild (copy of dev.prio; the sampler reads this, never the live table)
+        xq::DevBuf<float> upper;         // levels 1.. concatenated (padded), root last
         size_t off[8] = {0};              // offset of level lv inside `upper` (lv >= 1)
-        unsigned* scalars = nullptr;      // [0] max priority, live (atomicMax of float bits)  [1] its snapshot at the last rebuild
+        xq::DevBuf<unsigned> scalars;    // [0] max priority, live (atomicMax of float bits)  [1] its snapshot at the last rebuild
                                           // [2] max raw importance weight of the last sample (float bits)  [3] eligible slots (p > 0)
-        unsigned* wave_counts = nullptr;  // per-wave counts of non-zero leaves of the last rebuild (summed into scalars[3] by per_upper_kernel)
+        xq::DevBuf<unsigned> wave_counts;  // per-wave counts of non-zero leaves of the last rebuild (summed into scalars[3] by per_upper_kernel)
         bool wmax_clean = false;          // scalars[2] is zero (set by a rebuild, consumed by the next draw)
         bool draw_unconsumed = false;     // a prioritized draw whose TD step has not been queued yet: a rebuild must leave scalars[2] alone
-        float* is_w = nullptr;            // [slots_cap] raw importance weights of the last prioritized sample
+        xq::DevBuf<float> is_w;          // [slots_dev.n] raw importance weights of the last prioritized sample
         bool last_prioritized = false;
     } per;
 };
@@ -118,18 +169,18 @@ struct xq_env {
     uint32_t first_id = 0;
     hipStream_t stream = nullptr;
     bool own_stream = false;
-    uint32_t* boards = nullptr;        // [n][12]
-    uint4* meta = nullptr;             // [n] {moveCount|player<<16, red|black<<16, plies, episodes}
-    uint4* stats = nullptr;            // [n] {red wins, black wins, captures, explored}
-    xq_step_result* results = nullptr; // [n]
-    uint16_t* codes = nullptr;         // [n][128] scratch for legal_moves
-    int32_t* counts = nullptr;         // [n]
-    int32_t* actions = nullptr;        // [n] scratch for step()
-    float* q90 = nullptr;              // [n][96] scratch for selfplay_step_host
-    uint8_t* validmat = nullptr;       // [8100]
-    xq_episode_record* ep_ring = nullptr;
+    xq::DevBuf<uint32_t> boards;       // [n][12]
+    xq::DevBuf<uint4> meta;            // [n] {moveCount|player<<16, red|black<<16, plies, episodes}
+    xq::DevBuf<uint4> stats;           // [n] {red wins, black wins, captures, explored}
+    xq::DevBuf<xq_step_result> results; // [n]
+    xq::DevBuf<uint16_t> codes;        // [n][128] scratch for legal_moves
+    xq::DevBuf<int32_t> counts;        // [n]
+    xq::DevBuf<int32_t> actions;       // [n] scratch for step()
+    xq::DevBuf<float> q90;             // [n][96] scratch for selfplay_step_host
+    xq::DevBuf<uint8_t> validmat;      // [8100]
+    xq::DevBuf<xq_episode_record> ep_ring;
     int ep_cap = 0;
-    unsigned long long* ep_head = nullptr;   // device counter of finished episodes
+    xq::DevBuf<unsigned long long> ep_head;  // device counter of finished episodes
     uint64_t ep_drained = 0;
 };
 

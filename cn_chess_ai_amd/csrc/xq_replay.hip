@@ -192,15 +192,8 @@ int replay_per_sample(xq_replay* r, int batch, hipStream_t on) {
     if (!r || !r->per.enabled) return fail(XQ_ERR_INVALID_ARGUMENT, "prioritized replay is not enabled on this ring");
     if (batch <= 0) return fail(XQ_ERR_INVALID_ARGUMENT, "xq_replay_sample: batch must be > 0");
     hipStream_t s = on ? on : r->stream;
-    if (batch > r->slots_cap) {
-        XQ_HIP(hipDeviceSynchronize());
-        if (r->slots_dev) XQ_HIP(hipFree(r->slots_dev));
-        if (r->per.is_w) XQ_HIP(hipFree(r->per.is_w));
-        r->per.is_w = nullptr;
-        XQ_HIP(hipMalloc(&r->slots_dev, (size_t)batch * sizeof(int32_t)));
-        r->slots_cap = batch;
-    }
-    if (!r->per.is_w) XQ_HIP(hipMalloc(&r->per.is_w, (size_t)r->slots_cap * sizeof(float)));
+    XQ_TRY(r->slots_dev.reserve((size_t)batch));
+    XQ_TRY(r->per.is_w.reserve(r->slots_dev.n));         // the weights follow the slot list, whichever draw made it grow
     if (!r->caller_orders) {
         XQ_TRY(r->draw.write(s));        // the TD step that still reads the previous list / weights / batch maximum (its own stream) first
     }
@@ -285,11 +278,13 @@ static int replay_init(xq_replay* r, int capacity, uint64_t seed, void* hip_stre
     else { XQ_HIP(hipStreamCreate(&r->stream)); r->own_stream = true; }
     const size_t n = (size_t)capacity;
     r->dev.capacity = capacity;
-    XQ_HIP(hipMalloc(&r->dev.boards, n * kBoardWords * sizeof(uint32_t)));
-    XQ_HIP(hipMalloc(&r->dev.next_boards, n * kBoardWords * sizeof(uint32_t)));
-    XQ_HIP(hipMalloc(&r->dev.action_to, n * sizeof(int32_t)));
-    XQ_HIP(hipMalloc(&r->dev.reward, n * sizeof(float)));
-    XQ_HIP(hipMalloc(&r->dev.done, n));
+    XQ_TRY(r->boards.alloc(n * kBoardWords));
+    XQ_TRY(r->next_boards.alloc(n * kBoardWords));
+    XQ_TRY(r->action_to.alloc(n));
+    XQ_TRY(r->reward.alloc(n));
+    XQ_TRY(r->done.alloc(n));
+    r->dev.boards = r->boards; r->dev.next_boards = r->next_boards; r->dev.action_to = r->action_to; r->dev.reward = r->reward;
+    r->dev.done = r->done;
     XQ_HIP(hipMemsetAsync(r->dev.action_to, 0xFF, n * sizeof(int32_t), r->stream));   // -1: empty slot
     XQ_HIP(hipMemsetAsync(r->dev.boards, 0, n * kBoardWords * sizeof(uint32_t), r->stream));
     XQ_HIP(hipMemsetAsync(r->dev.next_boards, 0, n * kBoardWords * sizeof(uint32_t), r->stream));
@@ -302,9 +297,6 @@ int xq_replay_destroy(xq_replay* r) {
     if (!r) return XQ_OK;
     hipStreamSynchronize(r->stream);
     retire_stream(r->stream);        // synchronised above; unconditional: a caller-owned stream may be destroyed right after this call
-    hipFree(r->dev.boards); hipFree(r->dev.next_boards); hipFree(r->dev.action_to); hipFree(r->dev.reward);
-    hipFree(r->dev.done); hipFree(r->slots_dev);
-    hipFree(r->dev.prio); hipFree(r->per.leaves); hipFree(r->per.upper); hipFree(r->per.scalars); hipFree(r->per.wave_counts); hipFree(r->per.is_w);
     if (r->own_stream) hipStreamDestroy(r->stream);
     delete r;
     return XQ_OK;
@@ -368,19 +360,20 @@ int xq_replay_enable_per(xq_replay* r, double alpha, double beta, double eps) {
     }
     P.nlv = lv;
     XQ_HIP(hipStreamSynchronize(r->stream));
-    XQ_HIP(hipMalloc(&r->dev.prio, (size_t)P.p[0] * sizeof(float)));
-    XQ_HIP(hipMemset(r->dev.prio, 0, (size_t)P.p[0] * sizeof(float)));
-    XQ_HIP(hipMalloc(&P.leaves, (size_t)P.p[0] * sizeof(float)));
+    // (alloc() replaces: a call that failed part-way left `enabled` false, and the next one starts from whatever that one got)
+    XQ_TRY(r->prio.alloc((size_t)P.p[0]));
+    XQ_HIP(hipMemset(r->prio, 0, (size_t)P.p[0] * sizeof(float)));
+    XQ_TRY(P.leaves.alloc((size_t)P.p[0]));
     XQ_HIP(hipMemset(P.leaves, 0, (size_t)P.p[0] * sizeof(float)));
-    XQ_HIP(hipMalloc(&P.upper, std::max<size_t>(upper, 32) * sizeof(float)));
+    XQ_TRY(P.upper.alloc(std::max<size_t>(upper, 32)));
     XQ_HIP(hipMemset(P.upper, 0, std::max<size_t>(upper, 32) * sizeof(float)));
-    XQ_HIP(hipMalloc(&P.scalars, 4 * sizeof(unsigned)));
-    XQ_HIP(hipMalloc(&P.wave_counts, (size_t)((P.n[1] + 255) / 256 * 4 + 4) * sizeof(unsigned)));
+    XQ_TRY(P.scalars.alloc(4));
+    XQ_TRY(P.wave_counts.alloc((size_t)((P.n[1] + 255) / 256 * 4 + 4)));
     const float one = 1.0f;                      // initial maximum priority (Schaul et al.: new transitions get the maximum, 1 at start)
     unsigned init[4];
     memcpy(&init[0], &one, 4); init[1] = init[0]; init[2] = 0; init[3] = 0;
     XQ_HIP(hipMemcpy(P.scalars, init, sizeof init, hipMemcpyHostToDevice));
-    r->dev.pmax_snap = P.scalars + 1;
+    r->dev.prio = r->prio; r->dev.pmax_snap = P.scalars + 1;
     P.enabled = true;
     return XQ_OK;
 }
@@ -458,11 +451,7 @@ int xq_replay_sample_window(xq_replay* r, int batch, int start, int count, int32
     if (r->size <= 0 || count <= 0) return fail(XQ_ERR_RUNTIME, "xq_replay_sample: buffer is empty");
     if (count > r->size || start < 0 || start >= r->dev.capacity)
         return fail(XQ_ERR_INVALID_ARGUMENT, "xq_replay_sample_window: window (%d, %d) outside the %d filled slots", start, count, r->size);
-    if (batch > r->slots_cap) {
-        if (r->slots_dev) { XQ_HIP(hipStreamSynchronize(r->stream)); XQ_HIP(hipFree(r->slots_dev)); }
-        XQ_HIP(hipMalloc(&r->slots_dev, (size_t)batch * sizeof(int32_t)));
-        r->slots_cap = batch;
-    }
+    XQ_TRY(r->slots_dev.reserve((size_t)batch));
     if (!r->caller_orders) XQ_TRY(r->draw.write(r->stream));     // the TD step that still reads the previous list (its own stream) first
     hipLaunchKernelGGL(replay_sample_kernel, dim3((batch + 255) / 256), dim3(256), 0, r->stream, r->slots_dev, batch,
                        (uint32_t)start, (uint32_t)count, (uint32_t)r->dev.capacity, (uint32_t)r->sample_calls, (uint32_t)r->seed, (uint32_t)(r->seed >> 32));

@@ -254,15 +254,14 @@ int xq_env_search(xq_env* e, int depth, int32_t* values_host, int32_t* counts_ho
     if (!e || !values_host || !counts_host || !best_host) return fail(XQ_ERR_INVALID_ARGUMENT, "xq_env_search: null pointer");
     if (depth < 1 || depth > 3) return fail(XQ_ERR_INVALID_ARGUMENT, "xq_env_search: depth must be 1, 2 or 3 (got %d)", depth);
     const size_t n = (size_t)e->n;
-    int32_t* buf = nullptr;
-    XQ_HIP(hipMalloc(&buf, n * (kMaxMoves + 2) * sizeof(int32_t)));
+    DevBuf<int32_t> buf;
+    XQ_TRY(buf.alloc(n * (kMaxMoves + 2)));
     int rc = xq_env_search_dev(e, depth, buf, buf + n * kMaxMoves, buf + n * (kMaxMoves + 1));
     hipError_t he = hipSuccess;
     if (rc == XQ_OK) he = hipMemcpyAsync(values_host, buf, n * kMaxMoves * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream);
     if (rc == XQ_OK && he == hipSuccess) he = hipMemcpyAsync(counts_host, buf + n * kMaxMoves, n * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream);
     if (rc == XQ_OK && he == hipSuccess) he = hipMemcpyAsync(best_host, buf + n * (kMaxMoves + 1), n * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream);
-    const hipError_t hs = hipStreamSynchronize(e->stream);
-    (void)hipFree(buf);
+    const hipError_t hs = hipStreamSynchronize(e->stream);        // (the copies out of buf are done, or failed, before it goes)
     if (rc != XQ_OK) return rc;
     XQ_HIP(he);
     XQ_HIP(hs);

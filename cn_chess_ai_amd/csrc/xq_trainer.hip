@@ -52,9 +52,9 @@ struct xq_trainer {
     // counters from the learner's side {wins, draws, losses, ended} since xq_trainer_set_opponent
     bool vs_on = false;
     xq::CheckedPlayer vs;
-    int16_t* vs_pick = nullptr;
-    float* vs_q = nullptr;
-    uint4* vs_counts = nullptr;
+    xq::DevBuf<int16_t> vs_pick;
+    xq::DevBuf<float> vs_q;
+    xq::DevBuf<uint4> vs_counts;
     hipEvent_t vs_ev_env = nullptr, vs_ev_q = nullptr;
 };
 
@@ -130,7 +130,6 @@ int xq_trainer_destroy(xq_trainer* t) {
     if (t->ev_grads) hipEventDestroy(t->ev_grads);
     if (t->vs_ev_env) hipEventDestroy(t->vs_ev_env);
     if (t->vs_ev_q) hipEventDestroy(t->vs_ev_q);
-    hipFree(t->vs_pick); hipFree(t->vs_q); hipFree(t->vs_counts);
     retire_stream(t->stream);        // synchronised above; unconditional: a caller-owned stream may be destroyed right after this call
     xq_env_destroy(t->env);
     xq_dqn_destroy(t->dqn);
@@ -271,13 +270,11 @@ int xq_trainer_set_opponent(xq_trainer* t, const xq_arena_player* opp) {
     XQ_HIP(hipStreamSynchronize(t->stream));
     if (!opp) { t->vs_on = false; return XQ_OK; }
     const size_t n = (size_t)t->env->n;
-    if (!t->vs_counts) {
-        XQ_HIP(hipMalloc(&t->vs_counts, n * sizeof(uint4)));
-        XQ_HIP(hipMalloc(&t->vs_pick, n * sizeof(int16_t)));
-        XQ_HIP(hipMalloc(&t->vs_q, n * 96 * sizeof(float)));
-        XQ_HIP(hipEventCreateWithFlags(&t->vs_ev_env, stream_event_flags()));
-        XQ_HIP(hipEventCreateWithFlags(&t->vs_ev_q, stream_event_flags()));
-    }
+    XQ_TRY(t->vs_counts.reserve(n));                 // (first call only: the env's size is fixed)
+    XQ_TRY(t->vs_pick.reserve(n));
+    XQ_TRY(t->vs_q.reserve(n * 96));
+    if (!t->vs_ev_env) XQ_HIP(hipEventCreateWithFlags(&t->vs_ev_env, stream_event_flags()));
+    if (!t->vs_ev_q) XQ_HIP(hipEventCreateWithFlags(&t->vs_ev_q, stream_event_flags()));
     XQ_HIP(hipMemsetAsync(t->vs_counts, 0, n * sizeof(uint4), t->stream));
     XQ_HIP(hipStreamSynchronize(t->stream));
     t->vs = vs;

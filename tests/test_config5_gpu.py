@@ -372,7 +372,7 @@ def test_bf16_dense_backpropagate_refreshes_the_shadow(xq, trace):
 @pytest.mark.parametrize("td_rule,mode", [(2, 0), (0, 1)])
 def test_bf16_full_td_update_matches_oracle(xq, trace, td_rule, mode):
     """XQ_PRECISION_BF16_FULL at a batch the bf16 GEMM loop of its own takes (n = 256 = one 256-row tile; widths 512): forward chains,
-    hidden deltas and hidden weight gradients on gemm_bf16_kernel (xq_gemm_bf16.hip.h), against the oracle's bf16 = 2 definition."""
+    hidden deltas and hidden weight gradients on gemm_dma_kernel (xq_gemm_dma.hip.h), against the oracle's bf16 = 2 definition."""
     sizes = CFG4_NET
     n = 256
     S, A, R, D, S2 = transitions(trace, valid_indices(trace, n, seed=6))
