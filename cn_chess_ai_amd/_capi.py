@@ -19,6 +19,7 @@ BACKPROP_REFERENCE, BACKPROP_TEXTBOOK = 0, 1
 TD_ONLINE_NET, TD_TARGET_NET, TD_DOUBLE = 0, 1, 2
 PRECISION_F32, PRECISION_BF16, PRECISION_BF16_FULL = 0, 1, 2
 QMAX_FULL, QMAX_SCREENED = 0, 1
+OPT_SGD, OPT_ADAM = 0, 1
 ORDER_RING_CONTENTS, ORDER_RING_PRIORITIES, ORDER_RING_DRAW, ORDER_TRAINER_PARAMS, ORDER_ALL = 1, 2, 4, 8, 15
 
 STATUS_NAMES = {1: "XQ_ERR_INVALID_ARGUMENT", 2: "XQ_ERR_RUNTIME", 3: "XQ_ERR_NO_DEVICE", 4: "XQ_ERR_IO",
@@ -171,6 +172,11 @@ PROTOTYPES = {
     "xq_dqn_last_td_values": [_vp, _i, _pf, _pf],
     "xq_dqn_kernel_stats": [_vp, _i, C.POINTER(KernelStat), _i, _pi],
     "xq_dqn_set_fused_apply": [_vp, _i],
+    "xq_dqn_set_optimizer": [_vp, _i, _d, _d, _d],
+    "xq_dqn_get_optimizer": [_vp, _pi, _pd, _pd, _pd, _pu64],
+    "xq_dqn_reset_optimizer": [_vp],
+    "xq_dqn_get_optimizer_state": [_vp, _pf, _pf, _pu64],
+    "xq_dqn_set_optimizer_state": [_vp, _pf, _pf, _u64],
     "xq_dqn_kernel_filter": [_vp, C.c_char_p],
     "xq_dqn_kernel_timeline": [_vp, C.POINTER(KernelSpan), _i, _pi],
     "xq_comm_unique_id": [_pu8],
@@ -208,6 +214,10 @@ PROTOTYPES = {
     "xq_arena_env": [_vp, _pvp],
     "xq_arena_last_step": [_vp, C.POINTER(StepResult)],
 }
+# bound when the loaded library has them: an older build given through XQ_LIBXQHIP (same-box A/B) still imports, and a call
+# of one of these on it raises XqError instead
+LAZY = frozenset(("xq_dqn_set_optimizer", "xq_dqn_get_optimizer", "xq_dqn_reset_optimizer", "xq_dqn_get_optimizer_state",
+                  "xq_dqn_set_optimizer_state"))
 _RESTYPES = {"xq_last_error": C.c_char_p, "xq_env_boards_dev": C.c_void_p, "xq_env_meta_dev": C.c_void_p}
 
 _lib = None
@@ -230,6 +240,8 @@ def load():
         pass
     lib = C.CDLL(LIB_PATH)
     for name, argtypes in PROTOTYPES.items():
+        if name in LAZY and not hasattr(lib, name):
+            continue
         fn = getattr(lib, name)          # AttributeError if the library does not export a declared symbol
         fn.argtypes = argtypes
         fn.restype = _RESTYPES.get(name, C.c_int)
@@ -245,7 +257,10 @@ def check(rc):
 
 
 def call(name, *args):
-    return check(getattr(load(), name)(*args))
+    lib = load()
+    if name in LAZY and not hasattr(lib, name):
+        raise XqError(2, f"{name}: the loaded {LIB_PATH} predates this entry point")
+    return check(getattr(lib, name)(*args))
 
 
 def device_count():

@@ -125,6 +125,12 @@ struct xq_dqn {
     xq::DevBuf<float> grads_td;  size_t n_grads_td = 0;
     size_t g_w0 = 0, g_wh[XQ_MAX_LAYERS] = {0}, g_wout = 0, g_bh[XQ_MAX_LAYERS] = {0}, g_bout = 0;
     xq::DevBuf<float> grads_full;
+    // optimizer of xq_dqn_apply_grads (xq_dqn_set_optimizer): Adam's first and second moments in the layout of grads_td, allocated on
+    // the first switch to Adam; opt_t = Adam applies since the state was last reset
+    int opt_kind = XQ_OPT_SGD;
+    double opt_b1 = 0.9, opt_b2 = 0.999, opt_eps = 1e-8;
+    uint64_t opt_t = 0;
+    xq::DevBuf<float> adam_m, adam_v;
     xq::DevBuf<float> slabs;
     xq::DevBuf<float> slabs_l0;                 // layer-0 gradient partials
     // layer-0 gradient on the bf16 matrix pipe (xq_l0grad.hip.h): delta_0 as three bf16 planes, transposed [plane][column][sample]
@@ -981,6 +987,32 @@ static int sgd_apply(xq_dqn* d, SegTable t, double alpha) {
     const unsigned bx = (unsigned)std::max<long long>(1, std::min<long long>((mx + 255) / 256, 1024));
     ProfScope ps(d, t.reduce_only ? "reduce_slabs" : "sgd_apply", 0, 0, true);
     hipExtLaunchKernelGGL(sgd_segments_kernel, dim3(bx, t.nseg), dim3(256), 0, d->cur, ps.start(), ps.stop(), 0, t, (float)alpha);
+    XQ_HIP(hipGetLastError());
+    return XQ_OK;
+}
+
+// The same table through adam_segments_kernel: step t of Adam with the handle's betas and eps.  The bias corrections are taken on the
+// host in double and handed over as floats.
+static int adam_apply(xq_dqn* d, SegTable t, double lr, double grad_scale) {
+    long long mx = 0;
+    for (int i = 0; i < t.nseg; ++i) {
+        const uintptr_t bits = (uintptr_t)t.dst[i] | (uintptr_t)t.src[i] | ((uintptr_t)t.dst_bf[i] << 1);
+        t.vec4[i] = (bits & 15) == 0 && (t.len[i] & 3) == 0 && (t.nslabs[i] <= 0 || (t.stride[i] & 3) == 0) && (t.state_off[i] & 3) == 0;
+        mx = std::max(mx, t.vec4[i] ? t.len[i] / 4 : t.len[i]);
+    }
+    const unsigned bx = (unsigned)std::max<long long>(1, std::min<long long>((mx + 255) / 256, 1024));
+    d->opt_t += 1;
+    const double tt = (double)d->opt_t;
+    AdamArgs A;
+    A.m = d->adam_m; A.v = d->adam_v;
+    A.b1 = (float)d->opt_b1; A.omb1 = (float)(1.0 - d->opt_b1);
+    A.b2 = (float)d->opt_b2; A.omb2 = (float)(1.0 - d->opt_b2);
+    A.eps = (float)d->opt_eps;
+    A.a = (float)(lr / (1.0 - std::pow(d->opt_b1, tt)));
+    A.rbc2 = (float)(1.0 / std::sqrt(1.0 - std::pow(d->opt_b2, tt)));
+    A.gs = (float)grad_scale;
+    ProfScope ps(d, "adam_apply", 0, 0, true);
+    hipExtLaunchKernelGGL(adam_segments_kernel, dim3(bx, t.nseg), dim3(256), 0, d->cur, ps.start(), ps.stop(), 0, t, A);
     XQ_HIP(hipGetLastError());
     return XQ_OK;
 }
@@ -2006,27 +2038,95 @@ int xq_dqn_apply_grads(xq_dqn* d, double lr, double grad_scale) {
         p = xq_dqn::PendingSlab();
     };
     const bool bf = d->bf16();
-    t.dst[k] = d->w0t(0); t.src[k] = G + d->g_w0; t.len[k] = (long long)d->L[0] * d->L[1];
+    t.dst[k] = d->w0t(0); t.src[k] = G + d->g_w0; t.len[k] = (long long)d->L[0] * d->L[1]; t.state_off[k] = (long long)d->g_w0;
     if (bf) t.dst_bf[k] = d->wl_bf(0, 0);
     if (d->l0_pending > 0) { t.src[k] = d->slabs_l0; t.nslabs[k] = d->l0_pending; t.stride[k] = t.len[k]; d->l0_pending = 0; }
     ++k;
     for (int l = 1; l + 1 < d->nl; ++l) {
-        t.dst[k] = d->wl(0, l); t.src[k] = G + d->g_wh[l]; t.len[k] = (long long)d->L[l] * d->L[l + 1];
+        t.dst[k] = d->wl(0, l); t.src[k] = G + d->g_wh[l]; t.len[k] = (long long)d->L[l] * d->L[l + 1]; t.state_off[k] = (long long)d->g_wh[l];
         if (bf) t.dst_bf[k] = d->wl_bf(0, l);
         take(d->pend_hidden[l]);
         ++k;
     }
-    t.dst[k] = d->wl(0, d->nl - 1); t.src[k] = G + d->g_wout; t.len[k] = 96LL * d->hlast();
+    t.dst[k] = d->wl(0, d->nl - 1); t.src[k] = G + d->g_wout; t.len[k] = 96LL * d->hlast(); t.state_off[k] = (long long)d->g_wout;
     if (bf) t.dst_bf[k] = d->wl_bf(0, d->nl - 1);
     take(d->pend_wout); ++k;
     // hidden biases are contiguous in both layouts
-    t.dst[k] = d->bl(0, 0); t.src[k] = G + d->g_bh[0]; t.len[k] = (long long)(d->bo[d->nl - 1]); take(d->pend_bh); ++k;
-    t.dst[k] = d->bl(0, d->nl - 1); t.src[k] = G + d->g_bout; t.len[k] = 96; take(d->pend_bout); ++k;
+    t.dst[k] = d->bl(0, 0); t.src[k] = G + d->g_bh[0]; t.len[k] = (long long)(d->bo[d->nl - 1]); t.state_off[k] = (long long)d->g_bh[0];
+    take(d->pend_bh); ++k;
+    t.dst[k] = d->bl(0, d->nl - 1); t.src[k] = G + d->g_bout; t.len[k] = 96; t.state_off[k] = (long long)d->g_bout; take(d->pend_bout); ++k;
     t.nseg = k;
     d->sel_invalidate();                              // W0 / b0 change: the select chain's kept layer-0 sums are stale
     for (auto& K : d->sel_keep) { K.pays = K.calls >= 2; K.calls = 0; }
     d->params_version += 1;
+    if (d->opt_kind == XQ_OPT_ADAM) return adam_apply(d, t, lr, grad_scale);
     return sgd_apply(d, t, lr * grad_scale);
+}
+
+static bool td_step_pending(const xq_dqn* d) { return d->l0_pending > 0 || d->pend_wout.nslabs > 0 || d->pend_bh.nslabs > 0; }
+// m = v = 0, t = 0 (queued on the handle's stream, behind any apply in flight)
+static int adam_zero_state(xq_dqn* d) {
+    d->opt_t = 0;
+    if (!d->adam_m.p) return XQ_OK;
+    XQ_HIP(hipMemsetAsync(d->adam_m, 0, d->n_grads_td * sizeof(float), d->stream));
+    XQ_HIP(hipMemsetAsync(d->adam_v, 0, d->n_grads_td * sizeof(float), d->stream));
+    return XQ_OK;
+}
+
+int xq_dqn_set_optimizer(xq_dqn* d, int kind, double beta1, double beta2, double eps) {
+    if (!d) return fail(XQ_ERR_INVALID_ARGUMENT, "null dqn");
+    if (kind != XQ_OPT_SGD && kind != XQ_OPT_ADAM) return fail(XQ_ERR_INVALID_ARGUMENT, "xq_dqn_set_optimizer: unknown optimizer kind %d", kind);
+    if (!(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0) || !(eps >= 0.0))
+        return fail(XQ_ERR_INVALID_ARGUMENT, "xq_dqn_set_optimizer: beta1, beta2 must lie in [0, 1) and eps must not be negative");
+    if (td_step_pending(d)) return fail(XQ_ERR_RUNTIME, "xq_dqn_set_optimizer: a TD step is waiting for its apply_grads");
+    if (kind == XQ_OPT_ADAM && !d->adam_m.p) {
+        if (d->n_grads_td == 0) layout_td_grads(d);
+        XQ_TRY(d->adam_m.alloc(d->n_grads_td));
+        XQ_TRY(d->adam_v.alloc(d->n_grads_td));
+        XQ_TRY(adam_zero_state(d));
+    }
+    if (kind != d->opt_kind) XQ_TRY(adam_zero_state(d));
+    d->opt_kind = kind;
+    d->opt_b1 = beta1 != 0.0 ? beta1 : 0.9;
+    d->opt_b2 = beta2 != 0.0 ? beta2 : 0.999;
+    d->opt_eps = eps != 0.0 ? eps : 1e-8;
+    return XQ_OK;
+}
+
+int xq_dqn_get_optimizer(const xq_dqn* d, int* kind, double* beta1, double* beta2, double* eps, uint64_t* steps) {
+    if (!d) return fail(XQ_ERR_INVALID_ARGUMENT, "null dqn");
+    if (kind) *kind = d->opt_kind;
+    if (beta1) *beta1 = d->opt_b1;
+    if (beta2) *beta2 = d->opt_b2;
+    if (eps) *eps = d->opt_eps;
+    if (steps) *steps = d->opt_t;
+    return XQ_OK;
+}
+
+int xq_dqn_reset_optimizer(xq_dqn* d) {
+    if (!d) return fail(XQ_ERR_INVALID_ARGUMENT, "null dqn");
+    return adam_zero_state(d);
+}
+
+int xq_dqn_get_optimizer_state(xq_dqn* d, float* m_host, float* v_host, uint64_t* steps) {
+    if (!d) return fail(XQ_ERR_INVALID_ARGUMENT, "null dqn");
+    if (d->opt_kind != XQ_OPT_ADAM) return fail(XQ_ERR_RUNTIME, "xq_dqn_get_optimizer_state: the optimizer is SGD, which keeps no state");
+    XQ_HIP(hipStreamSynchronize(d->stream));
+    if (m_host) XQ_HIP(hipMemcpy(m_host, d->adam_m, d->n_grads_td * sizeof(float), hipMemcpyDeviceToHost));
+    if (v_host) XQ_HIP(hipMemcpy(v_host, d->adam_v, d->n_grads_td * sizeof(float), hipMemcpyDeviceToHost));
+    if (steps) *steps = d->opt_t;
+    return XQ_OK;
+}
+
+int xq_dqn_set_optimizer_state(xq_dqn* d, const float* m_host, const float* v_host, uint64_t steps) {
+    if (!d || !m_host || !v_host) return fail(XQ_ERR_INVALID_ARGUMENT, "xq_dqn_set_optimizer_state: null pointer");
+    if (d->opt_kind != XQ_OPT_ADAM) return fail(XQ_ERR_RUNTIME, "xq_dqn_set_optimizer_state: the optimizer is SGD, which keeps no state");
+    if (td_step_pending(d)) return fail(XQ_ERR_RUNTIME, "xq_dqn_set_optimizer_state: a TD step is waiting for its apply_grads");
+    XQ_HIP(hipStreamSynchronize(d->stream));
+    XQ_HIP(hipMemcpy(d->adam_m, m_host, d->n_grads_td * sizeof(float), hipMemcpyHostToDevice));
+    XQ_HIP(hipMemcpy(d->adam_v, v_host, d->n_grads_td * sizeof(float), hipMemcpyHostToDevice));
+    d->opt_t = steps;
+    return XQ_OK;
 }
 
 int xq_dqn_set_fused_apply(xq_dqn* d, int on) {

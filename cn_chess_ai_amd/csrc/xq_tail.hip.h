@@ -586,7 +586,8 @@ struct SegTable {
     uint16_t* dst_bf[16];      // bf16 Q-net: shadow of dst, refreshed with the rounded new value (nullptr: none)
     int nseg;
     int reduce_only;           // dst = the slab sum itself (no step): the gradient buffer a reader or an all-reduce needs, in one launch
-    int vec4[16];              // set by sgd_apply: every pointer 16-byte aligned, len and stride multiples of 4 — four elements per thread
+    int vec4[16];              // set by sgd_apply / adam_apply: every pointer 16-byte aligned, len and stride multiples of 4 — four elements per thread
+    long long state_off[16];   // Adam: where the segment's m and v start in the two state buffers (gradient-buffer layout, layout_td_grads)
 };
 
 // Q head with the k range split over blocks (q_head) or folded into the last hidden product (EPI_HEAD): q[m][j] = tanh(b_j + the sum of
@@ -677,5 +678,90 @@ __global__ void sgd_segments_kernel(SegTable t, float alpha) {
     }
 }
 
+// Adam (torch.optim.Adam's formula, amsgrad off, no weight decay; DESIGN.md section 4 "Optimizer") over the same segment walk:
+//   g' = gs g;  m = b1 m + (1 - b1) g';  v = b2 v + (1 - b2) g'^2;  p -= a m / (sqrt(v) rbc2 + eps)
+// a = lr / (1 - b1^t) and rbc2 = 1 / sqrt(1 - b2^t) are computed on the host in double.  m and v live in two fp32 buffers laid out like
+// the compact gradient buffer; a parameter that never receives a gradient keeps m = v = 0 and its step is exactly 0.
+struct AdamArgs {
+    float* m;  float* v;
+    float b1, omb1, b2, omb2, eps, a, rbc2, gs;
+};
+// One element: every product, sum, square root and quotient written out and rounded once, in this order, with no contraction left to
+// the compiler — the vec4 and the scalar loop both come through here, so the bits do not depend on which loop ran.
+__device__ __forceinline__ float adam_elem(const AdamArgs& A, float p, float g, float& m, float& v) {
+#pragma clang fp contract(off)
+    const float gp = A.gs * g;
+    const float mg = A.omb1 * gp;
+    m = __builtin_fmaf(A.b1, m, mg);
+    const float vg = (A.omb2 * gp) * gp;
+    v = __builtin_fmaf(A.b2, v, vg);
+    const float den = __builtin_fmaf(__builtin_sqrtf(v), A.rbc2, A.eps);
+    const float q = m / den;
+    return __builtin_fmaf(-A.a, q, p);
+}
+__global__ void adam_segments_kernel(SegTable t, AdamArgs A) {
+    const int sgm = (int)blockIdx.y;
+    if (sgm >= t.nseg) return;
+    float* d = t.dst[sgm];
+    const float* s = t.src[sgm];
+    const int nslabs = t.nslabs[sgm];
+    const long long len = t.len[sgm], st = t.stride[sgm];
+    uint16_t* db = t.dst_bf[sgm];
+    float* ms = A.m + t.state_off[sgm];
+    float* vs = A.v + t.state_off[sgm];
+    if (t.vec4[sgm]) {
+        const long long n4 = len >> 2, st4 = st >> 2;
+        const float4* s4 = reinterpret_cast<const float4*>(s);
+        float4* d4 = reinterpret_cast<float4*>(d);
+        float4* m4 = reinterpret_cast<float4*>(ms);
+        float4* v4 = reinterpret_cast<float4*>(vs);
+        for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long long)gridDim.x * blockDim.x) {
+            float4 g;
+            if (nslabs <= 0) g = s4[i];
+            else {          // the slabs, in the order of reduce_slabs_kernel: g has the bits the reduce-first path would have read
+                float4 s0 = make_float4(0.f, 0.f, 0.f, 0.f), s1 = s0, s2 = s0, s3 = s0;
+                int z = 0;
+                for (; z + 3 < nslabs; z += 4) {
+                    s0 = f4_add(s0, s4[(long long)z * st4 + i]);
+                    s1 = f4_add(s1, s4[(long long)(z + 1) * st4 + i]);
+                    s2 = f4_add(s2, s4[(long long)(z + 2) * st4 + i]);
+                    s3 = f4_add(s3, s4[(long long)(z + 3) * st4 + i]);
+                }
+                for (; z < nslabs; ++z) s0 = f4_add(s0, s4[(long long)z * st4 + i]);
+                g = f4_add(f4_add(s0, s1), f4_add(s2, s3));
+            }
+            const float4 w = d4[i];
+            float4 m = m4[i], v = v4[i], o;
+            o.x = adam_elem(A, w.x, g.x, m.x, v.x);
+            o.y = adam_elem(A, w.y, g.y, m.y, v.y);
+            o.z = adam_elem(A, w.z, g.z, m.z, v.z);
+            o.w = adam_elem(A, w.w, g.w, m.w, v.w);
+            m4[i] = m; v4[i] = v; d4[i] = o;
+            if (db) reinterpret_cast<uint2*>(db)[i] = make_uint2((uint32_t)bf16_bits(o.x) | ((uint32_t)bf16_bits(o.y) << 16),
+                                                                 (uint32_t)bf16_bits(o.z) | ((uint32_t)bf16_bits(o.w) << 16));
+        }
+        return;
+    }
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < len; i += (long long)gridDim.x * blockDim.x) {
+        float g;
+        if (nslabs <= 0) g = s[i];
+        else {
+            float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+            int z = 0;
+            for (; z + 3 < nslabs; z += 4) {
+                s0 += s[(long long)z * st + i];
+                s1 += s[(long long)(z + 1) * st + i];
+                s2 += s[(long long)(z + 2) * st + i];
+                s3 += s[(long long)(z + 3) * st + i];
+            }
+            for (; z < nslabs; ++z) s0 += s[(long long)z * st + i];
+            g = (s0 + s1) + (s2 + s3);
+        }
+        float m = ms[i], v = vs[i];
+        const float o = adam_elem(A, d[i], g, m, v);
+        ms[i] = m; vs[i] = v; d[i] = o;
+        if (db) db[i] = bf16_bits(o);
+    }
+}
 
 }  // namespace xq

@@ -305,6 +305,52 @@ def _set_fused_apply(self, on=True):
 DQN.set_fused_apply = _set_fused_apply
 
 
+_OPT_KINDS = {"sgd": _capi.OPT_SGD, "adam": _capi.OPT_ADAM}
+
+
+def _set_optimizer(self, kind="sgd", beta1=0.0, beta2=0.0, eps=0.0):
+    """Optimizer of apply_grads / the trainer's learn_apply: "sgd" (default) or "adam" (torch.optim.Adam's rule, no weight decay;
+    0 = the defaults 0.9 / 0.999 / 1e-8).  Changing the kind zeroes Adam's state.  backpropagate() stays plain SGD."""
+    if kind not in _OPT_KINDS:
+        raise ValueError(f"set_optimizer: expected 'sgd' or 'adam', got {kind!r}")
+    call("xq_dqn_set_optimizer", self._h, _OPT_KINDS[kind], float(beta1), float(beta2), float(eps))
+
+
+def _optimizer(self):
+    """dict(kind, beta1, beta2, eps, steps): steps = Adam applies since the state was last reset."""
+    k, t = C.c_int32(), C.c_uint64()
+    b1, b2, e = C.c_double(), C.c_double(), C.c_double()
+    call("xq_dqn_get_optimizer", self._h, C.byref(k), C.byref(b1), C.byref(b2), C.byref(e), C.byref(t))
+    return dict(kind={v: n for n, v in _OPT_KINDS.items()}[k.value], beta1=b1.value, beta2=b2.value, eps=e.value, steps=t.value)
+
+
+def _reset_optimizer(self):
+    """Adam's m, v and step count back to 0."""
+    call("xq_dqn_reset_optimizer", self._h)
+
+
+def _optimizer_state(self):
+    """(m, v, steps): Adam's moments as fp32 arrays in the layout of the gradient buffer; synchronises."""
+    n = self.grad_buffer()[1]
+    m, v, t = np.zeros(n, np.float32), np.zeros(n, np.float32), C.c_uint64()
+    call("xq_dqn_get_optimizer_state", self._h, _ptr(m, C.c_float), _ptr(v, C.c_float), C.byref(t))
+    return m, v, t.value
+
+
+def _set_optimizer_state(self, m, v, steps):
+    n = self.grad_buffer()[1]
+    m = np.ascontiguousarray(m, dtype=np.float32).reshape(n)
+    v = np.ascontiguousarray(v, dtype=np.float32).reshape(n)
+    call("xq_dqn_set_optimizer_state", self._h, _ptr(m, C.c_float), _ptr(v, C.c_float), int(steps))
+
+
+DQN.set_optimizer = _set_optimizer
+DQN.optimizer = _optimizer
+DQN.reset_optimizer = _reset_optimizer
+DQN.optimizer_state = _optimizer_state
+DQN.set_optimizer_state = _set_optimizer_state
+
+
 def _timeline(self, max_spans=8192):
     """(name, start_ms, end_ms) of every launch bracketed in the session closed by the last kernel_stats() call."""
     arr = (KernelSpan * max_spans)()

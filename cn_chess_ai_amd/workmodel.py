@@ -28,6 +28,7 @@ ROCPROF_NAMES = {
     "td_target_delta": "td_delta_kernel(",
     "colmax_reduce": "colmax_reduce_kernel(",
     "sgd_apply": "sgd_segments_kernel(",
+    "adam_apply": "adam_segments_kernel(",
     "env_selfplay_step": "env_kernel<2>(",
     "target_sync_copy": "__amd_rocclr_copyBuffer",
     "l0_grad_segsum": "l0_grad_kernel(",
@@ -115,8 +116,9 @@ def pick_splits(M, N, K):
 
 
 def step_work(layers, minibatch, n_games, plies=1, bf16=False, bf16_bwd=False, td="online", screened=True, derive=True,
-              prioritized=False, l0_mfma=True):
-    """{bracket name: dict(flops, hbm_bytes, bound, peak, peak_unit, what)} for one training step of the given configuration."""
+              prioritized=False, l0_mfma=True, optimizer="sgd"):
+    """{bracket name: dict(flops, hbm_bytes, bound, peak, peak_unit, what)} for one training step of the given configuration.
+    optimizer="adam" (xq_dqn_set_optimizer): adam_apply stands in place of sgd_apply; the default step knows no adam_apply."""
     h = list(layers[1:-1])
     H1, Hl, k = h[0], h[-1], len(h)
     B, n = minibatch, n_games
@@ -263,6 +265,13 @@ def step_work(layers, minibatch, n_games, plies=1, bf16=False, bf16_bwd=False, t
         touched = STATE * H1 + sum(h[l] * h[l - 1] for l in range(1, k)) + 96 * Hl + 96 + sum(h)
         put("sgd_apply", 2.0 * touched, 4 * (slabs + 2 * touched) + (2 * touched if bf16 else 0), "hbm",
             "ordered sum of every partial-sum slab + SGD step on the touched parameters (+ their bf16 shadow)")
+    if optimizer == "adam":
+        # the SGD kernel's bytes + m and v read and written: 16 B per touched element; ~12 fp32 operations per element
+        sgd = w.pop("sgd_apply")
+        put("adam_apply", 12.0 * touched, sgd["hbm_bytes"] + 16 * touched, "hbm",
+            "ordered sum of every partial-sum slab + Adam step on the touched parameters and their two moments" + (" (+ their bf16 shadow)" if bf16 else ""))
+    elif optimizer != "sgd":
+        raise ValueError("optimizer: 'sgd' or 'adam'")
     nw = STATE * H1 + sum(h[l] * h[l - 1] for l in range(1, k)) + Hl * NO
     nb = sum(h) + NO
     put("target_sync_copy", 0.0, 8.0 * (nw + nb), "hbm", "updateTargetNetwork(): device copy of all parameters")

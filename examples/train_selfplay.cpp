@@ -12,6 +12,7 @@
 //   --derive                      layer-0 sums of s' derived from those of s (what bench.py runs; another summation order)
 //   --prefill N                   N uniform-random plies in every game before training (spreads the games over all phases)
 //   --seed S                      seed of the batched games (default: time, like the reference's srand(time))
+//   adam                          the batched loop's optimizer: Adam (xq::Optimizer::adam(), defaults 0.9 / 0.999 / 1e-8) instead of SGD
 //   --json                        one JSON line with the loop's counters (bench.py's `facade` leg reads it)
 #include <chrono>
 #include <cstdio>
@@ -25,7 +26,7 @@ int main(int argc, char** argv) {
     int episodes = 1000, parallel = 8192, replay = 0, minibatch = 0, save_every = 100, prefill = 0, npos = 0;
     const char* file = "model.bin";
     std::vector<int> hidden;
-    bool derive = false, json = false;
+    bool derive = false, json = false, adam = false;
     unsigned long long seed = 0;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
@@ -37,6 +38,7 @@ int main(int argc, char** argv) {
         else if (a == "--seed") seed = std::strtoull(next(), nullptr, 0);
         else if (a == "--derive") derive = true;
         else if (a == "--json") json = true;
+        else if (a == "adam") adam = true;
         else if (a == "--hidden") {
             for (const char* p = next(); *p;) { hidden.push_back(std::atoi(p)); while (*p && *p != ',') ++p; if (*p == ',') ++p; }
         } else if (a.rfind("--", 0) == 0) { std::fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
@@ -54,6 +56,7 @@ int main(int argc, char** argv) {
             sizes.push_back(90 * 90);
             ai.setDQN(std::make_unique<xq::DQN>(sizes));
         }
+        if (adam) ai.setOptimizer(xq::Optimizer::adam());
         if (replay > 0) ai.setReplay(replay, minibatch);
         ai.setSaveInterval(save_every);
         ai.setLayer0Derive(derive);

@@ -189,6 +189,18 @@ private:
     xq_step_result last_{};
 };
 
+// Optimizer of the batched TD step (xq_dqn_set_optimizer; no upstream analogue): sgd() is the reference's p -= lr g, adam() is
+// torch.optim.Adam's rule without weight decay (0 = the defaults 0.9 / 0.999 / 1e-8).  DQN::backpropagate stays plain SGD.
+struct Optimizer {
+    int kind = XQ_OPT_SGD;
+    double beta1 = 0.0, beta2 = 0.0, eps = 0.0;
+    static Optimizer sgd() { return Optimizer(); }
+    static Optimizer adam(double beta1 = 0.0, double beta2 = 0.0, double eps = 0.0) {
+        Optimizer o; o.kind = XQ_OPT_ADAM; o.beta1 = beta1; o.beta2 = beta2; o.eps = eps;
+        return o;
+    }
+};
+
 // ---- DQN, dqn.h:97-116 ----------------------------------------------------------------------------------------------
 class DQN {
 public:
@@ -254,6 +266,14 @@ public:
         w.resize(nw); b.resize(nb);
         check(xq_dqn_get_params(h_, net, w.data(), b.data()));
     }
+    // what xq_dqn_apply_grads does with the gradients of a batched TD step; changing the kind zeroes Adam's state
+    void setOptimizer(const Optimizer& o) { check(xq_dqn_set_optimizer(h_, o.kind, o.beta1, o.beta2, o.eps)); }
+    Optimizer optimizer(uint64_t* steps = nullptr) const {       // the constants in force (defaults filled in), Adam applies so far
+        Optimizer o;
+        check(xq_dqn_get_optimizer(h_, &o.kind, &o.beta1, &o.beta2, &o.eps, steps));
+        return o;
+    }
+    void resetOptimizer() { check(xq_dqn_reset_optimizer(h_)); }
     const std::vector<int>& layerSizes() const { return layerSizes_; }
     double gamma() const { return gamma_; }
     xq_dqn* handle() const { return h_; }
@@ -655,6 +675,9 @@ public:
     void setCommunicator(Comm* comm) { comm_ = comm; }
     void setBatchSeed(uint64_t seed) { batchSeed_ = seed; }                  // 0 (default): time-seeded like upstream
     void setDQN(std::unique_ptr<DQN> d) { dqn = std::move(d); }
+    // Optimizer of the batched train(): forwarded to this agent's network (created now if need be), whose choice the batched loop takes
+    // over.  The sequential loop (parallelGames == 1) is the reference's backpropagate(lr): plain SGD whatever is set here.
+    void setOptimizer(const Optimizer& o) { initializeDQN(); dqn->setOptimizer(o); }
     DQN* network() { return dqn.get(); }
     std::vector<double> getStateRepresentation() {                           // chessai.cpp:268-289 (encoding only)
         std::vector<double> s(90 * 14, 0.0);
@@ -700,6 +723,8 @@ private:
         check(xq_dqn_update_target(td));
         check(xq_dqn_set_qmax_mode(td, XQ_QMAX_SCREENED));    // same max_a' Q(s',a'), found by exact screening (large batches only)
         check(xq_dqn_set_l0_derive(td, l0Derive_ ? 1 : 0));
+        const Optimizer opt = dqn->optimizer();
+        check(xq_dqn_set_optimizer(td, opt.kind, opt.beta1, opt.beta2, opt.eps));
         if (comm_) check(xq_trainer_set_comm(t, comm_->handle()));
         if (prefillPlies_ > 0) check(xq_trainer_random_plies(t, prefillPlies_));
         if (opponent_) check(xq_trainer_set_opponent(t, &opponent_->spec()));

@@ -336,7 +336,8 @@ int xq_dqn_qmax_stats(xq_dqn* d, uint64_t stats[4]);
 int xq_dqn_qmax_guard(xq_dqn* d, uint64_t* fallbacks, int* hold_steps_left);
 int xq_dqn_num_params(const xq_dqn* d, size_t* n_weights, size_t* n_biases);
 /* host_weights / host_biases in the REFERENCE flat layout (row-major [out][in] per layer, layers concatenated,
- * dqn.cu:112-140), fp64 like upstream.  set = copyToDevice() (dqn.cu:480-485), get = copyFromDevice() (:487-492). */
+ * dqn.cu:112-140), fp64 like upstream.  set = copyToDevice() (dqn.cu:480-485), get = copyFromDevice() (:487-492).  The optimizer
+ * state (xq_dqn_set_optimizer) is not touched: a caller that replaces the parameters of a run decides about xq_dqn_reset_optimizer. */
 int xq_dqn_set_params(xq_dqn* d, int which_net, const double* weights_host, const double* biases_host);
 int xq_dqn_get_params(xq_dqn* d, int which_net, double* weights_host, double* biases_host);
 /* DQN::getQValues / NeuralNetwork::forward (dqn.cpp:65-68, dqn.cu:199-260) for n dense states [n][layer_sizes[0]]
@@ -355,13 +356,15 @@ int xq_dqn_forward_boards_dev(xq_dqn* d, int which_net, const uint32_t* boards_d
 int xq_dqn_select_q_dev(xq_dqn* d, const uint32_t* boards_dev, int n, float* q_dev);
 /* DQN::backpropagate(state, target, lr) / NeuralNetwork::backpropagate (dqn.cpp:59-62, dqn.cu:323-467) for a batch of
  * n (state, target) pairs: gradients of all n samples are taken at the pre-update weights, summed, scaled by
- * grad_scale and applied once (n = 1, grad_scale = 1 is exactly the upstream call).  mode = XQ_BACKPROP_*. */
+ * grad_scale and applied once (n = 1, grad_scale = 1 is exactly the upstream call).  mode = XQ_BACKPROP_*.  The reference's own
+ * backpropagate(lr): plain SGD whatever xq_dqn_set_optimizer says, and it neither reads nor writes the optimizer state. */
 int xq_dqn_backpropagate(xq_dqn* d, const double* states_host, const double* targets_host, int n,
                          double learning_rate, double grad_scale, int mode);
 /* DQN::updateTargetNetwork() (dqn.cpp:71-73) — copies the TRAINED device weights (upstream copies stale host
- * vectors; documented divergence). */
+ * vectors; documented divergence).  The optimizer state stays as it is. */
 int xq_dqn_update_target(xq_dqn* d);
-/* DQN::saveModel / loadModel (dqn.cpp:76-154): raw LE fp64 weights, raw fp64 biases, BE u64 count, BE i32 sizes. */
+/* DQN::saveModel / loadModel (dqn.cpp:76-154): raw LE fp64 weights, raw fp64 biases, BE u64 count, BE i32 sizes.  The file holds no
+ * optimizer state and loading leaves the handle's alone. */
 int xq_dqn_save_model(xq_dqn* d, const char* path);
 int xq_dqn_load_model(xq_dqn* d, const char* path);
 
@@ -370,7 +373,7 @@ int xq_dqn_load_model(xq_dqn* d, const char* path);
  * action.to replaced by y;  backprop of 0.5*|Q(s)-target|^2.  Split in two so a multi-GPU caller can all-reduce
  * the gradient buffer in between:
  *   xq_dqn_td_grads  : forward + deltas + gradient reduction over the batch  -> compact gradient buffer (HBM)
- *   xq_dqn_apply_grads: params -= lr * grad_scale * grads
+ *   xq_dqn_apply_grads: params -= lr * grad_scale * grads   (or the Adam step of xq_dqn_set_optimizer)
  * boards/next_boards: [n][12] u32, optionally gathered through slots_dev ([n] row indices, NULL = identity).
  * td_net = XQ_TD_*.  loss_out_dev: optional, sum over the batch of 0.5*(Q(s,a)-y)^2. */
 int xq_dqn_td_grads(xq_dqn* d, const uint32_t* boards_dev, const uint32_t* next_boards_dev,
@@ -383,6 +386,29 @@ int xq_dqn_grad_buffer(xq_dqn* d, float** grads_dev, size_t* n_floats);
  * kernel fewer); the layer-0 segment of the gradient buffer is then NOT filled by xq_dqn_td_grads.  Leave 0 (default) when
  * anything reads the buffer between the two calls, e.g. a multi-GPU all-reduce. */
 int xq_dqn_set_fused_apply(xq_dqn* d, int on);
+/* The optimizer of xq_dqn_apply_grads (no upstream analogue: the reference knows p -= lr g only, dqn.cu:310-319).  XQ_OPT_SGD (default):
+ * params -= lr * grad_scale * grads, the bits, kernels and launches of a handle that was never asked.  XQ_OPT_ADAM: torch.optim.Adam's
+ * rule (amsgrad off, no weight decay) per touched parameter, at the t-th Adam apply since the state was last reset (t starts at 1):
+ *   g' = grad_scale * g;  m = beta1 m + (1 - beta1) g';  v = beta2 v + (1 - beta2) g'^2;
+ *   p -= (lr / (1 - beta1^t)) * m / (sqrt(v) / sqrt(1 - beta2^t) + eps)
+ * with lr the learning_rate of xq_dqn_apply_grads, m, v, p in fp32, the two bias corrections computed on the host in double.  One
+ * kernel in place of the SGD kernel (it sums pending partial sums itself in the same order, and refreshes the bf16 shadow); with a
+ * communicator it runs behind the all-reduce, identically on every replica.  m and v cover exactly what the TD rule produces gradients
+ * for (the layout of xq_dqn_grad_buffer); a parameter without a gradient keeps m = v = 0 and does not move, so output rows >= 96 stay
+ * untouched as under SGD.  beta1 / beta2 / eps = 0 mean the defaults 0.9 / 0.999 / 1e-8; beta outside [0, 1), eps < 0 or an unknown kind
+ * is XQ_ERR_INVALID_ARGUMENT; XQ_ERR_RUNTIME while a TD step waits for its apply_grads (as xq_dqn_set_fused_apply).  Changing the kind
+ * zeroes m, v and t; a call that keeps the kind only replaces beta1 / beta2 / eps.  xq_dqn_set_params, xq_dqn_load_model and
+ * xq_dqn_update_target leave the optimizer and its state alone; xq_dqn_backpropagate is always plain SGD. */
+enum { XQ_OPT_SGD = 0, XQ_OPT_ADAM = 1 };
+int xq_dqn_set_optimizer(xq_dqn* d, int kind, double beta1, double beta2, double eps);
+/* Kind, the three constants in force and t (Adam applies since the last reset; 0 under SGD).  Any out pointer may be NULL. */
+int xq_dqn_get_optimizer(const xq_dqn* d, int* kind, double* beta1, double* beta2, double* eps, uint64_t* steps);
+/* m = v = 0 and t = 0, in order on the handle's stream; the kind and the constants stay.  A no-op under XQ_OPT_SGD. */
+int xq_dqn_reset_optimizer(xq_dqn* d);
+/* Adam's state to / from the host, for resuming a run and for tests: m and v in the layout of the gradient buffer (n_floats of
+ * xq_dqn_grad_buffer each; get: either may be NULL), steps = t.  Both synchronise.  XQ_ERR_RUNTIME under XQ_OPT_SGD (no state). */
+int xq_dqn_get_optimizer_state(xq_dqn* d, float* m_host, float* v_host, uint64_t* steps);
+int xq_dqn_set_optimizer_state(xq_dqn* d, const float* m_host, const float* v_host, uint64_t steps);
 /* Convenience: sample-free TD update straight from a replay ring (slots from the last xq_replay_sample). */
 int xq_dqn_td_grads_replay(xq_dqn* d, xq_replay* r, int batch, int td_net, int mode);
 /* Host-buffer TD step for tests: n transitions as 90-byte boards. Returns Q(s,a) and y per sample if non-NULL. */
@@ -561,6 +587,8 @@ typedef struct {
 int xq_trainer_create(const xq_trainer_config* cfg, void* hip_stream, xq_trainer** out);
 int xq_trainer_destroy(xq_trainer* t);
 int xq_trainer_env(xq_trainer* t, xq_env** env);
+/* The trainer's network (borrowed).  Its optimizer is chosen here: xq_dqn_set_optimizer(dqn, ...) between iterations; learn_apply
+ * passes cfg.learning_rate and the gradient scale to xq_dqn_apply_grads whatever the kind. */
 int xq_trainer_dqn(xq_trainer* t, xq_dqn** dqn);
 int xq_trainer_replay(xq_trainer* t, xq_replay** replay);
 /* xq_dqn_set_comm on the trainer's network: learn_grads then carries the bucketed all-reduce, learn_apply(world) the mean. */
