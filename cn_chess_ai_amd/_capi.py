@@ -177,6 +177,9 @@ PROTOTYPES = {
     "xq_dqn_reset_optimizer": [_vp],
     "xq_dqn_get_optimizer_state": [_vp, _pf, _pf, _pu64],
     "xq_dqn_set_optimizer_state": [_vp, _pf, _pf, _u64],
+    "xq_dqn_set_grad_clip": [_vp, _d],
+    "xq_dqn_get_grad_clip": [_vp, _pd],
+    "xq_dqn_grad_clip_stats": [_vp, _pd, _pd, _pu64, _pu64],
     "xq_dqn_kernel_filter": [_vp, C.c_char_p],
     "xq_dqn_kernel_timeline": [_vp, C.POINTER(KernelSpan), _i, _pi],
     "xq_comm_unique_id": [_pu8],
@@ -218,6 +221,10 @@ PROTOTYPES = {
 # of one of these on it raises XqError instead
 LAZY = frozenset(("xq_dqn_set_optimizer", "xq_dqn_get_optimizer", "xq_dqn_reset_optimizer", "xq_dqn_get_optimizer_state",
                   "xq_dqn_set_optimizer_state"))
+# Gradient clipping's entry points are lazy in the same way.  They stand in a set of their own only because tests/test_adam_ref_cpu.py
+# pins LAZY to exactly the optimizer's five names; load() and call() look at the union.
+LAZY_GRAD_CLIP = frozenset(("xq_dqn_set_grad_clip", "xq_dqn_get_grad_clip", "xq_dqn_grad_clip_stats"))
+_LAZY_ALL = LAZY | LAZY_GRAD_CLIP
 _RESTYPES = {"xq_last_error": C.c_char_p, "xq_env_boards_dev": C.c_void_p, "xq_env_meta_dev": C.c_void_p}
 
 _lib = None
@@ -240,7 +247,7 @@ def load():
         pass
     lib = C.CDLL(LIB_PATH)
     for name, argtypes in PROTOTYPES.items():
-        if name in LAZY and not hasattr(lib, name):
+        if name in _LAZY_ALL and not hasattr(lib, name):
             continue
         fn = getattr(lib, name)          # AttributeError if the library does not export a declared symbol
         fn.argtypes = argtypes
@@ -258,7 +265,7 @@ def check(rc):
 
 def call(name, *args):
     lib = load()
-    if name in LAZY and not hasattr(lib, name):
+    if name in _LAZY_ALL and not hasattr(lib, name):
         raise XqError(2, f"{name}: the loaded {LIB_PATH} predates this entry point")
     return check(getattr(lib, name)(*args))
 

@@ -30,7 +30,7 @@
 #include <random>
 #include <unordered_map>
 
-namespace xq { struct TailArgs; }
+namespace xq { struct TailArgs; struct ClipRecord; }
 struct xq_dqn {
     int ns = 0, nl = 0;
     int L[XQ_MAX_LAYERS + 1] = {0};
@@ -131,6 +131,11 @@ struct xq_dqn {
     double opt_b1 = 0.9, opt_b2 = 0.999, opt_eps = 1e-8;
     uint64_t opt_t = 0;
     xq::DevBuf<float> adam_m, adam_v;
+    // gradient clipping of xq_dqn_apply_grads (xq_dqn_set_grad_clip): 0 = off; the per-block partials of grad_norm_kernel and the
+    // device record the apply kernel writes (norm, coefficient, counters), both allocated on the first switch-on
+    double clip_max_norm = 0.0;
+    xq::DevBuf<double> clip_partials;
+    xq::DevBuf<xq::ClipRecord> clip_rec;
     xq::DevBuf<float> slabs;
     xq::DevBuf<float> slabs_l0;                 // layer-0 gradient partials
     // layer-0 gradient on the bf16 matrix pipe (xq_l0grad.hip.h): delta_0 as three bf16 planes, transposed [plane][column][sample]
@@ -977,7 +982,7 @@ static int l0_gradient(xq_dqn* d, int n, float* dst) {
     return XQ_OK;
 }
 
-static int sgd_apply(xq_dqn* d, SegTable t, double alpha) {
+static int sgd_apply(xq_dqn* d, SegTable t, double alpha, const ClipArgs* clip = nullptr) {
     long long mx = 0;
     for (int i = 0; i < t.nseg; ++i) {
         const uintptr_t bits = (uintptr_t)t.dst[i] | (uintptr_t)t.src[i] | ((uintptr_t)t.dst_bf[i] << 1);   // the bf16 shadow: 8-byte pieces
@@ -986,6 +991,8 @@ static int sgd_apply(xq_dqn* d, SegTable t, double alpha) {
     }
     const unsigned bx = (unsigned)std::max<long long>(1, std::min<long long>((mx + 255) / 256, 1024));
     ProfScope ps(d, t.reduce_only ? "reduce_slabs" : "sgd_apply", 0, 0, true);
+    if (clip) hipExtLaunchKernelGGL(sgd_segments_clip_kernel, dim3(bx, t.nseg), dim3(256), 0, d->cur, ps.start(), ps.stop(), 0, t, (float)alpha, *clip);
+    else
     hipExtLaunchKernelGGL(sgd_segments_kernel, dim3(bx, t.nseg), dim3(256), 0, d->cur, ps.start(), ps.stop(), 0, t, (float)alpha);
     XQ_HIP(hipGetLastError());
     return XQ_OK;
@@ -993,7 +1000,7 @@ static int sgd_apply(xq_dqn* d, SegTable t, double alpha) {
 
 // The same table through adam_segments_kernel: step t of Adam with the handle's betas and eps.  The bias corrections are taken on the
 // host in double and handed over as floats.
-static int adam_apply(xq_dqn* d, SegTable t, double lr, double grad_scale) {
+static int adam_apply(xq_dqn* d, SegTable t, double lr, double grad_scale, const ClipArgs* clip = nullptr) {
     long long mx = 0;
     for (int i = 0; i < t.nseg; ++i) {
         const uintptr_t bits = (uintptr_t)t.dst[i] | (uintptr_t)t.src[i] | ((uintptr_t)t.dst_bf[i] << 1);
@@ -1012,8 +1019,37 @@ static int adam_apply(xq_dqn* d, SegTable t, double lr, double grad_scale) {
     A.rbc2 = (float)(1.0 / std::sqrt(1.0 - std::pow(d->opt_b2, tt)));
     A.gs = (float)grad_scale;
     ProfScope ps(d, "adam_apply", 0, 0, true);
+    if (clip) hipExtLaunchKernelGGL(adam_segments_clip_kernel, dim3(bx, t.nseg), dim3(256), 0, d->cur, ps.start(), ps.stop(), 0, t, A, *clip);
+    else
     hipExtLaunchKernelGGL(adam_segments_kernel, dim3(bx, t.nseg), dim3(256), 0, d->cur, ps.start(), ps.stop(), 0, t, A);
     XQ_HIP(hipGetLastError());
+    return XQ_OK;
+}
+
+// Gradient clipping, in front of the apply: the squares of the whole gradient summed in fp64 into one partial per block (grad_norm_kernel,
+// fixed grid), pending slabs summed into the gradient buffer on the way.  On return the table reads the buffer and nothing is pending;
+// the coefficient is formed inside the apply kernel from the partials, so nothing comes back to the host.
+static int grad_norm(xq_dqn* d, SegTable& t, double grad_scale, ClipArgs* C) {
+    if (t.nseg * kNormBlocks > kNormMaxPartials) return fail(XQ_ERR_RUNTIME, "grad_norm: %d segments", t.nseg);
+    float* G = d->grads_td;
+    SegTable n = t;
+    double bytes = 0;
+    for (int i = 0; i < n.nseg; ++i) {
+        n.dst[i] = G + n.state_off[i];
+        n.dst_bf[i] = nullptr;
+        const uintptr_t bits = (uintptr_t)n.dst[i] | (uintptr_t)n.src[i];
+        n.vec4[i] = (bits & 15) == 0 && (n.len[i] & 3) == 0 && (n.nslabs[i] <= 0 || (n.stride[i] & 3) == 0);
+        bytes += 4.0 * n.len[i] * (n.nslabs[i] > 0 ? n.nslabs[i] + 1 : 1);
+    }
+    {
+        ProfScope ps(d, "grad_norm", 0, bytes, true);
+        hipExtLaunchKernelGGL(grad_norm_kernel, dim3(kNormBlocks, n.nseg), dim3(256), 0, d->cur, ps.start(), ps.stop(), 0, n, d->clip_partials.p);
+        XQ_HIP(hipGetLastError());
+    }
+    for (int i = 0; i < t.nseg; ++i) { t.src[i] = G + t.state_off[i]; t.nslabs[i] = 0; t.stride[i] = 0; }
+    C->partials = d->clip_partials; C->npart = t.nseg * kNormBlocks;
+    C->max_norm = d->clip_max_norm; C->abs_scale = std::fabs(grad_scale);
+    C->rec = d->clip_rec;
     return XQ_OK;
 }
 
@@ -2059,8 +2095,11 @@ int xq_dqn_apply_grads(xq_dqn* d, double lr, double grad_scale) {
     d->sel_invalidate();                              // W0 / b0 change: the select chain's kept layer-0 sums are stale
     for (auto& K : d->sel_keep) { K.pays = K.calls >= 2; K.calls = 0; }
     d->params_version += 1;
-    if (d->opt_kind == XQ_OPT_ADAM) return adam_apply(d, t, lr, grad_scale);
-    return sgd_apply(d, t, lr * grad_scale);
+    ClipArgs C; memset(&C, 0, sizeof C);
+    const bool clip = d->clip_max_norm > 0.0;
+    if (clip) XQ_TRY(grad_norm(d, t, grad_scale, &C));
+    if (d->opt_kind == XQ_OPT_ADAM) return adam_apply(d, t, lr, grad_scale, clip ? &C : nullptr);
+    return sgd_apply(d, t, lr * grad_scale, clip ? &C : nullptr);
 }
 
 static bool td_step_pending(const xq_dqn* d) { return d->l0_pending > 0 || d->pend_wout.nslabs > 0 || d->pend_bh.nslabs > 0; }
@@ -2126,6 +2165,40 @@ int xq_dqn_set_optimizer_state(xq_dqn* d, const float* m_host, const float* v_ho
     XQ_HIP(hipMemcpy(d->adam_m, m_host, d->n_grads_td * sizeof(float), hipMemcpyHostToDevice));
     XQ_HIP(hipMemcpy(d->adam_v, v_host, d->n_grads_td * sizeof(float), hipMemcpyHostToDevice));
     d->opt_t = steps;
+    return XQ_OK;
+}
+
+int xq_dqn_set_grad_clip(xq_dqn* d, double max_norm) {
+    if (!d) return fail(XQ_ERR_INVALID_ARGUMENT, "null dqn");
+    if (!(max_norm >= 0.0)) return fail(XQ_ERR_INVALID_ARGUMENT, "xq_dqn_set_grad_clip: max_norm must be 0 (off), positive or +inf");
+    if (td_step_pending(d)) return fail(XQ_ERR_RUNTIME, "xq_dqn_set_grad_clip: a TD step is waiting for its apply_grads");
+    if (max_norm > 0.0 && d->clip_max_norm == 0.0) {            // switched on: norm, coefficient and both counters start at 0
+        if (!d->clip_rec.p) {
+            XQ_TRY(d->clip_partials.alloc(kNormMaxPartials));
+            XQ_TRY(d->clip_rec.alloc(1));
+        }
+        XQ_HIP(hipMemsetAsync(d->clip_rec, 0, sizeof(ClipRecord), d->stream));
+    }
+    d->clip_max_norm = max_norm;
+    return XQ_OK;
+}
+
+int xq_dqn_get_grad_clip(const xq_dqn* d, double* max_norm) {
+    if (!d) return fail(XQ_ERR_INVALID_ARGUMENT, "null dqn");
+    if (max_norm) *max_norm = d->clip_max_norm;
+    return XQ_OK;
+}
+
+int xq_dqn_grad_clip_stats(xq_dqn* d, double* last_norm, double* last_coef, uint64_t* applies, uint64_t* clipped) {
+    if (!d) return fail(XQ_ERR_INVALID_ARGUMENT, "null dqn");
+    if (!(d->clip_max_norm > 0.0)) return fail(XQ_ERR_RUNTIME, "xq_dqn_grad_clip_stats: gradient clipping is off");
+    ClipRecord r;
+    XQ_HIP(hipStreamSynchronize(d->stream));
+    XQ_HIP(hipMemcpy(&r, d->clip_rec, sizeof r, hipMemcpyDeviceToHost));
+    if (last_norm) *last_norm = r.norm;
+    if (last_coef) *last_coef = r.coef;
+    if (applies) *applies = r.applies;
+    if (clipped) *clipped = r.clipped;
     return XQ_OK;
 }
 

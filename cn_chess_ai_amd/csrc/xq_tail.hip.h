@@ -764,4 +764,189 @@ __global__ void adam_segments_kernel(SegTable t, AdamArgs A) {
     }
 }
 
+// ---- gradient clipping by the global L2 norm (DESIGN.md section 4 "Gradient clipping") ---------------------------------------------
+//   S = sum_i (double)g_i^2;  norm = |grad_scale| sqrt(S);  c = (float)min(1, max_norm / (norm + 1e-6))
+// grad_norm_kernel walks the segment table of the apply in front of it: grid (kNormBlocks, segments), both fixed by the net alone.
+// Element i of a segment belongs to quad i / 4, quad q to thread q mod (kNormBlocks * 256) of the segment's blocks; a thread adds the
+// squares of its quads in ascending order, x y z w inside a quad, every square and every sum in fp64 with contraction off.  The 16-byte
+// loop and the scalar loop differ in how a quad is loaded and in nothing else, and a slab sum has the bits reduce_slabs_kernel would
+// have written, so the partial of a block does not depend on where the gradient came from.  Block tree: __shfl_down by 32, 16, .. 1 in
+// each wave, then ((w0 + w1) + w2) + w3.  One fp64 partial per block, at [segment * kNormBlocks + block].
+// Where a segment has pending slabs their sum is written to the gradient buffer (t.dst here), which the apply kernel then reads.
+constexpr int kNormBlocks = 64;
+constexpr int kNormMaxPartials = 16 * kNormBlocks;
+struct ClipRecord {            // of the last clipped-mode apply / since clipping was switched on; written by one thread of the apply kernel
+    double norm, coef;
+    unsigned long long applies, clipped;
+};
+struct ClipArgs {
+    const double* partials;    // grad_norm_kernel's, npart of them
+    int npart;
+    double max_norm, abs_scale;
+    ClipRecord* rec;
+};
+__device__ __forceinline__ double sq_add(double acc, float g) {
+#pragma clang fp contract(off)
+    const double x = (double)g;
+    const double x2 = x * x;
+    return acc + x2;
+}
+__device__ __forceinline__ float slab_sum(const float* __restrict__ s, int nslabs, long long st, long long i) {
+    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+    int z = 0;
+    for (; z + 3 < nslabs; z += 4) {
+        s0 += s[(long long)z * st + i];
+        s1 += s[(long long)(z + 1) * st + i];
+        s2 += s[(long long)(z + 2) * st + i];
+        s3 += s[(long long)(z + 3) * st + i];
+    }
+    for (; z < nslabs; ++z) s0 += s[(long long)z * st + i];
+    return (s0 + s1) + (s2 + s3);
+}
+__global__ __launch_bounds__(256) void grad_norm_kernel(SegTable t, double* __restrict__ partials) {
+    const int sgm = (int)blockIdx.y;
+    if (sgm >= t.nseg) return;
+    float* out = t.dst[sgm];
+    const float* s = t.src[sgm];
+    const int nslabs = t.nslabs[sgm];
+    const long long len = t.len[sgm], st = t.stride[sgm];
+    const long long nq = (len + 3) >> 2;
+    const long long step = (long long)kNormBlocks * 256;
+    double acc = 0.0;
+    if (t.vec4[sgm]) {
+        const long long st4 = st >> 2;
+        const float4* s4 = reinterpret_cast<const float4*>(s);
+        float4* o4 = reinterpret_cast<float4*>(out);
+        for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < nq; q += step) {
+            float4 g;
+            if (nslabs <= 0) g = s4[q];
+            else {
+                float4 s0 = make_float4(0.f, 0.f, 0.f, 0.f), s1 = s0, s2 = s0, s3 = s0;
+                int z = 0;
+                for (; z + 3 < nslabs; z += 4) {
+                    s0 = f4_add(s0, s4[(long long)z * st4 + q]);
+                    s1 = f4_add(s1, s4[(long long)(z + 1) * st4 + q]);
+                    s2 = f4_add(s2, s4[(long long)(z + 2) * st4 + q]);
+                    s3 = f4_add(s3, s4[(long long)(z + 3) * st4 + q]);
+                }
+                for (; z < nslabs; ++z) s0 = f4_add(s0, s4[(long long)z * st4 + q]);
+                g = f4_add(f4_add(s0, s1), f4_add(s2, s3));
+                o4[q] = g;
+            }
+            acc = sq_add(sq_add(sq_add(sq_add(acc, g.x), g.y), g.z), g.w);
+        }
+    } else {
+        for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < nq; q += step) {
+            const long long i0 = q << 2, i1 = i0 + 4 < len ? i0 + 4 : len;
+            for (long long i = i0; i < i1; ++i) {
+                float g;
+                if (nslabs <= 0) g = s[i];
+                else { g = slab_sum(s, nslabs, st, i); out[i] = g; }
+                acc = sq_add(acc, g);
+            }
+        }
+    }
+    for (int off = 32; off >= 1; off >>= 1) acc += __shfl_down(acc, off, 64);
+    __shared__ double wsum[4];
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) partials[sgm * kNormBlocks + (int)blockIdx.x] = ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
+}
+// The coefficient, by every block of the apply kernel for itself: the partials added in index order by one thread, in fp64.  `writer`
+// (one block of the grid) also leaves norm and c in the record and bumps its counters: plain stores, one writer, launches in stream order.
+__device__ __forceinline__ float clip_coef(const ClipArgs& C, bool writer) {
+    __shared__ double sp[kNormMaxPartials];
+    __shared__ float sc;
+    for (int i = (int)threadIdx.x; i < C.npart; i += (int)blockDim.x) sp[i] = C.partials[i];
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double S = 0.0;
+        for (int i = 0; i < C.npart; ++i) S += sp[i];
+        const double norm = C.abs_scale * sqrt(S);
+        const double q = C.max_norm / (norm + 1e-6);
+        const float c = (float)(q > 1.0 ? 1.0 : q);
+        sc = c;
+        if (writer) {
+            C.rec->norm = norm;
+            C.rec->coef = (double)c;
+            C.rec->applies += 1;
+            if (c < 1.0f) C.rec->clipped += 1;
+        }
+    }
+    __syncthreads();
+    return sc;
+}
+__device__ __forceinline__ float clip_mul(float a, float c) {
+#pragma clang fp contract(off)
+    return a * c;
+}
+// SGD: p -= fl32(fl32(lr grad_scale) c) g;  Adam: g' = fl32(fl32(grad_scale) c) g.  c == 1: the products are exact, the bits those of the
+// unclipped kernels.  The table has no pending slabs left (grad_norm_kernel summed them into the gradient buffer), so these two are the
+// direct-gradient loops of sgd_segments_kernel / adam_segments_kernel, element for element the same expressions.
+__global__ void sgd_segments_clip_kernel(SegTable t, float alpha0, ClipArgs C) {
+    const float alpha = clip_mul(alpha0, clip_coef(C, blockIdx.x == 0 && blockIdx.y == 0));
+    const int sgm = (int)blockIdx.y;
+    if (sgm >= t.nseg) return;
+    float* d = t.dst[sgm];
+    const float* s = t.src[sgm];
+    const long long len = t.len[sgm];
+    uint16_t* db = t.dst_bf[sgm];
+    if (t.vec4[sgm]) {
+        const long long n4 = len >> 2;
+        const float4* s4 = reinterpret_cast<const float4*>(s);
+        float4* d4 = reinterpret_cast<float4*>(d);
+        for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long long)gridDim.x * blockDim.x) {
+            const float4 g = s4[i];
+            const float4 w = d4[i];
+            const float4 v = make_float4(w.x - alpha * g.x, w.y - alpha * g.y, w.z - alpha * g.z, w.w - alpha * g.w);
+            d4[i] = v;
+            if (db) reinterpret_cast<uint2*>(db)[i] = make_uint2((uint32_t)bf16_bits(v.x) | ((uint32_t)bf16_bits(v.y) << 16),
+                                                                 (uint32_t)bf16_bits(v.z) | ((uint32_t)bf16_bits(v.w) << 16));
+        }
+        return;
+    }
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < len; i += (long long)gridDim.x * blockDim.x) {
+        const float v = d[i] - alpha * s[i];
+        d[i] = v;
+        if (db) db[i] = bf16_bits(v);
+    }
+}
+__global__ void adam_segments_clip_kernel(SegTable t, AdamArgs A, ClipArgs C) {
+    A.gs = clip_mul(A.gs, clip_coef(C, blockIdx.x == 0 && blockIdx.y == 0));
+    const int sgm = (int)blockIdx.y;
+    if (sgm >= t.nseg) return;
+    float* d = t.dst[sgm];
+    const float* s = t.src[sgm];
+    const long long len = t.len[sgm];
+    uint16_t* db = t.dst_bf[sgm];
+    float* ms = A.m + t.state_off[sgm];
+    float* vs = A.v + t.state_off[sgm];
+    if (t.vec4[sgm]) {
+        const long long n4 = len >> 2;
+        const float4* s4 = reinterpret_cast<const float4*>(s);
+        float4* d4 = reinterpret_cast<float4*>(d);
+        float4* m4 = reinterpret_cast<float4*>(ms);
+        float4* v4 = reinterpret_cast<float4*>(vs);
+        for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long long)gridDim.x * blockDim.x) {
+            const float4 g = s4[i];
+            const float4 w = d4[i];
+            float4 m = m4[i], v = v4[i], o;
+            o.x = adam_elem(A, w.x, g.x, m.x, v.x);
+            o.y = adam_elem(A, w.y, g.y, m.y, v.y);
+            o.z = adam_elem(A, w.z, g.z, m.z, v.z);
+            o.w = adam_elem(A, w.w, g.w, m.w, v.w);
+            m4[i] = m; v4[i] = v; d4[i] = o;
+            if (db) reinterpret_cast<uint2*>(db)[i] = make_uint2((uint32_t)bf16_bits(o.x) | ((uint32_t)bf16_bits(o.y) << 16),
+                                                                 (uint32_t)bf16_bits(o.z) | ((uint32_t)bf16_bits(o.w) << 16));
+        }
+        return;
+    }
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < len; i += (long long)gridDim.x * blockDim.x) {
+        float m = ms[i], v = vs[i];
+        const float o = adam_elem(A, d[i], s[i], m, v);
+        ms[i] = m; vs[i] = v; d[i] = o;
+        if (db) db[i] = bf16_bits(o);
+    }
+}
+
 }  // namespace xq

@@ -351,6 +351,36 @@ DQN.optimizer_state = _optimizer_state
 DQN.set_optimizer_state = _set_optimizer_state
 
 
+def _set_grad_clip(self, max_norm):
+    """Clip the gradient of apply_grads / the trainer's learn_apply by its global L2 norm (torch.nn.utils.clip_grad_norm_'s rule, in
+    front of either optimizer): 0 = off (default), math.inf = measure the norm and never clip.  backpropagate() is never clipped."""
+    max_norm = float(max_norm)
+    if not max_norm >= 0.0:
+        raise ValueError(f"set_grad_clip: max_norm must be 0 (off), positive or inf, got {max_norm!r}")
+    call("xq_dqn_set_grad_clip", self._h, max_norm)
+
+
+def _grad_clip(self):
+    """max_norm in force (0.0 = off)."""
+    v = C.c_double()
+    call("xq_dqn_get_grad_clip", self._h, C.byref(v))
+    return v.value
+
+
+def _grad_clip_stats(self):
+    """dict(last_norm, last_coef, applies, clipped): norm and coefficient of the last clipped-mode apply; applies and how many of them
+    had a coefficient below 1 since clipping was last switched on.  Synchronises; raises XqError while clipping is off."""
+    n, c = C.c_double(), C.c_double()
+    a, k = C.c_uint64(), C.c_uint64()
+    call("xq_dqn_grad_clip_stats", self._h, C.byref(n), C.byref(c), C.byref(a), C.byref(k))
+    return dict(last_norm=n.value, last_coef=c.value, applies=a.value, clipped=k.value)
+
+
+DQN.set_grad_clip = _set_grad_clip
+DQN.grad_clip = _grad_clip
+DQN.grad_clip_stats = _grad_clip_stats
+
+
 def _timeline(self, max_spans=8192):
     """(name, start_ms, end_ms) of every launch bracketed in the session closed by the last kernel_stats() call."""
     arr = (KernelSpan * max_spans)()

@@ -29,6 +29,7 @@ ROCPROF_NAMES = {
     "colmax_reduce": "colmax_reduce_kernel(",
     "sgd_apply": "sgd_segments_kernel(",
     "adam_apply": "adam_segments_kernel(",
+    "grad_norm": "grad_norm_kernel(",
     "env_selfplay_step": "env_kernel<2>(",
     "target_sync_copy": "__amd_rocclr_copyBuffer",
     "l0_grad_segsum": "l0_grad_kernel(",
@@ -116,9 +117,11 @@ def pick_splits(M, N, K):
 
 
 def step_work(layers, minibatch, n_games, plies=1, bf16=False, bf16_bwd=False, td="online", screened=True, derive=True,
-              prioritized=False, l0_mfma=True, optimizer="sgd"):
+              prioritized=False, l0_mfma=True, optimizer="sgd", grad_clip=False):
     """{bracket name: dict(flops, hbm_bytes, bound, peak, peak_unit, what)} for one training step of the given configuration.
-    optimizer="adam" (xq_dqn_set_optimizer): adam_apply stands in place of sgd_apply; the default step knows no adam_apply."""
+    optimizer="adam" (xq_dqn_set_optimizer): adam_apply stands in place of sgd_apply; the default step knows no adam_apply.
+    grad_clip=True (xq_dqn_set_grad_clip): grad_norm stands in front of the apply and takes the slab sums over from it; the default
+    step knows no grad_norm."""
     h = list(layers[1:-1])
     H1, Hl, k = h[0], h[-1], len(h)
     B, n = minibatch, n_games
@@ -272,6 +275,12 @@ def step_work(layers, minibatch, n_games, plies=1, bf16=False, bf16_bwd=False, t
             "ordered sum of every partial-sum slab + Adam step on the touched parameters and their two moments" + (" (+ their bf16 shadow)" if bf16 else ""))
     elif optimizer != "sgd":
         raise ValueError("optimizer: 'sgd' or 'adam'")
+    if grad_clip:
+        # every slab read once and the gradient buffer written (the squares are summed on the way, in fp64); the apply kernel behind
+        # it reads the buffer instead of the slabs
+        put("grad_norm", 3.0 * touched + slabs, 4 * (slabs + touched), "hbm",
+            "ordered sum of every partial-sum slab into the gradient buffer + fp64 sum of its squares (global-norm clipping)")
+        w["adam_apply" if optimizer == "adam" else "sgd_apply"]["hbm_bytes"] -= 4 * (slabs - touched)
     nw = STATE * H1 + sum(h[l] * h[l - 1] for l in range(1, k)) + Hl * NO
     nb = sum(h) + NO
     put("target_sync_copy", 0.0, 8.0 * (nw + nb), "hbm", "updateTargetNetwork(): device copy of all parameters")

@@ -13,6 +13,7 @@
 //   --prefill N                   N uniform-random plies in every game before training (spreads the games over all phases)
 //   --seed S                      seed of the batched games (default: time, like the reference's srand(time))
 //   adam                          the batched loop's optimizer: Adam (xq::Optimizer::adam(), defaults 0.9 / 0.999 / 1e-8) instead of SGD
+//   clip=<max_norm>               clip the batched loop's gradient by its global L2 norm (xq::ChessAI::setGradClip; inf = measure only)
 //   --json                        one JSON line with the loop's counters (bench.py's `facade` leg reads it)
 #include <chrono>
 #include <cstdio>
@@ -28,6 +29,7 @@ int main(int argc, char** argv) {
     std::vector<int> hidden;
     bool derive = false, json = false, adam = false;
     unsigned long long seed = 0;
+    double clip = 0.0;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         auto next = [&]() -> const char* { if (i + 1 >= argc) { std::fprintf(stderr, "%s needs a value\n", a.c_str()); std::exit(2); } return argv[++i]; };
@@ -39,6 +41,11 @@ int main(int argc, char** argv) {
         else if (a == "--derive") derive = true;
         else if (a == "--json") json = true;
         else if (a == "adam") adam = true;
+        else if (a.rfind("clip=", 0) == 0) {
+            char* end = nullptr;
+            clip = std::strtod(a.c_str() + 5, &end);
+            if (end == a.c_str() + 5 || *end || !(clip >= 0.0)) { std::fprintf(stderr, "clip=: expected a max_norm >= 0 or inf, got %s\n", a.c_str() + 5); return 2; }
+        }
         else if (a == "--hidden") {
             for (const char* p = next(); *p;) { hidden.push_back(std::atoi(p)); while (*p && *p != ',') ++p; if (*p == ',') ++p; }
         } else if (a.rfind("--", 0) == 0) { std::fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
@@ -57,6 +64,7 @@ int main(int argc, char** argv) {
             ai.setDQN(std::make_unique<xq::DQN>(sizes));
         }
         if (adam) ai.setOptimizer(xq::Optimizer::adam());
+        if (clip != 0.0) ai.setGradClip(clip);
         if (replay > 0) ai.setReplay(replay, minibatch);
         ai.setSaveInterval(save_every);
         ai.setLayer0Derive(derive);

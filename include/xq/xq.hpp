@@ -274,6 +274,20 @@ public:
         return o;
     }
     void resetOptimizer() { check(xq_dqn_reset_optimizer(h_)); }
+    // clip the gradient of a batched TD step by its global L2 norm, in front of either optimizer (xq_dqn_set_grad_clip): 0 = off,
+    // +inf = measure only.  backpropagate stays unclipped.
+    void setGradClip(double maxNorm) { check(xq_dqn_set_grad_clip(h_, maxNorm)); }
+    double gradClip() const {
+        double m = 0.0;
+        check(xq_dqn_get_grad_clip(h_, &m));
+        return m;
+    }
+    struct GradClipStats { double lastNorm = 0.0, lastCoef = 0.0; uint64_t applies = 0, clipped = 0; };
+    GradClipStats gradClipStats() const {                        // synchronises; throws while clipping is off
+        GradClipStats s;
+        check(xq_dqn_grad_clip_stats(h_, &s.lastNorm, &s.lastCoef, &s.applies, &s.clipped));
+        return s;
+    }
     const std::vector<int>& layerSizes() const { return layerSizes_; }
     double gamma() const { return gamma_; }
     xq_dqn* handle() const { return h_; }
@@ -678,6 +692,8 @@ public:
     // Optimizer of the batched train(): forwarded to this agent's network (created now if need be), whose choice the batched loop takes
     // over.  The sequential loop (parallelGames == 1) is the reference's backpropagate(lr): plain SGD whatever is set here.
     void setOptimizer(const Optimizer& o) { initializeDQN(); dqn->setOptimizer(o); }
+    // Gradient clipping of the batched train(), carried onto the trainer's network like the optimizer (0 = off, +inf = measure only)
+    void setGradClip(double maxNorm) { initializeDQN(); dqn->setGradClip(maxNorm); }
     DQN* network() { return dqn.get(); }
     std::vector<double> getStateRepresentation() {                           // chessai.cpp:268-289 (encoding only)
         std::vector<double> s(90 * 14, 0.0);
@@ -725,6 +741,7 @@ private:
         check(xq_dqn_set_l0_derive(td, l0Derive_ ? 1 : 0));
         const Optimizer opt = dqn->optimizer();
         check(xq_dqn_set_optimizer(td, opt.kind, opt.beta1, opt.beta2, opt.eps));
+        check(xq_dqn_set_grad_clip(td, dqn->gradClip()));
         if (comm_) check(xq_trainer_set_comm(t, comm_->handle()));
         if (prefillPlies_ > 0) check(xq_trainer_random_plies(t, prefillPlies_));
         if (opponent_) check(xq_trainer_set_opponent(t, &opponent_->spec()));

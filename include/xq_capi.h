@@ -373,7 +373,7 @@ int xq_dqn_load_model(xq_dqn* d, const char* path);
  * action.to replaced by y;  backprop of 0.5*|Q(s)-target|^2.  Split in two so a multi-GPU caller can all-reduce
  * the gradient buffer in between:
  *   xq_dqn_td_grads  : forward + deltas + gradient reduction over the batch  -> compact gradient buffer (HBM)
- *   xq_dqn_apply_grads: params -= lr * grad_scale * grads   (or the Adam step of xq_dqn_set_optimizer)
+ *   xq_dqn_apply_grads: params -= lr * grad_scale * grads   (or the Adam step of xq_dqn_set_optimizer; clipped by xq_dqn_set_grad_clip)
  * boards/next_boards: [n][12] u32, optionally gathered through slots_dev ([n] row indices, NULL = identity).
  * td_net = XQ_TD_*.  loss_out_dev: optional, sum over the batch of 0.5*(Q(s,a)-y)^2. */
 int xq_dqn_td_grads(xq_dqn* d, const uint32_t* boards_dev, const uint32_t* next_boards_dev,
@@ -409,6 +409,29 @@ int xq_dqn_reset_optimizer(xq_dqn* d);
  * xq_dqn_grad_buffer each; get: either may be NULL), steps = t.  Both synchronise.  XQ_ERR_RUNTIME under XQ_OPT_SGD (no state). */
 int xq_dqn_get_optimizer_state(xq_dqn* d, float* m_host, float* v_host, uint64_t* steps);
 int xq_dqn_set_optimizer_state(xq_dqn* d, const float* m_host, const float* v_host, uint64_t steps);
+/* Gradient clipping by the global L2 norm, in front of whatever optimizer xq_dqn_apply_grads runs (torch.nn.utils.clip_grad_norm_'s
+ * rule; off by default, and a handle with it off runs the kernels, launches and bits of one that was never asked).  With g the summed
+ * gradient about to be applied — every entry of the xq_dqn_grad_buffer layout, pending partial sums added in reduce_slabs_kernel's
+ * order, behind an all-reduce the global sum:
+ *   S    = sum_i (double)g_i^2                        every square and every sum in fp64, in one fixed association
+ *   norm = |grad_scale| * sqrt(S)                     fp64: the norm of g' = grad_scale * g
+ *   c    = (float) min(1, max_norm / (norm + 1e-6))
+ *   SGD : p -= fl32(fl32(lr * grad_scale) * c) * g
+ *   Adam: g' = fl32(fl32(grad_scale) * c) * g, then the element update of xq_dqn_set_optimizer unchanged
+ * c == 1 makes both products exact: the update then has the bits of the unclipped one.  max_norm = +inf never clips and only measures
+ * the norm.  A non-finite S gets no special case.  One kernel (grad_norm_kernel: fixed grid of 64 blocks per segment, so S does not
+ * depend on the device or on whether the gradient arrived in slabs or in the buffer) in front of the apply kernel, which forms c itself
+ * from the per-block partials: nothing returns to the host.  Side effect under xq_dqn_set_fused_apply: that kernel writes the slab sums
+ * into the gradient buffer, which is therefore complete after the apply.  A gradient of 0 stays 0 (output rows >= 96 never move), the
+ * bf16 shadow is refreshed as before, xq_dqn_backpropagate is never clipped.  The setting survives xq_dqn_set_optimizer,
+ * xq_dqn_set_params, xq_dqn_load_model and xq_dqn_update_target.
+ * 0 = off (default).  > 0 or +inf = on.  Negative or NaN: XQ_ERR_INVALID_ARGUMENT.  XQ_ERR_RUNTIME while a TD step waits for its
+ * apply_grads. */
+int xq_dqn_set_grad_clip(xq_dqn* d, double max_norm);
+int xq_dqn_get_grad_clip(const xq_dqn* d, double* max_norm);
+/* Of the last clipped-mode apply: its norm and coefficient.  Since clipping was last switched on (a change from 0): applies and how
+ * many had c < 1.  Synchronises.  XQ_ERR_RUNTIME while off.  Any pointer may be NULL. */
+int xq_dqn_grad_clip_stats(xq_dqn* d, double* last_norm, double* last_coef, uint64_t* applies, uint64_t* clipped);
 /* Convenience: sample-free TD update straight from a replay ring (slots from the last xq_replay_sample). */
 int xq_dqn_td_grads_replay(xq_dqn* d, xq_replay* r, int batch, int td_net, int mode);
 /* Host-buffer TD step for tests: n transitions as 90-byte boards. Returns Q(s,a) and y per sample if non-NULL. */
