@@ -811,6 +811,15 @@ static int grad_splits(const xq_dqn* d, int M, int N, int K) {
     return s;
 }
 
+// dst[i] = the ordered sum of `nslabs` contiguous slabs of `len` floats, on d->cur
+static int launch_reduce_slabs(xq_dqn* d, const float* slabs, int nslabs, long long len, float* dst) {
+    ProfScope ps(d, "reduce_slabs", (double)nslabs * len, 4.0 * (nslabs + 1) * len);
+    hipLaunchKernelGGL(reduce_slabs_kernel, dim3((unsigned)std::min<long long>((len + 255) / 256, 2048)), dim3(256), 0, d->cur, slabs, nslabs,
+                       len, len, dst);
+    XQ_HIP(hipGetLastError());
+    return XQ_OK;
+}
+
 // dst[M][N] = sum over the batch: A(m,k) B(k,n), split-K slabs + ordered reduction.  a_bf / b_bf: the bf16 copies of the operands
 // ([batch][M] / [batch][N]) for the bf16 loop.
 template <int AL>
@@ -830,12 +839,7 @@ static int grad_gemm(xq_dqn* d, GemmArgs g, float* dst, const char* name, float*
         } else { b.C = dst; b.ldc = g.N; }
         XQ_TRY((launch_bf16_gemm<L_MCONTIG, L_MCONTIG, BG_STORE>(d, b, splits, name)));
         if (splits > 1 && defer) { defer->src = slabs; defer->nslabs = splits; defer->stride = len; return XQ_OK; }
-        if (splits > 1) {
-            ProfScope ps(d, "reduce_slabs", (double)splits * len, 4.0 * (splits + 1) * len);
-            hipLaunchKernelGGL(reduce_slabs_kernel, dim3((unsigned)std::min<long long>((len + 255) / 256, 2048)), dim3(256), 0,
-                               d->cur, slabs, splits, len, len, dst);
-            XQ_HIP(hipGetLastError());
-        }
+        if (splits > 1) XQ_TRY(launch_reduce_slabs(d, slabs, splits, len, dst));
         return XQ_OK;
     }
     const long long len = (long long)g.M * g.N;
@@ -852,12 +856,7 @@ static int grad_gemm(xq_dqn* d, GemmArgs g, float* dst, const char* name, float*
         defer->src = slabs; defer->nslabs = used; defer->stride = len;
         return XQ_OK;
     }
-    if (splits > 1) {
-        ProfScope ps(d, "reduce_slabs", (double)used * len, 4.0 * (used + 1) * len);
-        hipLaunchKernelGGL(reduce_slabs_kernel, dim3((unsigned)std::min<long long>((len + 255) / 256, 2048)), dim3(256), 0,
-                           d->cur, slabs, used, len, len, dst);
-        XQ_HIP(hipGetLastError());
-    }
+    if (splits > 1) XQ_TRY(launch_reduce_slabs(d, slabs, used, len, dst));
     return XQ_OK;
 }
 
@@ -974,22 +973,27 @@ static int l0_gradient(xq_dqn* d, int n, float* dst) {
     if (nchunks > 1 && d->fused()) {
         d->l0_pending = nchunks;                     // summed inside the SGD kernel: one kernel fewer on the critical chain
     } else if (nchunks > 1) {
-        ProfScope ps(d, "reduce_slabs", (double)nchunks * len, 4.0 * (nchunks + 1) * len);
-        hipLaunchKernelGGL(reduce_slabs_kernel, dim3((unsigned)std::min<long long>((len + 255) / 256, 2048)), dim3(256), 0, d->cur,
-                           d->slabs_l0, nchunks, len, len, dst);
-        XQ_HIP(hipGetLastError());
+        XQ_TRY(launch_reduce_slabs(d, d->slabs_l0, nchunks, len, dst));
     }
     return XQ_OK;
 }
 
-static int sgd_apply(xq_dqn* d, SegTable t, double alpha, const ClipArgs* clip = nullptr) {
+// Which segments go four elements to a thread (t.vec4: every pointer 16-byte aligned — the bf16 shadow, where there is one, is stored in
+// 8-byte pieces — len and slab stride multiples of 4; `state`: so is the offset into Adam's m and v), and the x size of a grid
+// (blocks, segments) of 256 threads that covers the longest segment, capped at 1024.
+static unsigned seg_grid(SegTable& t, bool state) {
     long long mx = 0;
     for (int i = 0; i < t.nseg; ++i) {
-        const uintptr_t bits = (uintptr_t)t.dst[i] | (uintptr_t)t.src[i] | ((uintptr_t)t.dst_bf[i] << 1);   // the bf16 shadow: 8-byte pieces
-        t.vec4[i] = (bits & 15) == 0 && (t.len[i] & 3) == 0 && (t.nslabs[i] <= 0 || (t.stride[i] & 3) == 0);
+        const uintptr_t bits = (uintptr_t)t.dst[i] | (uintptr_t)t.src[i] | ((uintptr_t)t.dst_bf[i] << 1);
+        t.vec4[i] = (bits & 15) == 0 && (t.len[i] & 3) == 0 && (t.nslabs[i] <= 0 || (t.stride[i] & 3) == 0) &&
+                    (!state || (t.state_off[i] & 3) == 0);
         mx = std::max(mx, t.vec4[i] ? t.len[i] / 4 : t.len[i]);
     }
-    const unsigned bx = (unsigned)std::max<long long>(1, std::min<long long>((mx + 255) / 256, 1024));
+    return (unsigned)std::max<long long>(1, std::min<long long>((mx + 255) / 256, 1024));
+}
+
+static int sgd_apply(xq_dqn* d, SegTable t, double alpha, const ClipArgs* clip = nullptr) {
+    const unsigned bx = seg_grid(t, false);
     ProfScope ps(d, t.reduce_only ? "reduce_slabs" : "sgd_apply", 0, 0, true);
     if (clip) hipExtLaunchKernelGGL(sgd_segments_clip_kernel, dim3(bx, t.nseg), dim3(256), 0, d->cur, ps.start(), ps.stop(), 0, t, (float)alpha, *clip);
     else
@@ -1001,13 +1005,7 @@ static int sgd_apply(xq_dqn* d, SegTable t, double alpha, const ClipArgs* clip =
 // The same table through adam_segments_kernel: step t of Adam with the handle's betas and eps.  The bias corrections are taken on the
 // host in double and handed over as floats.
 static int adam_apply(xq_dqn* d, SegTable t, double lr, double grad_scale, const ClipArgs* clip = nullptr) {
-    long long mx = 0;
-    for (int i = 0; i < t.nseg; ++i) {
-        const uintptr_t bits = (uintptr_t)t.dst[i] | (uintptr_t)t.src[i] | ((uintptr_t)t.dst_bf[i] << 1);
-        t.vec4[i] = (bits & 15) == 0 && (t.len[i] & 3) == 0 && (t.nslabs[i] <= 0 || (t.stride[i] & 3) == 0) && (t.state_off[i] & 3) == 0;
-        mx = std::max(mx, t.vec4[i] ? t.len[i] / 4 : t.len[i]);
-    }
-    const unsigned bx = (unsigned)std::max<long long>(1, std::min<long long>((mx + 255) / 256, 1024));
+    const unsigned bx = seg_grid(t, true);
     d->opt_t += 1;
     const double tt = (double)d->opt_t;
     AdamArgs A;
@@ -1036,11 +1034,10 @@ static int grad_norm(xq_dqn* d, SegTable& t, double grad_scale, ClipArgs* C) {
     double bytes = 0;
     for (int i = 0; i < n.nseg; ++i) {
         n.dst[i] = G + n.state_off[i];
-        n.dst_bf[i] = nullptr;
-        const uintptr_t bits = (uintptr_t)n.dst[i] | (uintptr_t)n.src[i];
-        n.vec4[i] = (bits & 15) == 0 && (n.len[i] & 3) == 0 && (n.nslabs[i] <= 0 || (n.stride[i] & 3) == 0);
+        n.dst_bf[i] = nullptr;                       // the norm reads and writes gradients only: no shadow in its alignment rule
         bytes += 4.0 * n.len[i] * (n.nslabs[i] > 0 ? n.nslabs[i] + 1 : 1);
     }
+    seg_grid(n, false);                              // its vec4[]; the grid is fixed (kNormBlocks)
     {
         ProfScope ps(d, "grad_norm", 0, bytes, true);
         hipExtLaunchKernelGGL(grad_norm_kernel, dim3(kNormBlocks, n.nseg), dim3(256), 0, d->cur, ps.start(), ps.stop(), 0, n, d->clip_partials.p);
@@ -1061,6 +1058,25 @@ static void layout_td_grads(xq_dqn* d) {
     d->g_bout = off; off += 96;                      // directly behind the output rows: one ordered reduction fills both
     for (int l = 0; l + 1 < d->nl; ++l) { d->g_bh[l] = off; off += (size_t)d->L[l + 1]; }
     d->n_grads_td = off;
+}
+// a TD step left partial-sum slabs for its apply_grads to add (fused_apply)
+static bool td_step_pending(const xq_dqn* d) { return d->l0_pending > 0 || d->pend_wout.nslabs > 0 || d->pend_bh.nslabs > 0; }
+// The segments a TD step touches, in THE order of every table built from them (the order is part of the clip norm's association):
+// W0^T, the hidden weights, output rows 0..95, the hidden biases (contiguous in both layouts), the output biases.  f(parameters, their
+// bf16 shadow or nullptr, offset in the gradient buffer, length, the segment's pending-slab slot) — f empties the slot it takes.
+template <class F>
+static void for_td_segments(xq_dqn* d, F f) {
+    const bool bf = d->bf16();
+    const int top = d->nl - 1;
+    const long long len0 = (long long)d->L[0] * d->L[1];
+    xq_dqn::PendingSlab p0;                          // layer 0 keeps a count, its slabs are slabs_l0
+    if (d->l0_pending > 0) { p0.src = d->slabs_l0; p0.nslabs = d->l0_pending; p0.stride = len0; }
+    f(d->w0t(0), bf ? d->wl_bf(0, 0) : nullptr, d->g_w0, len0, p0);
+    d->l0_pending = p0.nslabs;
+    for (int l = 1; l < top; ++l) f(d->wl(0, l), bf ? d->wl_bf(0, l) : nullptr, d->g_wh[l], (long long)d->L[l] * d->L[l + 1], d->pend_hidden[l]);
+    f(d->wl(0, top), bf ? d->wl_bf(0, top) : nullptr, d->g_wout, 96LL * d->hlast(), d->pend_wout);
+    f(d->bl(0, 0), (uint16_t*)nullptr, d->g_bh[0], (long long)d->bo[top], d->pend_bh);
+    f(d->bl(0, top), (uint16_t*)nullptr, d->g_bout, 96LL, d->pend_bout);
 }
 
 }  // namespace xq
@@ -1277,7 +1293,7 @@ int xq_dqn_qmax_guard(xq_dqn* d, uint64_t* fallbacks, int* hold_steps_left) {
 int xq_dqn_set_precision(xq_dqn* d, int precision) {
     if (!d || (precision != XQ_PRECISION_F32 && precision != XQ_PRECISION_BF16 && precision != XQ_PRECISION_BF16_FULL))
         return fail(XQ_ERR_INVALID_ARGUMENT, "bad precision");
-    if (d->l0_pending > 0 || d->pend_wout.nslabs > 0 || d->pend_bh.nslabs > 0)
+    if (td_step_pending(d))
         return fail(XQ_ERR_RUNTIME, "xq_dqn_set_precision: a TD step is waiting for its apply_grads");
     if (precision != XQ_PRECISION_F32) {
         for (int l = 1; l <= d->nl - 1; ++l)
@@ -1474,10 +1490,7 @@ static int side_gradients(xq_dqn* d, int n, float* const* outs, float* G) {
             d->pend_wout.src = out; d->pend_wout.nslabs = nchunks; d->pend_wout.stride = len_out;
             d->pend_bout.src = out + 96LL * Hl; d->pend_bout.nslabs = nchunks; d->pend_bout.stride = len_out;
         } else if (nchunks > 1) {
-            ProfScope ps(d, "reduce_slabs", (double)nchunks * len_out, 4.0 * (nchunks + 1) * len_out);
-            hipLaunchKernelGGL(reduce_slabs_kernel, dim3((unsigned)((len_out + 255) / 256)), dim3(256), 0, d->cur, out, nchunks, len_out,
-                               len_out, dst);
-            XQ_HIP(hipGetLastError());
+            XQ_TRY(launch_reduce_slabs(d, out, nchunks, len_out, dst));     // (len_out <= 96 * 961: under the grid cap, one thread per sum)
         }
     }
     bool waited = false;
@@ -1526,24 +1539,15 @@ static bool tail_eligible(xq_dqn* d, int n) {
         if (!d->small_tiles && (long long)((n + 127) / 128) * ((d->L[l + 1] + 127) / 128) >= 512) return false;   // launch_gemm would go 128x128
     return true;
 }
-// every pending partial-sum slab of the step summed into its place in the gradient buffer, one launch (the order of reduce_slabs_kernel)
+// every pending partial-sum slab of the step summed into its place in the gradient buffer, one launch (slab_sum's order)
 static int reduce_pending(xq_dqn* d) {
     SegTable t; memset(&t, 0, sizeof t);
     float* G = d->grads_td;
     int k = 0;
-    auto add = [&](float* dst, long long len, xq_dqn::PendingSlab& p) {
-        if (p.nslabs > 0) { t.dst[k] = dst; t.src[k] = p.src; t.len[k] = len; t.nslabs[k] = p.nslabs; t.stride[k] = p.stride; ++k; }
+    for_td_segments(d, [&](float*, uint16_t*, size_t goff, long long len, xq_dqn::PendingSlab& p) {
+        if (p.nslabs > 0) { t.dst[k] = G + goff; t.src[k] = p.src; t.len[k] = len; t.nslabs[k] = p.nslabs; t.stride[k] = p.stride; ++k; }
         p = xq_dqn::PendingSlab();
-    };
-    if (d->l0_pending > 0) {
-        xq_dqn::PendingSlab p; p.src = d->slabs_l0; p.nslabs = d->l0_pending; p.stride = (long long)d->L[0] * d->L[1];
-        add(G + d->g_w0, p.stride, p);
-        d->l0_pending = 0;
-    }
-    for (int l = 1; l + 1 < d->nl; ++l) add(G + d->g_wh[l], (long long)d->L[l] * d->L[l + 1], d->pend_hidden[l]);
-    add(G + d->g_wout, 96LL * d->hlast(), d->pend_wout);
-    add(G + d->g_bout, 96, d->pend_bout);
-    add(G + d->g_bh[0], (long long)d->bo[d->nl - 1], d->pend_bh);
+    });
     if (k == 0) return XQ_OK;
     t.nseg = k; t.reduce_only = 1;
     return sgd_apply(d, t, 0.0);
@@ -2047,7 +2051,7 @@ int xq_dqn_exchange_calibration(const xq_dqn* d, int* calibrated, double* allred
 
 int xq_dqn_set_comm(xq_dqn* d, xq_comm* comm) {
     if (!d) return fail(XQ_ERR_INVALID_ARGUMENT, "null dqn");
-    if (d->l0_pending > 0 || d->pend_wout.nslabs > 0 || d->pend_bh.nslabs > 0)
+    if (td_step_pending(d))
         return fail(XQ_ERR_RUNTIME, "xq_dqn_set_comm: a TD step is waiting for its apply_grads");
     d->comm = comm;
     d->exch_calibrated = false;
@@ -2059,7 +2063,7 @@ int xq_dqn_set_comm(xq_dqn* d, xq_comm* comm) {
 }
 int xq_allreduce_grads(xq_dqn* d, xq_comm* comm) {
     if (!d || !comm) return fail(XQ_ERR_INVALID_ARGUMENT, "null handle");
-    if (d->l0_pending > 0 || d->pend_wout.nslabs > 0 || d->pend_bh.nslabs > 0)
+    if (td_step_pending(d))
         return fail(XQ_ERR_RUNTIME, "xq_allreduce_grads: gradient slabs are still unreduced (xq_dqn_set_fused_apply is on)");
     return comm_allreduce_on(comm, d->grads_td, d->n_grads_td, d->stream);      // in order on the handle's stream
 }
@@ -2069,28 +2073,12 @@ int xq_dqn_apply_grads(xq_dqn* d, double lr, double grad_scale) {
     SegTable t; memset(&t, 0, sizeof t);
     const float* G = d->grads_td;
     int k = 0;
-    auto take = [&](xq_dqn::PendingSlab& p) {
-        if (p.nslabs > 0) { t.src[k] = p.src; t.nslabs[k] = p.nslabs; t.stride[k] = p.stride; }
+    for_td_segments(d, [&](float* dst, uint16_t* dst_bf, size_t goff, long long len, xq_dqn::PendingSlab& p) {
+        t.dst[k] = dst; t.dst_bf[k] = dst_bf; t.src[k] = G + goff; t.len[k] = len; t.state_off[k] = (long long)goff;
+        if (p.nslabs > 0) { t.src[k] = p.src; t.nslabs[k] = p.nslabs; t.stride[k] = p.stride; }     // summed by the apply (or the norm) itself
         p = xq_dqn::PendingSlab();
-    };
-    const bool bf = d->bf16();
-    t.dst[k] = d->w0t(0); t.src[k] = G + d->g_w0; t.len[k] = (long long)d->L[0] * d->L[1]; t.state_off[k] = (long long)d->g_w0;
-    if (bf) t.dst_bf[k] = d->wl_bf(0, 0);
-    if (d->l0_pending > 0) { t.src[k] = d->slabs_l0; t.nslabs[k] = d->l0_pending; t.stride[k] = t.len[k]; d->l0_pending = 0; }
-    ++k;
-    for (int l = 1; l + 1 < d->nl; ++l) {
-        t.dst[k] = d->wl(0, l); t.src[k] = G + d->g_wh[l]; t.len[k] = (long long)d->L[l] * d->L[l + 1]; t.state_off[k] = (long long)d->g_wh[l];
-        if (bf) t.dst_bf[k] = d->wl_bf(0, l);
-        take(d->pend_hidden[l]);
         ++k;
-    }
-    t.dst[k] = d->wl(0, d->nl - 1); t.src[k] = G + d->g_wout; t.len[k] = 96LL * d->hlast(); t.state_off[k] = (long long)d->g_wout;
-    if (bf) t.dst_bf[k] = d->wl_bf(0, d->nl - 1);
-    take(d->pend_wout); ++k;
-    // hidden biases are contiguous in both layouts
-    t.dst[k] = d->bl(0, 0); t.src[k] = G + d->g_bh[0]; t.len[k] = (long long)(d->bo[d->nl - 1]); t.state_off[k] = (long long)d->g_bh[0];
-    take(d->pend_bh); ++k;
-    t.dst[k] = d->bl(0, d->nl - 1); t.src[k] = G + d->g_bout; t.len[k] = 96; t.state_off[k] = (long long)d->g_bout; take(d->pend_bout); ++k;
+    });
     t.nseg = k;
     d->sel_invalidate();                              // W0 / b0 change: the select chain's kept layer-0 sums are stale
     for (auto& K : d->sel_keep) { K.pays = K.calls >= 2; K.calls = 0; }
@@ -2102,7 +2090,6 @@ int xq_dqn_apply_grads(xq_dqn* d, double lr, double grad_scale) {
     return sgd_apply(d, t, lr * grad_scale, clip ? &C : nullptr);
 }
 
-static bool td_step_pending(const xq_dqn* d) { return d->l0_pending > 0 || d->pend_wout.nslabs > 0 || d->pend_bh.nslabs > 0; }
 // m = v = 0, t = 0 (queued on the handle's stream, behind any apply in flight)
 static int adam_zero_state(xq_dqn* d) {
     d->opt_t = 0;

@@ -561,33 +561,45 @@ __global__ __launch_bounds__(256) void td_tail_kernel(const TailArgs a) {
     }
 }
 
+// ---- ordered slab sums and the segment walk of the optimizers ------------------------------------------------------------------------
+// THE order in which partial-sum slabs are added, stated once: four chains z = j, j + 4, .. (leftover slabs continue chain 0), then
+// (s0 + s1) + (s2 + s3).  T = float or float4 (element-wise: a quad has the bits of its four elements summed one by one).  Everything
+// that promises "the bits of reduce_slabs_kernel" calls this; colsum_final_kernel above spells the same order across four lanes.
+__device__ __forceinline__ float vadd(const float a, const float b) { return a + b; }
+__device__ __forceinline__ float4 vadd(const float4 a, const float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
+__device__ __forceinline__ void vzero(float& a) { a = 0.f; }
+__device__ __forceinline__ void vzero(float4& a) { a = make_float4(0.f, 0.f, 0.f, 0.f); }
+template <typename T>
+__device__ __forceinline__ T slab_sum(const T* __restrict__ s, int nslabs, long long st, long long i) {   // st, i in units of T
+    T s0, s1, s2, s3;
+    vzero(s0); vzero(s1); vzero(s2); vzero(s3);
+    int z = 0;
+    for (; z + 3 < nslabs; z += 4) {
+        s0 = vadd(s0, s[(long long)z * st + i]);
+        s1 = vadd(s1, s[(long long)(z + 1) * st + i]);
+        s2 = vadd(s2, s[(long long)(z + 2) * st + i]);
+        s3 = vadd(s3, s[(long long)(z + 3) * st + i]);
+    }
+    for (; z < nslabs; ++z) s0 = vadd(s0, s[(long long)z * st + i]);
+    return vadd(vadd(s0, s1), vadd(s2, s3));
+}
 // out[i] = sum_z slabs[z*stride + i], z ascending (deterministic)
 __global__ void reduce_slabs_kernel(const float* __restrict__ slabs, int nslabs, long long stride, long long len, float* __restrict__ out) {
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < len; i += (long long)gridDim.x * blockDim.x) {
-        float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-        int z = 0;
-        for (; z + 3 < nslabs; z += 4) {
-            s0 += slabs[(long long)z * stride + i];
-            s1 += slabs[(long long)(z + 1) * stride + i];
-            s2 += slabs[(long long)(z + 2) * stride + i];
-            s3 += slabs[(long long)(z + 3) * stride + i];
-        }
-        for (; z < nslabs; ++z) s0 += slabs[(long long)z * stride + i];
-        out[i] = (s0 + s1) + (s2 + s3);
-    }
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < len; i += (long long)gridDim.x * blockDim.x)
+        out[i] = slab_sum(slabs, nslabs, stride, i);
 }
 
 struct SegTable {
     float* dst[16];
     const float* src[16];
     long long len[16];
-    int nslabs[16];            // > 0: src holds that many partial-sum slabs `stride` apart; they are summed here, in the order
-    long long stride[16];      //      of reduce_slabs_kernel (bit-identical to reducing first), instead of by a kernel of their own
+    int nslabs[16];            // > 0: src holds that many partial-sum slabs `stride` apart; they are summed here (slab_sum: bit-identical
+    long long stride[16];      //      to reducing first), instead of by a kernel of their own
     uint16_t* dst_bf[16];      // bf16 Q-net: shadow of dst, refreshed with the rounded new value (nullptr: none)
     int nseg;
     int reduce_only;           // dst = the slab sum itself (no step): the gradient buffer a reader or an all-reduce needs, in one launch
-    int vec4[16];              // set by sgd_apply / adam_apply: every pointer 16-byte aligned, len and stride multiples of 4 — four elements per thread
-    long long state_off[16];   // Adam: where the segment's m and v start in the two state buffers (gradient-buffer layout, layout_td_grads)
+    int vec4[16];              // set by seg_grid: every pointer 16-byte aligned, len and stride multiples of 4 — four elements per thread
+    long long state_off[16];   // where the segment starts in the gradient-buffer layout (layout_td_grads): Adam's m and v, the norm's sums
 };
 
 // Q head with the k range split over blocks (q_head) or folded into the last hidden product (EPI_HEAD): q[m][j] = tanh(b_j + the sum of
@@ -613,72 +625,84 @@ __global__ void f32_to_bf16_kernel(const float* __restrict__ src, uint16_t* __re
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
         dst[i] = bf16_bits(src[i]);
 }
-// SGD: dst -= alpha * src per segment (updateWeightsBiasesKernel dqn.cu:310-319, batched form)
-__device__ __forceinline__ float4 f4_add(const float4 a, const float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
-__global__ void sgd_segments_kernel(SegTable t, float alpha) {
+__device__ __forceinline__ void store_bf16(uint16_t* db, long long i, const float v) { db[i] = bf16_bits(v); }
+__device__ __forceinline__ uint32_t pack_bf16x2(const float lo, const float hi) { return (uint32_t)bf16_bits(lo) | ((uint32_t)bf16_bits(hi) << 16); }
+__device__ __forceinline__ void store_bf16(uint16_t* db, long long i, const float4 v) {
+    reinterpret_cast<uint2*>(db)[i] = make_uint2(pack_bf16x2(v.x, v.y), pack_bf16x2(v.z, v.w));
+}
+
+// One walk over a SegTable for every optimizer: grid (blocks, segments), block (x, y) strides over segment y.  Per element (T = float) or
+// per quad of consecutive elements (T = float4 where t.vec4 says so: 16-byte loads, a quarter of the instructions for the same bytes)
+//   g = the gradient-buffer entry, or slab_sum of the pending slabs;  reduce_only: dst = g, nothing else
+//   dst = step.elem(dst, g, m, v) — a quad is four calls of the same scalar update, so the bits do not depend on which loop ran —
+//   and the bf16 shadow, where there is one, gets the rounded new value.
+// A step object supplies elem() and kState; with kState it also carries the two state buffers m and v, walked at t.state_off.
+template <class Step>
+__device__ __forceinline__ float step_elems(const Step& S, const float w, const float g, float& m, float& v) { return S.elem(w, g, m, v); }
+template <class Step>
+__device__ __forceinline__ float4 step_elems(const Step& S, const float4 w, const float4 g, float4& m, float4& v) {
+    float4 o;
+    o.x = S.elem(w.x, g.x, m.x, v.x);
+    o.y = S.elem(w.y, g.y, m.y, v.y);
+    o.z = S.elem(w.z, g.z, m.z, v.z);
+    o.w = S.elem(w.w, g.w, m.w, v.w);
+    return o;
+}
+// GridX: this thread's first index along x and the stride of the grid, taken in the __global__ function itself (blockDim read inside an
+// inlined device function compiles to a dependent load in the prologue; read in the kernel it is a kernel argument).  The loop: len and
+// st in units of T; "slabs or buffer" is asked inside it, the shape that measured fastest (profiles/NOTES.md, "One segment walk").
+struct GridX {
+    long long first, stride;
+};
+#define XQ_GRID_X GridX{(long long)blockIdx.x * blockDim.x + threadIdx.x, (long long)gridDim.x * blockDim.x}
+template <typename T, bool SLABS, class Step>
+__device__ __forceinline__ void segment_loop(const GridX x, const Step& S, float* d_, const float* s_, long long len, int nslabs, long long st,
+                                             uint16_t* db, float* m_, float* v_, bool reduce_only) {
+    T* d = reinterpret_cast<T*>(d_);
+    const T* s = reinterpret_cast<const T*>(s_);
+    T* ms = reinterpret_cast<T*>(m_);
+    T* vs = reinterpret_cast<T*>(v_);
+    for (long long i = x.first; i < len; i += x.stride) {
+        T g;
+        if (SLABS && nslabs > 0) {
+            g = slab_sum(s, nslabs, st, i);
+            if (reduce_only) { d[i] = g; continue; }
+        } else g = s[i];
+        const T w = d[i];
+        T m, v;
+        if (Step::kState) { m = ms[i]; v = vs[i]; }
+        else { vzero(m); vzero(v); }
+        const T o = step_elems(S, w, g, m, v);
+        if (Step::kState) { ms[i] = m; vs[i] = v; }
+        d[i] = o;
+        if (db) store_bf16(db, i, o);
+    }
+}
+// SLABS = false: the table is known to read the gradient buffer only (behind grad_norm_kernel) and the slab sums are not compiled.
+template <bool SLABS, class Step>
+__device__ __forceinline__ void segment_walk(const GridX x, const SegTable& t, const Step& S, float* m = nullptr, float* v = nullptr) {
     const int sgm = (int)blockIdx.y;
     if (sgm >= t.nseg) return;
     float* d = t.dst[sgm];
     const float* s = t.src[sgm];
-    const int nslabs = t.nslabs[sgm];
-    const long long len = t.len[sgm], st = t.stride[sgm];
+    const long long len = t.len[sgm];
     uint16_t* db = t.dst_bf[sgm];
-    if (t.vec4[sgm]) {
-        // four consecutive elements per thread (16-byte loads: a quarter of the instructions for the same bytes); per element the same
-        // chains and the same order as the scalar loop below, so the bits do not depend on which loop ran
-        const long long n4 = len >> 2, st4 = st >> 2;
-        const float4* s4 = reinterpret_cast<const float4*>(s);
-        float4* d4 = reinterpret_cast<float4*>(d);
-        for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long long)gridDim.x * blockDim.x) {
-            float4 g;
-            if (nslabs <= 0) g = s4[i];
-            else {
-                float4 s0 = make_float4(0.f, 0.f, 0.f, 0.f), s1 = s0, s2 = s0, s3 = s0;
-                int z = 0;
-                for (; z + 3 < nslabs; z += 4) {
-                    s0 = f4_add(s0, s4[(long long)z * st4 + i]);
-                    s1 = f4_add(s1, s4[(long long)(z + 1) * st4 + i]);
-                    s2 = f4_add(s2, s4[(long long)(z + 2) * st4 + i]);
-                    s3 = f4_add(s3, s4[(long long)(z + 3) * st4 + i]);
-                }
-                for (; z < nslabs; ++z) s0 = f4_add(s0, s4[(long long)z * st4 + i]);
-                g = f4_add(f4_add(s0, s1), f4_add(s2, s3));
-                if (t.reduce_only) { d4[i] = g; continue; }
-            }
-            const float4 w = d4[i];
-            const float4 v = make_float4(w.x - alpha * g.x, w.y - alpha * g.y, w.z - alpha * g.z, w.w - alpha * g.w);
-            d4[i] = v;
-            if (db) reinterpret_cast<uint2*>(db)[i] = make_uint2((uint32_t)bf16_bits(v.x) | ((uint32_t)bf16_bits(v.y) << 16),
-                                                                 (uint32_t)bf16_bits(v.z) | ((uint32_t)bf16_bits(v.w) << 16));
-        }
-        return;
-    }
-    if (nslabs <= 0) {
-        for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < len; i += (long long)gridDim.x * blockDim.x) {
-            const float v = d[i] - alpha * s[i];
-            d[i] = v;
-            if (db) db[i] = bf16_bits(v);
-        }
-        return;
-    }
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < len; i += (long long)gridDim.x * blockDim.x) {
-        float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-        int z = 0;
-        for (; z + 3 < nslabs; z += 4) {
-            s0 += s[(long long)z * st + i];
-            s1 += s[(long long)(z + 1) * st + i];
-            s2 += s[(long long)(z + 2) * st + i];
-            s3 += s[(long long)(z + 3) * st + i];
-        }
-        for (; z < nslabs; ++z) s0 += s[(long long)z * st + i];
-        if (t.reduce_only) { d[i] = (s0 + s1) + (s2 + s3); continue; }
-        const float v = d[i] - alpha * ((s0 + s1) + (s2 + s3));
-        d[i] = v;
-        if (db) db[i] = bf16_bits(v);
-    }
+    if (Step::kState) { m += t.state_off[sgm]; v += t.state_off[sgm]; }
+    const int nslabs = SLABS ? t.nslabs[sgm] : 0;
+    const long long st = SLABS ? t.stride[sgm] : 0;
+    if (t.vec4[sgm]) segment_loop<float4, SLABS>(x, S, d, s, len >> 2, nslabs, st >> 2, db, m, v, t.reduce_only != 0);
+    else segment_loop<float, SLABS>(x, S, d, s, len, nslabs, st, db, m, v, t.reduce_only != 0);
 }
 
-// Adam (torch.optim.Adam's formula, amsgrad off, no weight decay; DESIGN.md section 4 "Optimizer") over the same segment walk:
+// SGD: dst -= alpha * src per segment (updateWeightsBiasesKernel dqn.cu:310-319, batched form); the compiler's default contraction
+struct SgdStep {
+    static constexpr bool kState = false;
+    float alpha;
+    __device__ __forceinline__ float elem(const float w, const float g, float&, float&) const { return w - alpha * g; }
+};
+__global__ void sgd_segments_kernel(SegTable t, float alpha) { segment_walk<true>(XQ_GRID_X, t, SgdStep{alpha}); }
+
+// Adam (torch.optim.Adam's formula, amsgrad off, no weight decay; DESIGN.md section 4 "Optimizer"):
 //   g' = gs g;  m = b1 m + (1 - b1) g';  v = b2 v + (1 - b2) g'^2;  p -= a m / (sqrt(v) rbc2 + eps)
 // a = lr / (1 - b1^t) and rbc2 = 1 / sqrt(1 - b2^t) are computed on the host in double.  m and v live in two fp32 buffers laid out like
 // the compact gradient buffer; a parameter that never receives a gradient keeps m = v = 0 and its step is exactly 0.
@@ -687,7 +711,7 @@ struct AdamArgs {
     float b1, omb1, b2, omb2, eps, a, rbc2, gs;
 };
 // One element: every product, sum, square root and quotient written out and rounded once, in this order, with no contraction left to
-// the compiler — the vec4 and the scalar loop both come through here, so the bits do not depend on which loop ran.
+// the compiler.
 __device__ __forceinline__ float adam_elem(const AdamArgs& A, float p, float g, float& m, float& v) {
 #pragma clang fp contract(off)
     const float gp = A.gs * g;
@@ -699,79 +723,22 @@ __device__ __forceinline__ float adam_elem(const AdamArgs& A, float p, float g, 
     const float q = m / den;
     return __builtin_fmaf(-A.a, q, p);
 }
-__global__ void adam_segments_kernel(SegTable t, AdamArgs A) {
-    const int sgm = (int)blockIdx.y;
-    if (sgm >= t.nseg) return;
-    float* d = t.dst[sgm];
-    const float* s = t.src[sgm];
-    const int nslabs = t.nslabs[sgm];
-    const long long len = t.len[sgm], st = t.stride[sgm];
-    uint16_t* db = t.dst_bf[sgm];
-    float* ms = A.m + t.state_off[sgm];
-    float* vs = A.v + t.state_off[sgm];
-    if (t.vec4[sgm]) {
-        const long long n4 = len >> 2, st4 = st >> 2;
-        const float4* s4 = reinterpret_cast<const float4*>(s);
-        float4* d4 = reinterpret_cast<float4*>(d);
-        float4* m4 = reinterpret_cast<float4*>(ms);
-        float4* v4 = reinterpret_cast<float4*>(vs);
-        for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long long)gridDim.x * blockDim.x) {
-            float4 g;
-            if (nslabs <= 0) g = s4[i];
-            else {          // the slabs, in the order of reduce_slabs_kernel: g has the bits the reduce-first path would have read
-                float4 s0 = make_float4(0.f, 0.f, 0.f, 0.f), s1 = s0, s2 = s0, s3 = s0;
-                int z = 0;
-                for (; z + 3 < nslabs; z += 4) {
-                    s0 = f4_add(s0, s4[(long long)z * st4 + i]);
-                    s1 = f4_add(s1, s4[(long long)(z + 1) * st4 + i]);
-                    s2 = f4_add(s2, s4[(long long)(z + 2) * st4 + i]);
-                    s3 = f4_add(s3, s4[(long long)(z + 3) * st4 + i]);
-                }
-                for (; z < nslabs; ++z) s0 = f4_add(s0, s4[(long long)z * st4 + i]);
-                g = f4_add(f4_add(s0, s1), f4_add(s2, s3));
-            }
-            const float4 w = d4[i];
-            float4 m = m4[i], v = v4[i], o;
-            o.x = adam_elem(A, w.x, g.x, m.x, v.x);
-            o.y = adam_elem(A, w.y, g.y, m.y, v.y);
-            o.z = adam_elem(A, w.z, g.z, m.z, v.z);
-            o.w = adam_elem(A, w.w, g.w, m.w, v.w);
-            m4[i] = m; v4[i] = v; d4[i] = o;
-            if (db) reinterpret_cast<uint2*>(db)[i] = make_uint2((uint32_t)bf16_bits(o.x) | ((uint32_t)bf16_bits(o.y) << 16),
-                                                                 (uint32_t)bf16_bits(o.z) | ((uint32_t)bf16_bits(o.w) << 16));
-        }
-        return;
-    }
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < len; i += (long long)gridDim.x * blockDim.x) {
-        float g;
-        if (nslabs <= 0) g = s[i];
-        else {
-            float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-            int z = 0;
-            for (; z + 3 < nslabs; z += 4) {
-                s0 += s[(long long)z * st + i];
-                s1 += s[(long long)(z + 1) * st + i];
-                s2 += s[(long long)(z + 2) * st + i];
-                s3 += s[(long long)(z + 3) * st + i];
-            }
-            for (; z < nslabs; ++z) s0 += s[(long long)z * st + i];
-            g = (s0 + s1) + (s2 + s3);
-        }
-        float m = ms[i], v = vs[i];
-        const float o = adam_elem(A, d[i], g, m, v);
-        ms[i] = m; vs[i] = v; d[i] = o;
-        if (db) db[i] = bf16_bits(o);
-    }
-}
+struct AdamStep {
+    static constexpr bool kState = true;
+    AdamArgs A;
+    __device__ __forceinline__ float elem(const float w, const float g, float& m, float& v) const { return adam_elem(A, w, g, m, v); }
+};
+__global__ void adam_segments_kernel(SegTable t, AdamArgs A) { segment_walk<true>(XQ_GRID_X, t, AdamStep{A}, A.m, A.v); }
 
 // ---- gradient clipping by the global L2 norm (DESIGN.md section 4 "Gradient clipping") ---------------------------------------------
 //   S = sum_i (double)g_i^2;  norm = |grad_scale| sqrt(S);  c = (float)min(1, max_norm / (norm + 1e-6))
 // grad_norm_kernel walks the segment table of the apply in front of it: grid (kNormBlocks, segments), both fixed by the net alone.
 // Element i of a segment belongs to quad i / 4, quad q to thread q mod (kNormBlocks * 256) of the segment's blocks; a thread adds the
 // squares of its quads in ascending order, x y z w inside a quad, every square and every sum in fp64 with contraction off.  The 16-byte
-// loop and the scalar loop differ in how a quad is loaded and in nothing else, and a slab sum has the bits reduce_slabs_kernel would
-// have written, so the partial of a block does not depend on where the gradient came from.  Block tree: __shfl_down by 32, 16, .. 1 in
-// each wave, then ((w0 + w1) + w2) + w3.  One fp64 partial per block, at [segment * kNormBlocks + block].
+// loop and the scalar loop differ in how a quad is loaded and in nothing else, and both take pending slabs through slab_sum, so the
+// partial of a block does not depend on where the gradient came from.  Block tree: __shfl_down by 32, 16, .. 1 in each wave, then
+// ((w0 + w1) + w2) + w3.  One fp64 partial per block, at [segment * kNormBlocks + block].  This indexing is the kernel's own, which is
+// why it does not go through segment_walk.
 // Where a segment has pending slabs their sum is written to the gradient buffer (t.dst here), which the apply kernel then reads.
 constexpr int kNormBlocks = 64;
 constexpr int kNormMaxPartials = 16 * kNormBlocks;
@@ -791,18 +758,6 @@ __device__ __forceinline__ double sq_add(double acc, float g) {
     const double x2 = x * x;
     return acc + x2;
 }
-__device__ __forceinline__ float slab_sum(const float* __restrict__ s, int nslabs, long long st, long long i) {
-    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-    int z = 0;
-    for (; z + 3 < nslabs; z += 4) {
-        s0 += s[(long long)z * st + i];
-        s1 += s[(long long)(z + 1) * st + i];
-        s2 += s[(long long)(z + 2) * st + i];
-        s3 += s[(long long)(z + 3) * st + i];
-    }
-    for (; z < nslabs; ++z) s0 += s[(long long)z * st + i];
-    return (s0 + s1) + (s2 + s3);
-}
 __global__ __launch_bounds__(256) void grad_norm_kernel(SegTable t, double* __restrict__ partials) {
     const int sgm = (int)blockIdx.y;
     if (sgm >= t.nseg) return;
@@ -814,25 +769,12 @@ __global__ __launch_bounds__(256) void grad_norm_kernel(SegTable t, double* __re
     const long long step = (long long)kNormBlocks * 256;
     double acc = 0.0;
     if (t.vec4[sgm]) {
-        const long long st4 = st >> 2;
         const float4* s4 = reinterpret_cast<const float4*>(s);
         float4* o4 = reinterpret_cast<float4*>(out);
         for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < nq; q += step) {
             float4 g;
             if (nslabs <= 0) g = s4[q];
-            else {
-                float4 s0 = make_float4(0.f, 0.f, 0.f, 0.f), s1 = s0, s2 = s0, s3 = s0;
-                int z = 0;
-                for (; z + 3 < nslabs; z += 4) {
-                    s0 = f4_add(s0, s4[(long long)z * st4 + q]);
-                    s1 = f4_add(s1, s4[(long long)(z + 1) * st4 + q]);
-                    s2 = f4_add(s2, s4[(long long)(z + 2) * st4 + q]);
-                    s3 = f4_add(s3, s4[(long long)(z + 3) * st4 + q]);
-                }
-                for (; z < nslabs; ++z) s0 = f4_add(s0, s4[(long long)z * st4 + q]);
-                g = f4_add(f4_add(s0, s1), f4_add(s2, s3));
-                o4[q] = g;
-            }
+            else { g = slab_sum(s4, nslabs, st >> 2, q); o4[q] = g; }
             acc = sq_add(sq_add(sq_add(sq_add(acc, g.x), g.y), g.z), g.w);
         }
     } else {
@@ -881,72 +823,15 @@ __device__ __forceinline__ float clip_mul(float a, float c) {
     return a * c;
 }
 // SGD: p -= fl32(fl32(lr grad_scale) c) g;  Adam: g' = fl32(fl32(grad_scale) c) g.  c == 1: the products are exact, the bits those of the
-// unclipped kernels.  The table has no pending slabs left (grad_norm_kernel summed them into the gradient buffer), so these two are the
-// direct-gradient loops of sgd_segments_kernel / adam_segments_kernel, element for element the same expressions.
+// unclipped kernels.  The same walk and the same steps with the scaled factor; the table has no pending slabs left (grad_norm_kernel
+// summed them into the gradient buffer), so the slab loops are compiled out.
 __global__ void sgd_segments_clip_kernel(SegTable t, float alpha0, ClipArgs C) {
     const float alpha = clip_mul(alpha0, clip_coef(C, blockIdx.x == 0 && blockIdx.y == 0));
-    const int sgm = (int)blockIdx.y;
-    if (sgm >= t.nseg) return;
-    float* d = t.dst[sgm];
-    const float* s = t.src[sgm];
-    const long long len = t.len[sgm];
-    uint16_t* db = t.dst_bf[sgm];
-    if (t.vec4[sgm]) {
-        const long long n4 = len >> 2;
-        const float4* s4 = reinterpret_cast<const float4*>(s);
-        float4* d4 = reinterpret_cast<float4*>(d);
-        for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long long)gridDim.x * blockDim.x) {
-            const float4 g = s4[i];
-            const float4 w = d4[i];
-            const float4 v = make_float4(w.x - alpha * g.x, w.y - alpha * g.y, w.z - alpha * g.z, w.w - alpha * g.w);
-            d4[i] = v;
-            if (db) reinterpret_cast<uint2*>(db)[i] = make_uint2((uint32_t)bf16_bits(v.x) | ((uint32_t)bf16_bits(v.y) << 16),
-                                                                 (uint32_t)bf16_bits(v.z) | ((uint32_t)bf16_bits(v.w) << 16));
-        }
-        return;
-    }
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < len; i += (long long)gridDim.x * blockDim.x) {
-        const float v = d[i] - alpha * s[i];
-        d[i] = v;
-        if (db) db[i] = bf16_bits(v);
-    }
+    segment_walk<false>(XQ_GRID_X, t, SgdStep{alpha});
 }
 __global__ void adam_segments_clip_kernel(SegTable t, AdamArgs A, ClipArgs C) {
     A.gs = clip_mul(A.gs, clip_coef(C, blockIdx.x == 0 && blockIdx.y == 0));
-    const int sgm = (int)blockIdx.y;
-    if (sgm >= t.nseg) return;
-    float* d = t.dst[sgm];
-    const float* s = t.src[sgm];
-    const long long len = t.len[sgm];
-    uint16_t* db = t.dst_bf[sgm];
-    float* ms = A.m + t.state_off[sgm];
-    float* vs = A.v + t.state_off[sgm];
-    if (t.vec4[sgm]) {
-        const long long n4 = len >> 2;
-        const float4* s4 = reinterpret_cast<const float4*>(s);
-        float4* d4 = reinterpret_cast<float4*>(d);
-        float4* m4 = reinterpret_cast<float4*>(ms);
-        float4* v4 = reinterpret_cast<float4*>(vs);
-        for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long long)gridDim.x * blockDim.x) {
-            const float4 g = s4[i];
-            const float4 w = d4[i];
-            float4 m = m4[i], v = v4[i], o;
-            o.x = adam_elem(A, w.x, g.x, m.x, v.x);
-            o.y = adam_elem(A, w.y, g.y, m.y, v.y);
-            o.z = adam_elem(A, w.z, g.z, m.z, v.z);
-            o.w = adam_elem(A, w.w, g.w, m.w, v.w);
-            m4[i] = m; v4[i] = v; d4[i] = o;
-            if (db) reinterpret_cast<uint2*>(db)[i] = make_uint2((uint32_t)bf16_bits(o.x) | ((uint32_t)bf16_bits(o.y) << 16),
-                                                                 (uint32_t)bf16_bits(o.z) | ((uint32_t)bf16_bits(o.w) << 16));
-        }
-        return;
-    }
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < len; i += (long long)gridDim.x * blockDim.x) {
-        float m = ms[i], v = vs[i];
-        const float o = adam_elem(A, d[i], s[i], m, v);
-        ms[i] = m; vs[i] = v; d[i] = o;
-        if (db) db[i] = bf16_bits(o);
-    }
+    segment_walk<false>(XQ_GRID_X, t, AdamStep{A}, A.m, A.v);
 }
 
 }  // namespace xq

@@ -261,6 +261,62 @@ def test_slab_path_has_the_bits_of_the_buffer_path(xq, sizes, opt):
     assert abs(cr.norm(g1, 1.0 / n) - seq1[-1]["last_norm"]) <= k * 2.0 ** -52 * seq1[-1]["last_norm"]
 
 
+SCALAR_TD_NET = [1260, 127, 129, 132, 8100]
+
+
+@pytest.mark.parametrize("max_norm", [0.0, 1e-3], ids=["unclipped", "clipped"])
+@pytest.mark.parametrize("opt", ["sgd", "adam"])
+def test_scalar_slab_loops_have_the_bits_of_the_buffer_path(xq, opt, max_norm):
+    """No other fused-against-reduce-first test takes the scalar slab loops of the SGD, Adam and norm kernels: their nets have 16-byte
+    aligned segments throughout.  1260-127-129-132-8100: the first hidden segment has 16383 elements and every segment behind it starts
+    at an odd offset of the gradient buffer (176403, 193431, 206103, 206199), so all of them go through the scalar loops while layer 0
+    takes the 16-byte loop.  (1260-127-129-8100, MISALIGNED_NET, has the same offsets but cannot take a TD step: the output-gradient
+    kernel wants a last hidden width that is a multiple of 4, and with two hidden layers such a width puts every offset back on a
+    multiple of 4.  Hence a third hidden layer, and the textbook backward rule, since the reference's is undefined where a layer
+    widens.)  n = 1300: layer 0 in 2 slabs (the leftover loop alone), the output rows in 6 (one group of four, two leftovers), the bias
+    column sums in 20 (five groups of four).  Two TD steps with xq_dqn_set_fused_apply(1) and with 0: parameters (Adam: m and v)
+    bit-identical; clipping: norm, coefficient and the whole gradient buffer too.  The fused leg launched no reduce_slabs bracket and
+    the other one did, so the slabs really were pending."""
+    import torch
+    from cn_chess_ai_amd import dist as xd
+    sizes = SCALAR_TD_NET
+    lay = ar.layout(sizes)
+    assert (lay["wh"][1], lay["wh"][2], lay["wout"], lay["bout"], lay["bh"]) == (160020, 176403, 193431, 206103, 206199)
+    assert sizes[1] * sizes[2] == 16383
+    n = 1300
+    S = batch(xq, n, 83)
+    got = []
+    for fused in (1, 0):
+        d, _, _ = make_net(xq, sizes, seed=5)
+        d.set_optimizer(opt)
+        d.set_fused_apply(fused)
+        d.set_grad_clip(max_norm)
+        w_init = d.get_params()[0]
+        rp = ring(xq, S)
+        d.kernel_stats(2)
+        seq = []
+        for _ in range(2):
+            rp.sample(n)
+            d.td_grads_replay(rp, n, td_net=0, mode=1)
+            d.apply_grads(1e-2, 1.0 / n)
+            seq.append(d.grad_clip_stats() if max_norm else None)
+        launches = {s["name"]: s["launches"] for s in d.kernel_stats(0)}
+        ptr, k = d.grad_buffer()
+        torch.cuda.synchronize()
+        buf = xd.wrap_device_floats(ptr, k).cpu().numpy().copy()
+        got.append((seq, snapshot(d, opt == "adam"), buf, launches))
+        rp.close(); d.close()
+    (seq1, p1, g1, l1), (seq0, p0, g0, l0) = got
+    print("scalar slab loops", opt, max_norm, seq1, {k: v for k, v in l0.items() if k not in l1 or l1[k] != v})
+    assert "reduce_slabs" not in l1 and l0["reduce_slabs"] >= 2
+    assert same(p1, p0)
+    assert not np.array_equal(p1[0], w_init)
+    if max_norm:
+        assert seq1 == seq0 and seq1[-1]["applies"] == 2
+        assert all(s["last_coef"] < 1.0 for s in seq1)
+        assert np.array_equal(bits(g1), bits(g0))
+
+
 # ---- 4. against fp64 end to end ---------------------------------------------------------------------------------------------------
 def test_td_step_against_fp64_end_to_end(xq):
     """One TD step of 1024 self-play samples on 1260-256-256-8100 with clipping at half the reference's norm.  Gradient reference:
