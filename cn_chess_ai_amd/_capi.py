@@ -180,6 +180,9 @@ PROTOTYPES = {
     "xq_dqn_set_grad_clip": [_vp, _d],
     "xq_dqn_get_grad_clip": [_vp, _pd],
     "xq_dqn_grad_clip_stats": [_vp, _pd, _pd, _pu64, _pu64],
+    "xq_dqn_set_target_tau": [_vp, _d],
+    "xq_dqn_get_target_tau": [_vp, _pd],
+    "xq_dqn_soft_update_target": [_vp, _d],
     "xq_dqn_kernel_filter": [_vp, C.c_char_p],
     "xq_dqn_kernel_timeline": [_vp, C.POINTER(KernelSpan), _i, _pi],
     "xq_comm_unique_id": [_pu8],
@@ -199,6 +202,7 @@ PROTOTYPES = {
     "xq_trainer_replay": [_vp, _pvp],
     "xq_trainer_random_plies": [_vp, _i],
     "xq_trainer_set_td_net": [_vp, _i],
+    "xq_trainer_set_target_tau": [_vp, _d],
     "xq_trainer_set_opponent": [_vp, C.POINTER(ArenaPlayer)],
     "xq_trainer_versus_results": [_vp, _pu64],
     "xq_trainer_collect": [_vp],
@@ -224,7 +228,9 @@ LAZY = frozenset(("xq_dqn_set_optimizer", "xq_dqn_get_optimizer", "xq_dqn_reset_
 # Gradient clipping's entry points are lazy in the same way.  They stand in a set of their own only because tests/test_adam_ref_cpu.py
 # pins LAZY to exactly the optimizer's five names; load() and call() look at the union.
 LAZY_GRAD_CLIP = frozenset(("xq_dqn_set_grad_clip", "xq_dqn_get_grad_clip", "xq_dqn_grad_clip_stats"))
-_LAZY_ALL = LAZY | LAZY_GRAD_CLIP
+# ... and the soft target update's
+LAZY_TARGET_TAU = frozenset(("xq_dqn_set_target_tau", "xq_dqn_get_target_tau", "xq_dqn_soft_update_target", "xq_trainer_set_target_tau"))
+_LAZY_ALL = LAZY | LAZY_GRAD_CLIP | LAZY_TARGET_TAU
 _RESTYPES = {"xq_last_error": C.c_char_p, "xq_env_boards_dev": C.c_void_p, "xq_env_meta_dev": C.c_void_p}
 
 _lib = None

@@ -136,6 +136,13 @@ struct xq_dqn {
     double clip_max_norm = 0.0;
     xq::DevBuf<double> clip_partials;
     xq::DevBuf<xq::ClipRecord> clip_rec;
+    // soft target update of xq_dqn_apply_grads (xq_dqn_set_target_tau): 0 = off, (0, 1) = theta- += tau (theta - theta-) in the apply
+    // kernel, 1 = the hard copy behind every apply.  tgt_rest_synced: the target's parameters OUTSIDE the TD segments have the online
+    // net's bits (a fixed point of the rule), so the apply kernel's walk over the TD segments is the whole update; true behind
+    // xq_dqn_update_target (hence xq_dqn_create), false behind whatever can make the two nets differ there (xq_dqn_set_params of either
+    // net, hence xq_dqn_load_model, and xq_dqn_backpropagate) — then one whole-buffer kernel follows the apply instead
+    double target_tau = 0.0;
+    bool tgt_rest_synced = false;
     xq::DevBuf<float> slabs;
     xq::DevBuf<float> slabs_l0;                 // layer-0 gradient partials
     // layer-0 gradient on the bf16 matrix pipe (xq_l0grad.hip.h): delta_0 as three bf16 planes, transposed [plane][column][sample]
@@ -981,10 +988,12 @@ static int l0_gradient(xq_dqn* d, int n, float* dst) {
 // Which segments go four elements to a thread (t.vec4: every pointer 16-byte aligned — the bf16 shadow, where there is one, is stored in
 // 8-byte pieces — len and slab stride multiples of 4; `state`: so is the offset into Adam's m and v), and the x size of a grid
 // (blocks, segments) of 256 threads that covers the longest segment, capped at 1024.
-static unsigned seg_grid(SegTable& t, bool state) {
+// soft: the target net's pointers of a SOFT kernel and their shadows count like dst and dst_bf.
+static unsigned seg_grid(SegTable& t, bool state, const SoftArgs* soft = nullptr) {
     long long mx = 0;
     for (int i = 0; i < t.nseg; ++i) {
-        const uintptr_t bits = (uintptr_t)t.dst[i] | (uintptr_t)t.src[i] | ((uintptr_t)t.dst_bf[i] << 1);
+        uintptr_t bits = (uintptr_t)t.dst[i] | (uintptr_t)t.src[i] | ((uintptr_t)t.dst_bf[i] << 1);
+        if (soft) bits |= (uintptr_t)soft->tgt[i] | ((uintptr_t)soft->tgt_bf[i] << 1);
         t.vec4[i] = (bits & 15) == 0 && (t.len[i] & 3) == 0 && (t.nslabs[i] <= 0 || (t.stride[i] & 3) == 0) &&
                     (!state || (t.state_off[i] & 3) == 0);
         mx = std::max(mx, t.vec4[i] ? t.len[i] / 4 : t.len[i]);
@@ -992,10 +1001,13 @@ static unsigned seg_grid(SegTable& t, bool state) {
     return (unsigned)std::max<long long>(1, std::min<long long>((mx + 255) / 256, 1024));
 }
 
-static int sgd_apply(xq_dqn* d, SegTable t, double alpha, const ClipArgs* clip = nullptr) {
-    const unsigned bx = seg_grid(t, false);
+// soft (never with reduce_only): the SOFT form of the same kernel, which moves the target net's segments in the same walk.
+static int sgd_apply(xq_dqn* d, SegTable t, double alpha, const ClipArgs* clip = nullptr, const SoftArgs* soft = nullptr) {
+    const unsigned bx = seg_grid(t, false, soft);
     ProfScope ps(d, t.reduce_only ? "reduce_slabs" : "sgd_apply", 0, 0, true);
-    if (clip) hipExtLaunchKernelGGL(sgd_segments_clip_kernel, dim3(bx, t.nseg), dim3(256), 0, d->cur, ps.start(), ps.stop(), 0, t, (float)alpha, *clip);
+    if (soft && clip) hipExtLaunchKernelGGL(sgd_segments_clip_soft_kernel, dim3(bx, t.nseg), dim3(256), 0, d->cur, ps.start(), ps.stop(), 0, t, (float)alpha, *clip, *soft);
+    else if (soft) hipExtLaunchKernelGGL(sgd_segments_soft_kernel, dim3(bx, t.nseg), dim3(256), 0, d->cur, ps.start(), ps.stop(), 0, t, (float)alpha, *soft);
+    else if (clip) hipExtLaunchKernelGGL(sgd_segments_clip_kernel, dim3(bx, t.nseg), dim3(256), 0, d->cur, ps.start(), ps.stop(), 0, t, (float)alpha, *clip);
     else
     hipExtLaunchKernelGGL(sgd_segments_kernel, dim3(bx, t.nseg), dim3(256), 0, d->cur, ps.start(), ps.stop(), 0, t, (float)alpha);
     XQ_HIP(hipGetLastError());
@@ -1004,8 +1016,8 @@ static int sgd_apply(xq_dqn* d, SegTable t, double alpha, const ClipArgs* clip =
 
 // The same table through adam_segments_kernel: step t of Adam with the handle's betas and eps.  The bias corrections are taken on the
 // host in double and handed over as floats.
-static int adam_apply(xq_dqn* d, SegTable t, double lr, double grad_scale, const ClipArgs* clip = nullptr) {
-    const unsigned bx = seg_grid(t, true);
+static int adam_apply(xq_dqn* d, SegTable t, double lr, double grad_scale, const ClipArgs* clip = nullptr, const SoftArgs* soft = nullptr) {
+    const unsigned bx = seg_grid(t, true, soft);
     d->opt_t += 1;
     const double tt = (double)d->opt_t;
     AdamArgs A;
@@ -1017,7 +1029,9 @@ static int adam_apply(xq_dqn* d, SegTable t, double lr, double grad_scale, const
     A.rbc2 = (float)(1.0 / std::sqrt(1.0 - std::pow(d->opt_b2, tt)));
     A.gs = (float)grad_scale;
     ProfScope ps(d, "adam_apply", 0, 0, true);
-    if (clip) hipExtLaunchKernelGGL(adam_segments_clip_kernel, dim3(bx, t.nseg), dim3(256), 0, d->cur, ps.start(), ps.stop(), 0, t, A, *clip);
+    if (soft && clip) hipExtLaunchKernelGGL(adam_segments_clip_soft_kernel, dim3(bx, t.nseg), dim3(256), 0, d->cur, ps.start(), ps.stop(), 0, t, A, *clip, *soft);
+    else if (soft) hipExtLaunchKernelGGL(adam_segments_soft_kernel, dim3(bx, t.nseg), dim3(256), 0, d->cur, ps.start(), ps.stop(), 0, t, A, *soft);
+    else if (clip) hipExtLaunchKernelGGL(adam_segments_clip_kernel, dim3(bx, t.nseg), dim3(256), 0, d->cur, ps.start(), ps.stop(), 0, t, A, *clip);
     else
     hipExtLaunchKernelGGL(adam_segments_kernel, dim3(bx, t.nseg), dim3(256), 0, d->cur, ps.start(), ps.stop(), 0, t, A);
     XQ_HIP(hipGetLastError());
@@ -1077,6 +1091,37 @@ static void for_td_segments(xq_dqn* d, F f) {
     f(d->wl(0, top), bf ? d->wl_bf(0, top) : nullptr, d->g_wout, 96LL * d->hlast(), d->pend_wout);
     f(d->bl(0, 0), (uint16_t*)nullptr, d->g_bh[0], (long long)d->bo[top], d->pend_bh);
     f(d->bl(0, top), (uint16_t*)nullptr, d->g_bout, 96LL, d->pend_bout);
+}
+// The same segments of the target net, in the same order: what a SOFT apply kernel walks beside the table built from for_td_segments.
+static void soft_td_segments(const xq_dqn* d, SoftArgs* Z) {
+    const bool bf = d->bf16();
+    const int top = d->nl - 1;
+    int k = 0;
+    auto add = [&](float* t, uint16_t* tb) { Z->tgt[k] = t; Z->tgt_bf[k] = tb; ++k; };
+    add(d->w0t(1), bf ? d->wl_bf(1, 0) : nullptr);
+    for (int l = 1; l < top; ++l) add(d->wl(1, l), bf ? d->wl_bf(1, l) : nullptr);
+    add(d->wl(1, top), bf ? d->wl_bf(1, top) : nullptr);
+    add(d->bl(1, 0), nullptr);
+    add(d->bl(1, top), nullptr);
+}
+// One soft update of the whole target net from the online buffer (soft_target_kernel), on the handle's stream: every parameter and the
+// shadow of every weight.  Any row of the target's output layer may change, so a screening shadow that holds the target's rows >= 96 is
+// no longer valid (as behind xq_dqn_update_target).  Where the two nets agree nothing moves: tgt_rest_synced stays what it was.
+static int soft_target_whole(xq_dqn* d, double tau) {
+    const long long n = (long long)(d->nw + d->nb);
+    const float* p = d->params[0];
+    float* t = d->params[1];
+    uint16_t* tb = d->bf16() ? d->params_bf[1].p : nullptr;
+    const int vec = ((((uintptr_t)p | (uintptr_t)t) & 15) == 0 && ((uintptr_t)tb & 7) == 0) ? 1 : 0;
+    const long long items = vec ? (n >> 2) + 3 : n;
+    const unsigned blocks = (unsigned)std::max<long long>(1, std::min<long long>((items + 255) / 256, 2048));
+    d->params_version += 1;
+    if (d->scr_static_net == XQ_NET_TARGET) d->scr_static_net = -1;
+    ProfScope ps(d, "soft_target", 2.0 * n, 12.0 * n + (tb ? 2.0 * d->nw : 0.0), true);
+    hipExtLaunchKernelGGL(soft_target_kernel, dim3(blocks), dim3(256), 0, d->cur, ps.start(), ps.stop(), 0, p, t, tb, n, (long long)d->nw,
+                          (float)tau, vec);
+    XQ_HIP(hipGetLastError());
+    return XQ_OK;
 }
 
 }  // namespace xq
@@ -1198,6 +1243,7 @@ int xq_dqn_set_params(xq_dqn* d, int net, const double* w, const double* b) {
     XQ_HIP(hipMemcpy(d->params[net], p.data(), p.size() * sizeof(float), hipMemcpyHostToDevice));
     if (d->scr_static_net == net) d->scr_static_net = -1;       // screening shadow: rows >= 96 are no longer what it holds
     if (net == XQ_NET_ONLINE) d->sel_invalidate();              // kept layer-0 sums of the select chain belong to the old weights
+    d->tgt_rest_synced = false;                                 // soft target update: the nets may now differ outside the TD segments
     d->params_version += 1;
     XQ_TRY(refresh_shadow(d, net));
     XQ_HIP(hipStreamSynchronize(d->stream));                    // a host-buffer entry point returns with the parameters in place
@@ -1225,6 +1271,7 @@ int xq_dqn_update_target(xq_dqn* d) {
     d->params_version += 1;
     XQ_HIP(hipMemcpyAsync(d->params[1], d->params[0], (d->nw + d->nb) * sizeof(float), hipMemcpyDeviceToDevice, d->stream));
     if (d->scr_static_net == XQ_NET_TARGET) d->scr_static_net = -1;     // screening shadow: every row of the target net changed
+    d->tgt_rest_synced = true;                                          // soft target update: the nets agree everywhere
     if (d->bf16())
         XQ_HIP(hipMemcpyAsync(d->params_bf[1], d->params_bf[0], d->nw * sizeof(uint16_t), hipMemcpyDeviceToDevice, d->stream));
     return XQ_OK;
@@ -1430,6 +1477,7 @@ int xq_dqn_backpropagate(xq_dqn* d, const double* states, const double* targets,
     XQ_TRY(sgd_apply(d, t, lr * grad_scale));
     XQ_TRY(refresh_shadow(d, XQ_NET_ONLINE));          // bf16 Q-net: every later bf16 forward must see the updated weights
     if (d->scr_static_net == XQ_NET_ONLINE) d->scr_static_net = -1;    // dense update: every output row changed (screening shadow)
+    d->tgt_rest_synced = false;                        // ... and the target net, which this never touches, no longer has them
     d->sel_invalidate();
     XQ_HIP(hipStreamSynchronize(d->stream));
     return XQ_OK;
@@ -2086,8 +2134,42 @@ int xq_dqn_apply_grads(xq_dqn* d, double lr, double grad_scale) {
     ClipArgs C; memset(&C, 0, sizeof C);
     const bool clip = d->clip_max_norm > 0.0;
     if (clip) XQ_TRY(grad_norm(d, t, grad_scale, &C));
-    if (d->opt_kind == XQ_OPT_ADAM) return adam_apply(d, t, lr, grad_scale, clip ? &C : nullptr);
-    return sgd_apply(d, t, lr * grad_scale, clip ? &C : nullptr);
+    // soft target update (xq_dqn_set_target_tau): inside the apply kernel while the nets agree outside the TD segments, else the plain
+    // apply and one whole-buffer kernel behind it (the same element rule on the same values: the same bits); tau = 1 is the hard copy
+    // (decided on tau32, the value the kernels use: a tau that rounds to 0 is off, one that rounds to 1 is the copy)
+    const float tau32 = (float)d->target_tau;
+    const bool soft = tau32 > 0.f && tau32 < 1.f;
+    SoftArgs Z; memset(&Z, 0, sizeof Z);
+    const bool fused_soft = soft && d->tgt_rest_synced;
+    if (fused_soft) { soft_td_segments(d, &Z); Z.tau = tau32; }
+    const SoftArgs* z = fused_soft ? &Z : nullptr;
+    if (d->opt_kind == XQ_OPT_ADAM) XQ_TRY(adam_apply(d, t, lr, grad_scale, clip ? &C : nullptr, z));
+    else XQ_TRY(sgd_apply(d, t, lr * grad_scale, clip ? &C : nullptr, z));
+    if (soft && !fused_soft) return soft_target_whole(d, d->target_tau);
+    if (tau32 == 1.f) return xq_dqn_update_target(d);
+    return XQ_OK;
+}
+
+int xq_dqn_set_target_tau(xq_dqn* d, double tau) {
+    if (!d) return fail(XQ_ERR_INVALID_ARGUMENT, "null dqn");
+    if (!(tau >= 0.0 && tau <= 1.0)) return fail(XQ_ERR_INVALID_ARGUMENT, "xq_dqn_set_target_tau: tau must lie in [0, 1] (0 = off, 1 = the hard copy)");
+    if (td_step_pending(d)) return fail(XQ_ERR_RUNTIME, "xq_dqn_set_target_tau: a TD step is waiting for its apply_grads");
+    d->target_tau = tau;
+    return XQ_OK;
+}
+
+int xq_dqn_get_target_tau(const xq_dqn* d, double* tau) {
+    if (!d) return fail(XQ_ERR_INVALID_ARGUMENT, "null dqn");
+    if (tau) *tau = d->target_tau;
+    return XQ_OK;
+}
+
+int xq_dqn_soft_update_target(xq_dqn* d, double tau) {
+    if (!d) return fail(XQ_ERR_INVALID_ARGUMENT, "null dqn");
+    if (!(tau >= 0.0 && tau <= 1.0)) return fail(XQ_ERR_INVALID_ARGUMENT, "xq_dqn_soft_update_target: tau must lie in [0, 1]");
+    if ((float)tau == 0.f) return XQ_OK;
+    if ((float)tau == 1.f) return xq_dqn_update_target(d);
+    return soft_target_whole(d, tau);
 }
 
 // m = v = 0, t = 0 (queued on the handle's stream, behind any apply in flight)

@@ -631,11 +631,31 @@ __device__ __forceinline__ void store_bf16(uint16_t* db, long long i, const floa
     reinterpret_cast<uint2*>(db)[i] = make_uint2(pack_bf16x2(v.x, v.y), pack_bf16x2(v.z, v.w));
 }
 
+// Soft (Polyak) target update (DESIGN.md section 4 "Soft target update"): t' = fmaf(tau, fl32(p_new - t), t), the difference and the fma
+// rounded once each, no contraction left to the compiler.  p_new == t gives d = 0 and t' == t exactly: a parameter whose online and
+// target bits agree is a fixed point.  SoftArgs rides beside a SegTable (whose layout stays): per segment the target net's pointer and
+// its bf16 shadow (nullptr: none).
+struct SoftArgs {
+    float* tgt[16];
+    uint16_t* tgt_bf[16];
+    float tau;
+};
+__device__ __forceinline__ float soft_elem(const float tau, const float p, const float t) {
+#pragma clang fp contract(off)
+    const float d = p - t;
+    return __builtin_fmaf(tau, d, t);
+}
+__device__ __forceinline__ float soft_elems(const float tau, const float p, const float t) { return soft_elem(tau, p, t); }
+__device__ __forceinline__ float4 soft_elems(const float tau, const float4 p, const float4 t) {
+    return make_float4(soft_elem(tau, p.x, t.x), soft_elem(tau, p.y, t.y), soft_elem(tau, p.z, t.z), soft_elem(tau, p.w, t.w));
+}
+
 // One walk over a SegTable for every optimizer: grid (blocks, segments), block (x, y) strides over segment y.  Per element (T = float) or
 // per quad of consecutive elements (T = float4 where t.vec4 says so: 16-byte loads, a quarter of the instructions for the same bytes)
 //   g = the gradient-buffer entry, or slab_sum of the pending slabs;  reduce_only: dst = g, nothing else
 //   dst = step.elem(dst, g, m, v) — a quad is four calls of the same scalar update, so the bits do not depend on which loop ran —
 //   and the bf16 shadow, where there is one, gets the rounded new value.
+//   SOFT: the target net's element moves towards the value just produced (soft_elem; a quad is four calls of it) and its shadow follows.
 // A step object supplies elem() and kState; with kState it also carries the two state buffers m and v, walked at t.state_off.
 template <class Step>
 __device__ __forceinline__ float step_elems(const Step& S, const float w, const float g, float& m, float& v) { return S.elem(w, g, m, v); }
@@ -655,13 +675,15 @@ struct GridX {
     long long first, stride;
 };
 #define XQ_GRID_X GridX{(long long)blockIdx.x * blockDim.x + threadIdx.x, (long long)gridDim.x * blockDim.x}
-template <typename T, bool SLABS, class Step>
+template <typename T, bool SLABS, bool SOFT, class Step>
 __device__ __forceinline__ void segment_loop(const GridX x, const Step& S, float* d_, const float* s_, long long len, int nslabs, long long st,
-                                             uint16_t* db, float* m_, float* v_, bool reduce_only) {
+                                             uint16_t* db, float* m_, float* v_, bool reduce_only, float* tg_ = nullptr, uint16_t* tb = nullptr,
+                                             const float tau = 0.f) {
     T* d = reinterpret_cast<T*>(d_);
     const T* s = reinterpret_cast<const T*>(s_);
     T* ms = reinterpret_cast<T*>(m_);
     T* vs = reinterpret_cast<T*>(v_);
+    T* tg = reinterpret_cast<T*>(tg_);
     for (long long i = x.first; i < len; i += x.stride) {
         T g;
         if (SLABS && nslabs > 0) {
@@ -669,18 +691,26 @@ __device__ __forceinline__ void segment_loop(const GridX x, const Step& S, float
             if (reduce_only) { d[i] = g; continue; }
         } else g = s[i];
         const T w = d[i];
-        T m, v;
+        T m, v, tv;
         if (Step::kState) { m = ms[i]; v = vs[i]; }
         else { vzero(m); vzero(v); }
+        if (SOFT) tv = tg[i];                     // with the other loads of the element, ahead of the step's arithmetic
         const T o = step_elems(S, w, g, m, v);
         if (Step::kState) { ms[i] = m; vs[i] = v; }
         d[i] = o;
         if (db) store_bf16(db, i, o);
+        if (SOFT) {
+            const T tn = soft_elems(tau, o, tv);
+            tg[i] = tn;
+            if (tb) store_bf16(tb, i, tn);
+        }
     }
 }
 // SLABS = false: the table is known to read the gradient buffer only (behind grad_norm_kernel) and the slab sums are not compiled.
-template <bool SLABS, class Step>
-__device__ __forceinline__ void segment_walk(const GridX x, const SegTable& t, const Step& S, float* m = nullptr, float* v = nullptr) {
+// SOFT: Z names the same segments of the target net (never with reduce_only: the host picks a SOFT kernel for a stepping table only).
+template <bool SLABS, bool SOFT = false, class Step>
+__device__ __forceinline__ void segment_walk(const GridX x, const SegTable& t, const Step& S, float* m = nullptr, float* v = nullptr,
+                                             const SoftArgs* Z = nullptr) {
     const int sgm = (int)blockIdx.y;
     if (sgm >= t.nseg) return;
     float* d = t.dst[sgm];
@@ -690,8 +720,15 @@ __device__ __forceinline__ void segment_walk(const GridX x, const SegTable& t, c
     if (Step::kState) { m += t.state_off[sgm]; v += t.state_off[sgm]; }
     const int nslabs = SLABS ? t.nslabs[sgm] : 0;
     const long long st = SLABS ? t.stride[sgm] : 0;
-    if (t.vec4[sgm]) segment_loop<float4, SLABS>(x, S, d, s, len >> 2, nslabs, st >> 2, db, m, v, t.reduce_only != 0);
-    else segment_loop<float, SLABS>(x, S, d, s, len, nslabs, st, db, m, v, t.reduce_only != 0);
+    if (SOFT) {
+        float* tg = Z->tgt[sgm];
+        uint16_t* tb = Z->tgt_bf[sgm];
+        if (t.vec4[sgm]) segment_loop<float4, SLABS, true>(x, S, d, s, len >> 2, nslabs, st >> 2, db, m, v, false, tg, tb, Z->tau);
+        else segment_loop<float, SLABS, true>(x, S, d, s, len, nslabs, st, db, m, v, false, tg, tb, Z->tau);
+        return;
+    }
+    if (t.vec4[sgm]) segment_loop<float4, SLABS, false>(x, S, d, s, len >> 2, nslabs, st >> 2, db, m, v, t.reduce_only != 0);
+    else segment_loop<float, SLABS, false>(x, S, d, s, len, nslabs, st, db, m, v, t.reduce_only != 0);
 }
 
 // SGD: dst -= alpha * src per segment (updateWeightsBiasesKernel dqn.cu:310-319, batched form); the compiler's default contraction
@@ -701,6 +738,7 @@ struct SgdStep {
     __device__ __forceinline__ float elem(const float w, const float g, float&, float&) const { return w - alpha * g; }
 };
 __global__ void sgd_segments_kernel(SegTable t, float alpha) { segment_walk<true>(XQ_GRID_X, t, SgdStep{alpha}); }
+__global__ void sgd_segments_soft_kernel(SegTable t, float alpha, SoftArgs Z) { segment_walk<true, true>(XQ_GRID_X, t, SgdStep{alpha}, nullptr, nullptr, &Z); }
 
 // Adam (torch.optim.Adam's formula, amsgrad off, no weight decay; DESIGN.md section 4 "Optimizer"):
 //   g' = gs g;  m = b1 m + (1 - b1) g';  v = b2 v + (1 - b2) g'^2;  p -= a m / (sqrt(v) rbc2 + eps)
@@ -729,6 +767,7 @@ struct AdamStep {
     __device__ __forceinline__ float elem(const float w, const float g, float& m, float& v) const { return adam_elem(A, w, g, m, v); }
 };
 __global__ void adam_segments_kernel(SegTable t, AdamArgs A) { segment_walk<true>(XQ_GRID_X, t, AdamStep{A}, A.m, A.v); }
+__global__ void adam_segments_soft_kernel(SegTable t, AdamArgs A, SoftArgs Z) { segment_walk<true, true>(XQ_GRID_X, t, AdamStep{A}, A.m, A.v, &Z); }
 
 // ---- gradient clipping by the global L2 norm (DESIGN.md section 4 "Gradient clipping") ---------------------------------------------
 //   S = sum_i (double)g_i^2;  norm = |grad_scale| sqrt(S);  c = (float)min(1, max_norm / (norm + 1e-6))
@@ -832,6 +871,48 @@ __global__ void sgd_segments_clip_kernel(SegTable t, float alpha0, ClipArgs C) {
 __global__ void adam_segments_clip_kernel(SegTable t, AdamArgs A, ClipArgs C) {
     A.gs = clip_mul(A.gs, clip_coef(C, blockIdx.x == 0 && blockIdx.y == 0));
     segment_walk<false>(XQ_GRID_X, t, AdamStep{A}, A.m, A.v);
+}
+__global__ void sgd_segments_clip_soft_kernel(SegTable t, float alpha0, ClipArgs C, SoftArgs Z) {
+    const float alpha = clip_mul(alpha0, clip_coef(C, blockIdx.x == 0 && blockIdx.y == 0));
+    segment_walk<false, true>(XQ_GRID_X, t, SgdStep{alpha}, nullptr, nullptr, &Z);
+}
+__global__ void adam_segments_clip_soft_kernel(SegTable t, AdamArgs A, ClipArgs C, SoftArgs Z) {
+    A.gs = clip_mul(A.gs, clip_coef(C, blockIdx.x == 0 && blockIdx.y == 0));
+    segment_walk<false, true>(XQ_GRID_X, t, AdamStep{A}, A.m, A.v, &Z);
+}
+
+// The soft target update over a whole buffer (xq_dqn_soft_update_target; behind an apply whose target net may differ from the online net
+// outside the TD segments): t[i] = soft_elem(tau, p[i], t[i]) for i < n, and the bf16 shadow t_bf[i] (nullptr: none) for i < n_bf — the
+// shadow covers the weights only.  Grid-stride; vec != 0 (p, t 16-byte and t_bf 8-byte aligned): quads as 16-byte loads and stores, the
+// up to three elements left by one thread each; the bits are those of the scalar rule either way.
+__global__ __launch_bounds__(256) void soft_target_kernel(const float* __restrict__ p, float* __restrict__ t, uint16_t* __restrict__ t_bf,
+                                                          long long n, long long n_bf, float tau, int vec) {
+    const long long first = (long long)blockIdx.x * blockDim.x + threadIdx.x, stride = (long long)gridDim.x * blockDim.x;
+    long long done = 0;
+    if (vec) {
+        const long long nq = n >> 2;
+        const float4* p4 = reinterpret_cast<const float4*>(p);
+        float4* t4 = reinterpret_cast<float4*>(t);
+        for (long long q = first; q < nq; q += stride) {
+            const float4 o = soft_elems(tau, p4[q], t4[q]);
+            t4[q] = o;
+            const long long i0 = q << 2;
+            if (t_bf) {
+                if (i0 + 4 <= n_bf) store_bf16(t_bf, q, o);
+                else {
+                    const float e[4] = {o.x, o.y, o.z, o.w};
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) if (i0 + k < n_bf) t_bf[i0 + k] = bf16_bits(e[k]);
+                }
+            }
+        }
+        done = nq << 2;
+    }
+    for (long long i = done + first; i < n; i += stride) {
+        const float o = soft_elem(tau, p[i], t[i]);
+        t[i] = o;
+        if (t_bf && i < n_bf) t_bf[i] = bf16_bits(o);
+    }
 }
 
 }  // namespace xq

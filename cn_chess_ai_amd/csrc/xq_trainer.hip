@@ -251,6 +251,12 @@ int xq_trainer_set_comm(xq_trainer* t, xq_comm* comm) {
     return xq_dqn_set_comm(t->dqn, comm);
 }
 
+int xq_trainer_set_target_tau(xq_trainer* t, double tau) {
+    if (!t) return fail(XQ_ERR_INVALID_ARGUMENT, "null trainer");
+    if (t->grads_queued) return fail(XQ_ERR_RUNTIME, "xq_trainer_set_target_tau: call between iterations (after learn_apply)");
+    return xq_dqn_set_target_tau(t->dqn, tau);
+}
+
 int xq_trainer_set_td_net(xq_trainer* t, int td_net) {
     if (!t || (td_net != XQ_TD_ONLINE_NET && td_net != XQ_TD_TARGET_NET && td_net != XQ_TD_DOUBLE)) return fail(XQ_ERR_INVALID_ARGUMENT, "bad td_net");
     if (t->grads_queued) return fail(XQ_ERR_RUNTIME, "xq_trainer_set_td_net: call between iterations (after learn_apply)");

@@ -100,8 +100,13 @@ class DQN:
         call("xq_dqn_backpropagate", self._h, _ptr(x, C.c_double), _ptr(t, C.c_double), len(x), float(lr),
              float(grad_scale), int(mode))
 
-    def updateTargetNetwork(self):
-        call("xq_dqn_update_target", self._h)
+    def updateTargetNetwork(self, tau=None):
+        """DQN::updateTargetNetwork (dqn.cpp:71-74): the whole copy; with tau, one soft update of the whole target net now
+        (theta- += tau (theta - theta-); tau = 1 is the copy, tau = 0 a no-op), whatever set_target_tau says."""
+        if tau is None:
+            call("xq_dqn_update_target", self._h)
+        else:
+            call("xq_dqn_soft_update_target", self._h, _checked_tau("updateTargetNetwork", tau))
 
     def saveModel(self, filename):
         call("xq_dqn_save_model", self._h, str(filename).encode())
@@ -381,6 +386,31 @@ DQN.grad_clip = _grad_clip
 DQN.grad_clip_stats = _grad_clip_stats
 
 
+def _checked_tau(who, tau):
+    tau = float(tau)
+    if not 0.0 <= tau <= 1.0:
+        raise ValueError(f"{who}: tau must lie in [0, 1], got {tau!r}")
+    return tau
+
+
+def _set_target_tau(self, tau):
+    """Soft (Polyak) target update inside apply_grads / the trainer's learn_apply: theta- += tau (theta - theta-) after every update, in
+    the apply kernel itself.  0 = off (default), 1 = the hard copy after every update.  After set_params / loadModel / backpropagate
+    call updateTargetNetwork() once: until then a whole-buffer kernel follows every apply.  backpropagate() never moves the target."""
+    call("xq_dqn_set_target_tau", self._h, _checked_tau("set_target_tau", tau))
+
+
+def _target_tau(self):
+    """tau in force (0.0 = off)."""
+    v = C.c_double()
+    call("xq_dqn_get_target_tau", self._h, C.byref(v))
+    return v.value
+
+
+DQN.set_target_tau = _set_target_tau
+DQN.target_tau = _target_tau
+
+
 def _timeline(self, max_spans=8192):
     """(name, start_ms, end_ms) of every launch bracketed in the session closed by the last kernel_stats() call."""
     arr = (KernelSpan * max_spans)()
@@ -451,6 +481,11 @@ class Trainer:
 
     def set_td_net(self, td_net):
         call("xq_trainer_set_td_net", self._h, int(td_net))
+
+    def set_target_tau(self, tau):
+        """DQN.set_target_tau on the trainer's network; set target_sync_interval = 0 beside it (both set: both happen).  Call between
+        iterations."""
+        call("xq_trainer_set_target_tau", self._h, _checked_tau("set_target_tau", tau))
 
     def set_opponent(self, opponent):
         """Train against a fixed opponent from the next collect on (DESIGN.md §4 "Versus training"): None = self-play (the default),

@@ -117,11 +117,13 @@ def pick_splits(M, N, K):
 
 
 def step_work(layers, minibatch, n_games, plies=1, bf16=False, bf16_bwd=False, td="online", screened=True, derive=True,
-              prioritized=False, l0_mfma=True, optimizer="sgd", grad_clip=False):
+              prioritized=False, l0_mfma=True, optimizer="sgd", grad_clip=False, soft_target=False):
     """{bracket name: dict(flops, hbm_bytes, bound, peak, peak_unit, what)} for one training step of the given configuration.
     optimizer="adam" (xq_dqn_set_optimizer): adam_apply stands in place of sgd_apply; the default step knows no adam_apply.
     grad_clip=True (xq_dqn_set_grad_clip): grad_norm stands in front of the apply and takes the slab sums over from it; the default
-    step knows no grad_norm."""
+    step knows no grad_norm.
+    soft_target=True (xq_dqn_set_target_tau in (0, 1), the target net in step with the online net outside the TD segments): the apply
+    kernel also reads and writes the touched part of the target net (and writes its bf16 shadow); no bracket of its own."""
     h = list(layers[1:-1])
     H1, Hl, k = h[0], h[-1], len(h)
     B, n = minibatch, n_games
@@ -281,6 +283,12 @@ def step_work(layers, minibatch, n_games, plies=1, bf16=False, bf16_bwd=False, t
         put("grad_norm", 3.0 * touched + slabs, 4 * (slabs + touched), "hbm",
             "ordered sum of every partial-sum slab into the gradient buffer + fp64 sum of its squares (global-norm clipping)")
         w["adam_apply" if optimizer == "adam" else "sgd_apply"]["hbm_bytes"] -= 4 * (slabs - touched)
+    if soft_target:
+        # theta- += tau (theta - theta-) on the values the apply holds in registers: one read and one write of the touched target
+        a = w["adam_apply" if optimizer == "adam" else "sgd_apply"]
+        a["flops"] += 2.0 * touched
+        a["hbm_bytes"] += 8 * touched + (2 * touched if bf16 else 0)
+        a["what"] += " + soft update of the touched target parameters"
     nw = STATE * H1 + sum(h[l] * h[l - 1] for l in range(1, k)) + Hl * NO
     nb = sum(h) + NO
     put("target_sync_copy", 0.0, 8.0 * (nw + nb), "hbm", "updateTargetNetwork(): device copy of all parameters")

@@ -237,6 +237,8 @@ public:
     }
     std::vector<double> getQValues(const std::vector<double>& state) { return forward(state, XQ_NET_ONLINE); }
     void updateTargetNetwork() { check(xq_dqn_update_target(h_)); }
+    // one soft update of the whole target net now: theta- += tau (theta - theta-); tau = 1 is the copy above, tau = 0 a no-op
+    void updateTargetNetwork(double tau) { check(xq_dqn_soft_update_target(h_, tau)); }
     void saveModel(const std::string& filename) { check(xq_dqn_save_model(h_, filename.c_str())); }
     void loadModel(const std::string& filename) { check(xq_dqn_load_model(h_, filename.c_str())); }
     // dqn.cpp:157-172
@@ -287,6 +289,14 @@ public:
         GradClipStats s;
         check(xq_dqn_grad_clip_stats(h_, &s.lastNorm, &s.lastCoef, &s.applies, &s.clipped));
         return s;
+    }
+    // soft target update inside every batched TD apply (xq_dqn_set_target_tau): 0 = off, 0 < tau < 1 moves the target net towards the
+    // online net in the apply kernel, 1 = the hard copy after every apply.  backpropagate never moves the target.
+    void setTargetTau(double tau) { check(xq_dqn_set_target_tau(h_, tau)); }
+    double targetTau() const {
+        double t = 0.0;
+        check(xq_dqn_get_target_tau(h_, &t));
+        return t;
     }
     const std::vector<int>& layerSizes() const { return layerSizes_; }
     double gamma() const { return gamma_; }
@@ -694,6 +704,8 @@ public:
     void setOptimizer(const Optimizer& o) { initializeDQN(); dqn->setOptimizer(o); }
     // Gradient clipping of the batched train(), carried onto the trainer's network like the optimizer (0 = off, +inf = measure only)
     void setGradClip(double maxNorm) { initializeDQN(); dqn->setGradClip(maxNorm); }
+    // Soft target update of the batched train(), carried onto the trainer's network like the clip (0 = off)
+    void setTargetTau(double tau) { initializeDQN(); dqn->setTargetTau(tau); }
     DQN* network() { return dqn.get(); }
     std::vector<double> getStateRepresentation() {                           // chessai.cpp:268-289 (encoding only)
         std::vector<double> s(90 * 14, 0.0);
@@ -742,6 +754,7 @@ private:
         const Optimizer opt = dqn->optimizer();
         check(xq_dqn_set_optimizer(td, opt.kind, opt.beta1, opt.beta2, opt.eps));
         check(xq_dqn_set_grad_clip(td, dqn->gradClip()));
+        check(xq_trainer_set_target_tau(t, dqn->targetTau()));
         if (comm_) check(xq_trainer_set_comm(t, comm_->handle()));
         if (prefillPlies_ > 0) check(xq_trainer_random_plies(t, prefillPlies_));
         if (opponent_) check(xq_trainer_set_opponent(t, &opponent_->spec()));

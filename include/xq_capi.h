@@ -432,6 +432,25 @@ int xq_dqn_get_grad_clip(const xq_dqn* d, double* max_norm);
 /* Of the last clipped-mode apply: its norm and coefficient.  Since clipping was last switched on (a change from 0): applies and how
  * many had c < 1.  Synchronises.  XQ_ERR_RUNTIME while off.  Any pointer may be NULL. */
 int xq_dqn_grad_clip_stats(xq_dqn* d, double* last_norm, double* last_coef, uint64_t* applies, uint64_t* clipped);
+/* Soft (Polyak) update of the target net, theta- <- theta- + tau (theta - theta-): extends DQN::updateTargetNetwork (dqn.cpp:71-74, a whole
+ * copy) to the update a target-net user runs after every learn step.  Per parameter, with tau32 = (float)tau, p the online value and t the
+ * target value:   d = fl32(p - t);   t' = fmaf(tau32, d, t)   (one rounding each; p == t leaves t' == t exactly).
+ * xq_dqn_set_target_tau: tau in [0, 1], anything else or NaN is XQ_ERR_INVALID_ARGUMENT; XQ_ERR_RUNTIME while a TD step waits for its
+ * apply_grads.  0 = off (default): the kernels, launches and bits of a handle that was never asked.  0 < tau < 1: every
+ * xq_dqn_apply_grads moves the target net towards the online values it has just produced — SGD or Adam, clipped or not, from pending
+ * partial sums or the gradient buffer, behind the all-reduce when a communicator is attached (identical on every replica).  While the
+ * target's parameters outside what the TD rule touches have the online net's bits (after xq_dqn_create and xq_dqn_update_target) those
+ * are fixed points and the update rides in the apply kernel itself over the touched segments: no further launch, the bf16 shadow of the
+ * target follows.  After xq_dqn_set_params of either net, xq_dqn_load_model or xq_dqn_backpropagate one whole-buffer kernel follows the
+ * apply instead, until the next xq_dqn_update_target; both forms give the same bits.  tau = 1 is the hard copy: xq_dqn_update_target
+ * behind every apply (the element rule at 1 would not reproduce p where |t| >> |p|).  xq_dqn_backpropagate never touches the target.
+ * The setting survives xq_dqn_set_optimizer, xq_dqn_set_grad_clip, xq_dqn_set_params, xq_dqn_load_model and xq_dqn_update_target. */
+int xq_dqn_set_target_tau(xq_dqn* d, double tau);
+int xq_dqn_get_target_tau(const xq_dqn* d, double* tau);
+/* One soft update of the whole target net now, in order on the handle's stream, whatever xq_dqn_set_target_tau says (the facade's
+ * updateTargetNetwork(tau), dqn.cpp:71-74 with a rate; a caller's own schedule).  tau = 1 is xq_dqn_update_target, tau = 0 a no-op, outside
+ * [0, 1] or NaN XQ_ERR_INVALID_ARGUMENT. */
+int xq_dqn_soft_update_target(xq_dqn* d, double tau);
 /* Convenience: sample-free TD update straight from a replay ring (slots from the last xq_replay_sample). */
 int xq_dqn_td_grads_replay(xq_dqn* d, xq_replay* r, int batch, int td_net, int mode);
 /* Host-buffer TD step for tests: n transitions as 90-byte boards. Returns Q(s,a) and y per sample if non-NULL. */
@@ -623,6 +642,9 @@ int xq_trainer_random_plies(xq_trainer* t, int n_plies);
 /* Which rule gives the TD target from the next learn step on: XQ_TD_ONLINE_NET (ChessAI::train, chessai.cpp:126), XQ_TD_TARGET_NET
  * (DQN::train, dqn.cpp:166) or XQ_TD_DOUBLE.  Call between iterations. */
 int xq_trainer_set_td_net(xq_trainer* t, int td_net);
+/* xq_dqn_set_target_tau on the trainer's network (DQN::updateTargetNetwork, dqn.cpp:71-74, as a soft update inside every learn_apply).
+ * target_sync_interval keeps its meaning: a user of tau sets it to 0; if both are set, both happen.  Call between iterations. */
+int xq_trainer_set_target_tau(xq_trainer* t, double tau);
 /* Versus training (DESIGN.md §4 "Versus training"): from the next collect on, the learner plays against a fixed opponent instead of
  * itself — uniform-random play, the material search (depth 1..3, eps) or a borrowed network (eps; layer_sizes[0] == 1260, >= 90
  * outputs, not the trainer's own).  The learner plays Black in game g iff (first_game_id + g) & 1.  A collect still writes one
