@@ -14,6 +14,8 @@
 // row-major [out][in], concatenated] [b_0 .. b_out].  Keeping layers >= 1 in the reference's flat order lets the
 // bug-compatible hidden delta (dqn.cu:406-423 as written: wrong stride, reads across layer boundaries) be expressed
 // as the same GEMM with a different base/leading dimension.
+// The gradient half of a TD step is described once (plan_gradients, out_gradient, hidden_weight_gradient, hidden_bias_gradients,
+// l0_gradient) and emitted in two orders: side_gradients (two streams) and tail_launches (fused grids, TailGrid).
 // This file = the handle (struct xq_dqn) + host orchestration + the C ABI; the kernels live in xq_l0.hip.h (layer-0 gathers and
 // segmented sums), xq_tail.hip.h (TD delta, gradient sums, fused launches, SGD), xq_refine.hip.h (screening pass 2), xq_l0grad.hip.h
 // (layer-0 gradient on the matrix pipe), xq_gemm*.hip.h and xq_screen.hip.h (matrix-pipe products).
@@ -41,7 +43,7 @@ struct xq_dqn {
     hipStream_t stream = nullptr;
     bool own_stream = false;
     // side stream for work that is independent of the main chain inside one TD step (the s-chain forward runs beside the
-    // s'-chain + column-max GEMM; the layer-0 gradient beside the other gradient GEMMs); `cur` = stream launches go to
+    // s'-chain + column-max GEMM; the layer-0 gradient beside the other gradient GEMMs); `cur` = stream launches go to (OnStream)
     hipStream_t side = nullptr;
     hipStream_t cur = nullptr;
     int ncu = 256;                              // compute units of the device (persistent-kernel grid = 2 per CU)
@@ -152,11 +154,12 @@ struct xq_dqn {
     bool l0_sel_done = false;                   // this step's selector words rode in an earlier fused launch
     bool l0_mfma = true;                        // xq_dqn_set_l0_grad_mode (default since round 5: xq_l0grad.hip.h)
     xq_comm* comm = nullptr;                    // xq_dqn_set_comm: bucketed RCCL all-reduce of the gradient buffer inside td_grads
-    bool fused_apply = false;                   // xq_dqn_set_fused_apply: apply_grads may sum the layer-0 partials itself
-    int l0_pending = 0;                         // > 0: that many layer-0 slabs wait in slabs_l0, not yet reduced into grads_td
+    bool fused_apply = false;                   // xq_dqn_set_fused_apply: apply_grads may sum the partial-sum slabs itself
+    // nslabs > 0: that many partial-sum slabs of a segment of the TD gradient wait at src, not yet summed into grads_td.  One slot per
+    // segment of for_td_segments: layer 0 (its slabs are slabs_l0), the hidden weights, output rows 0..95 and their biases, the hidden
+    // biases (rows of column sums, bias_grads).  Filled by the gradient half of a TD step, emptied by whatever sums them.
     struct PendingSlab { const float* src = nullptr; int nslabs = 0; long long stride = 0; };
-    PendingSlab pend_hidden[XQ_MAX_LAYERS], pend_wout, pend_bout;   // same for the hidden / output-layer gradients (fused_apply)
-    PendingSlab pend_bh;                        // ... and the hidden biases (rows of column sums, bias_grads)
+    PendingSlab pend_w0, pend_hidden[XQ_MAX_LAYERS], pend_wout, pend_bout, pend_bh;
     xq::DevBuf<float> bias_work;
     // dense API scratch
     xq::DevBuf<float> xdense, qfull, tfull;
@@ -164,7 +167,8 @@ struct xq_dqn {
     xq::DevBuf<int32_t> ha;  xq::DevBuf<float> hr;  xq::DevBuf<uint8_t> hd;
     xq::Profiler prof;
     // fused launches of the TD step's tail (td_tail_kernel): while `tail_open`, the launch helpers of the small fp32 GEMMs, the
-    // output-layer / layer-0 segmented sums and the bias column sums append their blocks to `tail` instead of launching
+    // output-layer / layer-0 segmented sums and the bias column sums append their blocks to `tail` instead of launching.  Written by
+    // the scope objects TailGrid and LaunchNow alone
     xq::TailArgs* tail = nullptr;
     bool tail_open = false;
     bool td_tail = true;                        // xq_dqn_set_td_tail
@@ -176,9 +180,8 @@ struct xq_dqn {
     double exch_allreduce_us = 0.0, exch_threshold_us = 0.0;
     size_t tail_lds = 0;  double tail_flops = 0, tail_bytes = 0;
 
-    // partial-sum slabs may stay unreduced until the SGD kernel only when nothing (an all-reduce) reads the buffer in between
-    bool force_defer = false;   // the fused launches of the gradient half leave their partial sums pending whatever follows (tail_gradients)
-    bool fused() const { return (fused_apply && comm == nullptr) || force_defer; }
+    // partial-sum slabs may stay unreduced until the apply kernel only when nothing (an all-reduce) reads the buffer in between
+    bool fused() const { return fused_apply && comm == nullptr; }
     bool bf16() const { return precision != XQ_PRECISION_F32; }               // bf16 forward passes
     bool bf16_bwd() const { return precision == XQ_PRECISION_BF16_FULL; }     // ... and bf16 operands in the backward products
     uint16_t* wl_bf(int net, int l) const { return params_bf[net] + (l == 0 ? 0 : (size_t)L[0] * L[1] + (wo[l] - wo[1])); }
@@ -202,7 +205,7 @@ uint64_t dqn_params_version(const xq_dqn* d) { return d->params_version; }
 
 struct ProfScope {
     Profiler& p; hipStream_t s; int h; double flops, bytes;
-    // (while a fused tail launch is being assembled nothing is launched, so nothing is bracketed: tail_launch has its own scope)
+    // (while a fused tail launch is being assembled nothing is launched, so nothing is bracketed: TailGrid::launch has its own scope)
     // A launch on a stream that is neither the handle's nor its side stream belongs to the select chain of the self-play loop (the
     // trainer's collect stream): same kernels, other shapes, off the critical path — bracketed under "<name>@select".
     // attach: the scope is ONE kernel launch that takes start() / stop() as its own events (hipExtLaunchKernelGGL): kernel-exact time
@@ -222,6 +225,19 @@ struct ProfScope {
     ~ProfScope() { p.end(h, s, flops, bytes); }
 };
 
+// While one lives, the launch helpers launch — in front of the fused grid that is being assembled, if one is (TailGrid)
+struct LaunchNow {
+    xq_dqn* d; bool was_open;
+    explicit LaunchNow(xq_dqn* d_) : d(d_), was_open(d_->tail_open) { d->tail_open = false; }
+    ~LaunchNow() { d->tail_open = was_open; }
+};
+// While one lives, launches go to stream `s`
+struct OnStream {
+    xq_dqn* d; hipStream_t was;
+    OnStream(xq_dqn* d_, hipStream_t s) : d(d_), was(d_->cur) { d->cur = s; }
+    ~OnStream() { d->cur = was; }
+};
+
 }  // namespace xq
 
 // kernels (each header opens namespace xq itself)
@@ -238,8 +254,7 @@ static inline int vec_ok(const void* p, long long ld) { return (((uintptr_t)p) %
 
 // tile choice: 128x128 when that grid already fills the chip twice over, else 64x64 (4x the blocks)
 template <int AL, int BL, int EPI, int DT = DT_F32>
-static int launch_gemm(xq_dqn* d, GemmArgs g, int splits, const char* name, int* used_splits = nullptr, bool force_small = false,
-                       bool force_big = false) {
+static int launch_gemm(xq_dqn* d, GemmArgs g, int splits, const char* name, int* used_splits = nullptr, bool force_small = false) {
     if (used_splits) *used_splits = 0;
     if (g.M <= 0 || g.N <= 0 || g.K <= 0) return fail(XQ_ERR_INVALID_ARGUMENT, "empty GEMM %s (%d x %d x %d)", name, g.M, g.N, g.K);
     g.a_vec = vec_ok(g.A, g.lda);
@@ -250,7 +265,7 @@ static int launch_gemm(xq_dqn* d, GemmArgs g, int splits, const char* name, int*
     if (splits < 1) splits = 1;
     const int groups = g.grouped > 1 ? g.grouped : 1;
     const long long t128 = (long long)((g.M + 127) / 128) * ((g.N + 127) / 128) * (g.grouped ? groups : splits);
-    const bool big = force_big || (!force_small && !d->small_tiles && t128 >= 512);
+    const bool big = (!force_small && !d->small_tiles && t128 >= 512);
     const double kk = DT == DT_BF16 ? 2.0 * g.K : (double)g.K;       // bf16: K counts pairs
     if (d->tail_open) {                  // fused tail launch (td_tail_kernel): the blocks join the open grid instead of launching
         TailArgs& T = *d->tail;
@@ -288,7 +303,6 @@ static int launch_gemm(xq_dqn* d, GemmArgs g, int splits, const char* name, int*
     if (used_splits) *used_splits = splits;
     return XQ_OK;
 }
-#define XQ_GEMM(expr) XQ_TRY(expr)
 
 // A kernel's dynamic-LDS limit raised to `bytes` the first time it is asked for, per kernel address (every template instance has its own)
 static int ensure_max_dynamic_lds(const void* kernel, int bytes) {
@@ -534,7 +548,7 @@ static int chain_boards(xq_dqn* d, const ChainJob* jobs, int njobs, SlotSrc src,
                 if (k == 0) { g.A = A; g.B = B; g.C = C; g.bias = d->bl(jobs[k].net, l); g.Cb = jobs[k].outs_bf[l]; }
                 else { g.Ax[k - 1] = A; g.Bx[k - 1] = B; g.Cx[k - 1] = C; g.biasx[k - 1] = d->bl(jobs[k].net, l); g.Cbx[k - 1] = jobs[k].outs_bf[l]; }
             }
-            XQ_GEMM((launch_gemm<L_KCONTIG, L_KCONTIG, EPI_BIAS_TANH, DT_BF16>(d, g, 1, "gemm_hidden_fwd")));
+            XQ_TRY((launch_gemm<L_KCONTIG, L_KCONTIG, EPI_BIAS_TANH, DT_BF16>(d, g, 1, "gemm_hidden_fwd")));
         } else {
             g.K = d->L[l]; g.lda = g.ldb = d->L[l]; g.ldc = d->L[l + 1]; g.ldcb = d->L[l + 1];
             if (l == d->nl - 2 && njobs == 1 && jobs[0].head_slabs) {
@@ -584,7 +598,7 @@ static int chain_boards(xq_dqn* d, const ChainJob* jobs, int njobs, SlotSrc src,
                 XQ_HIP(hipGetLastError());
                 continue;
             }
-            XQ_GEMM((launch_gemm<L_KCONTIG, L_KCONTIG, EPI_BIAS_TANH>(d, g, 1, "gemm_hidden_fwd")));
+            XQ_TRY((launch_gemm<L_KCONTIG, L_KCONTIG, EPI_BIAS_TANH>(d, g, 1, "gemm_hidden_fwd")));
         }
     }
     return XQ_OK;
@@ -610,7 +624,7 @@ static int q_head(xq_dqn* d, int net, const float* a_last, int n, int n_out, flo
         g.B = reinterpret_cast<const float*>(d->wl_bf(net, d->nl - 1)); g.ldb = d->hlast() / 2;
         g.C = q; g.ldc = ldq;
         g.bias = d->bl(net, d->nl - 1);
-        XQ_GEMM((launch_gemm<L_KCONTIG, L_KCONTIG, EPI_BIAS_TANH, DT_BF16>(d, g, 1, name)));
+        XQ_TRY((launch_gemm<L_KCONTIG, L_KCONTIG, EPI_BIAS_TANH, DT_BF16>(d, g, 1, name)));
         return XQ_OK;
     }
     g.M = n; g.N = n_out; g.K = d->hlast();
@@ -631,7 +645,7 @@ static int q_head(xq_dqn* d, int net, const float* a_last, int n, int n_out, flo
         float* slab = nullptr;
         XQ_TRY(head_slabs(d, need, &slab));
         g.C = slab; g.ldc = nc; g.slab_stride = (long long)n * nc;
-        XQ_GEMM((launch_gemm<L_KCONTIG, L_KCONTIG, EPI_STORE>(d, g, nslabs, name, nullptr, true)));
+        XQ_TRY((launch_gemm<L_KCONTIG, L_KCONTIG, EPI_STORE>(d, g, nslabs, name, nullptr, true)));
         const long long total = (long long)n * n_out;
         hipLaunchKernelGGL(q_head_finish_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, d->cur, slab, g.slab_stride, nslabs, n, n_out, nc,
                            g.bias, q, ldq);
@@ -639,7 +653,7 @@ static int q_head(xq_dqn* d, int net, const float* a_last, int n, int n_out, flo
         return XQ_OK;
     }
     g.C = q; g.ldc = ldq;
-    XQ_GEMM((launch_gemm<L_KCONTIG, L_KCONTIG, EPI_BIAS_TANH>(d, g, 1, name)));
+    XQ_TRY((launch_gemm<L_KCONTIG, L_KCONTIG, EPI_BIAS_TANH>(d, g, 1, name)));
     return XQ_OK;
 }
 
@@ -789,7 +803,7 @@ static int hidden_deltas(xq_dqn* d, int n, const float* dnext, int ld_next, int 
                 d->l0_split_done = true;
             }
         }
-        XQ_GEMM((launch_gemm<L_KCONTIG, L_MCONTIG, EPI_DELTA>(d, g, 1, "gemm_hidden_delta")));
+        XQ_TRY((launch_gemm<L_KCONTIG, L_MCONTIG, EPI_DELTA>(d, g, 1, "gemm_hidden_delta")));
         up = d->deltas[l]; ld_up = d->L[l + 1]; nz = d->L[l + 1];
     }
     return XQ_OK;
@@ -832,39 +846,26 @@ static int launch_reduce_slabs(xq_dqn* d, const float* slabs, int nslabs, long l
 template <int AL>
 static int grad_gemm(xq_dqn* d, GemmArgs g, float* dst, const char* name, float* slab_base = nullptr,
                      xq_dqn::PendingSlab* defer = nullptr, const uint16_t* a_bf = nullptr, const uint16_t* b_bf = nullptr) {
-    const bool big = false;    // 64-tiles: more tiles, fewer k-splits, cheaper ordered reduction
     const bool use_bf = AL == L_MCONTIG && a_bf && b_bf && grad_bf16_ok(d, g.M, g.N, g.K);
-    int splits = use_bf ? grad_splits(d, g.M, g.N, g.K) : pick_splits(g.M, g.N, g.K);
-    if (use_bf) {
-        const long long len = (long long)g.M * g.N;
-        float* slabs = slab_base;
-        Bf16GemmArgs b; memset(&b, 0, sizeof b);
-        b.M = g.M; b.N = g.N; b.K = g.K; b.A = a_bf; b.lda = g.lda; b.B = b_bf; b.ldb = g.ldb; b.k_chunk = g.K / splits;
-        if (splits > 1) {
-            if (!slabs) { XQ_TRY(d->slabs.reserve((size_t)splits * (size_t)len)); slabs = d->slabs; }
-            b.C = slabs; b.ldc = g.N; b.slab_stride = len;
-        } else { b.C = dst; b.ldc = g.N; }
-        XQ_TRY((launch_bf16_gemm<L_MCONTIG, L_MCONTIG, BG_STORE>(d, b, splits, name)));
-        if (splits > 1 && defer) { defer->src = slabs; defer->nslabs = splits; defer->stride = len; return XQ_OK; }
-        if (splits > 1) XQ_TRY(launch_reduce_slabs(d, slabs, splits, len, dst));
-        return XQ_OK;
-    }
+    const int splits = use_bf ? grad_splits(d, g.M, g.N, g.K) : pick_splits(g.M, g.N, g.K);
     const long long len = (long long)g.M * g.N;
     float* slabs = slab_base;
-    if (splits > 1) {
-        if (!slabs) { XQ_TRY(d->slabs.reserve((size_t)splits * (size_t)len)); slabs = d->slabs; }
-        g.C = slabs; g.ldc = g.N; g.slab_stride = len;
-    } else {
-        g.C = dst; g.ldc = g.N; g.slab_stride = 0;
+    if (splits > 1 && !slabs) { XQ_TRY(d->slabs.reserve((size_t)splits * (size_t)len)); slabs = d->slabs; }
+    float* C = splits > 1 ? slabs : dst;
+    const long long slab_stride = splits > 1 ? len : 0;
+    int used = splits;
+    if (use_bf) {
+        Bf16GemmArgs b; memset(&b, 0, sizeof b);
+        b.M = g.M; b.N = g.N; b.K = g.K; b.A = a_bf; b.lda = g.lda; b.B = b_bf; b.ldb = g.ldb; b.k_chunk = g.K / splits;
+        b.C = C; b.ldc = g.N; b.slab_stride = slab_stride;
+        XQ_TRY((launch_bf16_gemm<L_MCONTIG, L_MCONTIG, BG_STORE>(d, b, splits, name)));
+    } else {                               // 64-tiles: more tiles, fewer k-splits, cheaper ordered reduction
+        g.C = C; g.ldc = g.N; g.slab_stride = slab_stride;
+        XQ_TRY((launch_gemm<AL, L_MCONTIG, EPI_STORE>(d, g, splits, name, &used, true)));
     }
-    int used = 0;
-    XQ_TRY((launch_gemm<AL, L_MCONTIG, EPI_STORE>(d, g, splits, name, &used, !big, big)));
-    if (splits > 1 && defer) {             // summed by the SGD kernel (xq_dqn_set_fused_apply)
-        defer->src = slabs; defer->nslabs = used; defer->stride = len;
-        return XQ_OK;
-    }
-    if (splits > 1) XQ_TRY(launch_reduce_slabs(d, slabs, used, len, dst));
-    return XQ_OK;
+    if (splits <= 1) return XQ_OK;
+    if (defer) { defer->src = slabs; defer->nslabs = used; defer->stride = len; return XQ_OK; }      // summed by the apply kernel
+    return launch_reduce_slabs(d, slabs, used, len, dst);
 }
 
 struct BiasJobs {
@@ -908,8 +909,9 @@ static int bias_grads(xq_dqn* d, BiasJobs& bj, int n, xq_dqn::PendingSlab* defer
     return XQ_OK;
 }
 
-// layer 0: per-(square, piece) segmented sums of delta_0 rows (no dense one-hot product); launches on d->cur
-static int l0_gradient(xq_dqn* d, int n, float* dst) {
+// layer 0: per-(square, piece) segmented sums of delta_0 rows (no dense one-hot product); launches on d->cur or joins the open fused
+// grid.  defer != nullptr: the chunks' partial sums are left to the apply kernel as slabs — one kernel fewer on the critical chain
+static int l0_gradient(xq_dqn* d, int n, float* dst, xq_dqn::PendingSlab* defer) {
     const int H = d->L[1];
     // samples per block (list entries hold 11 bits of sample index).  8192 samples: 1024 (2048 measured 56 against 52 us, round 2);
     // 16384 samples: 2048 — half the partial slabs for the SGD kernel to sum (41 -> 20 MB), bench --config 5 0.717 -> 0.704 ms
@@ -928,18 +930,18 @@ static int l0_gradient(xq_dqn* d, int n, float* dst) {
         XQ_TRY(ensure_l0_mfma(d, n));
         const size_t need_sel = l0sel_elems(kpad);
         const long long plane_stride = (long long)H * kpad;
-        const bool was_open = d->tail_open;
-        d->tail_open = false;                        // launches of their own, in front of the fused launch that is being assembled
-        if (!d->l0_sel_done) {                       // (fused TD step of a net with >= 2 hidden layers: rode in the launch before this one)
-            ProfScope ps(d, "l0_sel_words", 0.0, (double)n * 48 + 2.0 * need_sel);
-            hipLaunchKernelGGL(l0_sel_kernel, dim3(kpad / 64), dim3(256), 0, d->cur, d->gboards, n, kpad, d->l0_sel);
+        {
+            LaunchNow now(d);                        // launches of their own, in front of the fused launch that is being assembled
+            if (!d->l0_sel_done) {                   // (fused TD step of a net with >= 2 hidden layers: rode in the launch before this one)
+                ProfScope ps(d, "l0_sel_words", 0.0, (double)n * 48 + 2.0 * need_sel);
+                hipLaunchKernelGGL(l0_sel_kernel, dim3(kpad / 64), dim3(256), 0, d->cur, d->gboards, n, kpad, d->l0_sel);
+            }
+            if (!d->l0_split_done) {                 // (whole tiles: the delta product's epilogue wrote the planes)
+                ProfScope ps(d, "l0_delta_split", 8.0 * n * H, (double)n * H * 4 + 6.0 * H * kpad);
+                hipLaunchKernelGGL(delta_split_kernel, dim3(kpad / 64, H / 64), dim3(256), 0, d->cur, d->deltas[0], n, H, d->l0_planes, plane_stride, kpad);
+            }
+            d->l0_sel_done = d->l0_split_done = false;
         }
-        if (!d->l0_split_done) {                     // (whole tiles: the delta product's epilogue wrote the planes)
-            ProfScope ps(d, "l0_delta_split", 8.0 * n * H, (double)n * H * 4 + 6.0 * H * kpad);
-            hipLaunchKernelGGL(delta_split_kernel, dim3(kpad / 64, H / 64), dim3(256), 0, d->cur, d->deltas[0], n, H, d->l0_planes, plane_stride, kpad);
-        }
-        d->l0_sel_done = d->l0_split_done = false;
-        d->tail_open = was_open;
         XQ_HIP(hipGetLastError());
         const size_t shmem = l0m_lds_bytes();
         const double fl = 2.0 * 80 * 16 * (double)H * kpad * 3, by = 6.0 * H * kpad + 2.0 * need_sel + 4.0 * nchunks * len;
@@ -976,13 +978,9 @@ static int l0_gradient(xq_dqn* d, int n, float* dst) {
         XQ_HIP(hipGetLastError());
         }
     }
-    d->l0_pending = 0;
-    if (nchunks > 1 && d->fused()) {
-        d->l0_pending = nchunks;                     // summed inside the SGD kernel: one kernel fewer on the critical chain
-    } else if (nchunks > 1) {
-        XQ_TRY(launch_reduce_slabs(d, d->slabs_l0, nchunks, len, dst));
-    }
-    return XQ_OK;
+    if (nchunks <= 1) return XQ_OK;
+    if (defer) { defer->src = d->slabs_l0; defer->nslabs = nchunks; defer->stride = len; return XQ_OK; }
+    return launch_reduce_slabs(d, d->slabs_l0, nchunks, len, dst);
 }
 
 // Which segments go four elements to a thread (t.vec4: every pointer 16-byte aligned — the bf16 shadow, where there is one, is stored in
@@ -1074,7 +1072,7 @@ static void layout_td_grads(xq_dqn* d) {
     d->n_grads_td = off;
 }
 // a TD step left partial-sum slabs for its apply_grads to add (fused_apply)
-static bool td_step_pending(const xq_dqn* d) { return d->l0_pending > 0 || d->pend_wout.nslabs > 0 || d->pend_bh.nslabs > 0; }
+static bool td_step_pending(const xq_dqn* d) { return d->pend_w0.nslabs > 0 || d->pend_wout.nslabs > 0 || d->pend_bh.nslabs > 0; }
 // The segments a TD step touches, in THE order of every table built from them (the order is part of the clip norm's association):
 // W0^T, the hidden weights, output rows 0..95, the hidden biases (contiguous in both layouts), the output biases.  f(parameters, their
 // bf16 shadow or nullptr, offset in the gradient buffer, length, the segment's pending-slab slot) — f empties the slot it takes.
@@ -1082,11 +1080,7 @@ template <class F>
 static void for_td_segments(xq_dqn* d, F f) {
     const bool bf = d->bf16();
     const int top = d->nl - 1;
-    const long long len0 = (long long)d->L[0] * d->L[1];
-    xq_dqn::PendingSlab p0;                          // layer 0 keeps a count, its slabs are slabs_l0
-    if (d->l0_pending > 0) { p0.src = d->slabs_l0; p0.nslabs = d->l0_pending; p0.stride = len0; }
-    f(d->w0t(0), bf ? d->wl_bf(0, 0) : nullptr, d->g_w0, len0, p0);
-    d->l0_pending = p0.nslabs;
+    f(d->w0t(0), bf ? d->wl_bf(0, 0) : nullptr, d->g_w0, (long long)d->L[0] * d->L[1], d->pend_w0);
     for (int l = 1; l < top; ++l) f(d->wl(0, l), bf ? d->wl_bf(0, l) : nullptr, d->g_wh[l], (long long)d->L[l] * d->L[l + 1], d->pend_hidden[l]);
     f(d->wl(0, top), bf ? d->wl_bf(0, top) : nullptr, d->g_wout, 96LL * d->hlast(), d->pend_wout);
     f(d->bl(0, 0), (uint16_t*)nullptr, d->g_bh[0], (long long)d->bo[top], d->pend_bh);
@@ -1366,7 +1360,7 @@ static int chain_dense(xq_dqn* d, int net, const float* x, int n, float* const* 
     g.bias = d->bl(net, 0);
     g.libm_tanh = !XQ_L0_FAST_TANH;      // layer 0 takes the SAME tanh on both routes (tanh_l0 in the packed-board gather kernels): a dense
                                          // one-hot and the board it encodes then differ by summation order only
-    XQ_GEMM((launch_gemm<L_KCONTIG, L_MCONTIG, EPI_BIAS_TANH>(d, g, 1, "gemm_l0_dense_fwd")));
+    XQ_TRY((launch_gemm<L_KCONTIG, L_MCONTIG, EPI_BIAS_TANH>(d, g, 1, "gemm_l0_dense_fwd")));
     for (int l = 1; l + 1 < d->nl; ++l) {
         GemmArgs h; memset(&h, 0, sizeof h);
         h.M = n; h.N = d->L[l + 1]; h.K = d->L[l];
@@ -1374,7 +1368,7 @@ static int chain_dense(xq_dqn* d, int net, const float* x, int n, float* const* 
         h.B = d->wl(net, l); h.ldb = d->L[l];
         h.C = outs[l]; h.ldc = d->L[l + 1];
         h.bias = d->bl(net, l);
-        XQ_GEMM((launch_gemm<L_KCONTIG, L_KCONTIG, EPI_BIAS_TANH>(d, h, 1, "gemm_hidden_fwd")));
+        XQ_TRY((launch_gemm<L_KCONTIG, L_KCONTIG, EPI_BIAS_TANH>(d, h, 1, "gemm_hidden_fwd")));
     }
     return XQ_OK;
 }
@@ -1497,87 +1491,125 @@ int xq_dqn_td_grads(xq_dqn* d, const uint32_t* boards, const uint32_t* next_boar
     return td_grads_impl(d, boards, next_boards, action_to, reward, done, explicit_slots(slots), n, td_net, mode, nullptr);
 }
 
-// gradients that run on the side stream (d->cur == d->side), see td_grads_impl
-static int side_gradients(xq_dqn* d, int n, float* const* outs, float* G) {
-    const int nl = d->nl, Hl = d->hlast();
+// ---- the gradient half of a TD step: one description of each gradient, emitted in two orders -----------------------------------
+// Each helper below is the one place that knows its gradient's shapes, operands, accounting and pending slot; like bias_grads and
+// l0_gradient it appends to the open fused grid (TailGrid) or launches on d->cur.  side_gradients and tail_gradients are the two orders.
+
+// Where the partial-sum slabs of a step's output-layer and hidden weight gradients go in d->slabs.  defer: they wait for the apply
+// kernel (or reduce_pending), so every segment has a region of its own; otherwise each launch is followed by its ordered sum and they
+// use one region in turn.  (Layer 0 and the hidden biases have buffers of their own: slabs_l0, bias_work.)
+struct GradPlan {
+    bool defer;
+    int out_chunks;  long long len_out;  size_t out_lds;     // output-layer sums: blocks of kOutGradChunk samples, [96][Hl] + [96] per slab
+    size_t off_out, off_h[XQ_MAX_LAYERS];
+};
+// samples per block of the output-layer sums: small chunks level the load between popular and rare destination squares
+// (1024: 21.7 us and a side stream that ends with the critical one; 256: 16.4 us, step -10 us)
+static const int kOutGradChunk = 256;
+static int plan_gradients(xq_dqn* d, int n, bool defer, GradPlan* P) {
+    const int Hl = d->hlast();
+    memset(P, 0, sizeof *P);
+    P->defer = defer;
+    P->out_chunks = (n + kOutGradChunk - 1) / kOutGradChunk;
+    P->len_out = 96LL * Hl + 96;
+    P->out_lds = (size_t)16 * Hl * sizeof(float) + (size_t)kOutGradChunk * sizeof(uint16_t);
+    if (P->out_lds > 64 * 1024 || (Hl & 3))
+        return fail(XQ_ERR_INVALID_ARGUMENT, "last hidden layer width %d unsupported by the output-gradient kernel (multiple of 4, <= 960)", Hl);
+    size_t need = 0;
+    auto place = [&](int nslabs, size_t len) {
+        const size_t floats = nslabs > 1 ? (size_t)nslabs * len : 0, at = defer ? need : 0;
+        need = defer ? need + floats : std::max(need, floats);
+        return at;
+    };
+    P->off_out = place(P->out_chunks, (size_t)P->len_out);
+    for (int l = d->nl - 2; l >= 1; --l) P->off_h[l] = place(grad_splits(d, d->L[l + 1], d->L[l], n), (size_t)d->L[l + 1] * (size_t)d->L[l]);
+    XQ_TRY(d->slabs.reserve(need));
+    d->pend_w0 = d->pend_wout = d->pend_bout = d->pend_bh = xq_dqn::PendingSlab();
+    for (auto& p : d->pend_hidden) p = xq_dqn::PendingSlab();
+    return XQ_OK;
+}
+
+// output layer rows 0..95 + their biases (g_bout follows g_wout directly): segmented sums by action
+static int out_gradient(xq_dqn* d, const GradPlan& P, int n, const float* alast, float* G) {
+    const int Hl = d->hlast(), nchunks = P.out_chunks;
+    float* dst = G + d->g_wout;
+    float* out = nchunks > 1 ? d->slabs + P.off_out : dst;
+    const double fl = 2.0 * n * Hl, by = (double)n * (Hl * 4 + 8) + 4.0 * nchunks * P.len_out;
+    if (d->tail_open) {
+        TailArgs& T = *d->tail;
+        T.og_act = d->act_mb; T.og_dsc = d->dsc; T.og_alast = alast; T.og_n = n; T.og_H = Hl; T.og_chunk = kOutGradChunk; T.og_partial = out;
+        T.n_out = 24 * nchunks;
+        d->tail_flops += fl; d->tail_bytes += by;
+        d->tail_lds = std::max(d->tail_lds, P.out_lds);
+    } else {
+        ProfScope ps(d, "out_grad_segsum", fl, by);
+        hipLaunchKernelGGL(out_grad_kernel, dim3(24, nchunks), dim3(256), P.out_lds, d->cur, d->act_mb, d->dsc, alast, n, Hl, kOutGradChunk, out);
+        XQ_HIP(hipGetLastError());
+    }
+    if (nchunks <= 1) return XQ_OK;
+    if (P.defer) {
+        d->pend_wout.src = out; d->pend_wout.nslabs = nchunks; d->pend_wout.stride = P.len_out;
+        d->pend_bout.src = out + 96LL * Hl; d->pend_bout.nslabs = nchunks; d->pend_bout.stride = P.len_out;
+        return XQ_OK;
+    }
+    return launch_reduce_slabs(d, out, nchunks, P.len_out, dst);      // (len_out <= 96 * 961: under the grid cap, one thread per sum)
+}
+// weight gradient of hidden layer l >= 1: delta_l^T a_{l-1} (XQ_PRECISION_BF16_FULL: on the bf16 loop where the shape allows)
+static int hidden_weight_gradient(xq_dqn* d, const GradPlan& P, int l, int n, float* const* outs, float* G) {
+    GemmArgs g; memset(&g, 0, sizeof g);
+    g.M = d->L[l + 1]; g.N = d->L[l]; g.K = n;
+    g.A = d->deltas[l]; g.lda = d->L[l + 1];
+    g.B = outs[l - 1]; g.ldb = d->L[l];
+    const bool bf = d->bf16_bwd();
+    return grad_gemm<L_MCONTIG>(d, g, G + d->g_wh[l], "gemm_grad_hidden", d->slabs + P.off_h[l], P.defer ? &d->pend_hidden[l] : nullptr,
+                                bf ? d->deltas_bf[l].p : nullptr, bf ? d->acts_bf[l - 1].p : nullptr);
+}
+// the hidden biases: column sums of every hidden delta, in the order of the bias vector
+static int hidden_bias_gradients(xq_dqn* d, const GradPlan& P, int n, float* G) {
     BiasJobs bj;
-    const bool fused = d->fused();
-    const int chunk = 256;                           // samples per block: small chunks level the load between popular and rare destination squares
-                                                     // (1024: 21.7 us and a side stream that ends with the critical one; 256: 16.4 us, step -10 us)
-    const int nchunks = (n + chunk - 1) / chunk;
-    const long long len_out = 96LL * Hl + 96;
-    // fused_apply: every partial-sum slab of this step stays alive until the SGD kernel sums it => one region each
-    size_t off_out = 0, off_h[XQ_MAX_LAYERS] = {0}, need = 0;
-    if (fused) {
-        if (nchunks > 1) need += (size_t)nchunks * (size_t)len_out;
-        for (int l = nl - 2; l >= 1; --l) {
-            off_h[l] = need;
-            const int sp = grad_splits(d, d->L[l + 1], d->L[l], n);
-            if (sp > 1) need += (size_t)sp * (size_t)d->L[l + 1] * (size_t)d->L[l];
-        }
-        XQ_TRY(d->slabs.reserve(need));
-        for (int l = 0; l < XQ_MAX_LAYERS; ++l) d->pend_hidden[l] = xq_dqn::PendingSlab();
-        d->pend_wout = d->pend_bout = xq_dqn::PendingSlab();
-    }
-    {   // output layer rows 0..95 + their biases: segmented sums by action
-        float* dst = G + d->g_wout;                      // g_bout follows directly
-        float* out = dst;
-        if (nchunks > 1) {
-            if (fused) out = d->slabs + off_out;
-            else { XQ_TRY(d->slabs.reserve((size_t)nchunks * (size_t)len_out)); out = d->slabs; }
-        }
-        {
-            ProfScope ps(d, "out_grad_segsum", 2.0 * n * Hl, (double)n * (Hl * 4 + 8) + 4.0 * nchunks * len_out);
-            const size_t shmem = (size_t)16 * Hl * sizeof(float) + (size_t)chunk * sizeof(uint16_t);
-            if (shmem > 64 * 1024 || (Hl & 3)) return fail(XQ_ERR_INVALID_ARGUMENT, "last hidden layer width %d unsupported by the output-gradient kernel (multiple of 4, <= 960)", Hl);
-            hipLaunchKernelGGL(out_grad_kernel, dim3(24, nchunks), dim3(256), shmem, d->cur, d->act_mb, d->dsc, outs[nl - 2], n, Hl,
-                               chunk, out);
-            XQ_HIP(hipGetLastError());
-        }
-        if (nchunks > 1 && fused) {
-            d->pend_wout.src = out; d->pend_wout.nslabs = nchunks; d->pend_wout.stride = len_out;
-            d->pend_bout.src = out + 96LL * Hl; d->pend_bout.nslabs = nchunks; d->pend_bout.stride = len_out;
-        } else if (nchunks > 1) {
-            XQ_TRY(launch_reduce_slabs(d, out, nchunks, len_out, dst));     // (len_out <= 96 * 961: under the grid cap, one thread per sum)
-        }
-    }
+    for (int l = 0; l <= d->nl - 2; ++l) bj.add(d->deltas[l], d->L[l + 1], d->L[l + 1], G + d->g_bh[l]);
+    return bias_grads(d, bj, n, P.defer ? &d->pend_bh : nullptr);
+}
+
+// the order of the side stream (td_gradients_fork): each gradient as soon as its delta exists
+static int side_gradients(xq_dqn* d, const GradPlan& P, int n, float* const* outs, float* G) {
+    const int nl = d->nl;
+    XQ_TRY(out_gradient(d, P, n, outs[nl - 2], G));
     bool waited = false;
     for (int l = nl - 2; l >= 1; --l) {
         if (l < nl - 2 && !waited) { XQ_HIP(hipStreamWaitEvent(d->cur, d->ev_delta, 0)); waited = true; }   // delta_l, l < top, comes from the GEMMs
-        GemmArgs g; memset(&g, 0, sizeof g);
-        g.M = d->L[l + 1]; g.N = d->L[l]; g.K = n;
-        g.A = d->deltas[l]; g.lda = d->L[l + 1];
-        g.B = outs[l - 1]; g.ldb = d->L[l];
-        XQ_TRY((grad_gemm<L_MCONTIG>(d, g, G + d->g_wh[l], "gemm_grad_hidden", fused ? d->slabs + off_h[l] : nullptr,
-                                     fused ? &d->pend_hidden[l] : nullptr, d->bf16_bwd() ? d->deltas_bf[l] : nullptr,
-                                     d->bf16_bwd() ? d->acts_bf[l - 1] : nullptr)));
+        XQ_TRY(hidden_weight_gradient(d, P, l, n, outs, G));
     }
-    for (int l = 0; l <= nl - 2; ++l) bj.add(d->deltas[l], d->L[l + 1], d->L[l + 1], G + d->g_bh[l]);     // the order of the bias vector
     if (!waited) XQ_HIP(hipStreamWaitEvent(d->cur, d->ev_delta, 0));
-    d->pend_bh = xq_dqn::PendingSlab();
-    return bias_grads(d, bj, n, fused ? &d->pend_bh : nullptr);
+    return hidden_bias_gradients(d, P, n, G);
 }
 
 // ---- the same gradients as fused launches on the handle's stream (td_tail_kernel): no side stream, no event --------------------
-static void tail_begin(xq_dqn* d) {
-    if (!d->tail) d->tail = new TailArgs();
-    memset(d->tail, 0, sizeof(TailArgs));
-    d->tail_open = true; d->tail_lds = 0; d->tail_flops = d->tail_bytes = 0;
-}
-static int tail_launch(xq_dqn* d, bool last, const char* name) {
-    d->tail_open = false;
-    const TailArgs& T = *d->tail;
-    const long long total = (long long)T.n_l0 + T.n_grad + T.n_delta + T.n_out + T.n_colsum + T.n_sel;
-    if (total <= 0) return XQ_OK;
-    ProfScope ps(d, name, d->tail_flops, d->tail_bytes, true);      // one launch: timed by its own start / stop events
-    const auto kern = last ? (T.l0_planes != nullptr ? td_tail_kernel<TAIL_L0 | TAIL_GRAD | TAIL_OUT | TAIL_COLSUM, true>
-                                                     : td_tail_kernel<TAIL_L0 | TAIL_GRAD | TAIL_OUT | TAIL_COLSUM>)
-                           : (T.n_sel ? td_tail_kernel<TAIL_GRAD | TAIL_DELTA | TAIL_OUT | TAIL_SEL> : td_tail_kernel<TAIL_GRAD | TAIL_DELTA | TAIL_OUT>);
-    if (d->tail_lds > 48 * 1024) XQ_TRY(ensure_max_dynamic_lds(kern, 64 * 1024));
-    hipExtLaunchKernelGGL(kern, dim3((unsigned)total), dim3(256), d->tail_lds, d->cur, ps.start(), ps.stop(), 0, T);
-    XQ_HIP(hipGetLastError());
-    return XQ_OK;
-}
+// The assembly of one fused launch: from here until launch() (or the end of the scope, whichever comes first) the launch helpers
+// append their blocks to d->tail instead of launching.
+struct TailGrid {
+    xq_dqn* d;
+    explicit TailGrid(xq_dqn* d_) : d(d_) {
+        if (!d->tail) d->tail = new TailArgs();
+        memset(d->tail, 0, sizeof(TailArgs));
+        d->tail_open = true; d->tail_lds = 0; d->tail_flops = d->tail_bytes = 0;
+    }
+    ~TailGrid() { d->tail_open = false; }
+    int launch(bool last, const char* name) {
+        d->tail_open = false;
+        const TailArgs& T = *d->tail;
+        const long long total = (long long)T.n_l0 + T.n_grad + T.n_delta + T.n_out + T.n_colsum + T.n_sel;
+        if (total <= 0) return XQ_OK;
+        ProfScope ps(d, name, d->tail_flops, d->tail_bytes, true);      // one launch: timed by its own start / stop events
+        const auto kern = last ? (T.l0_planes != nullptr ? td_tail_kernel<TAIL_L0 | TAIL_GRAD | TAIL_OUT | TAIL_COLSUM, true>
+                                                         : td_tail_kernel<TAIL_L0 | TAIL_GRAD | TAIL_OUT | TAIL_COLSUM>)
+                               : (T.n_sel ? td_tail_kernel<TAIL_GRAD | TAIL_DELTA | TAIL_OUT | TAIL_SEL> : td_tail_kernel<TAIL_GRAD | TAIL_DELTA | TAIL_OUT>);
+        if (d->tail_lds > 48 * 1024) XQ_TRY(ensure_max_dynamic_lds(kern, 64 * 1024));
+        hipExtLaunchKernelGGL(kern, dim3((unsigned)total), dim3(256), d->tail_lds, d->cur, ps.start(), ps.stop(), 0, T);
+        XQ_HIP(hipGetLastError());
+        return XQ_OK;
+    }
+};
 // shapes the fused launches take: fp32 products on 64x64 tiles (what launch_gemm picks for them anyway).  Their partial sums stay
 // pending: with fused_apply and no communicator the SGD kernel adds them; otherwise ONE launch reduces all of them into the gradient
 // buffer behind the second fused launch (reduce_pending), and a communicator all-reduces that buffer behind it.
@@ -1600,76 +1632,23 @@ static int reduce_pending(xq_dqn* d) {
     t.nseg = k; t.reduce_only = 1;
     return sgd_apply(d, t, 0.0);
 }
-static int tail_gradients_impl(xq_dqn* d, int n, float* const* outs, float* G, int mode);
-static int tail_gradients(xq_dqn* d, int n, float* const* outs, float* G, int mode) {
-    const bool leave_pending = d->fused();          // fused_apply, no communicator: the SGD kernel adds the slabs
-    d->force_defer = true;
-    int rc = tail_gradients_impl(d, n, outs, G, mode);
-    d->force_defer = false;
-    d->tail_open = false;                            // a failed assembly must not leave the launch helpers appending to a dead grid
-    if (d->late_gate) {                              // the select chain starts here, beside the exchange — also behind a failed step: a
-        // collect that waits for ev_qmax must find this step's record, not the previous one's
-        if (hipEventRecord(d->ev_qmax, d->stream) != hipSuccess && rc == XQ_OK) rc = fail(XQ_ERR_RUNTIME, "hipEventRecord failed");
-    }
-    if (rc == XQ_OK && !leave_pending) {
-        rc = reduce_pending(d);
-        // data-parallel step: the whole buffer in one collective on the handle's stream, right behind its last producer
-        if (rc == XQ_OK && d->comm) {
-            ProfScope ps(d, "rccl_allreduce_grads", 0, 4.0 * d->n_grads_td);
-            rc = comm_allreduce_on(d->comm, G, d->n_grads_td, d->stream);
-        }
-    }
-    return rc;
-}
-static int tail_gradients_impl(xq_dqn* d, int n, float* const* outs, float* G, int mode) {
-    const int nl = d->nl, Hl = d->hlast();
-    const int chunk = 256;                           // out_grad: samples per block (see side_gradients)
-    const int nchunks = (n + chunk - 1) / chunk;
-    const long long len_out = 96LL * Hl + 96;
-    size_t off_h[XQ_MAX_LAYERS] = {0}, need = 0;
-    if (nchunks > 1) need += (size_t)nchunks * (size_t)len_out;
-    for (int l = nl - 2; l >= 1; --l) {
-        off_h[l] = need;
-        const int sp = grad_splits(d, d->L[l + 1], d->L[l], n);
-        if (sp > 1) need += (size_t)sp * (size_t)d->L[l + 1] * (size_t)d->L[l];
-    }
-    XQ_TRY(d->slabs.reserve(need));
-    for (int l = 0; l < XQ_MAX_LAYERS; ++l) d->pend_hidden[l] = xq_dqn::PendingSlab();
-    d->pend_wout = d->pend_bout = xq_dqn::PendingSlab();
-    const size_t og_lds = (size_t)16 * Hl * sizeof(float) + (size_t)chunk * sizeof(uint16_t);
-    if (og_lds > 64 * 1024 || (Hl & 3)) return fail(XQ_ERR_INVALID_ARGUMENT, "last hidden layer width %d unsupported by the output-gradient kernel (multiple of 4, <= 960)", Hl);
-    auto add_out_grad = [&]() {
-        TailArgs& T = *d->tail;
-        float* out = nchunks > 1 ? d->slabs : G + d->g_wout;
-        T.og_act = d->act_mb; T.og_dsc = d->dsc; T.og_alast = outs[nl - 2]; T.og_n = n; T.og_H = Hl; T.og_chunk = chunk; T.og_partial = out;
-        T.n_out = 24 * nchunks;
-        d->tail_flops += 2.0 * n * Hl; d->tail_bytes += (double)n * (Hl * 4 + 8) + 4.0 * nchunks * len_out;
-        d->tail_lds = std::max(d->tail_lds, og_lds);
-        if (nchunks > 1) {
-            d->pend_wout.src = out; d->pend_wout.nslabs = nchunks; d->pend_wout.stride = len_out;
-            d->pend_bout.src = out + 96LL * Hl; d->pend_bout.nslabs = nchunks; d->pend_bout.stride = len_out;
-        }
-    };
-    // one launch per hidden layer below the top one: delta_l from delta_{l+1}, the weight gradient of layer l+1 (delta_{l+1}, a_l)
-    // beside it, the output-layer sums beside the first
-    auto add_grad = [&](int ll) -> int {             // weight gradient of hidden layer ll: delta_ll^T a_{ll-1}
-        GemmArgs g; memset(&g, 0, sizeof g);
-        g.M = d->L[ll + 1]; g.N = d->L[ll]; g.K = n;
-        g.A = d->deltas[ll]; g.lda = d->L[ll + 1];
-        g.B = outs[ll - 1]; g.ldb = d->L[ll];
-        return grad_gemm<L_MCONTIG>(d, g, G + d->g_wh[ll], "gemm_grad_hidden", d->slabs + off_h[ll], &d->pend_hidden[ll]);
-    };
+// the order of the fused launches: one per hidden layer below the top one — delta_l from delta_{l+1}, the weight gradient of layer
+// l+1 (delta_{l+1}, a_l) beside it, the output-layer sums beside the first — then the layer-0 sums with the bias column sums
+static int tail_launches(xq_dqn* d, int n, float* const* outs, float* G, int mode) {
+    const int nl = d->nl;
+    GradPlan P;
+    XQ_TRY(plan_gradients(d, n, true, &P));          // a fused grid cannot be followed by its own ordered sums: every slab stays pending
     // two hidden layers: the one weight-gradient product runs beside the layer-0 sums (L2-bound) rather than beside the delta product
     // (both MFMA-bound, and the select chain's Q head is on the chip at that time): 0.2065 against 0.2086 ms per step of the headline
     // bench; three hidden layers (bench --config 4): no difference, kept beside the delta products
     const bool defer_grad = nl == 3;
     int waiting = -1;
     for (int l = nl - 3; l >= 0; --l) {
-        tail_begin(d);
+        TailGrid grid(d);
         XQ_TRY(hidden_deltas(d, n, d->deltas[l + 1], d->L[l + 2], d->L[l + 2], mode, l, l));
-        if (defer_grad) { if (waiting >= 0) XQ_TRY(add_grad(waiting)); waiting = l + 1; }
-        else XQ_TRY(add_grad(l + 1));
-        if (l == nl - 3) add_out_grad();
+        if (defer_grad) { if (waiting >= 0) XQ_TRY(hidden_weight_gradient(d, P, waiting, n, outs, G)); waiting = l + 1; }
+        else XQ_TRY(hidden_weight_gradient(d, P, l + 1, n, outs, G));
+        if (l == nl - 3) XQ_TRY(out_gradient(d, P, n, outs[nl - 2], G));
         if (l == 0 && l0_mfma_shape(d, n)) {
             // the selector half-words of the minibatch's boards (operand of the matrix-pipe layer-0 gradient in the NEXT launch): they
             // depend on the boards alone, so their blocks ride at the end of this grid, off the dependency chain
@@ -1681,19 +1660,31 @@ static int tail_gradients_impl(xq_dqn* d, int n, float* const* outs, float* G, i
             d->tail_lds = std::max(d->tail_lds, (size_t)64 * 13 * sizeof(uint32_t));
             d->l0_sel_done = true;
         }
-        XQ_TRY(tail_launch(d, false, "td_tail_deltas"));
+        XQ_TRY(grid.launch(false, "td_tail_deltas"));
     }
-    // last launch: the layer-0 sums and the bias column sums of every hidden delta (+ the output-layer sums of a net without a second
-    // hidden layer)
-    tail_begin(d);
-    XQ_TRY(l0_gradient(d, n, G + d->g_w0));
-    if (waiting >= 0) XQ_TRY(add_grad(waiting));
-    if (nl < 3) add_out_grad();
-    BiasJobs bj;
-    for (int l = 0; l <= nl - 2; ++l) bj.add(d->deltas[l], d->L[l + 1], d->L[l + 1], G + d->g_bh[l]);
-    d->pend_bh = xq_dqn::PendingSlab();
-    XQ_TRY(bias_grads(d, bj, n, &d->pend_bh));
-    return tail_launch(d, true, "td_tail_l0");
+    // last launch (+ the output-layer sums of a net without a second hidden layer)
+    TailGrid grid(d);
+    XQ_TRY(l0_gradient(d, n, G + d->g_w0, &d->pend_w0));
+    if (waiting >= 0) XQ_TRY(hidden_weight_gradient(d, P, waiting, n, outs, G));
+    if (nl < 3) XQ_TRY(out_gradient(d, P, n, outs[nl - 2], G));
+    XQ_TRY(hidden_bias_gradients(d, P, n, G));
+    return grid.launch(true, "td_tail_l0");
+}
+static int tail_gradients(xq_dqn* d, int n, float* const* outs, float* G, int mode) {
+    int rc = tail_launches(d, n, outs, G, mode);
+    if (d->late_gate) {                              // the select chain starts here, beside the exchange — also behind a failed step: a
+        // collect that waits for ev_qmax must find this step's record, not the previous one's
+        if (hipEventRecord(d->ev_qmax, d->stream) != hipSuccess && rc == XQ_OK) rc = fail(XQ_ERR_RUNTIME, "hipEventRecord failed");
+    }
+    if (rc == XQ_OK && !d->fused()) {                // (fused_apply, no communicator: the apply kernel adds the slabs)
+        rc = reduce_pending(d);
+        // data-parallel step: the whole buffer in one collective on the handle's stream, right behind its last producer
+        if (rc == XQ_OK && d->comm) {
+            ProfScope ps(d, "rccl_allreduce_grads", 0, 4.0 * d->n_grads_td);
+            rc = comm_allreduce_on(d->comm, G, d->n_grads_td, d->stream);
+        }
+    }
+    return rc;
 }
 
 // ---- one TD step (td_grads_impl): the stages below, in the order the step runs them -----------------------------------------------
@@ -1897,8 +1888,8 @@ static int qmax_exact(xq_dqn* d, const TdStep& s, bool bf_frag, bool gate_early)
                                  : (dbl ? gemm_colmax_persistent_kernel<2, 2, DT_F32, CM_ARG> : gemm_colmax_persistent_kernel<2, 2, DT_F32, CM_MAX>);
             hipLaunchKernelGGL(kern, dim3(grid), dim3(256), s.bias_lds, d->cur, g, tiles_m, total);
             XQ_HIP(hipGetLastError());
-        } else if (bf) XQ_GEMM((launch_gemm<L_KCONTIG, L_KCONTIG, EPI_COLMAX, DT_BF16>(d, g, 1, "gemm_qmax_rowmax")));
-        else XQ_GEMM((launch_gemm<L_KCONTIG, L_KCONTIG, EPI_COLMAX>(d, g, 1, "gemm_qmax_rowmax")));
+        } else if (bf) XQ_TRY((launch_gemm<L_KCONTIG, L_KCONTIG, EPI_COLMAX, DT_BF16>(d, g, 1, "gemm_qmax_rowmax")));
+        else XQ_TRY((launch_gemm<L_KCONTIG, L_KCONTIG, EPI_COLMAX>(d, g, 1, "gemm_qmax_rowmax")));
     }
     if (!d->late_gate && !gate_early) XQ_HIP(hipEventRecord(d->ev_qmax, d->stream));
     {   // the partial maxima of every sample folded into kReduceParts values (+ row indices): coalesced, block-cooperative
@@ -1941,6 +1932,9 @@ static int td_delta(xq_dqn* d, const TdStep& s, int zparts) {
 static int td_gradients_fork(xq_dqn* d, const TdStep& s) {
     const int n = s.n, nl = s.nl;
     float* G = d->grads_td;
+    GradPlan P;
+    XQ_TRY(plan_gradients(d, n, d->fused(), &P));
+    xq_dqn::PendingSlab* defer_w0 = P.defer ? &d->pend_w0 : nullptr;
     XQ_HIP(hipEventRecord(d->ev_fork, d->stream));
     XQ_HIP(hipStreamWaitEvent(d->side, d->ev_fork, 0));
     if (nl >= 3) XQ_TRY(hidden_deltas(d, n, d->deltas[nl - 2], d->L[nl - 1], d->L[nl - 1], s.mode, nl - 3));
@@ -1950,15 +1944,15 @@ static int td_gradients_fork(xq_dqn* d, const TdStep& s) {
     // output-layer weights, all biases: ready first) is issued first and the layer-0 bucket (the last thing computed, the only exposed one)
     // second; every rank issues in this order.  Without a communicator the layer-0 sums are issued first.
     const size_t n0 = (size_t)d->L[0] * d->L[1];
-    if (!d->comm) XQ_TRY(l0_gradient(d, n, G + d->g_w0));
-    d->cur = d->side;
-    const int rc = side_gradients(d, n, s.outs, G);
-    d->cur = d->stream;
-    if (rc != XQ_OK) return rc;
+    if (!d->comm) XQ_TRY(l0_gradient(d, n, G + d->g_w0, defer_w0));
+    {
+        OnStream side(d, d->side);
+        XQ_TRY(side_gradients(d, P, n, s.outs, G));
+    }
     if (d->comm) XQ_TRY(comm_allreduce_on(d->comm, G + n0, d->n_grads_td - n0, d->side));
     XQ_HIP(hipEventRecord(d->ev_join, d->side));
     if (d->comm) {
-        XQ_TRY(l0_gradient(d, n, G + d->g_w0));
+        XQ_TRY(l0_gradient(d, n, G + d->g_w0, defer_w0));
         XQ_TRY(comm_allreduce_on(d->comm, G, n0, d->stream));
     }
     XQ_HIP(hipStreamWaitEvent(d->stream, d->ev_join, 0));
@@ -2273,8 +2267,7 @@ int xq_dqn_grad_clip_stats(xq_dqn* d, double* last_norm, double* last_coef, uint
 
 int xq_dqn_set_fused_apply(xq_dqn* d, int on) {
     if (!d) return fail(XQ_ERR_INVALID_ARGUMENT, "null dqn");
-    if (d->l0_pending > 0 || d->pend_wout.nslabs > 0 || d->pend_bh.nslabs > 0)
-        return fail(XQ_ERR_RUNTIME, "xq_dqn_set_fused_apply: a TD step is waiting for its apply_grads");
+    if (td_step_pending(d)) return fail(XQ_ERR_RUNTIME, "xq_dqn_set_fused_apply: a TD step is waiting for its apply_grads");
     d->fused_apply = on != 0;
     return XQ_OK;
 }

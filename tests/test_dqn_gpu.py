@@ -903,3 +903,69 @@ def test_layer0_gradient_on_the_matrix_pipe_matches_the_segmented_sums(xq, trace
     u = br.accumulate(net, f, br.backward(net, f, 0))
     for got_w, got_b in outs:
         br.check_update(net, u, f, got_w, got_b, lr, scale, br.PRECISION_F32)
+
+
+def _selfplay_transitions(xq, n, seed=5):
+    """(s, s', action.to, reward, done) of one seeded self-play ply of n games, as the fused-launch test above builds it."""
+    env = xq.VecEnv(n, seed=seed)
+    for _ in range(23):
+        env.selfplay_step(None)
+    S, _ = env.get_state()
+    res = env.selfplay_step(None)
+    S2, _ = env.get_state()
+    env.close()
+    D = res["done"].copy()
+    D[::9] = 1
+    return S, S2, (res["action"] % 90).astype(np.int32), (res["reward"] / 100.0).astype(np.float32), D
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n", [1024, 1100])
+def test_bf16_backward_slabs_deferred_equal_reduced_bitwise(xq, n):
+    """XQ_PRECISION_BF16_FULL, 1260-256-256-8100: the partial-sum slabs of the backward pass left to the apply kernel (set_fused_apply(1))
+    against summed behind each product (0).  n = 1024: the hidden weight gradient on the bf16 loop with 16 k-slabs, the delta product on
+    the bf16 loop; n = 1100: the same net on the fp32 loops (partial tiles, 5 output chunks, 2 layer-0 chunks).  Either way the same
+    slabs are added in the same order, so two TD steps leave bit-identical parameters, Q(s,a) and y."""
+    from cn_chess_ai_amd import _capi
+    batch = _selfplay_transitions(xq, n)
+    out = {}
+    for fused in (1, 0):
+        d, w, b = make_net(xq, CFG2_NET, seed=31)
+        d.set_precision(_capi.PRECISION_BF16_FULL)
+        d.set_fused_apply(fused)
+        for _ in range(2):
+            qsa, y = d.td_update(*batch, td_net=0, mode=0, learning_rate=0.05, grad_scale=1.0 / n)
+        out[fused] = (d.get_params(), qsa.copy(), y.copy())
+        d.close()
+    (w1, b1), q1, y1 = out[1]
+    (w0, b0), q0, y0 = out[0]
+    assert np.array_equal(q1.view(np.uint32), q0.view(np.uint32)) and np.array_equal(y1.view(np.uint32), y0.view(np.uint32))
+    assert np.array_equal(w1, w0) and np.array_equal(b1, b0)
+    w32, b32 = w.astype(np.float32), b.astype(np.float32)                  # what set_params stored
+    assert np.abs(w1 - w32).max() > 0 and np.abs(b1 - b32).max() > 0      # ... and the updates did move the parameters
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("tail", [1, 0])
+def test_a_refused_td_step_leaves_nothing_open(xq, tail):
+    """1260-64-130-8100: the last hidden width is no multiple of 4, so the output-gradient shape check refuses the step on the host,
+    in the middle of the gradient half (fused launches being assembled / side stream selected).  Afterwards no step is "waiting for its
+    apply" — the setters that refuse in that state accept — and a forward pass on the same handle gives the bits it gave before: the
+    parameters are untouched, nothing is left appending to a dead grid or launching on the side stream."""
+    from cn_chess_ai_amd import _capi
+    n = 300
+    batch = _selfplay_transitions(xq, n)
+    d, w, b = make_net(xq, [1260, 64, 130, 8100], seed=31)
+    d.set_td_tail(tail)
+    x = one_hot(batch[0][:4])
+    q_before = d.getQValues(x).copy()
+    with pytest.raises(_capi.XqError) as e:
+        d.td_update(*batch, td_net=0, mode=_capi.BACKPROP_TEXTBOOK, learning_rate=0.05, grad_scale=1.0 / n)
+    assert e.value.code == 1 and "output-gradient kernel" in str(e.value)          # XQ_ERR_INVALID_ARGUMENT, from that check
+    d.set_optimizer("adam")
+    d.set_grad_clip(1.0)
+    d.set_fused_apply(1)
+    assert np.array_equal(d.getQValues(x), q_before)
+    w1, b1 = d.get_params()
+    assert np.array_equal(w1, w.astype(np.float32)) and np.array_equal(b1, b.astype(np.float32))
+    d.close()

@@ -1,0 +1,128 @@
+"""The bits and the launches of a TD step over a fixed seeded matrix, and whether another build of the library gives the same ones.
+
+    python tools/td_step_bits.py [--parent OTHER/libxqhip.so]
+
+Cells: net {1260-128-8100, 1260-256-256-8100, 1260-512-512-512-8100, 1260-127-129-132-8100 (textbook rule)} x minibatch {333: one
+layer-0 chunk, partial tiles; 1100: slabs everywhere, no epilogue planes; and, for the two nets of even 256 / 512 widths, 2048: whole
+chunks — the planes come from the delta product's epilogue and the selector words ride in the first fused launch} x td_tail {0, 1} x
+fused_apply {0, 1} x precision {fp32, BF16_FULL where the hidden widths are even} x one-rank communicator {absent, attached; skipped
+when RCCL cannot be loaded}; two TD steps from one seeded self-play batch per cell.  One line per cell: a SHA-256 over the parameters,
+the gradient buffer, Q(s,a), y and the (kernel name, calls) list of xq_dqn_kernel_stats.  The tests compare the paths of one build with
+each other; this compares two builds — the host side of the gradient half decides which kernels run, where their partial sums go and
+who adds them, and a change there that moves every path alike shows only here.
+--parent LIB: the matrix again in a fresh child process on that library (XQ_LIBXQHIP); exit status 1 if any cell differs."""
+import argparse
+import hashlib
+import itertools
+import json
+import os
+import subprocess
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+REF_NET = (1260, 128, 8100)
+CFG2_NET = (1260, 256, 256, 8100)
+CFG4_NET = (1260, 512, 512, 512, 8100)
+SCALAR_NET = (1260, 127, 129, 132, 8100)
+SHAPES = [(REF_NET, (333, 1100)), (CFG2_NET, (333, 1100, 2048)), (CFG4_NET, (333, 1100, 2048)), (SCALAR_NET, (333, 1100))]
+
+
+def selfplay_batch(xq, n, seed):
+    import numpy as np
+    env = xq.VecEnv(n, seed=seed)
+    for _ in range(13):
+        env.selfplay_step(None)
+    S, _ = env.get_state()
+    res = env.selfplay_step(None)
+    S2, _ = env.get_state()
+    env.close()
+    D = res["done"].copy()
+    D[::7] = 1
+    return S, S2, (res["action"] % 90).astype(np.int32), (res["reward"] / 100.0).astype(np.float32), D
+
+
+def cell(xq, sizes, batch, n, tail, fused, precision, comm):
+    import numpy as np
+    import torch
+    from cn_chess_ai_amd import _capi, dist as xd
+    d = xq.DQN(sizes, 0.001, 0.99, seed=5)
+    rng = np.random.default_rng(len(sizes) * 1000 + sizes[1])
+    d.set_params(rng.uniform(-0.05, 0.05, size=d.n_weights), rng.uniform(-0.05, 0.05, size=d.n_biases))
+    d.updateTargetNetwork()
+    d.set_precision(precision)
+    d.set_td_tail(tail)
+    d.set_fused_apply(fused)
+    if comm is not None:
+        d.set_comm(comm)
+    # the reference's backward rule is undefined where a hidden layer widens (127 -> 129 -> 132): the textbook rule there
+    mode = _capi.BACKPROP_TEXTBOOK if sizes == SCALAR_NET else _capi.BACKPROP_REFERENCE
+    h = hashlib.sha256()
+    d.kernel_stats(enable=2)
+    for _ in range(2):
+        qsa, y = d.td_update(*batch, td_net=0, mode=mode, learning_rate=0.05, grad_scale=1.0 / n)
+        h.update(qsa.tobytes()); h.update(y.tobytes())
+    launches = sorted((k["name"], k["launches"]) for k in d.kernel_stats(enable=0))
+    h.update(json.dumps(launches).encode())
+    for x in d.get_params():
+        h.update(np.ascontiguousarray(x).tobytes())
+    ptr, k = d.grad_buffer()
+    torch.cuda.synchronize()
+    h.update(xd.wrap_device_floats(ptr, k).cpu().numpy().tobytes())
+    d.close()
+    return h.hexdigest()
+
+
+def matrix():
+    import cn_chess_ai_amd as xq
+    from cn_chess_ai_amd import _capi, dist as xd
+    out, skipped = {}, []
+    try:
+        comm = xd.Comm(rank=0, world=1)
+    except Exception as e:                         # no RCCL on this machine: the cells with a communicator are skipped, and counted
+        comm = None
+        print("no communicator:", e, flush=True)
+    for sizes, ns in SHAPES:
+        for n in ns:
+            batch = selfplay_batch(xq, n, seed=83)
+            for tail, fused, prec, with_comm in itertools.product((0, 1), (0, 1), (_capi.PRECISION_F32, _capi.PRECISION_BF16_FULL), (0, 1)):
+                if prec and any(x & 1 for x in sizes[1:-1]):
+                    continue                       # (the bf16 Q-net needs even hidden widths: not a cell)
+                name = "%s n=%d tail=%d fused=%d %s comm=%d" % ("-".join(map(str, sizes)), n, tail, fused, "bf16_full" if prec else "fp32", with_comm)
+                if with_comm and comm is None:
+                    skipped.append(name)
+                    continue
+                out[name] = cell(xq, sizes, batch, n, tail, fused, prec, comm if with_comm else None)
+                print(out[name], name, flush=True)
+    if comm is not None:
+        comm.close()
+    print("%d cells run, %d skipped (no communicator)" % (len(out), len(skipped)), flush=True)
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--parent")
+    ap.add_argument("--json", action="store_true", help="(the child process of --parent) the cells as one JSON line at the end")
+    args = ap.parse_args()
+    mine = matrix()
+    if args.json:
+        print("CELLS " + json.dumps(mine), flush=True)
+    if not args.parent:
+        return 0
+    env = dict(os.environ, XQ_LIBXQHIP=os.path.abspath(args.parent))
+    r = subprocess.run([sys.executable, os.path.abspath(__file__), "--json"], env=env, stdout=subprocess.PIPE, text=True, timeout=900)
+    if r.returncode != 0:
+        print("the run on", args.parent, "ended with", r.returncode, flush=True)
+        return 1
+    other = json.loads([l for l in r.stdout.splitlines() if l.startswith("CELLS ")][-1][6:])
+    differ = [k for k in mine if other.get(k) != mine[k]]
+    for k in differ:
+        print("DIFFERS", k, mine[k], other.get(k), flush=True)
+    print("%d cells, %d differ" % (len(mine), len(differ)), flush=True)
+    return 1 if differ or len(other) != len(mine) else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
