@@ -55,12 +55,10 @@ int borrowed_forward(xq_dqn* d, const uint32_t* boards_dev, int n, int n_out, fl
                      hipEvent_t ev_q) {
     hipStream_t ds = dqn_stream(d);
     if (ds != s) XQ_HIP(hipStreamWaitEvent(ds, ev_env, 0));
-    Profiler* prof = dqn_profiler(d);
-    const bool was = prof->enabled;
-    prof->enabled = false;                   // not the handle's work
-    const int rc = xq_dqn_forward_boards_dev(d, XQ_NET_ONLINE, boards_dev, n, n_out, q_rows_dev, 96);
-    prof->enabled = was;
-    XQ_TRY(rc);
+    {
+        ProfilerOff off(dqn_profiler(d));    // not the handle's work
+        XQ_TRY(xq_dqn_forward_boards_dev(d, XQ_NET_ONLINE, boards_dev, n, n_out, q_rows_dev, 96));
+    }
     if (ds != s) {
         XQ_HIP(hipEventRecord(ev_q, ds));
         XQ_HIP(hipStreamWaitEvent(s, ev_q, 0));

@@ -14,6 +14,9 @@
 // row-major [out][in], concatenated] [b_0 .. b_out].  Keeping layers >= 1 in the reference's flat order lets the
 // bug-compatible hidden delta (dqn.cu:406-423 as written: wrong stride, reads across layer boundaries) be expressed
 // as the same GEMM with a different base/leading dimension.
+// The forward half is described once too: layer 0 (l0_select_forward with kept sums, l0_forward grouped) and one function per hidden
+// product (hidden_bf16_dma, hidden_bf16_tile, hidden_f32_head, hidden_f32_walk, the fp32 tile kernel), each with its own shape test,
+// operands, accounting and launch; hidden_forward picks one, chain_boards is the argument checks, the layer-0 call and the loop.
 // The gradient half of a TD step is described once (plan_gradients, out_gradient, hidden_weight_gradient, hidden_bias_gradients,
 // l0_gradient) and emitted in two orders: side_gradients (two streams) and tail_launches (fused grids, TailGrid).
 // This file = the handle (struct xq_dqn) + host orchestration + the C ABI; the kernels live in xq_l0.hip.h (layer-0 gathers and
@@ -49,7 +52,6 @@ struct xq_dqn {
     int ncu = 256;                              // compute units of the device (persistent-kernel grid = 2 per CU)
     hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_delta = nullptr;
     hipEvent_t ev_qmax = nullptr;               // recorded behind the column-max GEMM of the last TD step (trainer: collect starts here)
-    hipEvent_t fwd_stop_ev = nullptr;           // set: the last grouped forward product of chain_boards completes this event itself (taken = reset)
     xq::DevBuf<float> params[2];
     uint64_t params_version = 0;                // ++ whenever an operation that rewrites parameters is queued (xq_trainer: is ev_params still current?)
     // bf16 Q-net (xq_dqn_set_precision): bf16 shadow of the WEIGHTS of both nets, same element order as params[] (biases stay fp32);
@@ -85,7 +87,7 @@ struct xq_dqn {
     } sel_keep[2];
     void sel_invalidate() { sel_keep[0].valid = sel_keep[1].valid = false; }
     xq::DevBuf<float> qh_slabs[2];              // k-slabs of the select head (handle stream / any other stream)
-    bool small_tiles = false;                   // force 64x64 GEMM tiles (<= 80 VGPRs: fits beside the persistent GEMM)
+    bool small_tiles = false;                   // force 64x64 GEMM tiles (<= 80 VGPRs: fits beside the persistent GEMM); written by SmallTiles alone
     bool l0_derive = false;                     // xq_dqn_set_l0_derive: layer-0 sums of s' from those of s (online TD rule, fp32 net)
     // exact screening of max_a' Q(s', a') (xq_dqn_set_qmax_mode): bf16 copies of the output-layer weights and of
     // the last hidden activations of s', the two screening partial arrays, the largest row norm of the weights, counters
@@ -211,7 +213,7 @@ struct ProfScope {
     // attach: the scope is ONE kernel launch that takes start() / stop() as its own events (hipExtLaunchKernelGGL): kernel-exact time
     ProfScope(xq_dqn* d, const char* name, double fl, double by, bool attach = false) : p(d->prof), s(d->cur), flops(fl), bytes(by) {
         h = -1;
-        if (d->tail_open || !p.enabled) return;
+        if (!name || d->tail_open || !p.enabled) return;     // (no name: a launch that is not bracketed)
         if (d->cur != d->stream && d->cur != d->side) {
             char nm[48];
             snprintf(nm, sizeof nm, "%s@select", name);
@@ -236,6 +238,12 @@ struct OnStream {
     xq_dqn* d; hipStream_t was;
     OnStream(xq_dqn* d_, hipStream_t s) : d(d_), was(d_->cur) { d->cur = s; }
     ~OnStream() { d->cur = was; }
+};
+// While one lives, the tile kernels take 64x64 tiles if `small` (the select chain beside a TD step)
+struct SmallTiles {
+    xq_dqn* d; bool was;
+    SmallTiles(xq_dqn* d_, bool small) : d(d_), was(d_->small_tiles) { d->small_tiles = small; }
+    ~SmallTiles() { d->small_tiles = was; }
 };
 
 }  // namespace xq
@@ -470,137 +478,153 @@ struct ChainJob {
     int sel_keep;               // fp32 net, one chain: 1 = layer 0 through l0_select_kernel (sums kept in sel_state->z1 for the next ply),
                                 //   2 = ... and derived from the sums kept last time
 };
-static int chain_boards(xq_dqn* d, const ChainJob* jobs, int njobs, SlotSrc src, int n, const ShadowJob* shadow = nullptr) {
+// A chain's views into a family of workspaces: a_{l+1} in buffer l % period of `fp` (nullptr unless `fp32`) and of `bits`
+static void chain_views(const xq_dqn* d, const DevBuf<float>* fp, const DevBuf<uint16_t>* bits, int period, bool fp32, float** outs, uint16_t** outs_bf) {
+    for (int l = 0; l + 1 < d->nl; ++l) { outs[l] = fp32 ? fp[l % period].p : nullptr; outs_bf[l] = bits[l % period]; }
+}
+// Chain k's operands in a grouped argument block (GemmArgs, Bf16GemmArgs): group 0 in the plain fields, group k in slot k - 1 of the *x arrays
+template <class G, class T>
+static void set_group(G& g, int k, const T* A, const T* B, float* C, const float* bias, uint16_t* Cb) {
+    if (k == 0) { g.A = A; g.B = B; g.C = C; g.bias = bias; g.Cb = Cb; }
+    else { g.Ax[k - 1] = A; g.Bx[k - 1] = B; g.Cx[k - 1] = C; g.biasx[k - 1] = bias; g.Cbx[k - 1] = Cb; }
+}
+
+// Layer 0 of one fp32 chain through l0_select_kernel: the sums are kept for the next ply, or derived from those kept last time
+static int l0_select_forward(xq_dqn* d, const ChainJob& job, int n) {
+    const int H = d->L[1];
+    ProfScope ps(d, "l0_forward_gather", 2.0 * n * 32 * H, (double)n * (96 + (job.sel_keep == 2 ? 4.0 : 32.0) * H * 4 + H * 12), true);
+    xq_dqn::SelKeep& K = d->sel_keep[d->cur == d->stream ? 0 : 1];
+    hipExtLaunchKernelGGL(l0_select_kernel, dim3((n + 3) / 4), dim3(256), 0, d->cur, ps.start(), ps.stop(), 0, job.boards, K.prev_boards.p, d->w0t(job.net),
+                       d->bl(job.net, 0), K.z1.p, job.outs[0], n, H, job.sel_keep == 2 ? 1 : 0);
+    XQ_HIP(hipGetLastError());
+    return XQ_OK;
+}
+// Layer 0 of up to three chains in one gather grid (blockIdx.y = chain), the s' chain derived and the screening shadow riding where they can
+static int l0_forward(xq_dqn* d, const ChainJob* jobs, int njobs, SlotSrc src, int n, const ShadowJob* shadow) {
+    const int H = d->L[1];
+    const bool bf = d->bf16();
+    L0Jobs J; memset(&J, 0, sizeof J);
+    J.njobs = njobs;
+    for (int k = 0; k < njobs; ++k) {
+        J.boards[k] = jobs[k].boards; J.W0T[k] = d->w0t(jobs[k].net); J.b0[k] = d->bl(jobs[k].net, 0);
+        J.out[k] = jobs[k].outs ? jobs[k].outs[0] : nullptr; J.gathered[k] = jobs[k].gathered;
+        if (bf) { J.W0T_bf[k] = d->wl_bf(jobs[k].net, 0); J.out_bf[k] = jobs[k].outs_bf[0]; }
+        else if (d->nl == 2) { J.out_bf[k] = jobs[k].last_bf; if (jobs[k].last_bf && jobs[k].last_bf_frag) J.out_bf_frag = 1; }
+    }
+    // online TD rule on an fp32 net: the s' chain (job 1, same net, same slots) is derived inside job 0's waves
+    // (bf16 net: in the 16-byte gather path only; Double DQN's third chain — the target net — is gathered as before)
+    const bool wide_bf = bf && (H & 7) == 0 && ((H >= 512 && (H & 511) == 0) || (H >= 64 && 512 % H == 0));
+    const bool derive = d->l0_derive && njobs >= 2 && jobs[0].net == jobs[1].net && jobs[1].gathered == nullptr &&
+                        (bf ? wide_bf : (njobs == 2 && (H & 3) == 0));
+    J.derive_next = derive ? 1 : 0;
+    J.nrows = njobs - (derive ? 1 : 0);
+    // the screening shadow of the output-layer weights rides in the same grid (one more row of blocks) when the grid is wide
+    // enough for it; a launch of its own otherwise
+    const bool ride = shadow && shadow->nblocks <= (n + 3) / 4;
+    if (ride) J.shadow = *shadow;
+    else if (shadow) {
+        hipLaunchKernelGGL(screen_shadow_kernel, dim3(shadow->nblocks), dim3(256), 0, d->cur, *shadow);
+        XQ_HIP(hipGetLastError());
+    }
+    ProfScope ps(d, "l0_forward_gather", 2.0 * njobs * n * 32 * H, (double)njobs * n * (48 + 32.0 * H * (bf ? 2 : 4) + H * 4), true);
+    // (grid rows: the job rows that are really gathered, then the shadow row; the kernel tests blockIdx.y == J.nrows for it)
+    if (bf) hipExtLaunchKernelGGL(l0_forward_kernel<true>, dim3((n + 3) / 4, J.nrows), dim3(256), 0, d->cur, ps.start(), ps.stop(), 0, J, src, n, H);
+    else hipExtLaunchKernelGGL(l0_forward_kernel<false>, dim3((n + 3) / 4, J.nrows + (ride ? 1 : 0)), dim3(256), 0, d->cur, ps.start(), ps.stop(), 0, J, src, n, H);
+    XQ_HIP(hipGetLastError());
+    return XQ_OK;
+}
+
+// The hidden products a_{l+1} = tanh(W_l a_l + b_l) of the chains (the groups of one launch); hidden_forward picks the first whose test holds.
+// bf16 net, whole 256 x 128 tiles: the bf16 loop of its own (xq_gemm_dma.hip.h)
+static bool hidden_bf16_dma_shape(const xq_dqn* d, int l, int n) { return (n % kBgBM) == 0 && (d->L[l + 1] % kBgBN) == 0 && (d->L[l] % kBgBK) == 0; }
+static int hidden_bf16_dma(xq_dqn* d, const ChainJob* jobs, int njobs, int l, int n) {
+    Bf16GemmArgs b; memset(&b, 0, sizeof b);
+    b.M = n; b.N = d->L[l + 1]; b.K = d->L[l]; b.lda = b.ldb = d->L[l]; b.k_chunk = b.K;
+    b.ldc = b.ldcb = d->L[l + 1]; b.groups = njobs;
+    for (int k = 0; k < njobs; ++k) {
+        set_group(b, k, jobs[k].outs_bf[l - 1], d->wl_bf(jobs[k].net, l), jobs[k].outs ? jobs[k].outs[l] : nullptr, d->bl(jobs[k].net, l), jobs[k].outs_bf[l]);
+        // the chain's last activations in B-fragment order when only screen_top2_kernel reads them (bf16 net: max / arg-max pass)
+        if (l == d->nl - 2 && jobs[k].last_bf_frag) b.cb_frag_mask |= 1 << k;
+    }
+    return launch_bf16_gemm<L_KCONTIG, L_KCONTIG, BG_TANH>(d, b, njobs, "gemm_hidden_fwd");
+}
+// M, N, K (kdiv = 2: bf16 pairs), the leading dimensions and the group count of layer l's product on the tile kernels
+static GemmArgs hidden_tile_shape(const xq_dqn* d, int njobs, int l, int n, int kdiv) {
+    GemmArgs g; memset(&g, 0, sizeof g);
+    g.M = n; g.N = d->L[l + 1]; g.K = d->L[l] / kdiv;
+    g.grouped = njobs > 1 ? njobs : 0;
+    g.lda = g.ldb = g.K; g.ldc = g.ldcb = d->L[l + 1];
+    return g;
+}
+// bf16 net, any other shape: the tile kernel on bf16 pairs
+static int hidden_bf16_tile(xq_dqn* d, const ChainJob* jobs, int njobs, int l, int n) {
+    if (d->L[l] & 1) return fail(XQ_ERR_INVALID_ARGUMENT, "bf16 Q-net needs even layer widths (layer %d has %d)", l, d->L[l]);
+    GemmArgs g = hidden_tile_shape(d, njobs, l, n, 2);
+    for (int k = 0; k < njobs; ++k)
+        set_group(g, k, reinterpret_cast<const float*>(jobs[k].outs_bf[l - 1]), reinterpret_cast<const float*>(d->wl_bf(jobs[k].net, l)),
+                  jobs[k].outs ? jobs[k].outs[l] : nullptr, d->bl(jobs[k].net, l), jobs[k].outs_bf[l]);
+    return launch_gemm<L_KCONTIG, L_KCONTIG, EPI_BIAS_TANH, DT_BF16>(d, g, 1, "gemm_hidden_fwd");
+}
+// fp32 net, the last hidden product of one chain that asks for it: the select head rides (EPI_HEAD; its k-slabs instead of a_last)
+static int hidden_f32_head(xq_dqn* d, const ChainJob& job, int l, int n) {
+    GemmArgs g = hidden_tile_shape(d, 1, l, n, 1);
+    if ((n & 63) || (g.N & 63) || (g.K & 31) || d->nout() < 128) return fail(XQ_ERR_RUNTIME, "select head cannot ride on this hidden product");
+    set_group(g, 0, job.outs[l - 1], d->wl(job.net, l), job.outs[l], d->bl(job.net, l), nullptr);
+    g.a_vec = vec_ok(g.A, g.lda); g.b_vec = vec_ok(g.B, g.ldb); g.k_chunk = g.K;
+    g.head_W = d->wl(job.net, d->nl - 1); g.head_ldw = g.N;
+    g.head_slabs = job.head_slabs; g.head_slab_stride = (long long)n * 96; g.head_ld = 96;
+    if (!g.a_vec || !g.b_vec || !vec_ok(g.head_W, g.head_ldw)) return fail(XQ_ERR_RUNTIME, "select head: unaligned operand");
+    ProfScope ps(d, "gemm_hidden_fwd", 2.0 * n * g.N * (g.K + 96.0), 4.0 * ((double)n * g.K + (double)g.N * g.K + (double)(g.N / 64) * n * 96), true);
+    hipExtLaunchKernelGGL((gemm_f32_kernel<L_KCONTIG, L_KCONTIG, EPI_HEAD, 1, 1>), dim3(n / 64, g.N / 64, 1), dim3(256), 0, d->cur, ps.start(), ps.stop(), 0, g);
+    XQ_HIP(hipGetLastError());
+    return XQ_OK;
+}
+// fp32 net: the operands of the chains, for the walk and the tile kernel alike; *aligned: every A and B takes 16-byte loads
+static GemmArgs hidden_f32_args(const xq_dqn* d, const ChainJob* jobs, int njobs, int l, int n, bool* aligned) {
+    GemmArgs g = hidden_tile_shape(d, njobs, l, n, 1);
+    *aligned = true;
+    for (int k = 0; k < njobs; ++k) {
+        uint16_t* cb = (l == d->nl - 2) ? jobs[k].last_bf : nullptr;
+        if (cb && jobs[k].last_bf_frag) g.cb_frag = 1;
+        set_group(g, k, jobs[k].outs[l - 1], d->wl(jobs[k].net, l), jobs[k].outs[l], d->bl(jobs[k].net, l), cb);
+        *aligned = *aligned && vec_ok(jobs[k].outs[l - 1], g.lda) && vec_ok(d->wl(jobs[k].net, l), g.ldb);
+    }
+    return g;
+}
+// fp32 net, whole 128-row x 128-column tiles, not the select chain: the persistent walk (gemm_fwd_persistent_kernel; same bits as the
+// tile kernel).  8192 x 512 x 512 x 2 chains: 90 -> 76 us (128 x 128 tiles, 2 blocks per CU walk 512 tiles); 8192 x 256 x 256 x 2:
+// 27.5 -> 26.3 us (64 x 128 tiles) — tools/f32_fwd_probe.hip.  stop_ev: the event the trainer's select chain waits for rides on this
+// kernel's own completion signal when it is the last of the chains on the handle's stream (no marker packet: ~1.5 us less than a record,
+// tools/sync_probe.hip variant 5) — taken = cleared; a launch that is being timed carries the profiler's events and leaves it to the caller
+static int hidden_f32_walk(xq_dqn* d, GemmArgs g, int l, hipEvent_t* stop_ev) {
+    const int n = g.M, groups = g.grouped > 1 ? g.grouped : 1;
+    const bool big = (n / 128) * (g.N / 128) * groups >= 512;              // 128 x 128 tiles, else 64 x 128
+    const int tiles_m = big ? n / 128 : n / 64, total = tiles_m * (g.N / 128) * groups;
+    g.k_chunk = g.K; g.a_vec = g.b_vec = 1;
+    ProfScope ps(d, "gemm_hidden_fwd", 2.0 * n * (double)g.N * g.K * groups, 4.0 * groups * ((double)n * g.K + (double)g.N * g.K + (double)n * g.N), true);
+    hipEvent_t stop = ps.stop();
+    if (!stop && stop_ev && l == d->nl - 2 && d->cur == d->stream) { stop = *stop_ev; *stop_ev = nullptr; }
+    hipExtLaunchKernelGGL(big ? gemm_fwd_persistent_kernel<2, 2, 2> : gemm_fwd_persistent_kernel<1, 2, 2>, dim3(std::min(total, 2 * d->ncu)), dim3(256), 0,
+                          d->cur, ps.start(), stop, 0, g, tiles_m, g.N / 128, total);
+    XQ_HIP(hipGetLastError());
+    return XQ_OK;
+}
+static int hidden_forward(xq_dqn* d, const ChainJob* jobs, int njobs, int l, int n, hipEvent_t* stop_ev) {
+    if (d->bf16()) return hidden_bf16_dma_shape(d, l, n) ? hidden_bf16_dma(d, jobs, njobs, l, n) : hidden_bf16_tile(d, jobs, njobs, l, n);
+    if (l == d->nl - 2 && njobs == 1 && jobs[0].head_slabs) return hidden_f32_head(d, jobs[0], l, n);
+    bool aligned = true;
+    const GemmArgs g = hidden_f32_args(d, jobs, njobs, l, n, &aligned);
+    if (aligned && !d->small_tiles && !d->tail_open && (n % 128) == 0 && (g.N % 128) == 0 && (g.K % GBK) == 0) return hidden_f32_walk(d, g, l, stop_ev);
+    return launch_gemm<L_KCONTIG, L_KCONTIG, EPI_BIAS_TANH>(d, g, 1, "gemm_hidden_fwd");       // any other shape, and the select chain: the tile kernel
+}
+
+// The forward chains of a launch group.  stop_ev (optional): see hidden_f32_walk — still set on return when no product could take it
+static int chain_boards(xq_dqn* d, const ChainJob* jobs, int njobs, SlotSrc src, int n, const ShadowJob* shadow = nullptr, hipEvent_t* stop_ev = nullptr) {
     if (d->L[0] != kStateSize) return fail(XQ_ERR_INVALID_ARGUMENT, "board input needs layer_sizes[0] == 1260 (got %d)", d->L[0]);
     if (njobs < 1 || njobs > kMaxChains) return fail(XQ_ERR_INVALID_ARGUMENT, "1..3 forward chains per launch group");
-    const bool bf = d->bf16();
-    if (njobs == 1 && jobs[0].sel_keep && !bf && !shadow && !src.implicit && !src.slots) {
-        const int H = d->L[1];
-        ProfScope ps(d, "l0_forward_gather", 2.0 * n * 32 * H, (double)n * (96 + (jobs[0].sel_keep == 2 ? 4.0 : 32.0) * H * 4 + H * 12), true);
-        xq_dqn::SelKeep& K = d->sel_keep[d->cur == d->stream ? 0 : 1];
-        hipExtLaunchKernelGGL(l0_select_kernel, dim3((n + 3) / 4), dim3(256), 0, d->cur, ps.start(), ps.stop(), 0, jobs[0].boards, K.prev_boards.p, d->w0t(jobs[0].net),
-                           d->bl(jobs[0].net, 0), K.z1.p, jobs[0].outs[0], n, H, jobs[0].sel_keep == 2 ? 1 : 0);
-        XQ_HIP(hipGetLastError());
-    } else
-    {
-        const int H = d->L[1];
-        L0Jobs J; memset(&J, 0, sizeof J);
-        J.njobs = njobs;
-        for (int k = 0; k < njobs; ++k) {
-            J.boards[k] = jobs[k].boards; J.W0T[k] = d->w0t(jobs[k].net); J.b0[k] = d->bl(jobs[k].net, 0);
-            J.out[k] = jobs[k].outs ? jobs[k].outs[0] : nullptr; J.gathered[k] = jobs[k].gathered;
-            if (bf) { J.W0T_bf[k] = d->wl_bf(jobs[k].net, 0); J.out_bf[k] = jobs[k].outs_bf[0]; }
-            else if (d->nl == 2) { J.out_bf[k] = jobs[k].last_bf; if (jobs[k].last_bf && jobs[k].last_bf_frag) J.out_bf_frag = 1; }
-        }
-        // the screening shadow of the output-layer weights rides in the same grid (one more row of blocks) when the grid is wide
-        // enough for it; a launch of its own otherwise
-        // online TD rule on an fp32 net: the s' chain (job 1, same net, same slots) is derived inside job 0's waves
-        // (bf16 net: in the 16-byte gather path only; Double DQN's third chain — the target net — is gathered as before)
-        const bool wide_bf = bf && (H & 7) == 0 && ((H >= 512 && (H & 511) == 0) || (H >= 64 && 512 % H == 0));
-        const bool derive = d->l0_derive && njobs >= 2 && jobs[0].net == jobs[1].net && jobs[1].gathered == nullptr &&
-                            (bf ? wide_bf : (njobs == 2 && (H & 3) == 0));
-        J.derive_next = derive ? 1 : 0;
-        J.nrows = njobs - (derive ? 1 : 0);
-        bool ride = false;
-        if (shadow) {
-            const int sblocks = shadow->nblocks;
-            ride = sblocks <= (n + 3) / 4;
-            if (ride) J.shadow = *shadow;
-            else {
-                hipLaunchKernelGGL(screen_shadow_kernel, dim3(sblocks), dim3(256), 0, d->cur, *shadow);
-                XQ_HIP(hipGetLastError());
-            }
-        }
-        ProfScope ps(d, "l0_forward_gather", 2.0 * njobs * n * 32 * H, (double)njobs * n * (48 + 32.0 * H * (bf ? 2 : 4) + H * 4), true);
-        // (grid rows: the job rows that are really gathered, then the shadow row; the kernel tests blockIdx.y == J.nrows for it)
-        if (bf) hipExtLaunchKernelGGL(l0_forward_kernel<true>, dim3((n + 3) / 4, J.nrows), dim3(256), 0, d->cur, ps.start(), ps.stop(), 0, J, src, n, H);
-        else hipExtLaunchKernelGGL(l0_forward_kernel<false>, dim3((n + 3) / 4, J.nrows + (ride ? 1 : 0)), dim3(256), 0, d->cur, ps.start(), ps.stop(), 0, J, src, n, H);
-        XQ_HIP(hipGetLastError());
-    }
-    for (int l = 1; l + 1 < d->nl; ++l) {
-        GemmArgs g; memset(&g, 0, sizeof g);
-        g.M = n; g.N = d->L[l + 1];
-        g.grouped = njobs > 1 ? njobs : 0;
-        if (bf && (n % kBgBM) == 0 && (d->L[l + 1] % kBgBN) == 0 && (d->L[l] % kBgBK) == 0) {
-            // the bf16 loop of its own (xq_gemm_dma.hip.h): whole 256 x 128 tiles only, the chains as groups of one launch
-            Bf16GemmArgs b; memset(&b, 0, sizeof b);
-            b.M = n; b.N = d->L[l + 1]; b.K = d->L[l]; b.lda = b.ldb = d->L[l]; b.k_chunk = b.K;
-            b.ldc = d->L[l + 1]; b.ldcb = d->L[l + 1];
-            b.groups = njobs;
-            for (int k = 0; k < njobs; ++k) {
-                const uint16_t* A = jobs[k].outs_bf[l - 1];
-                const uint16_t* B = d->wl_bf(jobs[k].net, l);
-                float* C = jobs[k].outs ? jobs[k].outs[l] : nullptr;
-                if (k == 0) { b.A = A; b.B = B; b.C = C; b.bias = d->bl(jobs[k].net, l); b.Cb = jobs[k].outs_bf[l]; }
-                else { b.Ax[k - 1] = A; b.Bx[k - 1] = B; b.Cx[k - 1] = C; b.biasx[k - 1] = d->bl(jobs[k].net, l); b.Cbx[k - 1] = jobs[k].outs_bf[l]; }
-                // the chain's last activations in B-fragment order when only screen_top2_kernel reads them (bf16 net: max / arg-max pass)
-                if (l == d->nl - 2 && jobs[k].last_bf_frag) b.cb_frag_mask |= 1 << k;
-            }
-            XQ_TRY((launch_bf16_gemm<L_KCONTIG, L_KCONTIG, BG_TANH>(d, b, njobs, "gemm_hidden_fwd")));
-        } else if (bf) {
-            if (d->L[l] & 1) return fail(XQ_ERR_INVALID_ARGUMENT, "bf16 Q-net needs even layer widths (layer %d has %d)", l, d->L[l]);
-            g.K = d->L[l] / 2; g.lda = g.ldb = d->L[l] / 2;
-            g.ldc = d->L[l + 1]; g.ldcb = d->L[l + 1];
-            for (int k = 0; k < njobs; ++k) {
-                const float* A = reinterpret_cast<const float*>(jobs[k].outs_bf[l - 1]);
-                const float* B = reinterpret_cast<const float*>(d->wl_bf(jobs[k].net, l));
-                float* C = jobs[k].outs ? jobs[k].outs[l] : nullptr;
-                if (k == 0) { g.A = A; g.B = B; g.C = C; g.bias = d->bl(jobs[k].net, l); g.Cb = jobs[k].outs_bf[l]; }
-                else { g.Ax[k - 1] = A; g.Bx[k - 1] = B; g.Cx[k - 1] = C; g.biasx[k - 1] = d->bl(jobs[k].net, l); g.Cbx[k - 1] = jobs[k].outs_bf[l]; }
-            }
-            XQ_TRY((launch_gemm<L_KCONTIG, L_KCONTIG, EPI_BIAS_TANH, DT_BF16>(d, g, 1, "gemm_hidden_fwd")));
-        } else {
-            g.K = d->L[l]; g.lda = g.ldb = d->L[l]; g.ldc = d->L[l + 1]; g.ldcb = d->L[l + 1];
-            if (l == d->nl - 2 && njobs == 1 && jobs[0].head_slabs) {
-                if ((n & 63) || (g.N & 63) || (g.K & 31) || d->nout() < 128) return fail(XQ_ERR_RUNTIME, "select head cannot ride on this hidden product");
-                g.A = jobs[0].outs[l - 1]; g.B = d->wl(jobs[0].net, l); g.C = jobs[0].outs[l]; g.bias = d->bl(jobs[0].net, l);
-                g.a_vec = vec_ok(g.A, g.lda); g.b_vec = vec_ok(g.B, g.ldb); g.k_chunk = g.K;
-                g.head_W = d->wl(jobs[0].net, d->nl - 1); g.head_ldw = g.N;
-                g.head_slabs = jobs[0].head_slabs; g.head_slab_stride = (long long)n * 96; g.head_ld = 96;
-                if (!g.a_vec || !g.b_vec || !vec_ok(g.head_W, g.head_ldw)) return fail(XQ_ERR_RUNTIME, "select head: unaligned operand");
-                ProfScope ps(d, "gemm_hidden_fwd", 2.0 * n * g.N * (g.K + 96.0), 4.0 * ((double)n * g.K + (double)g.N * g.K + (double)(g.N / 64) * n * 96), true);
-                hipExtLaunchKernelGGL((gemm_f32_kernel<L_KCONTIG, L_KCONTIG, EPI_HEAD, 1, 1>), dim3(n / 64, g.N / 64, 1), dim3(256), 0, d->cur, ps.start(), ps.stop(), 0, g);
-                XQ_HIP(hipGetLastError());
-                continue;
-            }
-            bool aligned = true;
-            for (int k = 0; k < njobs; ++k) {
-                uint16_t* cb = (l == d->nl - 2) ? jobs[k].last_bf : nullptr;
-                if (cb && jobs[k].last_bf_frag) g.cb_frag = 1;
-                if (k == 0) { g.A = jobs[k].outs[l - 1]; g.B = d->wl(jobs[k].net, l); g.C = jobs[k].outs[l]; g.bias = d->bl(jobs[k].net, l); g.Cb = cb; }
-                else { g.Ax[k - 1] = jobs[k].outs[l - 1]; g.Bx[k - 1] = d->wl(jobs[k].net, l); g.Cx[k - 1] = jobs[k].outs[l]; g.biasx[k - 1] = d->bl(jobs[k].net, l); g.Cbx[k - 1] = cb; }
-                aligned = aligned && vec_ok(jobs[k].outs[l - 1], g.lda) && vec_ok(d->wl(jobs[k].net, l), g.ldb);
-            }
-            // whole 128-row x 128-column tiles on the handle's stream: the persistent walk (gemm_fwd_persistent_kernel; same bits as the
-            // tile kernel).  8192 x 512 x 512 x 2 chains: 90 -> 76 us (128 x 128 tiles, 2 blocks per CU walk 512 tiles); 8192 x 256 x
-            // 256 x 2: 27.5 -> 26.3 us (64 x 128 tiles) — tools/f32_fwd_probe.hip.  The select chain keeps the 64 x 64 tile kernel.
-            if (aligned && !d->small_tiles && !d->tail_open && (n % 128) == 0 && (g.N % 128) == 0 && (g.K % GBK) == 0) {
-                const int groups = njobs;
-                const int t128 = (n / 128) * (g.N / 128) * groups;
-                g.k_chunk = g.K; g.a_vec = g.b_vec = 1;
-                ProfScope ps(d, "gemm_hidden_fwd", 2.0 * n * (double)g.N * g.K * groups,
-                             4.0 * groups * ((double)n * g.K + (double)g.N * g.K + (double)n * g.N), true);
-                // the event the trainer's select chain waits for rides on this kernel's own completion signal when it is the last of
-                // the chains (no marker packet on the stream: ~1.5 us less than a record, tools/sync_probe.hip variant 5)
-                // (a launch that is being timed carries the profiler's events instead: the fork is then recorded by the caller)
-                hipEvent_t stop = (l == d->nl - 2 && d->cur == d->stream && !ps.stop()) ? d->fwd_stop_ev : nullptr;
-                if (stop) d->fwd_stop_ev = nullptr;
-                hipEvent_t start = ps.start();
-                if (ps.stop()) stop = ps.stop();
-                if (t128 >= 512) {
-                    hipExtLaunchKernelGGL((gemm_fwd_persistent_kernel<2, 2, 2>), dim3(std::min(t128, 2 * d->ncu)), dim3(256), 0, d->cur, start, stop, 0,
-                                          g, n / 128, g.N / 128, t128);
-                } else {
-                    const int total = (n / 64) * (g.N / 128) * groups;
-                    hipExtLaunchKernelGGL((gemm_fwd_persistent_kernel<1, 2, 2>), dim3(std::min(total, 2 * d->ncu)), dim3(256), 0, d->cur, start, stop, 0,
-                                          g, n / 64, g.N / 128, total);
-                }
-                XQ_HIP(hipGetLastError());
-                continue;
-            }
-            XQ_TRY((launch_gemm<L_KCONTIG, L_KCONTIG, EPI_BIAS_TANH>(d, g, 1, "gemm_hidden_fwd")));
-        }
-    }
+    if (njobs == 1 && jobs[0].sel_keep && !d->bf16() && !shadow && !src.implicit && !src.slots) XQ_TRY(l0_select_forward(d, jobs[0], n));
+    else XQ_TRY(l0_forward(d, jobs, njobs, src, n, shadow));
+    for (int l = 1; l + 1 < d->nl; ++l) XQ_TRY(hidden_forward(d, jobs, njobs, l, n, stop_ev));
     return XQ_OK;
 }
 
@@ -612,25 +636,32 @@ static int head_slabs(xq_dqn* d, size_t floats, float** slab) {
     *slab = b;
     return XQ_OK;
 }
+// q[m][0..n_out) = tanh(the ordered sum of the head's k-slabs + bias) (q_head_finish_kernel); name != nullptr: bracketed under it
+static int q_head_finish(xq_dqn* d, const float* slab, long long slab_stride, int nslabs, int n, int n_out, int nc, const float* bias, float* q, int ldq,
+                         const char* name = nullptr) {
+    ProfScope ps(d, name, (double)n * n_out * nslabs, 4.0 * n * n_out * (nslabs + 1));
+    hipLaunchKernelGGL(q_head_finish_kernel, dim3((unsigned)(((long long)n * n_out + 255) / 256)), dim3(256), 0, d->cur, slab, slab_stride, nslabs, n, n_out, nc,
+                       bias, q, ldq);
+    XQ_HIP(hipGetLastError());
+    return XQ_OK;
+}
 
 // Q head on the first n_out outputs: q[m][0..n_out) = tanh(W_out[0:n_out] a_last + b_out); a_last_bf != nullptr: bf16 operands
 // (weights from the shadow), fp32 result (the output layer is never rounded)
 static int q_head(xq_dqn* d, int net, const float* a_last, int n, int n_out, float* q, int ldq, const char* name,
                   const uint16_t* a_last_bf = nullptr) {
     GemmArgs g; memset(&g, 0, sizeof g);
+    g.M = n; g.N = n_out; g.bias = d->bl(net, d->nl - 1);
     if (a_last_bf) {
-        g.M = n; g.N = n_out; g.K = d->hlast() / 2;
+        g.K = d->hlast() / 2;
         g.A = reinterpret_cast<const float*>(a_last_bf); g.lda = d->hlast() / 2;
         g.B = reinterpret_cast<const float*>(d->wl_bf(net, d->nl - 1)); g.ldb = d->hlast() / 2;
         g.C = q; g.ldc = ldq;
-        g.bias = d->bl(net, d->nl - 1);
-        XQ_TRY((launch_gemm<L_KCONTIG, L_KCONTIG, EPI_BIAS_TANH, DT_BF16>(d, g, 1, name)));
-        return XQ_OK;
+        return launch_gemm<L_KCONTIG, L_KCONTIG, EPI_BIAS_TANH, DT_BF16>(d, g, 1, name);
     }
-    g.M = n; g.N = n_out; g.K = d->hlast();
+    g.K = d->hlast();
     g.A = a_last; g.lda = d->hlast();
     g.B = d->wl(net, d->nl - 1); g.ldb = d->hlast();
-    g.bias = d->bl(net, d->nl - 1);
     g.libm_tanh = 1;                     // the output layer's tanh stays libm's (as in q_head_finish_kernel / the env kernel / the TD kernels)
     // The select head (selectAction reads q[action.to] only, dqn.cpp:47): 8192 x 96 x K is two column tiles of 64 — 256 blocks, one per
     // CU, each walking all K / 32 k-tiles behind one another with nothing to hide the load latency behind (20 us at K = 256, 32 us at
@@ -646,24 +677,16 @@ static int q_head(xq_dqn* d, int net, const float* a_last, int n, int n_out, flo
         XQ_TRY(head_slabs(d, need, &slab));
         g.C = slab; g.ldc = nc; g.slab_stride = (long long)n * nc;
         XQ_TRY((launch_gemm<L_KCONTIG, L_KCONTIG, EPI_STORE>(d, g, nslabs, name, nullptr, true)));
-        const long long total = (long long)n * n_out;
-        hipLaunchKernelGGL(q_head_finish_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, d->cur, slab, g.slab_stride, nslabs, n, n_out, nc,
-                           g.bias, q, ldq);
-        XQ_HIP(hipGetLastError());
-        return XQ_OK;
+        return q_head_finish(d, slab, g.slab_stride, nslabs, n, n_out, nc, g.bias, q, ldq);
     }
     g.C = q; g.ldc = ldq;
-    XQ_TRY((launch_gemm<L_KCONTIG, L_KCONTIG, EPI_BIAS_TANH>(d, g, 1, name)));
-    return XQ_OK;
+    return launch_gemm<L_KCONTIG, L_KCONTIG, EPI_BIAS_TANH>(d, g, 1, name);
 }
 
 static int ensure_select_capacity(xq_dqn* d, int n) {
     for (int l = 0; l + 1 < d->nl; ++l) XQ_TRY(d->sel_acts[l].reserve((size_t)n * d->L[l + 1]));
-    return d->sel_q90.reserve((size_t)n * 96);
-}
-static int ensure_select_capacity_bf(xq_dqn* d, int n) {
-    if (!d->bf16()) return XQ_OK;
-    for (int l = 0; l + 1 < d->nl; ++l) XQ_TRY(d->sel_acts_bf[l].reserve((size_t)round_up(n, 128) * d->L[l + 1]));
+    XQ_TRY(d->sel_q90.reserve((size_t)n * 96));
+    for (int l = 0; d->bf16() && l + 1 < d->nl; ++l) XQ_TRY(d->sel_acts_bf[l].reserve((size_t)round_up(n, 128) * d->L[l + 1]));
     return XQ_OK;
 }
 
@@ -674,67 +697,50 @@ int dqn_q90_boards(xq_dqn* d, const uint32_t* boards_dev, int n, float** q90_dev
     if (qs) memset(qs, 0, sizeof *qs);
     float* outs[XQ_MAX_LAYERS];
     uint16_t* outs_bf[XQ_MAX_LAYERS] = {nullptr};
-    float* q = nullptr;
     const bool bf = d->bf16();
-    if (on) {
-        XQ_TRY(ensure_select_capacity(d, n));
-        XQ_TRY(ensure_select_capacity_bf(d, n));
-        for (int l = 0; l + 1 < d->nl; ++l) { outs[l] = bf ? nullptr : d->sel_acts[l]; outs_bf[l] = d->sel_acts_bf[l]; }
-        q = d->sel_q90;
-        d->cur = on;
-        d->small_tiles = true;
-    } else {
+    if (on) XQ_TRY(ensure_select_capacity(d, n));
+    else {
         XQ_TRY(ensure_capacity(d, n));
         XQ_TRY(ensure_ext_capacity(d, n, false));
-        for (int l = 0; l + 1 < d->nl; ++l) { outs[l] = bf ? nullptr : d->acts[l]; outs_bf[l] = d->acts_bf[l]; }
-        q = d->q90;
     }
+    chain_views(d, on ? d->sel_acts : d->acts, on ? d->sel_acts_bf : d->acts_bf, XQ_MAX_LAYERS, !bf, outs, outs_bf);
+    float* q = on ? d->sel_q90 : d->q90;
+    OnStream on_stream(d, on ? on : d->cur);          // restored on every way out, like the tile choice
+    SmallTiles small(d, on != nullptr);
     ChainJob job{XQ_NET_ONLINE, boards_dev, outs, outs_bf, nullptr};
     // layer-0 sums kept from ply to ply (xq_dqn_set_l0_derive) — when that pays: keeping costs 16 MB of stores per call, deriving saves
     // ~20 row reads per board, so it is used from the second call of an update period on and, once a period had several calls, from
     // its first (one ply per update, the headline: never; bench --config 4, four plies: 0.976 -> 0.964 ms)
     xq_dqn::SelKeep& K = d->sel_keep[on ? 1 : 0];
     K.calls += 1;
-    bool kept = false;
-    int rc = XQ_OK;
-    if (d->l0_derive && !bf && (d->L[1] & 3) == 0 && (K.pays || K.calls >= 2)) {
+    const bool kept = d->l0_derive && !bf && (d->L[1] & 3) == 0 && (K.pays || K.calls >= 2);
+    if (kept) {
         if ((size_t)n * d->L[1] > K.z1.n) K.valid = false;          // new buffers keep nothing (nor does a growth that fails)
-        rc = K.z1.reserve((size_t)n * d->L[1]);
-        if (rc == XQ_OK) rc = K.prev_boards.reserve((size_t)n * kBoardWords);
         job.sel_keep = (K.valid && K.boards == boards_dev && K.n == n) ? 2 : 1;
-        K.valid = false;                   // true again once the launch that keeps the sums has been queued
-        kept = true;
+        K.valid = false;                   // true again once every launch of this call has been queued
+        XQ_TRY(K.z1.reserve((size_t)n * d->L[1]));
+        XQ_TRY(K.prev_boards.reserve((size_t)n * kBoardWords));
     }
     // fp32 net with >= 2 hidden layers, whole 64 x 64 tiles, the batch sizes q_head splits into k-slabs: the head rides on the last hidden
     // product (same slabs, same bits) — its operand never goes to HBM and back (2 x 17 MB at 8192 x 512), one launch fewer per ply
     const int Hl = d->hlast();
     const bool ride = !bf && d->nl >= 3 && n >= 2048 && (n & 63) == 0 && (Hl % 128) == 0 && (d->L[d->nl - 2] & 31) == 0 && d->nout() >= 128 &&
                       vec_ok(d->wl(XQ_NET_ONLINE, d->nl - 1), Hl) && vec_ok(d->wl(XQ_NET_ONLINE, d->nl - 2), d->L[d->nl - 2]);
-    if (rc == XQ_OK && ride) {
+    if (ride) {
         const int nslabs = Hl / 64;
         float* slab = nullptr;
-        rc = head_slabs(d, (size_t)nslabs * n * 96, &slab);
+        XQ_TRY(head_slabs(d, (size_t)nslabs * n * 96, &slab));
         job.head_slabs = slab;
-        float* keep = outs[d->nl - 2];
         outs[d->nl - 2] = nullptr;                       // nobody else reads the select chain's last activations
-        if (rc == XQ_OK) rc = chain_boards(d, &job, 1, explicit_slots(nullptr), n);
-        outs[d->nl - 2] = keep;
-        if (rc == XQ_OK && qs) {                         // the env kernel finishes the values it needs itself
+        XQ_TRY(chain_boards(d, &job, 1, explicit_slots(nullptr), n));
+        if (qs) {                                        // the env kernel finishes the values it needs itself
             qs->slabs = slab; qs->slab_stride = (long long)n * 96; qs->nslabs = nslabs; qs->bias = d->bl(XQ_NET_ONLINE, d->nl - 1);
             q = nullptr;
-        } else if (rc == XQ_OK) {
-            ProfScope ps(d, "gemm_q90_select", (double)n * 96 * nslabs, 4.0 * n * 96 * (nslabs + 1));
-            hipLaunchKernelGGL(q_head_finish_kernel, dim3((unsigned)(((long long)n * 96 + 255) / 256)), dim3(256), 0, d->cur, slab, (long long)n * 96,
-                               nslabs, n, 96, 96, d->bl(XQ_NET_ONLINE, d->nl - 1), q, 96);
-            if (hipGetLastError() != hipSuccess) rc = fail(XQ_ERR_RUNTIME, "q_head_finish_kernel launch failed");
-        }
-    } else if (rc == XQ_OK) {
-    rc = chain_boards(d, &job, 1, explicit_slots(nullptr), n);
-    if (rc == XQ_OK) rc = q_head(d, XQ_NET_ONLINE, outs[d->nl - 2], n, 96, q, 96, "gemm_q90_select", bf ? outs_bf[d->nl - 2] : nullptr);
+        } else XQ_TRY(q_head_finish(d, slab, (long long)n * 96, nslabs, n, 96, 96, d->bl(XQ_NET_ONLINE, d->nl - 1), q, 96, "gemm_q90_select"));
+    } else {
+        XQ_TRY(chain_boards(d, &job, 1, explicit_slots(nullptr), n));
+        XQ_TRY(q_head(d, XQ_NET_ONLINE, outs[d->nl - 2], n, 96, q, 96, "gemm_q90_select", bf ? outs_bf[d->nl - 2] : nullptr));
     }
-    d->cur = d->stream;
-    d->small_tiles = false;
-    XQ_TRY(rc);
     if (kept) { K.valid = true; K.boards = boards_dev; K.n = n; }
     *q90_dev = q;
     *q_stride = 96;
@@ -1361,15 +1367,10 @@ static int chain_dense(xq_dqn* d, int net, const float* x, int n, float* const* 
     g.libm_tanh = !XQ_L0_FAST_TANH;      // layer 0 takes the SAME tanh on both routes (tanh_l0 in the packed-board gather kernels): a dense
                                          // one-hot and the board it encodes then differ by summation order only
     XQ_TRY((launch_gemm<L_KCONTIG, L_MCONTIG, EPI_BIAS_TANH>(d, g, 1, "gemm_l0_dense_fwd")));
-    for (int l = 1; l + 1 < d->nl; ++l) {
-        GemmArgs h; memset(&h, 0, sizeof h);
-        h.M = n; h.N = d->L[l + 1]; h.K = d->L[l];
-        h.A = outs[l - 1]; h.lda = d->L[l];
-        h.B = d->wl(net, l); h.ldb = d->L[l];
-        h.C = outs[l]; h.ldc = d->L[l + 1];
-        h.bias = d->bl(net, l);
-        XQ_TRY((launch_gemm<L_KCONTIG, L_KCONTIG, EPI_BIAS_TANH>(d, h, 1, "gemm_hidden_fwd")));
-    }
+    const ChainJob job{net, nullptr, outs};          // the hidden layers: the fp32 tile product of chain_boards with one chain
+    bool aligned;
+    for (int l = 1; l + 1 < d->nl; ++l)
+        XQ_TRY((launch_gemm<L_KCONTIG, L_KCONTIG, EPI_BIAS_TANH>(d, hidden_f32_args(d, &job, 1, l, n, &aligned), 1, "gemm_hidden_fwd")));
     return XQ_OK;
 }
 
@@ -1406,7 +1407,7 @@ int xq_dqn_forward_boards_dev(xq_dqn* d, int net, const uint32_t* boards_dev, in
     XQ_TRY(ensure_ext_capacity(d, n, false));
     float* outs[XQ_MAX_LAYERS];
     uint16_t* outs_bf[XQ_MAX_LAYERS] = {nullptr};
-    for (int l = 0; l + 1 < d->nl; ++l) { outs[l] = d->acts[l]; outs_bf[l] = d->acts_bf[l]; }
+    chain_views(d, d->acts, d->acts_bf, XQ_MAX_LAYERS, true, outs, outs_bf);
     ChainJob job{net, boards_dev, outs, outs_bf, nullptr};
     XQ_TRY(chain_boards(d, &job, 1, explicit_slots(nullptr), n));
     return q_head(d, net, outs[d->nl - 2], n, n_out, q_dev, ldq, n_out <= 96 ? "gemm_q90_select" : "gemm_q_full",
@@ -1983,11 +1984,9 @@ static int td_grads_impl(xq_dqn* d, const uint32_t* boards, const uint32_t* next
     TdStep s;
     s.action_to = action_to; s.reward = reward; s.done = done; s.slots = slots; s.per = per;
     s.n = n; s.mode = mode; s.nl = nl; s.Hl = Hl; s.NO = NO; s.dbl = dbl; s.bf = bf; s.sel_net = td_net == XQ_TD_TARGET_NET ? XQ_NET_TARGET : XQ_NET_ONLINE;
-    for (int l = 0; l + 1 < nl; ++l) {
-        s.outs[l] = d->acts[l]; s.outs_bf[l] = d->acts_bf[l];
-        s.touts[l] = bf ? nullptr : d->tacts[l & 1]; s.touts_bf[l] = d->tacts_bf[l & 1];
-        s.t2outs[l] = bf ? nullptr : d->t2acts[l & 1]; s.t2outs_bf[l] = d->t2acts_bf[l & 1];
-    }
+    chain_views(d, d->acts, d->acts_bf, XQ_MAX_LAYERS, true, s.outs, s.outs_bf);
+    chain_views(d, d->tacts, d->tacts_bf, 2, !bf, s.touts, s.touts_bf);
+    chain_views(d, d->t2acts, d->t2acts_bf, 2, !bf, s.t2outs, s.t2outs_bf);
     // the max pass is launched transposed (rows = output neurons, columns = samples): the max over the 8100 outputs then runs over
     // accumulator registers inside one lane instead of across the 32 lanes of a row
     s.big_tiles = (long long)((NO + 127) / 128) * ((n + 127) / 128) >= 512;
@@ -2020,12 +2019,9 @@ static int td_grads_impl(xq_dqn* d, const uint32_t* boards, const uint32_t* next
     // the step no difference; --config 4 / 5 -0.3 % / -0.9 %.  The product's stop event rather than a marker behind it: 0.1740 -> 0.1728 ms.
     // The full fp32 product keeps the chip to itself: there the chain starts behind it (qmax_exact).
     const bool gate_early = (screened || bf) && !d->late_gate;
-    d->fwd_stop_ev = gate_early ? d->ev_qmax : nullptr;
-    const int chain_rc = chain_boards(d, jobs, dbl ? 3 : 2, slots, n, screened ? &shadow : nullptr);
-    const bool fork_pending = d->fwd_stop_ev != nullptr;            // chain_boards did not take the stop event: a marker instead
-    d->fwd_stop_ev = nullptr;
-    XQ_TRY(chain_rc);
-    if (fork_pending) XQ_HIP(hipEventRecord(d->ev_qmax, d->stream));
+    hipEvent_t fork = gate_early ? d->ev_qmax : nullptr;
+    XQ_TRY(chain_boards(d, jobs, dbl ? 3 : 2, slots, n, screened ? &shadow : nullptr, &fork));
+    if (fork) XQ_HIP(hipEventRecord(fork, d->stream));             // chain_boards did not take the stop event: a marker instead
     // 2. max_a' Q(s', a'); 3. the TD delta, unless the refine kernel did it
     bool td_fused = false;
     if (screened) XQ_TRY(qmax_screened(d, s, scr_new, parity, &td_fused));

@@ -269,6 +269,11 @@ struct Profiler {
     void reset() { collect(); cats.clear(); }
     ~Profiler() { collect(); for (auto e : pool) (void)hipEventDestroy(e); }
 };
+struct ProfilerOff {                  // while one lives, the profiler brackets nothing
+    Profiler& p; bool was;
+    explicit ProfilerOff(Profiler* q) : p(*q), was(q->enabled) { p.enabled = false; }
+    ~ProfilerOff() { p.enabled = was; }
+};
 
 // communicator internals (xq_comm.hip)
 int comm_allreduce_on(xq_comm* c, float* buf, size_t n_floats, hipStream_t stream);   // in-place sum over all ranks

@@ -969,3 +969,22 @@ def test_a_refused_td_step_leaves_nothing_open(xq, tail):
     w1, b1 = d.get_params()
     assert np.array_equal(w1, w.astype(np.float32)) and np.array_equal(b1, b.astype(np.float32))
     d.close()
+
+
+@pytest.mark.gpu
+def test_a_refused_select_query_leaves_the_handle_as_it_was(xq):
+    """40-24-24-96 takes no packed boards: xq_dqn_select_q_dev is refused inside the select chain, after the chain's workspaces and
+    its stream / tile choice were set up.  A dense forward pass on the same handle gives the same bits before and after (nothing is
+    left launching elsewhere or on other tiles), and a further query is refused the same way."""
+    from cn_chess_ai_amd import _capi
+    sizes = [40, 24, 24, 96]
+    d, w, b = make_net(xq, sizes, seed=7)
+    env = xq.VecEnv(8, seed=3)
+    x = np.random.default_rng(4).uniform(-1, 1, size=(5, 40))
+    q_before = d.getQValues(x).copy()
+    for _ in range(2):
+        with pytest.raises(_capi.XqError) as e:
+            d.select_q(env)
+        assert e.value.code == 1 and "board input needs layer_sizes[0] == 1260" in str(e.value)
+        assert np.array_equal(d.getQValues(x), q_before)
+    env.close(); d.close()

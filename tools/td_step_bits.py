@@ -1,6 +1,6 @@
 """The bits and the launches of a TD step over a fixed seeded matrix, and whether another build of the library gives the same ones.
 
-    python tools/td_step_bits.py [--parent OTHER/libxqhip.so]
+    python tools/td_step_bits.py [--forward] [--parent OTHER/libxqhip.so]
 
 Cells: net {1260-128-8100, 1260-256-256-8100, 1260-512-512-512-8100, 1260-127-129-132-8100 (textbook rule)} x minibatch {333: one
 layer-0 chunk, partial tiles; 1100: slabs everywhere, no epilogue planes; and, for the two nets of even 256 / 512 widths, 2048: whole
@@ -10,6 +10,14 @@ when RCCL cannot be loaded}; two TD steps from one seeded self-play batch per ce
 the gradient buffer, Q(s,a), y and the (kernel name, calls) list of xq_dqn_kernel_stats.  The tests compare the paths of one build with
 each other; this compares two builds — the host side of the gradient half decides which kernels run, where their partial sums go and
 who adds them, and a change there that moves every path alike shows only here.
+--forward: a second matrix, over what the host side of the FORWARD half decides (layer-0 form, which hidden product, where the fork
+event comes from): TD rule {online, target, Double} x qmax {full, screened: fp32 net, not Double} x l0_derive {0, 1} x precision {fp32,
+BF16, BF16_FULL} x the three even-width nets x minibatch {333, 1100, 2048: whole 128-row tiles and whole 256-row bf16 tiles; screening
+engages from 897 samples}, hashed like the cells above; per net and batch {333, 2048} a select cell (select_q three times on the same
+boards with l0_derive on: plain, kept and derived layer-0 sums; the Q rows and the kernel list); per net a trainer cell (overlapped
+collect, two plies per update, 2048 games so that the select head rides on the last hidden product, screened maximum, four iterations;
+the final parameters of both nets and the kernel list).  The select cells, the trainer cells and the screened / bf16 TD cells run once
+more with the profiler off and without the kernel list ("prof=0"): only then does the forward product take the fork event itself.
 --parent LIB: the matrix again in a fresh child process on that library (XQ_LIBXQHIP); exit status 1 if any cell differs."""
 import argparse
 import hashlib
@@ -43,15 +51,21 @@ def selfplay_batch(xq, n, seed):
     return S, S2, (res["action"] % 90).astype(np.int32), (res["reward"] / 100.0).astype(np.float32), D
 
 
-def cell(xq, sizes, batch, n, tail, fused, precision, comm):
+def seeded_net(xq, sizes, precision):
     import numpy as np
-    import torch
-    from cn_chess_ai_amd import _capi, dist as xd
     d = xq.DQN(sizes, 0.001, 0.99, seed=5)
     rng = np.random.default_rng(len(sizes) * 1000 + sizes[1])
     d.set_params(rng.uniform(-0.05, 0.05, size=d.n_weights), rng.uniform(-0.05, 0.05, size=d.n_biases))
     d.updateTargetNetwork()
     d.set_precision(precision)
+    return d
+
+
+def cell(xq, sizes, batch, n, tail, fused, precision, comm):
+    import numpy as np
+    import torch
+    from cn_chess_ai_amd import _capi, dist as xd
+    d = seeded_net(xq, sizes, precision)
     d.set_td_tail(tail)
     d.set_fused_apply(fused)
     if comm is not None:
@@ -101,18 +115,118 @@ def matrix():
     return out
 
 
+def kernel_list(d, h, prof):
+    """The (name, calls) list into the hash, and the profiler off again (prof = 0: it never was on, nothing is hashed)."""
+    if prof:
+        h.update(json.dumps(sorted((k["name"], k["launches"]) for k in d.kernel_stats(enable=0))).encode())
+
+
+def forward_td_cell(xq, sizes, batch, n, td_net, screened, derive, precision, prof):
+    import numpy as np
+    import torch
+    from cn_chess_ai_amd import _capi, dist as xd
+    d = seeded_net(xq, sizes, precision)
+    rng = np.random.default_rng(sizes[1] + 7)                  # a target net of its own: the target and Double rules read other weights
+    d.set_params(rng.uniform(-0.05, 0.05, size=d.n_weights), rng.uniform(-0.05, 0.05, size=d.n_biases), net=_capi.NET_TARGET)
+    d.set_qmax_mode(_capi.QMAX_SCREENED if screened else _capi.QMAX_FULL)
+    d.set_l0_derive(derive)
+    h = hashlib.sha256()
+    if prof:
+        d.kernel_stats(enable=2)
+    for _ in range(2):
+        qsa, y = d.td_update(*batch, td_net=td_net, mode=_capi.BACKPROP_REFERENCE, learning_rate=0.05, grad_scale=1.0 / n)
+        h.update(qsa.tobytes()); h.update(y.tobytes())
+    kernel_list(d, h, prof)
+    for x in d.get_params():
+        h.update(np.ascontiguousarray(x).tobytes())
+    ptr, k = d.grad_buffer()
+    torch.cuda.synchronize()
+    h.update(xd.wrap_device_floats(ptr, k).cpu().numpy().tobytes())
+    d.close()
+    return h.hexdigest()
+
+
+def select_cell(xq, sizes, n, prof):
+    from cn_chess_ai_amd import _capi
+    env = xq.VecEnv(n, seed=29)
+    for _ in range(13):
+        env.selfplay_step(None)
+    d = seeded_net(xq, sizes, _capi.PRECISION_F32)
+    d.set_l0_derive(True)
+    h = hashlib.sha256()
+    if prof:
+        d.kernel_stats(enable=2)
+    for _ in range(3):                                 # the first call of a period keeps nothing, the second keeps, the third derives
+        h.update(d.select_q(env).cpu().numpy().tobytes())
+    kernel_list(d, h, prof)
+    env.close(); d.close()
+    return h.hexdigest()
+
+
+def trainer_cell(xq, sizes, prof):
+    import numpy as np
+    from cn_chess_ai_amd import _capi
+    cfg = xq.TrainerConfig(n_games=2048, layer_sizes=sizes, replay_capacity=1 << 14, minibatch=2048, collects_per_update=2,
+                           target_sync_interval=2, td_net=_capi.TD_ONLINE_NET, overlap_collect=1, seed=0x5EED, first_game_id=2048)
+    t = xq.Trainer(cfg)
+    t.dqn.set_qmax_mode(_capi.QMAX_SCREENED)
+    t.dqn.set_l0_derive(True)
+    t.random_plies(20)
+    h = hashlib.sha256()
+    if prof:
+        t.dqn.kernel_stats(enable=2)
+    t.step(4)
+    t.synchronize()
+    kernel_list(t.dqn, h, prof)
+    for net in (_capi.NET_ONLINE, _capi.NET_TARGET):
+        for x in t.dqn.get_params(net=net):
+            h.update(np.ascontiguousarray(x).tobytes())
+    t.close()
+    return h.hexdigest()
+
+
+def forward_matrix():
+    import cn_chess_ai_amd as xq
+    from cn_chess_ai_amd import _capi
+    out = {}
+
+    def run(name, f, *a):
+        out[name] = f(xq, *a)
+        print(out[name], name, flush=True)
+
+    precisions = ((_capi.PRECISION_F32, "fp32"), (_capi.PRECISION_BF16, "bf16"), (_capi.PRECISION_BF16_FULL, "bf16_full"))
+    for sizes in (REF_NET, CFG2_NET, CFG4_NET):
+        net = "-".join(map(str, sizes))
+        for n in (333, 1100, 2048):
+            batch = selfplay_batch(xq, n, seed=83)
+            for td_net, screened, derive, (prec, pname) in itertools.product((0, 1, 2), (0, 1), (0, 1), precisions):
+                if screened and (prec != _capi.PRECISION_F32 or td_net == _capi.TD_DOUBLE):
+                    continue                       # (the screened maximum is defined for the fp32 net and one s' chain: not a cell)
+                for prof in ((1, 0) if screened or prec != _capi.PRECISION_F32 else (1,)):
+                    run("td %s n=%d rule=%d screened=%d derive=%d %s prof=%d" % (net, n, td_net, screened, derive, pname, prof),
+                        forward_td_cell, sizes, batch, n, td_net, screened, derive, prec, prof)
+        for n, prof in itertools.product((333, 2048), (1, 0)):
+            run("select %s n=%d prof=%d" % (net, n, prof), select_cell, sizes, n, prof)
+        for prof in (1, 0):
+            run("trainer %s prof=%d" % (net, prof), trainer_cell, sizes, prof)
+    print("%d cells run" % len(out), flush=True)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--parent")
+    ap.add_argument("--forward", action="store_true", help="the forward-half matrix instead of the gradient-half one")
     ap.add_argument("--json", action="store_true", help="(the child process of --parent) the cells as one JSON line at the end")
     args = ap.parse_args()
-    mine = matrix()
+    mine = forward_matrix() if args.forward else matrix()
     if args.json:
         print("CELLS " + json.dumps(mine), flush=True)
     if not args.parent:
         return 0
     env = dict(os.environ, XQ_LIBXQHIP=os.path.abspath(args.parent))
-    r = subprocess.run([sys.executable, os.path.abspath(__file__), "--json"], env=env, stdout=subprocess.PIPE, text=True, timeout=900)
+    r = subprocess.run([sys.executable, os.path.abspath(__file__), "--json"] + (["--forward"] if args.forward else []), env=env,
+                       stdout=subprocess.PIPE, text=True, timeout=900)
     if r.returncode != 0:
         print("the run on", args.parent, "ended with", r.returncode, flush=True)
         return 1
