@@ -20,6 +20,7 @@ TD_ONLINE_NET, TD_TARGET_NET, TD_DOUBLE = 0, 1, 2
 PRECISION_F32, PRECISION_BF16, PRECISION_BF16_FULL = 0, 1, 2
 QMAX_FULL, QMAX_SCREENED = 0, 1
 OPT_SGD, OPT_ADAM = 0, 1
+LOSS_SQUARED, LOSS_HUBER = 0, 1
 ORDER_RING_CONTENTS, ORDER_RING_PRIORITIES, ORDER_RING_DRAW, ORDER_TRAINER_PARAMS, ORDER_ALL = 1, 2, 4, 8, 15
 
 STATUS_NAMES = {1: "XQ_ERR_INVALID_ARGUMENT", 2: "XQ_ERR_RUNTIME", 3: "XQ_ERR_NO_DEVICE", 4: "XQ_ERR_IO",
@@ -183,6 +184,9 @@ PROTOTYPES = {
     "xq_dqn_set_target_tau": [_vp, _d],
     "xq_dqn_get_target_tau": [_vp, _pd],
     "xq_dqn_soft_update_target": [_vp, _d],
+    "xq_dqn_set_td_loss": [_vp, _i, _d],
+    "xq_dqn_get_td_loss": [_vp, _pi, _pd],
+    "xq_dqn_td_error_stats": [_vp, _pu64, _pd, _pd, _pd, _pu64],
     "xq_dqn_kernel_filter": [_vp, C.c_char_p],
     "xq_dqn_kernel_timeline": [_vp, C.POINTER(KernelSpan), _i, _pi],
     "xq_comm_unique_id": [_pu8],
@@ -230,7 +234,9 @@ LAZY = frozenset(("xq_dqn_set_optimizer", "xq_dqn_get_optimizer", "xq_dqn_reset_
 LAZY_GRAD_CLIP = frozenset(("xq_dqn_set_grad_clip", "xq_dqn_get_grad_clip", "xq_dqn_grad_clip_stats"))
 # ... and the soft target update's
 LAZY_TARGET_TAU = frozenset(("xq_dqn_set_target_tau", "xq_dqn_get_target_tau", "xq_dqn_soft_update_target", "xq_trainer_set_target_tau"))
-_LAZY_ALL = LAZY | LAZY_GRAD_CLIP | LAZY_TARGET_TAU
+# ... and the TD loss's
+LAZY_TD_LOSS = frozenset(("xq_dqn_set_td_loss", "xq_dqn_get_td_loss", "xq_dqn_td_error_stats"))
+_LAZY_ALL = LAZY | LAZY_GRAD_CLIP | LAZY_TARGET_TAU | LAZY_TD_LOSS
 _RESTYPES = {"xq_last_error": C.c_char_p, "xq_env_boards_dev": C.c_void_p, "xq_env_meta_dev": C.c_void_p}
 
 _lib = None

@@ -30,12 +30,14 @@
 #include "xq_l0grad.hip.h"
 
 #include <algorithm>
+#include <cfloat>
 #include <cmath>
+#include <limits>
 #include <mutex>
 #include <random>
 #include <unordered_map>
 
-namespace xq { struct TailArgs; struct ClipRecord; }
+namespace xq { struct TailArgs; struct ClipRecord; struct TdStatsRecord; }
 struct xq_dqn {
     int ns = 0, nl = 0;
     int L[XQ_MAX_LAYERS + 1] = {0};
@@ -147,6 +149,12 @@ struct xq_dqn {
     // net, hence xq_dqn_load_model, and xq_dqn_backpropagate) — then one whole-buffer kernel follows the apply instead
     double target_tau = 0.0;
     bool tgt_rest_synced = false;
+    // TD loss of xq_dqn_td_grads* (xq_dqn_set_td_loss): squared, or Huber with kappa (loss_kappa32 = the float the kernels clamp at; +inf
+    // allowed).  td_stats_rec: the record of td_error_stats_kernel, allocated by the first xq_dqn_td_error_stats
+    int loss_kind = XQ_LOSS_SQUARED;
+    double loss_kappa = 1.0;
+    float loss_kappa32 = 1.0f;
+    xq::DevBuf<xq::TdStatsRecord> td_stats_rec;
     xq::DevBuf<float> slabs;
     xq::DevBuf<float> slabs_l0;                 // layer-0 gradient partials
     // layer-0 gradient on the bf16 matrix pipe (xq_l0grad.hip.h): delta_0 as three bf16 planes, transposed [plane][column][sample]
@@ -1830,10 +1838,19 @@ static int qmax_screened(xq_dqn* d, const TdStep& s, bool scr_new, int parity, b
             }
             // whole groups: 2 = the popular ones through LDS when the launch has room for it, 1 = all of them four per round trip
             const int whole_mode = stage ? 2 : 1;
-            const auto kern = *td_fused ? qmax_refine2_kernel<256, true> : Hl == 256 ? qmax_refine2_kernel<256> : qmax_refine2_kernel<512>;
-            XQ_TRY(ensure_max_dynamic_lds(kern, 152 * 1024));     // the staged pass asks for ~145 KB
-            hipExtLaunchKernelGGL(kern, grid, dim3(256), lds, d->cur, ps.start(), ps.stop(), 0, d->scr_R.p, scr_ranges, scr_gpr, d->scr_p1.p, d->scr_p2.p,
-                                  G, n, ldp, d->scr_na.p, a_last, Hl, W, bias, NO, d->scr_wmax.p, parity, d->zmax.p, d->scr_stats.p, T, whole_mode);
+            if (*td_fused && d->loss_kind == XQ_LOSS_HUBER) {
+                const auto kern = qmax_refine2_kernel<256, true, HuberLoss>;
+                XQ_TRY(ensure_max_dynamic_lds(kern, 152 * 1024));
+                hipExtLaunchKernelGGL(kern, grid, dim3(256), lds, d->cur, ps.start(), ps.stop(), 0, d->scr_R.p, scr_ranges, scr_gpr, d->scr_p1.p, d->scr_p2.p,
+                                      G, n, ldp, d->scr_na.p, a_last, Hl, W, bias, NO, d->scr_wmax.p, parity, d->zmax.p, d->scr_stats.p, T, whole_mode,
+                                      HuberLoss{d->loss_kappa32});
+            } else {
+                const auto kern = *td_fused ? qmax_refine2_kernel<256, true> : Hl == 256 ? qmax_refine2_kernel<256> : qmax_refine2_kernel<512>;
+                XQ_TRY(ensure_max_dynamic_lds(kern, 152 * 1024));     // the staged pass asks for ~145 KB
+                hipExtLaunchKernelGGL(kern, grid, dim3(256), lds, d->cur, ps.start(), ps.stop(), 0, d->scr_R.p, scr_ranges, scr_gpr, d->scr_p1.p, d->scr_p2.p,
+                                      G, n, ldp, d->scr_na.p, a_last, Hl, W, bias, NO, d->scr_wmax.p, parity, d->zmax.p, d->scr_stats.p, T, whole_mode,
+                                      SquaredLoss{});
+            }
         } else {
             const bool small = G <= 8 * 32;
             const auto kern = Hl == 256 ? (small ? qmax_refine_kernel<256, 32> : qmax_refine_kernel<256, 64>)
@@ -1921,9 +1938,15 @@ static int td_delta(xq_dqn* d, const TdStep& s, int zparts) {
         X.is_w = per->is_w; X.is_wmax = per->is_wmax; X.prio = per->prio; X.pmax_live = per->pmax_live;
         X.per_eps = per->eps; X.per_alpha = per->alpha;
     }
-    hipLaunchKernelGGL(td_delta_kernel, dim3((n + 3) / 4), dim3(256), 0, d->cur, n, s.slots, s.action_to, s.reward, s.done,
-                       s.outs[lt], Hl, d->wl(XQ_NET_ONLINE, nl - 1), d->bl(XQ_NET_ONLINE, nl - 1), d->zmax, zparts,
-                       (float)d->gamma, s.view, s.view_ld, s.view_kmax, d->deltas[lt], d->dsc, d->act_mb, d->qsa, d->yv, d->lossv, X);
+    if (d->loss_kind == XQ_LOSS_HUBER)
+        hipLaunchKernelGGL(td_delta_huber_kernel, dim3((n + 3) / 4), dim3(256), 0, d->cur, n, s.slots, s.action_to, s.reward, s.done,
+                           s.outs[lt], Hl, d->wl(XQ_NET_ONLINE, nl - 1), d->bl(XQ_NET_ONLINE, nl - 1), d->zmax, zparts,
+                           (float)d->gamma, s.view, s.view_ld, s.view_kmax, d->deltas[lt], d->dsc, d->act_mb, d->qsa, d->yv, d->lossv, X,
+                           d->loss_kappa32);
+    else
+        hipLaunchKernelGGL(td_delta_kernel, dim3((n + 3) / 4), dim3(256), 0, d->cur, n, s.slots, s.action_to, s.reward, s.done,
+                           s.outs[lt], Hl, d->wl(XQ_NET_ONLINE, nl - 1), d->bl(XQ_NET_ONLINE, nl - 1), d->zmax, zparts,
+                           (float)d->gamma, s.view, s.view_ld, s.view_kmax, d->deltas[lt], d->dsc, d->act_mb, d->qsa, d->yv, d->lossv, X);
     XQ_HIP(hipGetLastError());
     return XQ_OK;
 }
@@ -2258,6 +2281,47 @@ int xq_dqn_grad_clip_stats(xq_dqn* d, double* last_norm, double* last_coef, uint
     if (last_coef) *last_coef = r.coef;
     if (applies) *applies = r.applies;
     if (clipped) *clipped = r.clipped;
+    return XQ_OK;
+}
+
+int xq_dqn_set_td_loss(xq_dqn* d, int kind, double kappa) {
+    if (!d) return fail(XQ_ERR_INVALID_ARGUMENT, "null dqn");
+    if (kind != XQ_LOSS_SQUARED && kind != XQ_LOSS_HUBER) return fail(XQ_ERR_INVALID_ARGUMENT, "xq_dqn_set_td_loss: unknown loss %d", kind);
+    // (the kernels clamp at (float)kappa: one that rounds to 0 there would clamp every error to 0)
+    const float k32 = kappa > (double)FLT_MAX ? std::numeric_limits<float>::infinity() : (float)kappa;
+    if (kind == XQ_LOSS_HUBER && !(kappa > 0.0 && k32 > 0.f))
+        return fail(XQ_ERR_INVALID_ARGUMENT, "xq_dqn_set_td_loss: kappa must be positive or +inf");
+    if (td_step_pending(d)) return fail(XQ_ERR_RUNTIME, "xq_dqn_set_td_loss: a TD step is waiting for its apply_grads");
+    d->loss_kind = kind;
+    if (kind == XQ_LOSS_HUBER) {
+        d->loss_kappa = kappa;
+        d->loss_kappa32 = k32;
+    }
+    return XQ_OK;
+}
+
+int xq_dqn_get_td_loss(const xq_dqn* d, int* kind, double* kappa) {
+    if (!d) return fail(XQ_ERR_INVALID_ARGUMENT, "null dqn");
+    if (kind) *kind = d->loss_kind;
+    if (kappa) *kappa = d->loss_kappa;
+    return XQ_OK;
+}
+
+int xq_dqn_td_error_stats(xq_dqn* d, uint64_t* live, double* mean_abs, double* max_abs, double* mean_loss, uint64_t* linear) {
+    if (!d) return fail(XQ_ERR_INVALID_ARGUMENT, "null dqn");
+    if (d->last_n <= 0) return fail(XQ_ERR_RUNTIME, "xq_dqn_td_error_stats: no TD step has run yet");
+    if (!d->td_stats_rec.p) XQ_TRY(d->td_stats_rec.alloc(1));
+    const float kappa = d->loss_kind == XQ_LOSS_HUBER ? d->loss_kappa32 : std::numeric_limits<float>::infinity();
+    hipLaunchKernelGGL(td_error_stats_kernel, dim3(1), dim3(256), 0, d->stream, d->qsa.p, d->yv.p, d->act_mb.p, d->last_n, kappa, d->td_stats_rec.p);
+    XQ_HIP(hipGetLastError());
+    TdStatsRecord r;
+    XQ_HIP(hipStreamSynchronize(d->stream));
+    XQ_HIP(hipMemcpy(&r, d->td_stats_rec, sizeof r, hipMemcpyDeviceToHost));
+    if (live) *live = r.live;
+    if (mean_abs) *mean_abs = r.live ? r.sum_abs / (double)r.live : 0.0;
+    if (max_abs) *max_abs = r.max_abs;
+    if (mean_loss) *mean_loss = r.live ? r.sum_loss / (double)r.live : 0.0;
+    if (linear) *linear = r.linear;
     return XQ_OK;
 }
 

@@ -222,13 +222,15 @@ __host__ __device__ inline size_t refine_cand_words(int G) { const size_t w = (s
 // bytes of the whole-group list, and of the extra dynamic LDS of the staged pass (activation rows + the rows of two more groups), K = 256
 __host__ __device__ inline size_t refine_wlist_bytes(int G) { return ((size_t)G * 32 * sizeof(uint16_t) + 15) & ~(size_t)15; }
 __host__ __device__ inline size_t refine_stage_bytes() { return (size_t)3 * 32 * 256 * sizeof(float); }
-template <int KFIX, bool TD = false>
+// Loss (TD only): the TD loss object of xq_tail.hip.h, the kernel's LAST argument — behind whole_mode it lies in what was padding in front
+// of the hidden arguments (an empty SquaredLoss, or HuberLoss's one float), so the argument block of every other instantiation stays as it was.
+template <int KFIX, bool TD = false, class Loss = SquaredLoss>
 __global__ __launch_bounds__(256) void qmax_refine2_kernel(const float* __restrict__ R, int ranges, int gpr /* groups per range */,
                                                            const float* __restrict__ P1, const float* __restrict__ P2, int G, int n, long long ldp,
                                                            const float* __restrict__ na_all, const float* __restrict__ a_last, int K,
                                                            const float* __restrict__ W, const float* __restrict__ bias, int NO,
                                                            unsigned* __restrict__ wm, int parity, float* __restrict__ zmax,
-                                                           unsigned long long* __restrict__ stats, const TdFused T, int whole_mode) {
+                                                           unsigned long long* __restrict__ stats, const TdFused T, int whole_mode, const Loss L) {
     extern __shared__ __attribute__((aligned(16))) uint32_t cand[];            // [G * 32]: sample | row << 5
     uint16_t* wlist = reinterpret_cast<uint16_t*>(cand + refine_cand_words(G));          // [G * 32]: sample | group << 5
     __shared__ float sv[8][32];
@@ -467,7 +469,7 @@ __global__ __launch_bounds__(256) void qmax_refine2_kernel(const float* __restri
             if (live) {
                 q = tanhf(z + bo);
                 y = dn ? r : r + T.gamma * tanhf(zm);
-                delta = (q - y) * (1.f - q * q) * 1.f;
+                delta = L.err(q - y) * td_dtanh(q) * 1.f;
             }
             if (bb < n) {                                         // wave-uniform
                 float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -480,7 +482,7 @@ __global__ __launch_bounds__(256) void qmax_refine2_kernel(const float* __restri
                     T.dsc[bb] = delta;
                     T.act[bb] = live ? a : -1;
                     T.qsa[bb] = q; T.yv[bb] = y;
-                    T.lossv[bb] = live ? 0.5f * (q - y) * (q - y) : 0.f;
+                    T.lossv[bb] = live ? L.loss(q - y) : 0.f;
                 }
             }
         }

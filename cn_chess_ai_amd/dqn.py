@@ -386,6 +386,43 @@ DQN.grad_clip = _grad_clip
 DQN.grad_clip_stats = _grad_clip_stats
 
 
+_LOSS_KINDS = {"squared": _capi.LOSS_SQUARED, "huber": _capi.LOSS_HUBER}
+
+
+def _set_td_loss(self, kind="squared", kappa=1.0):
+    """Loss of the TD step (td_grads* / the trainer's learn_grads): "squared" (default) or "huber" — the error e = Q(s,a) - y enters
+    the output delta clamped to [-kappa, kappa] (Mnih et al. 2015), the importance weight multiplies behind the clamp and the priority
+    written back stays that of the raw error.  kappa > 0 or math.inf; ignored for "squared".  backpropagate() is never affected."""
+    if kind not in _LOSS_KINDS:
+        raise ValueError(f"set_td_loss: expected 'squared' or 'huber', got {kind!r}")
+    kappa = float(kappa)
+    if kind == "huber" and not kappa > 0.0:
+        raise ValueError(f"set_td_loss: kappa must be positive or inf, got {kappa!r}")
+    call("xq_dqn_set_td_loss", self._h, _LOSS_KINDS[kind], kappa)
+
+
+def _td_loss(self):
+    """dict(kind, kappa): the loss in force and the last kappa given to "huber" (1.0 before the first)."""
+    k, v = C.c_int32(), C.c_double()
+    call("xq_dqn_get_td_loss", self._h, C.byref(k), C.byref(v))
+    return dict(kind={v_: n for n, v_ in _LOSS_KINDS.items()}[k.value], kappa=v.value)
+
+
+def _td_error_stats(self):
+    """dict(live, mean_abs, max_abs, mean_loss, linear) of the TD errors e = Q(s,a) - y of the last TD step's live samples: linear =
+    samples with |e| > kappa (0 under the squared loss), mean_loss under the loss in force.  One small kernel on request; synchronises;
+    raises XqError before the first TD step."""
+    n, k = C.c_uint64(), C.c_uint64()
+    ma, mx, ml = C.c_double(), C.c_double(), C.c_double()
+    call("xq_dqn_td_error_stats", self._h, C.byref(n), C.byref(ma), C.byref(mx), C.byref(ml), C.byref(k))
+    return dict(live=n.value, mean_abs=ma.value, max_abs=mx.value, mean_loss=ml.value, linear=k.value)
+
+
+DQN.set_td_loss = _set_td_loss
+DQN.td_loss = _td_loss
+DQN.td_error_stats = _td_error_stats
+
+
 def _checked_tau(who, tau):
     tau = float(tau)
     if not 0.0 <= tau <= 1.0:

@@ -201,6 +201,18 @@ struct Optimizer {
     }
 };
 
+// Loss of the batched TD step (xq_dqn_set_td_loss; no upstream analogue): squared() is the reference's 0.5 e^2, huber(kappa) the error-clipped
+// loss of Mnih et al. 2015 — the error enters the output delta clamped to [-kappa, kappa] (kappa > 0 or +inf).  DQN::backpropagate is never affected.
+struct TdLoss {
+    int kind = XQ_LOSS_SQUARED;
+    double kappa = 1.0;
+    static TdLoss squared() { return TdLoss(); }
+    static TdLoss huber(double kappa = 1.0) {
+        TdLoss l; l.kind = XQ_LOSS_HUBER; l.kappa = kappa;
+        return l;
+    }
+};
+
 // ---- DQN, dqn.h:97-116 ----------------------------------------------------------------------------------------------
 class DQN {
 public:
@@ -297,6 +309,20 @@ public:
         double t = 0.0;
         check(xq_dqn_get_target_tau(h_, &t));
         return t;
+    }
+    // loss of the batched TD step (xq_dqn_set_td_loss): TdLoss::squared() (default) or TdLoss::huber(kappa)
+    void setTdLoss(const TdLoss& l) { check(xq_dqn_set_td_loss(h_, l.kind, l.kappa)); }
+    TdLoss tdLoss() const {
+        TdLoss l;
+        check(xq_dqn_get_td_loss(h_, &l.kind, &l.kappa));
+        return l;
+    }
+    // TD errors e = Q(s,a) - y of the last batched TD step's live samples: linear = those with |e| > kappa (0 under the squared loss)
+    struct TdErrorStats { uint64_t live = 0; double meanAbs = 0.0, maxAbs = 0.0, meanLoss = 0.0; uint64_t linear = 0; };
+    TdErrorStats tdErrorStats() const {                          // one small kernel on request; synchronises; throws before the first TD step
+        TdErrorStats s;
+        check(xq_dqn_td_error_stats(h_, &s.live, &s.meanAbs, &s.maxAbs, &s.meanLoss, &s.linear));
+        return s;
     }
     const std::vector<int>& layerSizes() const { return layerSizes_; }
     double gamma() const { return gamma_; }
@@ -706,6 +732,8 @@ public:
     void setGradClip(double maxNorm) { initializeDQN(); dqn->setGradClip(maxNorm); }
     // Soft target update of the batched train(), carried onto the trainer's network like the clip (0 = off)
     void setTargetTau(double tau) { initializeDQN(); dqn->setTargetTau(tau); }
+    // Loss of the batched train(), carried onto the trainer's network like the clip (TdLoss::squared() = the reference's)
+    void setTdLoss(const TdLoss& l) { initializeDQN(); dqn->setTdLoss(l); }
     DQN* network() { return dqn.get(); }
     std::vector<double> getStateRepresentation() {                           // chessai.cpp:268-289 (encoding only)
         std::vector<double> s(90 * 14, 0.0);
@@ -755,6 +783,8 @@ private:
         check(xq_dqn_set_optimizer(td, opt.kind, opt.beta1, opt.beta2, opt.eps));
         check(xq_dqn_set_grad_clip(td, dqn->gradClip()));
         check(xq_trainer_set_target_tau(t, dqn->targetTau()));
+        const TdLoss loss = dqn->tdLoss();
+        check(xq_dqn_set_td_loss(td, loss.kind, loss.kappa));
         if (comm_) check(xq_trainer_set_comm(t, comm_->handle()));
         if (prefillPlies_ > 0) check(xq_trainer_random_plies(t, prefillPlies_));
         if (opponent_) check(xq_trainer_set_opponent(t, &opponent_->spec()));

@@ -375,7 +375,7 @@ int xq_dqn_load_model(xq_dqn* d, const char* path);
  *   xq_dqn_td_grads  : forward + deltas + gradient reduction over the batch  -> compact gradient buffer (HBM)
  *   xq_dqn_apply_grads: params -= lr * grad_scale * grads   (or the Adam step of xq_dqn_set_optimizer; clipped by xq_dqn_set_grad_clip)
  * boards/next_boards: [n][12] u32, optionally gathered through slots_dev ([n] row indices, NULL = identity).
- * td_net = XQ_TD_*.  loss_out_dev: optional, sum over the batch of 0.5*(Q(s,a)-y)^2. */
+ * td_net = XQ_TD_*.  loss_out_dev: optional, sum over the batch of 0.5*(Q(s,a)-y)^2 (of the Huber loss under xq_dqn_set_td_loss). */
 int xq_dqn_td_grads(xq_dqn* d, const uint32_t* boards_dev, const uint32_t* next_boards_dev,
                     const int32_t* action_to_dev, const float* reward_dev, const uint8_t* done_dev,
                     const int32_t* slots_dev, int n, int td_net, int mode);
@@ -451,13 +451,37 @@ int xq_dqn_get_target_tau(const xq_dqn* d, double* tau);
  * updateTargetNetwork(tau), dqn.cpp:71-74 with a rate; a caller's own schedule).  tau = 1 is xq_dqn_update_target, tau = 0 a no-op, outside
  * [0, 1] or NaN XQ_ERR_INVALID_ARGUMENT. */
 int xq_dqn_soft_update_target(xq_dqn* d, double tau);
+/* The loss of the TD step (xq_dqn_td_grads*): the squared error (default; the bits, kernels and launches of a handle that was never asked)
+ * or the error-clipped loss of Mnih et al. 2015 (Huber).  Per live sample (0 <= action.to < 96), with e = fl32(q - y), k = (float)kappa
+ * and isw the importance weight of prioritized replay (1 otherwise):
+ *   XQ_LOSS_SQUARED:  c = e                          loss = 0.5f e e
+ *   XQ_LOSS_HUBER:    c = fminf(fmaxf(e, -k), k)     loss = |e| <= k ? 0.5f e e : k (|e| - 0.5f k)
+ *   delta = c * (1 - q q) * isw
+ * Only this scalar output delta changes: the hidden deltas, every gradient sum, both backprop modes, Adam, the clip, tau and the
+ * all-reduce consume it as before; Double DQN and the bf16 nets take the same rule.  The importance weight multiplies behind the clamp,
+ * and the priority written back stays (|e| + eps)^alpha of the RAW error, so what a run samples does not depend on kappa.  Where
+ * |e| <= k, c has the bits of e: kappa above every |e| of a batch (+inf included) reproduces the squared loss bit for bit.
+ * xq_dqn_last_loss (and the trainer's loss) carry the Huber loss while it is on; xq_dqn_backpropagate is never affected.
+ * kappa > 0 or +inf for XQ_LOSS_HUBER (ignored for XQ_LOSS_SQUARED, which keeps the last one); an unknown kind, kappa <= 0, NaN or a kappa
+ * that rounds to 0 as a float is XQ_ERR_INVALID_ARGUMENT; XQ_ERR_RUNTIME while a TD step waits for its apply_grads.  The setting survives
+ * xq_dqn_set_optimizer, xq_dqn_set_grad_clip, xq_dqn_set_target_tau, xq_dqn_set_params, xq_dqn_load_model, xq_dqn_update_target and
+ * xq_dqn_set_precision. */
+enum { XQ_LOSS_SQUARED = 0, XQ_LOSS_HUBER = 1 };
+int xq_dqn_set_td_loss(xq_dqn* d, int kind, double kappa);
+int xq_dqn_get_td_loss(const xq_dqn* d, int* kind, double* kappa);
+/* TD errors of the last xq_dqn_td_grads*, summarised on the device on request (one small kernel, off the step; synchronises): over the
+ * live samples, with e = fl32(q - y) as the step formed it: their number, the mean of |e|, max |e|, the mean loss under the loss in force
+ * (each sample's loss and both sums in fp64, one fixed association: the record does not depend on the device) and the number of samples
+ * in the linear part, |e| > (float)kappa (0 under XQ_LOSS_SQUARED).  Means over 0 live samples are 0.  XQ_ERR_RUNTIME before the first
+ * TD step.  Any out pointer may be NULL. */
+int xq_dqn_td_error_stats(xq_dqn* d, uint64_t* live, double* mean_abs, double* max_abs, double* mean_loss, uint64_t* linear);
 /* Convenience: sample-free TD update straight from a replay ring (slots from the last xq_replay_sample). */
 int xq_dqn_td_grads_replay(xq_dqn* d, xq_replay* r, int batch, int td_net, int mode);
 /* Host-buffer TD step for tests: n transitions as 90-byte boards. Returns Q(s,a) and y per sample if non-NULL. */
 int xq_dqn_td_update_host(xq_dqn* d, int n, const uint8_t* boards90, const uint8_t* next_boards90,
                           const int32_t* action_to, const float* reward, const uint8_t* done, int td_net, int mode,
                           double learning_rate, double grad_scale, float* q_sa_out, float* y_out);
-/* Sum-of-squared TD error of the last xq_dqn_td_grads (synchronises). */
+/* Sum-of-squared TD error of the last xq_dqn_td_grads, i.e. the sum of the per-sample loss in force (xq_dqn_set_td_loss; synchronises). */
 int xq_dqn_last_loss(xq_dqn* d, double* loss);
 /* Q(s,a) and the TD target y of the first n samples of the last xq_dqn_td_grads* (tests / interop; synchronises).  Either pointer
  * may be NULL. */
