@@ -779,6 +779,7 @@ static int ensure_l0_mfma(xq_dqn* d, int n) {
 // hidden deltas l = nl-2 .. 0 from the output-side delta `dnext` ([n][ld_next], only the first k_nz columns can be
 // non-zero).  reference mode: delta_l = (dnext[:, :L[l+1]] x View) * (1-a^2), View[i][idx] = Wflat[wo[l+1] + i*L[l] + idx];
 // textbook: View[k][idx] = W_{l+1}[k][idx], k < L[l+2].
+static bool grad_bf16_ok(const xq_dqn* d, int M, int N, int K);
 static int hidden_deltas(xq_dqn* d, int n, const float* dnext, int ld_next, int k_nz, int mode, int l_start = -1, int l_stop = 0) {
     const float* up = dnext;
     int ld_up = ld_next, nz = k_nz;
@@ -818,6 +819,17 @@ static int hidden_deltas(xq_dqn* d, int n, const float* dnext, int ld_next, int 
             }
         }
         XQ_TRY((launch_gemm<L_KCONTIG, L_MCONTIG, EPI_DELTA>(d, g, 1, "gemm_hidden_delta")));
+        if (d->bf16_bwd() && l >= 1) {
+            // XQ_PRECISION_BF16_FULL off the whole tiles: this product leaves no bf16 copy of delta_l, and the products that read one (the
+            // delta below, this layer's weight gradient) pick the bf16 loop by their OWN shapes — rounded here when one of them does
+            const int k_below = std::min(mode == XQ_BACKPROP_REFERENCE ? d->L[l] : d->L[l + 1], d->L[l + 1]);
+            const bool delta_below = (n % kBgBM) == 0 && (d->L[l] % kBgBN) == 0 && (k_below % kBgBK) == 0;
+            if (delta_below || grad_bf16_ok(d, d->L[l + 1], d->L[l], n)) {
+                hipLaunchKernelGGL(f32_to_bf16_kernel, dim3(std::min((n * d->L[l + 1] + 255) / 256, 1024)), dim3(256), 0, d->cur, d->deltas[l].p,
+                                   d->deltas_bf[l].p, (long long)n * d->L[l + 1]);
+                XQ_HIP(hipGetLastError());
+            }
+        }
         up = d->deltas[l]; ld_up = d->L[l + 1]; nz = d->L[l + 1];
     }
     return XQ_OK;
@@ -923,6 +935,18 @@ static int bias_grads(xq_dqn* d, BiasJobs& bj, int n, xq_dqn::PendingSlab* defer
     return XQ_OK;
 }
 
+// Launch shape of the segmented layer-0 sums (l0_grad_block): the column slab per block (grid z; wide layers keep the H = 256 shape), one
+// accumulator set per wave while they fit in 60 KB of LDS, and the dynamic LDS of a block.  Widest H with lds <= 64 KB: 1132 at chunk 1024.
+struct L0SegShape { int HS, nsets; size_t lds; };
+static L0SegShape l0_seg_shape(int H, int chunk) {
+    L0SegShape s;
+    s.HS = (H > 256 && H % 256 == 0) ? 256 : H;
+    s.nsets = 4;
+    while (s.nsets > 1 && (size_t)s.nsets * 14 * s.HS * sizeof(float) > 60 * 1024) s.nsets >>= 1;
+    s.lds = (size_t)s.nsets * 14 * s.HS * sizeof(float) + (size_t)chunk * sizeof(uint16_t);
+    return s;
+}
+
 // layer 0: per-(square, piece) segmented sums of delta_0 rows (no dense one-hot product); launches on d->cur or joins the open fused
 // grid.  defer != nullptr: the chunks' partial sums are left to the apply kernel as slabs — one kernel fewer on the critical chain
 static int l0_gradient(xq_dqn* d, int n, float* dst, xq_dqn::PendingSlab* defer) {
@@ -975,11 +999,9 @@ static int l0_gradient(xq_dqn* d, int n, float* dst, xq_dqn::PendingSlab* defer)
         }
     } else {
         ProfScope ps(d, "l0_grad_segsum", 2.0 * n * 32 * H, (double)n * (32.0 * H * 4 + 48) + 4.0 * nchunks * len);
-        const int HS = (H > 256 && H % 256 == 0) ? 256 : H;     // column slab per block (grid z): wide layers keep the H = 256 shape
-        int nsets = 4;                               // one accumulator set per wave while they fit in 60 KB of LDS
-        while (nsets > 1 && (size_t)nsets * 14 * HS * sizeof(float) > 60 * 1024) nsets >>= 1;
-        const size_t shmem = (size_t)nsets * 14 * HS * sizeof(float) + (size_t)chunk * sizeof(uint16_t);
-        if (shmem > 64 * 1024) return fail(XQ_ERR_INVALID_ARGUMENT, "first hidden layer too wide for the layer-0 gradient kernel (%d)", H);
+        const L0SegShape shape = l0_seg_shape(H, chunk);
+        const int HS = shape.HS, nsets = shape.nsets;
+        const size_t shmem = shape.lds;              // (<= 64 KB: plan_gradients refused the step otherwise, before its first gradient launch)
         if (d->tail_open) {              // fused tail launch
             TailArgs& T = *d->tail;
             T.l0_boards = d->gboards; T.l0_delta = d->deltas[0]; T.l0_n = n; T.l0_H = H; T.l0_HS = HS; T.l0_chunk = chunk; T.l0_nsets = nsets;
@@ -987,6 +1009,7 @@ static int l0_gradient(xq_dqn* d, int n, float* dst, xq_dqn::PendingSlab* defer)
             d->tail_flops += 2.0 * n * 32 * H; d->tail_bytes += (double)n * (32.0 * H * 4 + 48) + 4.0 * nchunks * len;
             d->tail_lds = std::max(d->tail_lds, shmem);
         } else {
+        if (shmem > 48 * 1024) XQ_TRY(ensure_max_dynamic_lds(l0_grad_kernel, 64 * 1024));
         hipLaunchKernelGGL(l0_grad_kernel, dim3(kSquares, nchunks, H / HS), dim3(256), shmem, d->cur, d->gboards, d->deltas[0], n, H, HS,
                            chunk, nsets, out);
         XQ_HIP(hipGetLastError());
@@ -1524,6 +1547,8 @@ static int plan_gradients(xq_dqn* d, int n, bool defer, GradPlan* P) {
     P->out_lds = (size_t)16 * Hl * sizeof(float) + (size_t)kOutGradChunk * sizeof(uint16_t);
     if (P->out_lds > 64 * 1024 || (Hl & 3))
         return fail(XQ_ERR_INVALID_ARGUMENT, "last hidden layer width %d unsupported by the output-gradient kernel (multiple of 4, <= 960)", Hl);
+    if (!l0_mfma_shape(d, n) && l0_seg_shape(d->L[1], l0_chunk_of(n)).lds > 64 * 1024)
+        return fail(XQ_ERR_INVALID_ARGUMENT, "first hidden layer too wide for the layer-0 gradient kernel (%d)", d->L[1]);
     size_t need = 0;
     auto place = [&](int nslabs, size_t len) {
         const size_t floats = nslabs > 1 ? (size_t)nslabs * len : 0, at = defer ? need : 0;

@@ -1,0 +1,136 @@
+"""The table of small TD steps that sit on the kernel-selection boundaries of xq_dqn.hip, shared by tests/test_td_shape_edges_gpu.py (one
+device step per case against the fp64 reference) and the CPU negative control of tests/test_batch_ref_cpu.py (the same cases, lr, scale
+and seeds: a damaged update must leave the bound).  Test infrastructure only.
+
+The shape rules below restate the library's predicates as plain arithmetic on (layer sizes, n, precision, switches); nothing here is
+imported from the library, so a predicate that moves without its documentation fails the path assertions of the GPU test.
+"""
+from collections import namedtuple
+
+# switches of a case: the bench headline's, unless the case overrides one
+HEADLINE = dict(qmax="screened", derive=True, fused=True, tail=True, l0grad=1)
+
+Case = namedtuple("Case", "family sizes n rule mode prec sw seed lr scale")
+
+
+def reference_mode_defined(sizes):
+    """mode 0 (the hidden delta as written upstream) stays inside its buffers: check_reference_topology / batch_ref.UndefinedTopology"""
+    L, nl = sizes, len(sizes) - 1
+    wo, nw = [], 0
+    for i, o in zip(L[:-1], L[1:]):
+        wo.append(nw)
+        nw += i * o
+    for l in range(nl - 2, -1, -1):
+        if L[l + 2] < L[l + 1] or L[l] < L[l + 1] or wo[l + 1] + (L[l + 1] - 1) * L[l] + (L[l + 1] - 1) >= nw:
+            return False
+    return True
+
+
+def _case(family, net, n, rule=0, prec=0, mode=None, seed=0, **sw):
+    sizes = [int(s) for s in net.split("-")]
+    if mode is None:                                   # mode 1 wherever mode 0 is refused
+        mode = 0 if reference_mode_defined(sizes) else 1
+    # lr * scale = 16 / n, as in the full-size file: the bound's ulp32(new) term must not swallow one sample's contribution
+    return Case(family, sizes, n, rule, mode, prec, dict(HEADLINE, **sw), seed, 1.0, 16.0 / n)
+
+
+def _name(c, extra=""):
+    sw = "".join(f"_{k}{int(v) if not isinstance(v, str) else v}" for k, v in sorted(c.sw.items()) if HEADLINE[k] != v)
+    return f"{c.family}_{'-'.join(str(s) for s in c.sizes[1:])}_n{c.n}_r{c.rule}_m{c.mode}_p{c.prec}{sw}{extra}"
+
+
+def _table():
+    t = []
+    A = "1260-256-256-8100"
+    # a. bf16 nets off the whole 256 x 128 x 64 tiles.  n = 256: hidden_bf16_dma_shape holds, the exact max pass on launch_gemm's bf16 pairs
+    # (n < 1024); 300: the tile kernel on bf16 pairs, every backward product on fp32 operands; 1024: the screen kernel's exact mode with
+    # bf_frag; 1100: the same kernel without it, screen_padded_samples, 2 layer-0 chunks
+    for n in (256, 300, 1024, 1100):
+        for prec in (1, 2):
+            t.append(_case("a", A, n, 0, prec))
+    for n in (300, 1100):
+        for rule in (1, 2):
+            for prec in (1, 2):
+                t.append(_case("a", A, n, rule, prec))
+    t.append(_case("a", A, 256, 0, 2, mode=1))
+    # b. one layer on the bf16 loop of its own, its neighbour on the tile kernel (hidden_bf16_dma_shape: N % 128, K % 64); first hidden
+    # layers outside wide_bf (96, 320: 512 % H != 0)
+    for net in ("1260-256-192-256-8100", "1260-96-128-8100", "1260-320-128-8100"):
+        for n in (256, 300):
+            for prec in (1, 2):
+                t.append(_case("b", net, n, 0, prec))
+    # c. even widths that are no multiple of 8: bf16 rows with ld % 4 != 0 take the scalar loads of the tile kernel (vec_ok)
+    for prec in (1, 2):
+        t.append(_case("c", "1260-100-132-8100", 37, 0, prec))
+    # d. hidden_forward: n % 128 == 0 and N % 128 == 0 walk (gemm_fwd_persistent_kernel), n = 129 and N = 160 the tile kernel
+    t.append(_case("d", "1260-128-128-8100", 128))
+    t.append(_case("d", "1260-128-128-8100", 129))
+    t.append(_case("d", "1260-128-160-8100", 128))
+    # e. segmented layer-0 sums (l0_seg_shape): H = 96 (H % 64 != 0: l0_mfma_shape refuses) with HS = H and 4 accumulator sets; the
+    # multiples of 64 with the matrix-pipe form switched off: 320 gives 2 sets, 768 three column slabs of 256; 1132 is the widest H
+    # whose one set + sample list fit 64 KB of LDS
+    t.append(_case("e", "1260-96-96-8100", 300))
+    t.append(_case("e", "1260-320-64-8100", 300, l0grad=0))
+    t.append(_case("e", "1260-768-64-8100", 300, l0grad=0))
+    t.append(_case("e", "1260-1132-64-8100", 37))
+    t.append(_case("e", "1260-1132-64-8100", 37, tail=False, fused=False))
+    # f. chunk edges: bias_grads' R = n / 64 rows of partial sums (63, 64, 65, 127, 129), kOutGradChunk (256 | 257), l0_mfma_shape
+    # (n >= 256), l0_chunk_of (1024 | 1025), big_tiles and with it the screened max pass (64 x ceil(n / 128) >= 512)
+    F = "1260-64-64-8100"
+    for n in (63, 64, 65, 127, 129, 256, 257, 1024, 1025):
+        t.append(_case("f", F, n))
+    for n in (257, 1025):                              # kernel by kernel on two streams, every slab summed behind its product
+        t.append(_case("f", F, n, tail=False, fused=False))
+    # g. output counts: 96 is the least the TD path takes; 130 leaves 2 rows in the max pass's last 64-row tile
+    t.append(_case("g", "1260-64-64-96", 300))
+    t.append(_case("g", "1260-64-64-130", 300))
+    return {_name(c): c for c in t}
+
+
+CASES = _table()
+
+# one case of each family for the CPU negative control
+CONTROL = ["a_256-256-8100_n300_r2_m0_p2", "b_256-192-256-8100_n256_r0_m1_p2", "c_100-132-8100_n37_r0_m1_p1",
+           "d_128-160-8100_n128_r0_m1_p0", "e_320-64-8100_n300_r0_m1_p0_l0grad0", "f_64-64-8100_n257_r0_m0_p0",
+           "g_64-64-130_n300_r0_m1_p0"]
+
+
+# ---- the shape rules ------------------------------------------------------------------------------------------------------------------
+def bf16_delta_layers(c):
+    """hidden layers l whose delta product delta_{l+1} x view takes bf16 operands: XQ_PRECISION_BF16_FULL, below the top hidden layer
+    (its delta comes from the TD-delta kernel), and M = n, N = L[l+1], K whole 256 x 128 x 64 tiles; K = L[l+1] columns of delta_{l+1}
+    in mode 0, all L[l+2] in mode 1"""
+    L, nl = c.sizes, len(c.sizes) - 1
+    out = set()
+    for l in range(nl - 2):
+        K = L[l + 1] if c.mode == 0 else L[l + 2]
+        if c.prec == 2 and c.n % 256 == 0 and L[l + 1] % 128 == 0 and K >= 64 and K % 64 == 0:
+            out.add(l)
+    return out
+
+
+def bf16_grad_layers(c):
+    """hidden layers l >= 1 whose weight gradient delta_l^T a_l takes the bf16 delta: M = L[l+1] % 256, N = L[l] % 128, K = n >= 64, % 64"""
+    L, nl = c.sizes, len(c.sizes) - 1
+    return {l for l in range(1, nl - 1) if c.prec == 2 and L[l + 1] % 256 == 0 and L[l] % 128 == 0 and c.n >= 64 and c.n % 64 == 0}
+
+
+def expected_paths(c):
+    """bracket name -> whether a step of the case launches it (kernel_stats), for the names that tell the paths apart"""
+    L, n, nl = c.sizes, c.n, len(c.sizes) - 1
+    bf, H, Hl, NO = c.prec != 0, c.sizes[1], c.sizes[-2], c.sizes[-1]
+    t128 = lambda rows, cols: ((rows + 127) // 128) * ((cols + 127) // 128)
+    # fused launches: an fp32 net whose hidden products stay on 64 x 64 tiles (tail_eligible)
+    tail = c.sw["tail"] and not bf and all(t128(n, L[l + 1]) < 512 for l in range(nl - 2))
+    # matrix-pipe layer-0 gradient (l0_mfma_shape); its planes come from the fp32 delta product's epilogue at whole chunks, from
+    # l0_delta_split otherwise (the bf16 loop's epilogue writes none)
+    mfma = c.sw["l0grad"] == 1 and H % 64 == 0 and n >= 256
+    chunk = 2048 if n >= 16384 else 1024
+    planes_ride = nl >= 3 and 0 not in bf16_delta_layers(c) and n % chunk == 0 and t128(n, H) < 512
+    big_tiles = t128(NO, n) >= 512
+    screen = c.sw["qmax"] == "screened" and not bf and c.rule != 2 and big_tiles and Hl % 64 == 0 and Hl <= 1024
+    # ordered sums of their own: only when nothing is left to the apply kernel, and then wherever a product has more than one slab
+    # (at least the output-layer sums: n > 256)
+    reduce = (not c.sw["fused"]) and not tail and n > 256
+    return {"td_tail_deltas": tail, "td_tail_l0": tail, "l0_delta_split": mfma and not planes_ride, "reduce_slabs": reduce,
+            "gemm_qmax_screen": screen, "gemm_qmax_rowmax": not screen}

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import batch_ref as br
+import td_edge_cases as tc
 import xqoracle as xo
 from test_dqn_gpu import transitions, valid_indices
 
@@ -91,6 +92,33 @@ def test_batched_reference_equals_the_oracle(trace, sizes, mode):
                         assert abs(tq[A[i]] - f.y[i]) <= 1e-12 * max(1.0, abs(f.y[i]))
                     _close(gw, nw, ("nn gw", mode)); _close(gb, nb, ("nn gb", mode))
                 assert abs(br.loss(f) - 0.5 * np.sum((q - y) ** 2)) <= 1e-12 * max(br.loss(f), 1e-300)
+
+
+@pytest.mark.parametrize("sizes", [CFG2_NET, CFG4_NET, SMALL_NET], ids=["cfg2", "cfg4", "small"])
+@pytest.mark.parametrize("mode", [0, 1])
+def test_named_bf16_layers_span_bf16_full_to_bf16(trace, sizes, mode):
+    """backward / accumulate with the layers of the bf16 backward products named (the device rounds by shape): every hidden
+    layer named is the oracle's PRECISION_BF16_FULL, none named its PRECISION_BF16 — the two share their forward half."""
+    n = 12
+    S, A, R, D, S2 = _batch(trace, sizes, n, seed=4)
+    w, b = _params(sizes, 5)
+    wt, bt = _params(sizes, 6)
+    xs, x2s = [_x(s) for s in S], [_x(s) for s in S2]
+    net = br.Net(sizes, w, b, 2)
+    f = br.forward(net, S, S2, A, R, D, 0.99, 2, 2, target=br.Net(sizes, wt, bt, 2))
+    every = set(range(net.nl - 1))
+    for layers, prec in ((every, 2), ((), 1)):
+        u = br.accumulate(net, f, br.backward(net, f, mode, 2, bf16_layers=layers), 2, bf16_layers=layers)
+        gw, gb = br.flat_grads(net, u)
+        ow, ob = np.zeros_like(w), np.zeros_like(b)
+        for i in range(n):
+            xo.ext_td_accum(sizes, w, b, wt, bt, xs[i], x2s[i], int(A[i]), float(R[i]), int(D[i]), 0.99, 2, mode, prec, 1.0, ow, ob)
+        _close(gw, ow, ("gw", prec)); _close(gb, ob, ("gb", prec))
+    if net.nl >= 4:                                   # ... and a set in between is neither
+        some = br.accumulate(net, f, br.backward(net, f, mode, 2, bf16_layers={0}), 2, bf16_layers={1})
+        assert not np.array_equal(some.gW[0], u.gW[0]) and not np.array_equal(some.gW[1], u.gW[1])
+    with pytest.raises(AssertionError):
+        br.backward(net, f, mode, 1, bf16_layers={0})
 
 
 def test_undefined_topology_is_an_error_in_both():
@@ -198,3 +226,68 @@ def test_comparator_rejects_full_size_bugs_bf16_full(trace):
     u32 = br.accumulate(net32, f32, br.backward(net32, f32, 0, prec, wts), prec)
     seen = _controls(net, f, bk, prec, lr, scale, 2048, ragged=False, extra={"fp32 forward": u32})
     assert min(seen.values()) >= 4.0, seen
+
+
+# --------------------------------------------------------------------------------- negative control of the shape-edge cases
+def _ragged_layer(sizes):
+    """index k >= 1 of the widest layer width that is no multiple of 128 among the hidden layers (all multiples: the widest)"""
+    hidden = list(range(1, len(sizes) - 1))
+    pool = [k for k in hidden if sizes[k] % 128] or hidden
+    return max(pool, key=lambda k: sizes[k])
+
+
+@pytest.mark.parametrize("name", [k for k, c in tc.CASES.items() if c.rule == 2])
+def test_edge_case_double_dqn_near_ties_leave_room_under_the_flip_cap(trace, name):
+    """A precondition of the Double DQN edge cases, weaker than the cap itself: check_q_y asserts on the device that at most
+    MAX_FLIP_FRACTION of the samples take another near-maximal action's y.  Here, on the reference trace with the case's net (the device
+    cases draw self-play boards of their own), the samples whose two largest online outputs lie within 5e-4 stay under that cap.  5e-4:
+    the device sums the same bf16 operands in fp32 (~1e-5 off at K = 256), and a hidden sum that close to a bf16 rounding boundary moves
+    its activation by one bf16 ulp, an output by up to 0.06 * 2^-8 = 2.3e-4; two of those.  Within CAND_MARGIN = 5e-3 itself, which
+    is set at the full-size nets, a third of the samples of a freshly initialised 256-256 net have a second candidate (107 of 300), so
+    that count cannot be kept under the cap by choosing seeds."""
+    c = tc.CASES[name]
+    S, A, R, D, S2 = _full_batch(trace, c.n, seed=20 + c.seed)
+    w, _ = xo.init_weights(c.sizes, 21 + c.seed)
+    b = np.random.default_rng(21 + c.seed + 100).uniform(-0.05, 0.05, size=xo.nn_counts(c.sizes)[1])
+    net = br.Net(c.sizes, w.astype(np.float32).astype(np.float64), b.astype(np.float32).astype(np.float64), c.prec)
+    zn = net.z_out(net.hidden(br.one_hot(S2))[-1])
+    top2 = np.partition(zn, -2, axis=1)[:, -2:]
+    ties = int(((top2[:, 1] - top2[:, 0] < 5e-4) & (D == 0)).sum())
+    assert ties <= br.MAX_FLIP_FRACTION[c.prec] * c.n, (ties, c.n)
+
+
+@pytest.mark.parametrize("name", tc.CONTROL)
+def test_edge_case_bound_rejects_a_dropped_sample_and_a_dropped_column(trace, name):
+    """One case of each family of tests/td_edge_cases.py (the table tests/test_td_shape_edges_gpu.py runs on the device), with the
+    case's net seed, lr and scale: the fp64 update stored in fp32 passes check_update; the update without the batch's last sample, and
+    the one whose gradient misses its last column at the widest ragged width (what a wrong mask on a last partial tile loses), do not."""
+    c = tc.CASES[name]
+    sizes, n, prec = c.sizes, c.n, c.prec
+    S, A, R, D, S2 = _full_batch(trace, n, seed=20 + c.seed)
+    D[-1] = 0
+    w, _ = xo.init_weights(sizes, 21 + c.seed)                        # test_dqn_gpu.make_net's parameters, as the device stores them
+    b = np.random.default_rng(21 + c.seed + 100).uniform(-0.05, 0.05, size=xo.nn_counts(sizes)[1])
+    wt, _ = xo.init_weights(sizes, 99 + c.seed)
+    bt = np.random.default_rng(98 + c.seed).uniform(-0.05, 0.05, size=len(b))
+    f32 = lambda v: v.astype(np.float32).astype(np.float64)
+    net = br.Net(sizes, f32(w), f32(b), prec)
+    f = br.forward(net, S, S2, A, R, D, 0.99, c.rule, prec, target=br.Net(sizes, f32(wt), f32(bt), prec) if c.rule else None)
+    dl, gl = tc.bf16_delta_layers(c), tc.bf16_grad_layers(c)
+    bk = br.backward(net, f, c.mode, prec, bf16_layers=dl)
+    u = br.accumulate(net, f, bk, prec, bf16_layers=gl)
+
+    def check(gw, gb):
+        ls = c.lr * c.scale
+        return br.check_update(net, u, f, f32(net.w - ls * gw), f32(net.b - ls * gb), c.lr, c.scale, prec)
+
+    gw, gb = br.flat_grads(net, u)
+    ok = check(gw, gb)
+    assert max(ok.values()) <= 0.5, ok                                # only the fp32 store rounds
+    keep = np.ones(n, bool); keep[-1] = False
+    with pytest.raises(AssertionError, match="outside the bound"):
+        check(*br.flat_grads(net, br.accumulate(net, f, bk, prec, mask=keep, bf16_layers=gl)))
+    k = _ragged_layer(sizes)
+    gw2 = gw.copy()
+    gw2[net.wo[k]:net.wo[k] + sizes[k] * min(sizes[k + 1], u.gW[k].shape[0])].reshape(-1, sizes[k])[:, -1] = 0.0
+    with pytest.raises(AssertionError, match="outside the bound"):
+        check(gw2, gb)
