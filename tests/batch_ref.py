@@ -11,6 +11,7 @@ importance weights the oracle defines.
     bwd = backward(net, fwd, mode, precision, weights)                              # per-sample deltas
     upd = accumulate(net, fwd, bwd, precision)                                      # gradient sums + error-scale sums
     worst = check_update(net, upd, new_w, new_b, lr, scale, precision, fwd.boards)  # the bound of TOLERANCES below
+    q = q_rows(net, boards_or_dense, n_out)                                         # what the inference entry points return
 
 Parameters are flat float64 arrays in the reference layout (dqn.cu:112-140): layer l's weights are an (L[l+1], L[l]) row-major
 block at offset wo[l], its biases a block of L[l+1] at bo[l].
@@ -118,6 +119,17 @@ class Net:
 
     def z_out(self, a_last):
         return self.Bf[-1] + a_last @ self.Wf[-1].T
+
+
+def q_rows(net, boards_or_dense, n_out, chunk=CHUNK):
+    """Q(s)[0 .. n_out) of every row, what the inference entry points return: tanh of the first n_out outputs behind the last hidden
+    layer (xo.nn_forward; xo.ext_forward's z through tanh in the bf16 arithmetic, where Net rounds operands and activations)."""
+    x = _inputs(boards_or_dense)
+    q = np.empty((len(x), n_out))
+    for c0 in range(0, len(x), chunk):
+        a_last = net.hidden(one_hot(x[c0:c0 + chunk]))[-1]
+        q[c0:c0 + chunk] = np.tanh(net.Bf[-1][:n_out] + a_last @ net.Wf[-1][:n_out].T)     # = z_out(a_last)[:, :n_out], only those rows
+    return q
 
 
 class Forward:

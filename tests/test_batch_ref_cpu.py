@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import batch_ref as br
+import infer_edge_cases as ic
 import td_edge_cases as tc
 import xqoracle as xo
 from test_dqn_gpu import transitions, valid_indices
@@ -291,3 +292,194 @@ def test_edge_case_bound_rejects_a_dropped_sample_and_a_dropped_column(trace, na
     gw2[net.wo[k]:net.wo[k] + sizes[k] * min(sizes[k + 1], u.gW[k].shape[0])].reshape(-1, sizes[k])[:, -1] = 0.0
     with pytest.raises(AssertionError, match="outside the bound"):
         check(gw2, gb)
+
+
+# ------------------------------------------------------------------------------------------------ the inference rows (q_rows)
+@pytest.mark.parametrize("sizes", [REF_NET, [1260, 127, 129, 132, 8100], [1260, 100, 132, 8100], SMALL_NET], ids=["ref", "odd3", "even2", "small"])
+def test_q_rows_equals_the_oracle(trace, sizes):
+    """batch_ref.q_rows against xo.nn_forward (fp32 nets) and tanh of xo.ext_forward(..., bf16=True)'s z (the bf16 Q-net arithmetic): an
+    odd-width net with three hidden layers, boards and dense inputs, all outputs and the first 90 / 96 / 1."""
+    n = 9
+    rng = np.random.default_rng(2)
+    x = trace["board"][rng.choice(len(trace["board"]), n, replace=False)] if sizes[0] == 1260 else rng.uniform(-1, 1, (n, sizes[0]))
+    w, b = _params(sizes, 11)
+    for prec in (0, 1):
+        net = br.Net(sizes, w, b, prec)
+        if prec == 0:
+            want = np.stack([xo.nn_forward(sizes, w, b, _x(s)) for s in x])
+        else:
+            want = np.tanh(np.stack([xo.ext_forward(sizes, w, b, _x(s), bf16=True)[1] for s in x]))
+        for n_out in (sizes[-1], 1, 90 if sizes[-1] >= 96 else 7, 96 if sizes[-1] >= 96 else 56):
+            got = br.q_rows(net, x, n_out, chunk=4)                   # three chunks, the last one ragged
+            assert got.shape == (n, n_out)
+            _close(got, want[:, :n_out], ("q_rows", prec, n_out))
+        if sizes[0] == 1260:                                          # a board and its one-hot rows are the same input
+            assert np.array_equal(br.q_rows(net, br.one_hot(x), 96), br.q_rows(net, x, 96))
+
+
+# --------------------------------------------------------------------- negative controls of the inference cases (infer_edge_cases)
+_cpu_positions = {}
+
+
+def oracle_positions(n=2048, plies=25, seed=0x5EED):
+    """(boards, side to move, legal destinations) of n games after `plies` uniform-random plies of the oracle's self-play loop: what
+    xq_trainer_random_plies leaves on the device for the same seed (tests/test_env_gpu.py pins the two loops to each other)"""
+    key = (n, plies, seed)
+    if key not in _cpu_positions:
+        S, P, dests = np.zeros((n, 90), np.uint8), np.zeros(n, np.int64), []
+        for g in range(n):
+            b, k = xo.new_board(), 0
+            for _ in range(plies):
+                k += int(xo.selfplay_step(b, None, seed, g, k, 0).action_code >= 0)
+            S[g], P[g] = b.squares(), b.currentPlayer
+            codes, cnt = xo.all_valid_actions(b, b.currentPlayer)
+            dests.append(codes[:cnt].astype(np.int64) % 90)
+        _cpu_positions[key] = (S, P, dests)
+    return _cpu_positions[key]
+
+
+def _infer_net(c):
+    """test_dqn_gpu.make_net's parameters for the case with the output layer scaled, as the device stores them"""
+    w, _ = xo.init_weights(c.sizes, 21 + c.seed)
+    b = np.random.default_rng(21 + c.seed + 100).uniform(-0.05, 0.05, size=xo.nn_counts(c.sizes)[1])
+    w[br.offsets(c.sizes)[0][-1]:] *= c.wscale
+    f32 = lambda v: v.astype(np.float32).astype(np.float64)
+    return br.Net(c.sizes, f32(w), f32(b), c.prec)
+
+
+def _infer_boards(c):
+    S = oracle_positions()[0]
+    return S[np.arange(c.n) % len(S)]
+
+
+def _after_layer0(net, z1):
+    """the last hidden activations from the layer-0 sums z1 (bias included)"""
+    rnd = br.bf16_round if net.bf else (lambda v: v)
+    a = rnd(np.tanh(z1))
+    for l in range(1, net.nl - 1):
+        a = rnd(np.tanh(net.Bf[l] + a @ net.Wf[l].T))
+    return a
+
+
+def _head_damages(net, a_last, n_out, j):
+    """name -> Q rows [n][n_out] the way a wrong head would leave them; "right" is q_rows"""
+    W, B = net.Wf[-1][:n_out], net.Bf[-1][:n_out]
+    z = B + a_last @ W.T
+    two = min(128, a_last.shape[1])
+    out = {"right": z, "one 64-column k-slab left out": z - a_last[:, :64] @ W[:, :64].T, "rows shifted by one sample": np.roll(z, 1, axis=0)}
+    out["two slabs of one output summed twice"] = z.copy()
+    out["two slabs of one output summed twice"][:, j] += a_last[:, :two] @ W[j, :two]
+    out["the bias of one output dropped"] = z.copy()
+    out["the bias of one output dropped"][:, j] -= B[j]
+    return {k: np.tanh(v) for k, v in out.items()}
+
+
+def _derived_damages(net, prev, cur):
+    """name -> layer-0 sums of `cur` derived from those of `prev` the way a wrong kernel would: the take-out row of the first changed
+    square that held a piece skipped (every row with such a square), and the 9th pair dropped (rows with exactly 9 differences, had the
+    kernel derived them instead of summing in full)"""
+    z = net.Bf[0] + br.one_hot(cur) @ net.Wf[0].T
+    skip, ninth = z.copy(), z.copy()
+    hit = [0, 0]
+    for i in range(len(cur)):
+        diff = np.nonzero(prev[i] != cur[i])[0]
+        held = [s for s in diff if prev[i, s]]
+        if held and len(diff) <= 8:
+            skip[i] += net.Wf[0][:, held[0] * 14 + int(prev[i, held[0]]) - 1]
+            hit[0] += 1
+        if len(diff) == 9:
+            s = diff[8]
+            if prev[i, s]:
+                ninth[i] += net.Wf[0][:, s * 14 + int(prev[i, s]) - 1]
+            if cur[i, s]:
+                ninth[i] -= net.Wf[0][:, s * 14 + int(cur[i, s]) - 1]
+            hit[1] += 1
+    assert min(hit) > 0
+    return {"a take-out row skipped": skip, "the 9th pair dropped": ninth}
+
+
+@pytest.mark.parametrize("name", [k for k in ic.CONTROL if ic.CASES[k].kind in ("boards", "select", "dense")])
+def test_inference_bar_rejects_a_wrong_head_and_a_wrong_derived_sum(name):
+    """One case of families A, B, D and E of tests/infer_edge_cases.py with the case's net: the fp64 rows stored in fp32 pass the case's
+    bar; a head without one k-slab, with two slabs of one output summed twice, with the rows shifted by one sample or without one
+    output's bias does not; for the select chain neither do rows whose derived layer-0 sum skipped a take-out row or dropped its 9th pair
+    (against the wider bar of derived rows)."""
+    c = ic.CASES[name]
+    net = _infer_net(c)
+    S = _infer_boards(c)
+    x = S
+    if c.kind == "dense":
+        x = br.one_hot(S)
+        x[-32:] = np.random.default_rng(c.seed).uniform(-1, 1, size=(32, c.sizes[0]))
+    bar = br.BF16_QTOL if c.prec else ic.BAR_F32
+    want = br.q_rows(net, x, c.n_out)
+    a_last = net.hidden(br.one_hot(x))[-1]
+    assert np.array_equal(_after_layer0(net, net.Bf[0] + br.one_hot(x) @ net.Wf[0].T), a_last)
+    j = int(np.argmax(np.abs(net.Bf[-1][:c.n_out])))
+    assert abs(net.Bf[-1][j]) > (1e-3 if not c.prec else 2e-2)
+    for what, q in _head_damages(net, a_last, c.n_out, j).items():
+        err = float(np.abs(q.astype(np.float32).astype(np.float64) - want).max())
+        assert (err < 0.1 * bar) if what == "right" else (err > bar), (what, err, bar)
+    if c.kind == "select":
+        cur, nds = ic.edit_boards(S, 2, c.seed)
+        want = br.q_rows(net, cur, c.n_out)
+        for what, z1 in _derived_damages(net, S, cur).items():
+            q = np.tanh(net.Bf[-1][:c.n_out] + _after_layer0(net, z1) @ net.Wf[-1][:c.n_out].T)
+            err = np.abs(q - want).max(axis=1)
+            assert err.max() > ic.BAR_DERIVED and (err[nds == 0] == 0).all(), (what, float(err.max()))
+
+
+def test_td_bound_rejects_a_wrong_head_and_a_wrong_derived_sum():
+    """Family F's control: Q(s,a) and y of the crafted (S, S2) pairs from a damaged head of s' or s, or from a damaged derived layer-0
+    sum of s', leave check_q_y's bound; the undamaged ones stored in fp32 pass it."""
+    c = ic.CASES[[k for k in ic.CONTROL if ic.CASES[k].kind == "td"][0]]
+    net = _infer_net(c)
+    S = _infer_boards(c)
+    S2, nds = ic.edit_boards(S, 0, c.seed)
+    rng = np.random.default_rng(c.seed + 5)
+    A = rng.integers(0, 90, c.n).astype(np.int32)
+    R = rng.uniform(-0.5, 0.5, c.n).astype(np.float32)
+    D = np.zeros(c.n, np.uint8)
+    f = br.forward(net, S, S2, A, R, D, 0.99, 0, c.prec)
+    NO = c.sizes[-1]
+    a_s, a_s2 = net.hidden(br.one_hot(S))[-1], net.hidden(br.one_hot(S2))[-1]
+    j = int(A[np.argmax(np.abs(net.Bf[-1][A]))])
+    assert abs(net.Bf[-1][j]) > 1e-3
+
+    def q_y(qs, qs2):
+        return qs[np.arange(c.n), A].astype(np.float32), (R + 0.99 * qs2.max(axis=1)).astype(np.float32)
+
+    ds, ds2 = _head_damages(net, a_s, NO, j), _head_damages(net, a_s2, NO, j)
+    br.check_q_y(f, *q_y(ds["right"], ds2["right"]), c.prec)
+    for what in ds:
+        if what == "right":
+            continue
+        for qs, qs2 in ((ds[what], ds2["right"]), (ds["right"], ds2[what])):
+            if what in ("two slabs of one output summed twice", "the bias of one output dropped") and qs2 is not ds2["right"]:
+                continue                                              # one output of s' shows in y only where it is the maximum
+            with pytest.raises(AssertionError):
+                br.check_q_y(f, *q_y(qs, qs2), c.prec)
+    for what, z1 in _derived_damages(net, S, S2).items():
+        qs2 = np.tanh(net.z_out(_after_layer0(net, z1)))
+        with pytest.raises(AssertionError):
+            br.check_q_y(f, *q_y(ds["right"], qs2), c.prec)
+
+
+@pytest.mark.parametrize("name", [k for k, c in ic.CASES.items() if c.kind == "collect"])
+def test_collect_cases_have_a_clear_best_move_in_the_reference_alone(name):
+    """The precondition of family C's third check, without a device: on the oracle's positions after 25 random plies (the trainer's, for
+    the case's seed) with the oracle's move generator and q_rows, the games whose best legal destination leads the runner-up by more than
+    2 x 5e-6 are at least 95 % of the 2048; the first best move in list order passes the move checks, and the moves chosen from Q rows
+    shifted by one game do not.  (The versus case plays from these positions one opponent half-ply later in the games it opens.)"""
+    c = ic.CASES[name]
+    S, P, dests = oracle_positions(c.n, 25, 0x5EED + c.seed)
+    q = br.q_rows(_infer_net(c), S, 90)
+
+    def greedy(rows):
+        return np.array([d[np.argmax(rows[g, d])] if len(d) else -1 for g, d in enumerate(dests)], np.int64)
+
+    clear, bad = ic.move_checks(q, greedy(q), dests, ic.BAR_F32)
+    assert not bad, bad[:3]
+    assert clear >= 0.95 * c.n, clear
+    _, bad = ic.move_checks(q, greedy(np.roll(q, 1, axis=0)), dests, ic.BAR_F32)
+    assert len(bad) > 0.5 * c.n, len(bad)
