@@ -204,9 +204,12 @@ __global__ __launch_bounds__(256) void qmax_refine_kernel(const float* __restric
 // ||a|| <= ||bf16(a)|| (1 + 2^-7): inside the slack of kScreenEps (2^-7 * 0.0625 - 2^-12 - 2^-16 = 2.3e-4 against 6.1e-5 + the fp32
 // rounding of the sum of squares).  Same block shape, candidate lists and fp32 re-evaluation as qmax_refine_kernel.
 // TD: the work of td_delta_kernel (its fp32, 256-wide fast path: same loads, same arithmetic, same bits) for the block's 32 samples —
-// wave w owns samples 8w .. 8w+7.  Everything that does not depend on the maximum (action, reward, Q(s,a) = the dot of two 1-KB rows) is
-// requested at the very top and lands under the refine phases; once the block's maxima exist the targets, the scalar deltas and the top
-// hidden deltas follow.  One launch and ~10 us of exposed latency chain fewer on the step's critical stream.
+// wave w owns samples 8w .. 8w+7.
+// The block is a chain of dependent memory round trips, so the loads are grouped by what their ADDRESSES need (profiles/NOTES.md, "Refine
+// kernel: four dependent levels"): level 0 {R, na, wm, stats, action / reward / done}; level 1 {P1, then P2, of the ranges that reach the
+// threshold; the rows of the TD arithmetic: a_s, W_out[action], the view row, b_out[action]}; level 2 {candidate rows of W and a_last with
+// their biases}; level 3: TD target, delta, top hidden delta and the stores, from registers.  The arithmetic of every value is that of
+// td_delta_kernel, operation for operation; what a wave computed 64 times over (the tanh of its eight samples) one lane per sample computes.
 struct TdFused {
     SlotSrc src;
     const int32_t* action_to; const float* reward; const uint8_t* done;
@@ -224,7 +227,55 @@ __host__ __device__ inline size_t refine_wlist_bytes(int G) { return ((size_t)G 
 __host__ __device__ inline size_t refine_stage_bytes() { return (size_t)3 * 32 * 256 * sizeof(float); }
 // Loss (TD only): the TD loss object of xq_tail.hip.h, the kernel's LAST argument — behind whole_mode it lies in what was padding in front
 // of the hidden arguments (an empty SquaredLoss, or HuberLoss's one float), so the argument block of every other instantiation stays as it was.
-template <int KFIX, bool TD = false, class Loss = SquaredLoss>
+// DBG (tools/refine_probe.hip only; 0 in the library): 1 = s_memtime stamps at the level boundaries into refine_dbg[block][16] (every stamp
+// drains the wave's loads first: read shares, not lengths), 2 = the second-largest values loaded beside the largest ones.  The stamp buffer and
+// the clock exist only where the probe defines XQ_REFINE_PROBE in front of this header: the library has neither the symbol nor the code.
+#ifdef XQ_REFINE_PROBE
+__device__ unsigned long long* refine_dbg;
+__device__ __forceinline__ unsigned long long refine_clock() {
+    unsigned long long t;
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t) :: "memory");
+    return t;
+}
+__device__ __forceinline__ unsigned long long refine_realtime() { return __builtin_amdgcn_s_memrealtime(); }
+__device__ __forceinline__ void refine_stamp_out(int k, unsigned long long v) { refine_dbg[(size_t)blockIdx.x * 16 + k] = v; }
+#else
+__device__ __forceinline__ unsigned long long refine_clock() { return 0ull; }
+__device__ __forceinline__ unsigned long long refine_realtime() { return 0ull; }
+__device__ __forceinline__ void refine_stamp_out(int, unsigned long long) {}
+#endif
+// Sixteen groups of one range (g .. g + 15, the range ends in front of g1) for one sample: largest and second-largest screened values.
+// Every load is unconditional and its ADDRESS is selected (a select of the value, or a branch, per load costs a wait per load): a thread
+// whose range does not reach the threshold (`on` false) and the groups past g1 read a word that is in the cache anyway.  Ps = P + sample;
+// ld < 2^32 (n is an int), so a group's offset is one 32 x 32 -> 64 bit multiply-add.
+struct RefineChunk { float v[16], w[16]; };
+// (an empty range, g >= g1, counts as `on` false: nothing is read past the last group, whatever geometry the launcher hands in)
+__device__ __forceinline__ unsigned refine_chunk_last(bool on, int g, int g1) { return on && g1 > g ? (unsigned)(g1 - 1 - g) : 0u; }
+__device__ __forceinline__ void refine_chunk_p1(RefineChunk& c, const float* __restrict__ P1s, bool on, int g, int g1, unsigned ld) {
+    const float* base = P1s + (unsigned long long)(unsigned)(on && g1 > g ? g : 0) * ld;
+    const unsigned last = refine_chunk_last(on, g, g1);
+#pragma unroll
+    for (unsigned u = 0; u < 16; ++u) c.v[u] = base[(unsigned long long)min(u, last) * ld];
+}
+// the second values of the groups that reach the threshold (the others read the chunk's first group again), all in flight together; or — EAGER —
+// of every group, independent of P1
+template <bool EAGER>
+__device__ __forceinline__ void refine_chunk_p2(RefineChunk& c, const float* __restrict__ P2s, bool on, int g, int g1, unsigned ld, float t) {
+    const float* base = P2s + (unsigned long long)(unsigned)(on && g1 > g ? g : 0) * ld;
+    const unsigned last = refine_chunk_last(on, g, g1);
+#pragma unroll
+    for (unsigned u = 0; u < 16; ++u) {
+        if (EAGER) c.w[u] = base[(unsigned long long)min(u, last) * ld];
+        else c.w[u] = base[(unsigned long long)((u <= last && c.v[u] >= t) ? u : 0u) * ld];
+    }
+}
+// the loaded values as opaque registers: without it the compiler sinks the loads of group 0 into the branch that uses them (a dependent round
+// trip inside the candidate loop)
+__device__ __forceinline__ void refine_chunk_pin(float (&x)[16]) {
+#pragma unroll
+    for (int u = 0; u < 16; ++u) asm volatile("" : "+v"(x[u]));
+}
+template <int KFIX, bool TD = false, class Loss = SquaredLoss, int DBG = 0>
 __global__ __launch_bounds__(256) void qmax_refine2_kernel(const float* __restrict__ R, int ranges, int gpr /* groups per range */,
                                                            const float* __restrict__ P1, const float* __restrict__ P2, int G, int n, long long ldp,
                                                            const float* __restrict__ na_all, const float* __restrict__ a_last, int K,
@@ -234,28 +285,41 @@ __global__ __launch_bounds__(256) void qmax_refine2_kernel(const float* __restri
     extern __shared__ __attribute__((aligned(16))) uint32_t cand[];            // [G * 32]: sample | row << 5
     uint16_t* wlist = reinterpret_cast<uint16_t*>(cand + refine_cand_words(G));          // [G * 32]: sample | group << 5
     __shared__ float sv[8][32];
-    __shared__ float thr[32];
     __shared__ int best[32];
     __shared__ int cnt, nexp;
     __shared__ unsigned gbits[256];     // per group: the samples of the block that ask for it as a whole group (G <= 256: see stage_ok)
     __shared__ unsigned long long gpop[4];      // per wave: the groups tid that >= 8 samples ask for
     const int tid = (int)threadIdx.x;
+    unsigned long long stp[13] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    if (DBG & 1) { stp[11] = refine_realtime(); stp[0] = refine_clock(); }
     const int sl = tid & 31, phase = tid >> 5;
     const int ql = tid & 15, quarter = tid >> 4;
     const int b0 = (int)blockIdx.x * kRefineSamples;
     const int b = b0 + sl;
     const bool ok = b < n;
     const int bc = min(b, n - 1);
+    // Level 0: everything whose address is known at the start, in ONE batch, the values the first barrier needs first (loads return in order).
+    // The per-range maxima of this thread's ranges (phase and phase + 8) stay in registers for the candidate scan; more than 16 ranges or more
+    // than 16 groups per range (a block-uniform test): the scan reads them again, range by range.
+    const bool two = ranges <= 16 && gpr <= 16;
+    float r0 = kColmaxPadBias, r1 = kColmaxPadBias;
+    float m = kColmaxPadBias;
+    if (two) {
+        r0 = R[(long long)min(phase, ranges - 1) * ldp + bc];
+        r1 = R[(long long)min(phase + 8, ranges - 1) * ldp + bc];
+    }
+    // the threshold's inputs (broadcast loads; every thread forms its sample's threshold itself behind the barrier: no second barrier)
+    const float na_b = na_all[bc];
+    const unsigned wm_w = wm[parity], wm_ws = wm[4], wm_b = wm[2 + parity], wm_bs = wm[5];
     if (tid == 0) { cnt = 0; nexp = 0; if (blockIdx.x == 0) { wm[parity ^ 1] = 0u; wm[2 + (parity ^ 1)] = 0u; } }   // next step's slots
     unsigned long long st_pairs = 0, st_whole = 0;   // candidate counters: [block][2] running totals, one writer per slot (stream order)
     if (tid == 0) { st_pairs = stats[2 * blockIdx.x]; st_whole = stats[2 * blockIdx.x + 1]; }
     if (tid < 32) best[tid] = (int)0x80000000;
     const bool stage_ok = KFIX > 0 && G <= 256;
-    gbits[tid] = 0u;                    // (ordered before the scan below by the barriers in between)
-    // TD: lanes 0..7 of each wave hold action / reward / done / output bias of the wave's eight samples; zq[i] = Q(s,a) before the tanh
+    gbits[tid] = 0u;                    // (ordered before the scan below by the barrier in between)
+    // TD: lanes 0..7 of each wave hold action / reward / done / output bias of the wave's eight samples, and later their Q(s,a), y and delta
     const int td_lane = tid & 63, td_w = tid >> 6;
-    int td_a = -1; float td_r = 0.f, td_bo = 0.f; bool td_dn = false;
-    float zq[8];
+    int td_a = -1; float td_r = 0.f, td_bo = 0.f; unsigned td_dn = 0u;
     if (TD) {
         static_assert(!TD || KFIX == 256, "fused TD delta: 256-wide last hidden layer");
         if (td_lane < 8) {
@@ -263,65 +327,133 @@ __global__ __launch_bounds__(256) void qmax_refine2_kernel(const float* __restri
             const int sslot = slot_of(T.src, bb);
             td_a = T.action_to[sslot];
             td_r = T.reward[sslot];
-            td_dn = T.done[sslot] != 0;
-            td_bo = T.b_out[(td_a >= 0 && td_a < 96) ? td_a : 0];
+            td_dn = T.done[sslot];
         }
+    }
+    if (two) {
+        if (phase < ranges) m = fmaxf(m, r0);
+        if (phase + 8 < ranges) m = fmaxf(m, r1);
+    } else {
+        for (int r = phase; r < ranges; r += 8) m = fmaxf(m, R[(long long)r * ldp + bc]);
+    }
+    sv[phase][sl] = m;
+    if (DBG & 1) stp[1] = refine_clock();
+    __syncthreads();
+    if (DBG & 1) stp[2] = refine_clock();
+    // Level 1, first half: the rows of the TD arithmetic (a_s, W_out[action], the view row of the top hidden delta, b_out[action]) go out in
+    // front of the scan's loads and land under them; nothing waits for them before the scan is over
+    float4 tav[8], twv[8], tvv[8];
+    if (TD) {
+        if (td_lane < 8) td_bo = T.b_out[(td_a >= 0 && td_a < 96) ? td_a : 0];
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
             const int bb = min(b0 + td_w * 8 + i, n - 1);
             const int a = __shfl(td_a, i, 64);
             const int ac = (a >= 0 && a < 96) ? a : 0;
-            const float4 av = *reinterpret_cast<const float4*>(T.a_s + (long long)bb * 256 + td_lane * 4);
-            const float4 wv = *reinterpret_cast<const float4*>(T.w_out + (long long)ac * 256 + td_lane * 4);
-            zq[i] = (av.x * wv.x + av.y * wv.y) + (av.z * wv.z + av.w * wv.w);
+            // (a sample without a view row reads row 0 of W_out instead: its value is never used, and an unconditional load has no branch)
+            const float* vp = (a >= 0 && a < 96 && a < T.view_kmax) ? T.view + (long long)a * T.view_ld : T.w_out;
+            tav[i] = *reinterpret_cast<const float4*>(T.a_s + (long long)bb * 256 + td_lane * 4);
+            twv[i] = *reinterpret_cast<const float4*>(T.w_out + (long long)ac * 256 + td_lane * 4);
+            tvv[i] = *reinterpret_cast<const float4*>(vp + td_lane * 4);
         }
     }
-    float m = kColmaxPadBias;
-    for (int r = phase; r < ranges; r += 8) m = fmaxf(m, R[(long long)r * ldp + bc]);
-    sv[phase][sl] = m;
-    __syncthreads();
-    if (tid < 32) {
+    if (DBG & 1) stp[3] = refine_clock();
+    float t;
+    {
         m = sv[0][sl];
 #pragma unroll
         for (int p = 1; p < 8; ++p) m = fmaxf(m, sv[p][sl]);
-        const float wmx = fmaxf(__builtin_bit_cast(float, wm[parity]), __builtin_bit_cast(float, wm[4]));
-        const float bmx = fmaxf(__builtin_bit_cast(float, wm[2 + parity]), __builtin_bit_cast(float, wm[5]));
-        const float B = kScreenEps * sqrtf(na_all[bc]) * wmx + kScreenBiasEps * bmx;
+        const float wmx = fmaxf(__builtin_bit_cast(float, wm_w), __builtin_bit_cast(float, wm_ws));
+        const float bmx = fmaxf(__builtin_bit_cast(float, wm_b), __builtin_bit_cast(float, wm_bs));
+        const float B = kScreenEps * sqrtf(na_b) * wmx + kScreenBiasEps * bmx;
         float t0 = m - 2.f * B * 1.03125f - 1.52587890625e-05f * (fabsf(m) + 2.f * B);
         if (!(t0 == t0)) t0 = -__builtin_inff();      // a non-finite norm (diverged net): every group is a candidate, like the full product
-        thr[sl] = ok ? t0 : __builtin_inff();            // no candidates past n
+        t = ok ? t0 : __builtin_inff();                  // no candidates past n
     }
-    __syncthreads();
+    // Level 1, second half: the groups of the ranges that reach the threshold, sixteen at a time per range, all loads in flight, then the
+    // second-largest values of the groups that reach it, again all in flight.  (A net whose per-range maxima all lie within the bound of each
+    // other — some fresh nets do, for a whole run — scans every range of every sample: that kernel read 65 us instead of 27 with four loads
+    // in flight.)  Both of a thread's ranges are decided first and their loads share one round trip.
     {
-        const float t = thr[sl];
-        for (int r = phase; r < ranges; r += 8) {
-            if (R[(long long)r * ldp + bc] < t) continue;        // no group of this range reaches the threshold
-            const int g0 = r * gpr, g1 = min(G, g0 + gpr);
-            // the groups of a range sixteen at a time, all loads in flight, then the second-largest values of the groups that reach the
-            // threshold, again all in flight: two round trips per range instead of one per four groups plus one per hit.  (A net whose
-            // per-range maxima all lie within the bound of each other — some fresh nets do, for a whole run — scans every range of every
-            // sample: that kernel read 65 us instead of 27 with four loads in flight.)
-            for (int g = g0; g < g1; g += 16) {
-                float v[16], v2[16];
+        const float *P1s = P1 + bc, *P2s = P2 + bc;
+        const unsigned ld = (unsigned)ldp;
+        // (One returning LDS atomic per candidate, which the compiler turns into one per wave and list.  One per thread with the thread's
+        // count, the entries written behind it, measured: 15.4 against 13.5 us alone on the chip — the wave-wide scan of the counts costs more.)
+        const auto emit = [&](const RefineChunk& c, bool on, int g, int g1) {
 #pragma unroll
-                for (int u = 0; u < 16; ++u) v[u] = P1[(long long)min(g + u, g1 - 1) * ldp + bc];
-#pragma unroll
-                for (int u = 0; u < 16; ++u) v2[u] = (g + u < g1 && v[u] >= t) ? P2[(long long)(g + u) * ldp + bc] : 0.f;
-#pragma unroll
-                for (int u = 0; u < 16; ++u) {
-                    if (g + u < g1 && v[u] >= t) {
-                        if (v2[u] >= t) { wlist[atomicAdd(&nexp, 1)] = (uint16_t)(sl | ((g + u) << 5)); if (stage_ok) atomicOr(&gbits[g + u], 1u << sl); }
-                        else cand[atomicAdd(&cnt, 1)] = (uint32_t)sl | ((uint32_t)screen_row(g + u, (int)(__builtin_bit_cast(uint32_t, v[u]) & 31u)) << 5);
-                    }
+            for (int u = 0; u < 16; ++u) {
+                if (on && g + u < g1 && c.v[u] >= t) {
+                    if (c.w[u] >= t) { wlist[atomicAdd(&nexp, 1)] = (uint16_t)(sl | ((g + u) << 5)); if (stage_ok) atomicOr(&gbits[g + u], 1u << sl); }
+                    else cand[atomicAdd(&cnt, 1)] = (uint32_t)sl | ((uint32_t)screen_row(g + u, (int)(__builtin_bit_cast(uint32_t, c.v[u]) & 31u)) << 5);
                 }
             }
+        };
+        constexpr bool EAGER = (DBG & 2) != 0;
+        if (two) {
+            const bool hit0 = phase < ranges && !(r0 < t), hit1 = phase + 8 < ranges && !(r1 < t);
+            const int ga = phase * gpr, gb = (phase + 8) * gpr;
+            const int ea = hit0 ? min(G, ga + gpr) : ga, eb = hit1 ? min(G, gb + gpr) : gb;      // (no hit: an empty range)
+            if (hit0 || hit1) {                  // straight-line code (a loop here makes the compiler drain the TD rows in front of it)
+                RefineChunk ca, cb;
+                refine_chunk_p1(ca, P1s, hit0, ga, ea, ld);
+                refine_chunk_p1(cb, P1s, hit1, gb, eb, ld);
+                if (EAGER) { refine_chunk_p2<true>(ca, P2s, hit0, ga, ea, ld, t); refine_chunk_p2<true>(cb, P2s, hit1, gb, eb, ld, t); }
+                __builtin_amdgcn_sched_barrier(0);       // all the loads out before the first value is looked at
+                if (DBG & 1) stp[4] = refine_clock();
+                refine_chunk_pin(ca.v); refine_chunk_pin(cb.v);
+                if (!EAGER) {
+                    refine_chunk_p2<false>(ca, P2s, hit0, ga, ea, ld, t); refine_chunk_p2<false>(cb, P2s, hit1, gb, eb, ld, t);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+                if (DBG & 1) stp[5] = refine_clock();
+                refine_chunk_pin(ca.w); refine_chunk_pin(cb.w);
+                emit(ca, hit0, ga, ea);
+                emit(cb, hit1, gb, eb);
+            }
+        } else {
+            for (int r = phase; r < ranges; r += 8) {
+                if (R[(long long)r * ldp + bc] < t) continue;        // no group of this range reaches the threshold
+                const int g0 = r * gpr, g1 = min(G, g0 + gpr);
+                for (int g = g0; g < g1; g += 16) {
+                    RefineChunk c;
+                    refine_chunk_p1(c, P1s, true, g, g1, ld);
+                    refine_chunk_pin(c.v);
+                    refine_chunk_p2<EAGER>(c, P2s, true, g, g1, ld, t);
+                    refine_chunk_pin(c.w);
+                    emit(c, true, g, g1);
+                }
+            }
+            // (nothing of this path is in flight where the two paths meet: the compiler's wait counters are merged there, and a load pending on
+            // this side would make the other side wait for its TD rows in front of the scan.)  The immediate is the gfx9 / CDNA encoding of
+            // s_waitcnt: vmcnt = bits 15:14 and 3:0 (here 0), expcnt = bits 6:4 (7: no wait), lgkmcnt = bits 11:8 (15: no wait).
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx950__)
+#error "qmax_refine2_kernel: the s_waitcnt immediate below is encoded for gfx950"
+#endif
+            __builtin_amdgcn_s_waitcnt(0x0F70);
         }
     }
+    if (DBG & 1) { stp[6] = refine_clock(); if (stp[4] == 0) stp[4] = stp[5] = stp[6]; }      // (a wave without a range that reaches the threshold)
+    // TD: Q(s,a) of the wave's eight samples, behind the scan (its rows have landed with the scan's loads).  The dot's sum ends in every lane;
+    // lane i keeps sample i's and takes the tanh once (the same function of the same value as ever, in one lane instead of all 64).
+    float td_q = 0.f;
+    if (TD) {
+        float zmine = 0.f;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const float4 av = tav[i], wv = twv[i];
+            float z = (av.x * wv.x + av.y * wv.y) + (av.z * wv.z + av.w * wv.w);
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) z += __shfl_xor(z, off, 64);
+            if (td_lane == i) zmine = z;
+        }
+        if (td_lane < 8 && td_a >= 0 && td_a < 96) td_q = tanhf(zmine + td_bo);
+    }
     __syncthreads();
-    // fp32 dots of the candidates (the maximum does not depend on the order they are visited in)
+    if (DBG & 1) stp[7] = refine_clock();
+    // Level 2: fp32 dots of the candidates (the maximum does not depend on the order they are visited in); a row's bias travels with the row
     const int singles = cnt, wholes = nexp;
     for (int e0 = 0; e0 < singles; e0 += 64) {                   // 16 quarters x 4 rows per round, all loads of a round in flight
-        float z[4];
+        float z[4], bj[4];
         int s2[4], row[4];
         bool live[4];
 #pragma unroll
@@ -331,14 +463,16 @@ __global__ __launch_bounds__(256) void qmax_refine2_kernel(const float* __restri
             const uint32_t ent = cand[live[r] ? e : 0];
             s2[r] = (int)(ent & 31u);
             row[r] = min((int)(ent >> 5), NO - 1);
+            bj[r] = bias[row[r]];
             z[r] = quarter_dot<KFIX>(a_last + (long long)(b0 + s2[r]) * K, W + (long long)row[r] * K, K, ql);
         }
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            z[r] = quarter_sum(z[r]) + bias[row[r]];
+            z[r] = quarter_sum(z[r]) + bj[r];
             if (live[r] && ql == 0 && z[r] == z[r]) atomicMax(&best[s2[r]], float_order_key(z[r]));   // (a NaN output never wins: fmaxf semantics)
         }
     }
+    if (DBG & 1) stp[8] = refine_clock();
     // Whole groups that MANY samples of the block ask for (>= 8 of 32; nets whose two largest outputs of a sample sit in ONE group within the
     // bound of each other — the trained rows 0..95 in about a fifth of the runs from time-seeded weights — ask for the same group for nearly
     // every sample): the group's 32 rows of W are staged into LDS once (the candidate list's space: the round of single rows is over) and
@@ -428,66 +562,69 @@ __global__ __launch_bounds__(256) void qmax_refine2_kernel(const float* __restri
         const int s2 = ent & 31, g = ent >> 5;
         if (staged_pass && __popc(gbits[g]) >= 8) continue;      // block-uniform
         float zb = kColmaxPadBias;
+        float bj[2];
+#pragma unroll
+        for (int r = 0; r < 2; ++r) bj[r] = bias[min(screen_row(g, quarter + 16 * r), NO - 1)];
 #pragma unroll
         for (int r = 0; r < 2; ++r) {
             const int row = screen_row(g, quarter + 16 * r);
             const int rc = min(row, NO - 1);
-            const float z = quarter_sum(quarter_dot<KFIX>(a_last + (long long)(b0 + s2) * K, W + (long long)rc * K, K, ql)) + bias[rc];
+            const float z = quarter_sum(quarter_dot<KFIX>(a_last + (long long)(b0 + s2) * K, W + (long long)rc * K, K, ql)) + bj[r];
             if (row < NO) zb = fmaxf(zb, z);
         }
         if (ql == 0) atomicMax(&best[s2], float_order_key(zb));
     }
     __syncthreads();
+    if (DBG & 1) stp[9] = refine_clock();
     if (tid < 32 && ok) zmax[b] = float_from_key(best[sl]);
     if (tid == 0) {                                  // this block's own running totals (512 same-address atomics per launch cost the
         stats[2 * blockIdx.x] = st_pairs + (unsigned long long)(singles + wholes);      // step 5 us)
         stats[2 * blockIdx.x + 1] = st_whole + (unsigned long long)wholes;
     }
+    // Level 3 (TD): no loads.  Lane i finishes sample i (target, delta, loss: the per-sample records leave as one 8-lane store each); the top
+    // hidden delta of each sample is the delta times the rows that stayed in registers.
     if (TD) {
-        // the rows for the top hidden delta (L2-hot: read a moment ago / shared by every sample with the same action), all in flight
-        float4 av[8], vv[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const int bb = min(b0 + td_w * 8 + i, n - 1);
-            const int a = __shfl(td_a, i, 64);
-            const bool has_view = a >= 0 && a < 96 && a < T.view_kmax;
-            av[i] = *reinterpret_cast<const float4*>(T.a_s + (long long)bb * 256 + td_lane * 4);
-            vv[i] = has_view ? *reinterpret_cast<const float4*>(T.view + (long long)a * T.view_ld + td_lane * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
+        const bool mine = td_a >= 0 && td_a < 96;
+        float q = 0.f, y = 0.f, delta = 0.f;
+        if (td_lane < 8) {
+            const float zm = float_from_key(best[td_w * 8 + td_lane]);
+            const float r = td_r;
+            const bool dn = td_dn != 0u;
+            if (mine) {
+                q = td_q;
+                y = dn ? r : r + T.gamma * tanhf(zm);
+                delta = L.err(q - y) * td_dtanh(q) * 1.f;
+            }
+            const int bb = b0 + td_w * 8 + td_lane;
+            if (bb < n) {
+                T.dsc[bb] = delta;
+                T.act[bb] = mine ? td_a : -1;
+                T.qsa[bb] = q; T.yv[bb] = y;
+                T.lossv[bb] = mine ? L.loss(q - y) : 0.f;
+            }
         }
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
             const int bb = b0 + td_w * 8 + i;
             const int a = __shfl(td_a, i, 64);
-            const float r = __shfl(td_r, i, 64), bo = __shfl(td_bo, i, 64);
-            const bool dn = __shfl((int)td_dn, i, 64) != 0;
+            const float dl = __shfl(delta, i, 64);
             const bool live = a >= 0 && a < 96;
-            float z = zq[i];
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) z += __shfl_xor(z, off, 64);
-            const float zm = float_from_key(best[td_w * 8 + i]);
-            float q = 0.f, y = 0.f, delta = 0.f;
-            if (live) {
-                q = tanhf(z + bo);
-                y = dn ? r : r + T.gamma * tanhf(zm);
-                delta = L.err(q - y) * td_dtanh(q) * 1.f;
-            }
             if (bb < n) {                                         // wave-uniform
                 float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
                 if (live && a < T.view_kmax) {
-                    o.x = delta * vv[i].x * (1.f - av[i].x * av[i].x); o.y = delta * vv[i].y * (1.f - av[i].y * av[i].y);
-                    o.z = delta * vv[i].z * (1.f - av[i].z * av[i].z); o.w = delta * vv[i].w * (1.f - av[i].w * av[i].w);
+                    o.x = dl * tvv[i].x * (1.f - tav[i].x * tav[i].x); o.y = dl * tvv[i].y * (1.f - tav[i].y * tav[i].y);
+                    o.z = dl * tvv[i].z * (1.f - tav[i].z * tav[i].z); o.w = dl * tvv[i].w * (1.f - tav[i].w * tav[i].w);
                 }
                 *reinterpret_cast<float4*>(T.dtop + (long long)bb * 256 + td_lane * 4) = o;
-                if (td_lane == 0) {
-                    T.dsc[bb] = delta;
-                    T.act[bb] = live ? a : -1;
-                    T.qsa[bb] = q; T.yv[bb] = y;
-                    T.lossv[bb] = live ? L.loss(q - y) : 0.f;
-                }
             }
         }
     }
+    if (DBG & 1) {
+        stp[10] = refine_clock(); stp[12] = refine_realtime();
+        if (tid == 0)
+#pragma unroll
+            for (int k = 0; k < 13; ++k) refine_stamp_out(k, stp[k]);
+    }
 }
-
 
 }  // namespace xq
