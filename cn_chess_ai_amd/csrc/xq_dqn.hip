@@ -19,6 +19,9 @@
 // operands, accounting and launch; hidden_forward picks one, chain_boards is the argument checks, the layer-0 call and the loop.
 // The gradient half of a TD step is described once (plan_gradients, out_gradient, hidden_weight_gradient, hidden_bias_gradients,
 // l0_gradient) and emitted in two orders: side_gradients (two streams) and tail_launches (fused grids, TailGrid).
+// The screened max pass is described once as well: xq::Screen owns its buffers, counters and guard, and plans each step's part of it
+// (ScreenPlan in TdStep); qmax_screened is the launches.  What a write of the parameters makes stale is described once: params_written,
+// the one place that touches params_version, the screen's kept rows, the select chain's kept sums and tgt_rest_synced.
 // This file = the handle (struct xq_dqn) + host orchestration + the C ABI; the kernels live in xq_l0.hip.h (layer-0 gathers and
 // segmented sums), xq_tail.hip.h (TD delta, gradient sums, fused launches, SGD), xq_refine.hip.h (screening pass 2), xq_l0grad.hip.h
 // (layer-0 gradient on the matrix pipe), xq_gemm*.hip.h and xq_screen.hip.h (matrix-pipe products).
@@ -37,7 +40,50 @@
 #include <random>
 #include <unordered_map>
 
-namespace xq { struct TailArgs; struct ClipRecord; struct TdStatsRecord; }
+struct TdStep; struct ScreenPlan;
+namespace xq {
+struct TailArgs; struct ClipRecord; struct TdStatsRecord; struct ShadowJob;
+// Exact screening of max_a' Q(s', a') (xq_dqn_set_qmax_mode), state and host logic: bf16 copies of the output-layer weights
+// and of the last hidden activations of s', the two screening partial arrays, the largest row norm of the weights, counters, the guard
+struct Screen {
+    int mode = XQ_QMAX_FULL;
+    int refine_stage = -1;                      // xq_dqn_set_refine_stage: -1 by the counters (stage_whole), 0 never, 1 whenever it fits
+    DevBuf<uint16_t> wb;                        // [round_up(nout,128)][hlast] (rows >= nout zero)
+    DevBuf<uint16_t> ab;                        // [round_up(cap,512)][hlast]: row-major, or B-fragment order for screen_top2_kernel
+    DevBuf<float> p1, p2;                       // [4*tiles_m][round_up(cap,512)]
+    DevBuf<float> R, na;                        // [chunks][round_up(cap,512)] per-range maxima, [round_up(cap,512)] ||bf16(a)||^2
+    // bits of the largest row norm / largest |bias| of the output layer (non-negative floats order like unsigned): [0..1] rows 0..95 by
+    // step parity, [2..3] their biases by step parity, [4] rows >= 96, [5] their biases.  Only rows 0..95 change under the TD rule
+    // (xq_dqn_td_grads never touches the others), so the shadow of rows >= 96 and slots [4], [5] are kept from step to step:
+    DevBuf<unsigned> wmax;
+    int static_net = -1;                        // net whose rows >= 96 the shadow holds (-1: none — the next step converts everything)
+    DevBuf<unsigned long long> stats;           // [refine blocks][2] running totals per block: candidate (sample, group) pairs, pairs recomputed as whole groups
+    int stat_blocks = 0;                        // blocks the array (and its pinned copy) has room for
+    unsigned long long carry[2] = {0, 0};       // totals of an array that was replaced by a larger one
+    unsigned long long host_steps = 0, host_samples = 0;
+    // guard: every kScreenCheckEvery screened steps the candidate counters are copied back asynchronously and evaluated kScreenCheckEvery
+    // steps later; a net that leaves the screen too many candidates (outputs all within the bf16 bound of each other) gets the full
+    // product for the next kScreenHoldSteps steps
+    PinnedBuf<unsigned long long> guard_host;   // pinned copy of stats
+    hipEvent_t guard_ev = nullptr;              // created on first use (reserve)
+    bool guard_pending = false;
+    unsigned long long guard_samples = 0, guard_queued_at = 0;      // host_samples, host_steps when the pending copy was queued
+    bool stage_whole = false;                   // the last counter window showed whole groups for many samples: the refine kernel is launched with the LDS of its
+                                                // staged pass (145 KB: otherwise it would keep the select chain's blocks off its CUs for nothing — +3 us per step)
+    unsigned long long seen[3] = {0, 0, 0};     // samples, pairs, whole groups at the last evaluation
+    int hold = 0;                               // > 0: that many TD steps still run the full product
+    unsigned long long fallbacks = 0;
+    ~Screen() { if (guard_ev) hipEventDestroy(guard_ev); }
+    void set_mode(int m) { mode = m; hold = 0; }         // an explicit request starts with the screen switched on again
+    void rows_rewritten(int net) { if (static_net == net) static_net = -1; }     // rows >= 96 of `net` are no longer what the shadow holds
+    // (defined below the kernel headers, whose constants they use)
+    int reserve(int NO, int Hl, int n, const void* params, const void* acts);
+    void totals_of(const unsigned long long* h, unsigned long long sums[2]) const;  int totals(unsigned long long sums[2]) const;
+    void guard_decide(const unsigned long long totals[2]);  int guard_tick(bool* screened);  int guard_queue(int n, hipStream_t s);
+    int shadow_job(const xq_dqn* d, int sel_net, int parity, hipStream_t s, ShadowJob* shadow);
+    int plan(xq_dqn* d, const TdStep& s, ScreenPlan* P);
+};
+}  // namespace xq
 struct xq_dqn {
     int ns = 0, nl = 0;
     int L[XQ_MAX_LAYERS + 1] = {0};
@@ -55,7 +101,7 @@ struct xq_dqn {
     hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_delta = nullptr;
     hipEvent_t ev_qmax = nullptr;               // recorded behind the column-max GEMM of the last TD step (trainer: collect starts here)
     xq::DevBuf<float> params[2];
-    uint64_t params_version = 0;                // ++ whenever an operation that rewrites parameters is queued (xq_trainer: is ev_params still current?)
+    uint64_t params_version = 0;                // ++ whenever an operation that rewrites parameters is queued (params_written; xq_trainer: is ev_params still current?)
     // bf16 Q-net (xq_dqn_set_precision): bf16 shadow of the WEIGHTS of both nets, same element order as params[] (biases stay fp32);
     // forward kernels read the shadow, the backward pass and the SGD step work on the fp32 master copy and refresh the shadow
     int precision = XQ_PRECISION_F32;
@@ -91,37 +137,7 @@ struct xq_dqn {
     xq::DevBuf<float> qh_slabs[2];              // k-slabs of the select head (handle stream / any other stream)
     bool small_tiles = false;                   // force 64x64 GEMM tiles (<= 80 VGPRs: fits beside the persistent GEMM); written by SmallTiles alone
     bool l0_derive = false;                     // xq_dqn_set_l0_derive: layer-0 sums of s' from those of s (online TD rule, fp32 net)
-    // exact screening of max_a' Q(s', a') (xq_dqn_set_qmax_mode): bf16 copies of the output-layer weights and of
-    // the last hidden activations of s', the two screening partial arrays, the largest row norm of the weights, counters
-    int qmax_mode = XQ_QMAX_FULL;
-    xq::DevBuf<uint16_t> scr_wb;                // [round_up(nout,128)][hlast] (rows >= nout zero)
-    xq::DevBuf<uint16_t> scr_ab;                // [round_up(cap,512)][hlast]: row-major, or B-fragment order for screen_top2_kernel
-    xq::DevBuf<float> scr_p1, scr_p2;           // [4*tiles_m][round_up(cap,512)]
-    xq::DevBuf<float> scr_R, scr_na;            // [chunks][round_up(cap,512)] per-range maxima, [round_up(cap,512)] ||bf16(a)||^2
-    // bits of the largest row norm / largest |bias| of the output layer (non-negative floats order like unsigned): [0..1] rows 0..95 by
-    // step parity, [2..3] their biases by step parity, [4] rows >= 96, [5] their biases.  Only rows 0..95 change under the TD rule
-    // (xq_dqn_td_grads never touches the others), so the shadow of rows >= 96 and slots [4], [5] are kept from step to step:
-    xq::DevBuf<unsigned> scr_wmax;
-    int scr_static_net = -1;                    // net whose rows >= 96 the shadow holds (-1: none — the next step converts everything)
-    xq::DevBuf<unsigned long long> scr_stats;   // [refine blocks][2] running totals per block: candidate (sample, group) pairs, pairs recomputed as whole groups
-    int scr_stat_blocks = 0;                    // blocks the array (and its pinned copy) has room for
-    unsigned long long scr_carry[2] = {0, 0};   // totals of an array that was replaced by a larger one
-    unsigned long long scr_host_steps = 0, scr_host_samples = 0;
-    // guard: every kScreenCheckEvery screened steps the candidate counters are copied back asynchronously and evaluated kScreenCheckEvery
-    // steps later; a net that leaves the screen too many candidates (outputs all within the bf16 bound of each other) gets the full
-    // product for the next kScreenHoldSteps steps
-    xq::PinnedBuf<unsigned long long> scr_guard_host;  // pinned copy of scr_stats
-    hipEvent_t scr_guard_ev = nullptr;
-    bool scr_guard_pending = false;
-    unsigned long long scr_guard_samples = 0;          // scr_host_samples when the pending copy was queued
-    unsigned long long scr_guard_queued_at = 0;        // scr_host_steps when it was queued
-    int refine_stage = -1;                             // xq_dqn_set_refine_stage: -1 by the counters (scr_stage_whole), 0 never, 1 whenever it fits
-    bool scr_stage_whole = false;                      // the last counter window showed whole groups for many samples: the refine kernel is
-                                                       // launched with the LDS of its staged pass (145 KB: otherwise it would keep the select
-                                                       // chain's blocks off its CUs for nothing — +3 us per step, same-box A/B)
-    unsigned long long scr_seen[3] = {0, 0, 0};        // samples, pairs, whole groups at the last evaluation
-    int scr_hold = 0;                                  // > 0: that many TD steps still run the full product
-    unsigned long long scr_fallbacks = 0;
+    xq::Screen scr;                             // the screened max_a' Q(s', a') of a TD step (xq_dqn_set_qmax_mode)
     xq::DevBuf<float> partial;                  // row-max partials
     xq::DevBuf<float> zmax;  xq::DevBuf<int> zidx;  // [kReduceParts][cap] their reduction per sample (colmax_reduce_kernel)
     xq::DevBuf<float> qsa, yv, lossv;
@@ -144,9 +160,8 @@ struct xq_dqn {
     xq::DevBuf<xq::ClipRecord> clip_rec;
     // soft target update of xq_dqn_apply_grads (xq_dqn_set_target_tau): 0 = off, (0, 1) = theta- += tau (theta - theta-) in the apply
     // kernel, 1 = the hard copy behind every apply.  tgt_rest_synced: the target's parameters OUTSIDE the TD segments have the online
-    // net's bits (a fixed point of the rule), so the apply kernel's walk over the TD segments is the whole update; true behind
-    // xq_dqn_update_target (hence xq_dqn_create), false behind whatever can make the two nets differ there (xq_dqn_set_params of either
-    // net, hence xq_dqn_load_model, and xq_dqn_backpropagate) — then one whole-buffer kernel follows the apply instead
+    // net's bits (a fixed point of the rule), so the apply kernel's walk over the TD segments is the whole update; written by
+    // params_written alone (its table); while false, one whole-buffer kernel follows the apply instead
     double target_tau = 0.0;
     bool tgt_rest_synced = false;
     // TD loss of xq_dqn_td_grads* (xq_dqn_set_td_loss): squared, or Huber with kappa (loss_kappa32 = the float the kernels clamp at; +inf
@@ -408,64 +423,64 @@ static SlotSrc explicit_slots(const int32_t* slots) {
     SlotSrc s; memset(&s, 0, sizeof s); s.slots = slots; return s;
 }
 
-// totals of the per-block candidate counters (synchronises the device)
-static int screen_stat_sums(xq_dqn* d, unsigned long long sums[2]) {
-    sums[0] = d->scr_carry[0]; sums[1] = d->scr_carry[1];
-    if (!d->scr_stat_blocks) return XQ_OK;
-    std::vector<unsigned long long> h((size_t)2 * d->scr_stat_blocks);
-    XQ_HIP(hipDeviceSynchronize());
-    XQ_HIP(hipMemcpy(h.data(), d->scr_stats, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    for (int i = 0; i < d->scr_stat_blocks; ++i) { sums[0] += h[2 * i]; sums[1] += h[2 * i + 1]; }
+// totals of the per-block candidate counters: the carry plus a host copy `h` of the array ...
+void Screen::totals_of(const unsigned long long* h, unsigned long long sums[2]) const {
+    sums[0] = carry[0]; sums[1] = carry[1];
+    for (int i = 0; i < stat_blocks; ++i) { sums[0] += h[2 * i]; sums[1] += h[2 * i + 1]; }
+}
+// ... or of the array as it stands (synchronises the device)
+int Screen::totals(unsigned long long sums[2]) const {
+    std::vector<unsigned long long> h((size_t)2 * stat_blocks);
+    if (stat_blocks) {
+        XQ_HIP(hipDeviceSynchronize());
+        XQ_HIP(hipMemcpy(h.data(), stats, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    }
+    totals_of(h.data(), sums);
     return XQ_OK;
 }
-static void screen_stat_sums_of(const xq_dqn* d, const unsigned long long* h, unsigned long long sums[2]) {
-    sums[0] = d->scr_carry[0]; sums[1] = d->scr_carry[1];
-    for (int i = 0; i < d->scr_stat_blocks; ++i) { sums[0] += h[2 * i]; sums[1] += h[2 * i + 1]; }
-}
-// buffers of the screened maximum (xq_dqn_set_qmax_mode), allocated on first use
-static int ensure_screen_capacity(xq_dqn* d, int n) {
-    const int NO = d->nout(), Hl = d->hlast();
+// buffers of the screened maximum (xq_dqn_set_qmax_mode), allocated on first use (params, acts: for the XQ_DEBUG_PTRS print alone)
+int Screen::reserve(int NO, int Hl, int n, const void* params, const void* acts) {
     const size_t wrows = (size_t)round_up(NO, 128);
     bool grew = false;
-    XQ_TRY(d->scr_wb.reserve(wrows * Hl, &grew));
+    XQ_TRY(wb.reserve(wrows * Hl, &grew));
     if (grew) {
-        XQ_HIP(hipMemset(d->scr_wb, 0, wrows * Hl * sizeof(uint16_t)));
-        d->scr_static_net = -1;
+        XQ_HIP(hipMemset(wb, 0, wrows * Hl * sizeof(uint16_t)));
+        static_net = -1;
     }
     grew = false;
-    XQ_TRY(d->scr_wmax.reserve(6, &grew));
-    if (grew) XQ_HIP(hipMemset(d->scr_wmax, 0, 6 * sizeof(unsigned)));
-    if (!d->scr_guard_ev) XQ_HIP(hipEventCreateWithFlags(&d->scr_guard_ev, hipEventDisableTiming));
+    XQ_TRY(wmax.reserve(6, &grew));
+    if (grew) XQ_HIP(hipMemset(wmax, 0, 6 * sizeof(unsigned)));
+    if (!guard_ev) XQ_HIP(hipEventCreateWithFlags(&guard_ev, hipEventDisableTiming));
     // sample dimension padded to whole blocks of screen_top2_kernel (512): it stores every column of its panels unconditionally
     const size_t rows = (size_t)round_up(n, 512), G = (size_t)4 * ((NO + 127) / 128);
     grew = false;
-    XQ_TRY(d->scr_ab.reserve(rows * Hl, &grew));
-    if (grew) XQ_HIP(hipMemset(d->scr_ab, 0, rows * Hl * sizeof(uint16_t)));
-    XQ_TRY(d->scr_p1.reserve(G * rows, &grew));
-    XQ_TRY(d->scr_p2.reserve(G * rows, &grew));
-    XQ_TRY(d->scr_R.reserve((size_t)((NO + 63) / 64) * rows, &grew));       // at most one range per 64-row chunk
-    XQ_TRY(d->scr_na.reserve(rows, &grew));
+    XQ_TRY(ab.reserve(rows * Hl, &grew));
+    if (grew) XQ_HIP(hipMemset(ab, 0, rows * Hl * sizeof(uint16_t)));
+    XQ_TRY(p1.reserve(G * rows, &grew));
+    XQ_TRY(p2.reserve(G * rows, &grew));
+    XQ_TRY(R.reserve((size_t)((NO + 63) / 64) * rows, &grew));       // at most one range per 64-row chunk
+    XQ_TRY(na.reserve(rows, &grew));
     if (grew)
         if (const char* e = getenv("XQ_DEBUG_PTRS")) if (e[0] == '1')
-            fprintf(stderr, "[xq] screening buffers: P1 %p P2 %p R %p ab %p na %p params %p acts %p\n", (void*)d->scr_p1.p, (void*)d->scr_p2.p,
-                    (void*)d->scr_R.p, (void*)d->scr_ab.p, (void*)d->scr_na.p, (void*)d->params[0].p, (void*)d->tacts[0].p);
+            fprintf(stderr, "[xq] screening buffers: P1 %p P2 %p R %p ab %p na %p params %p acts %p\n", (void*)p1.p, (void*)p2.p,
+                    (void*)R.p, (void*)ab.p, (void*)na.p, params, acts);
     // candidate counters: one pair per refine block (32 samples); the totals of the array it replaces are carried on the host.
-    // scr_stat_blocks is the capacity of the pair (array + pinned copy): 0 while it is being replaced, so that a failure in between
-    // leaves totals that screen_stat_sums still gets right and a pair that the next call allocates again
+    // stat_blocks is the capacity of the pair (array + pinned copy): 0 while it is being replaced, so that a failure in between
+    // leaves totals that totals() still gets right and a pair that the next call allocates again
     const int blocks = (int)(rows / kRefineSamples);
-    if (blocks > d->scr_stat_blocks) {
-        if (d->scr_stat_blocks) {
+    if (blocks > stat_blocks) {
+        if (stat_blocks) {
             unsigned long long sums[2];
-            XQ_TRY(screen_stat_sums(d, sums));
-            d->scr_carry[0] = sums[0]; d->scr_carry[1] = sums[1];
-            d->scr_guard_pending = false;
+            XQ_TRY(totals(sums));
+            carry[0] = sums[0]; carry[1] = sums[1];
+            guard_pending = false;
         }
-        d->scr_stat_blocks = 0;
-        XQ_TRY(d->scr_stats.reserve((size_t)2 * blocks));
-        XQ_HIP(hipMemset(d->scr_stats, 0, d->scr_stats.n * sizeof(unsigned long long)));
-        XQ_TRY(d->scr_guard_host.reserve((size_t)2 * blocks));
-        memset(d->scr_guard_host, 0, d->scr_guard_host.n * sizeof(unsigned long long));
-        d->scr_stat_blocks = blocks;
+        stat_blocks = 0;
+        XQ_TRY(stats.reserve((size_t)2 * blocks));
+        XQ_HIP(hipMemset(stats, 0, stats.n * sizeof(unsigned long long)));
+        XQ_TRY(guard_host.reserve((size_t)2 * blocks));
+        memset(guard_host, 0, guard_host.n * sizeof(unsigned long long));
+        stat_blocks = blocks;
     }
     return XQ_OK;
 }
@@ -1135,9 +1150,34 @@ static void soft_td_segments(const xq_dqn* d, SoftArgs* Z) {
     add(d->bl(1, 0), nullptr);
     add(d->bl(1, top), nullptr);
 }
+// What a write of params[] or params_bf[] makes stale.  Every site that queues one calls this exactly once and touches none of the derived
+// state itself; how the bf16 shadow is brought up to date stays at the site (the mechanisms differ).
+//   write                                                        params_version  screen rows >= 96         kept sums of select  tgt_rest_synced
+//   ONLINE_WHOLE  set_params(0), so load_model; backpropagate    +1              invalid if the online's   dropped              false
+//   TARGET_HOST   set_params(1)                                  +1              invalid if the target's   kept                 false
+//   TARGET_COPY   target := online (update_target)               +1              invalid if the target's   kept                 true
+//   TARGET_BLEND  whole-buffer soft update (soft_target_whole)   +1              invalid if the target's   kept                 unchanged
+//   TD_SEGMENTS   apply_grads (fused soft form: the target's     +1              kept (only rows 0..95     dropped, pays/calls  unchanged
+//                 TD segments too)                                               move)                     rolled over
+//   BF16_SHADOW   set_precision rebuilds the shadow              +1              kept                      kept                 unchanged
+// (params_version: is the trainer's ev_params still current?  The kept layer-0 sums are the online net's alone.)
+// Order: what invalidates comes before the write is queued, so a launch that fails leaves the derived state on the conservative side.
+// TARGET_COPY is the one row that asserts something: its site calls behind the copy, once that was queued successfully.
+enum class ParamWrite { ONLINE_WHOLE, TARGET_HOST, TARGET_COPY, TARGET_BLEND, TD_SEGMENTS, BF16_SHADOW };
+static void params_written(xq_dqn* d, ParamWrite what) {
+    d->params_version += 1;
+    switch (what) {
+    case ParamWrite::ONLINE_WHOLE:  d->scr.rows_rewritten(XQ_NET_ONLINE); d->sel_invalidate(); d->tgt_rest_synced = false; break;
+    case ParamWrite::TARGET_HOST:   d->scr.rows_rewritten(XQ_NET_TARGET); d->tgt_rest_synced = false; break;
+    case ParamWrite::TARGET_COPY:   d->scr.rows_rewritten(XQ_NET_TARGET); d->tgt_rest_synced = true; break;
+    case ParamWrite::TARGET_BLEND:  d->scr.rows_rewritten(XQ_NET_TARGET); break;
+    case ParamWrite::TD_SEGMENTS:   d->sel_invalidate(); for (auto& K : d->sel_keep) { K.pays = K.calls >= 2; K.calls = 0; } break;
+    case ParamWrite::BF16_SHADOW:   break;
+    }
+}
+
 // One soft update of the whole target net from the online buffer (soft_target_kernel), on the handle's stream: every parameter and the
-// shadow of every weight.  Any row of the target's output layer may change, so a screening shadow that holds the target's rows >= 96 is
-// no longer valid (as behind xq_dqn_update_target).  Where the two nets agree nothing moves: tgt_rest_synced stays what it was.
+// shadow of every weight.
 static int soft_target_whole(xq_dqn* d, double tau) {
     const long long n = (long long)(d->nw + d->nb);
     const float* p = d->params[0];
@@ -1146,8 +1186,7 @@ static int soft_target_whole(xq_dqn* d, double tau) {
     const int vec = ((((uintptr_t)p | (uintptr_t)t) & 15) == 0 && ((uintptr_t)tb & 7) == 0) ? 1 : 0;
     const long long items = vec ? (n >> 2) + 3 : n;
     const unsigned blocks = (unsigned)std::max<long long>(1, std::min<long long>((items + 255) / 256, 2048));
-    d->params_version += 1;
-    if (d->scr_static_net == XQ_NET_TARGET) d->scr_static_net = -1;
+    params_written(d, ParamWrite::TARGET_BLEND);
     ProfScope ps(d, "soft_target", 2.0 * n, 12.0 * n + (tb ? 2.0 * d->nw : 0.0), true);
     hipExtLaunchKernelGGL(soft_target_kernel, dim3(blocks), dim3(256), 0, d->cur, ps.start(), ps.stop(), 0, p, t, tb, n, (long long)d->nw,
                           (float)tau, vec);
@@ -1243,7 +1282,6 @@ int xq_dqn_destroy(xq_dqn* d) {
     if (d->ev_join) hipEventDestroy(d->ev_join);
     if (d->ev_delta) hipEventDestroy(d->ev_delta);
     if (d->ev_qmax) hipEventDestroy(d->ev_qmax);
-    if (d->scr_guard_ev) hipEventDestroy(d->scr_guard_ev);
     if (d->own_stream) hipStreamDestroy(d->stream);
     delete d;                                                // the buffers go here: behind the synchronises above
     return XQ_OK;
@@ -1271,11 +1309,8 @@ int xq_dqn_set_params(xq_dqn* d, int net, const double* w, const double* b) {
     for (size_t i = d->wo[1]; i < d->nw; ++i) p[i] = (float)w[i];
     for (size_t i = 0; i < d->nb; ++i) p[d->nw + i] = (float)b[i];
     XQ_HIP(hipStreamSynchronize(d->stream));
+    params_written(d, net == XQ_NET_ONLINE ? ParamWrite::ONLINE_WHOLE : ParamWrite::TARGET_HOST);
     XQ_HIP(hipMemcpy(d->params[net], p.data(), p.size() * sizeof(float), hipMemcpyHostToDevice));
-    if (d->scr_static_net == net) d->scr_static_net = -1;       // screening shadow: rows >= 96 are no longer what it holds
-    if (net == XQ_NET_ONLINE) d->sel_invalidate();              // kept layer-0 sums of the select chain belong to the old weights
-    d->tgt_rest_synced = false;                                 // soft target update: the nets may now differ outside the TD segments
-    d->params_version += 1;
     XQ_TRY(refresh_shadow(d, net));
     XQ_HIP(hipStreamSynchronize(d->stream));                    // a host-buffer entry point returns with the parameters in place
     return XQ_OK;
@@ -1299,10 +1334,8 @@ int xq_dqn_get_params(xq_dqn* d, int net, double* w, double* b) {
 int xq_dqn_update_target(xq_dqn* d) {
     if (!d) return fail(XQ_ERR_INVALID_ARGUMENT, "null dqn");
     ProfScope ps(d, "target_sync_copy", 0, 8.0 * (d->nw + d->nb));
-    d->params_version += 1;
     XQ_HIP(hipMemcpyAsync(d->params[1], d->params[0], (d->nw + d->nb) * sizeof(float), hipMemcpyDeviceToDevice, d->stream));
-    if (d->scr_static_net == XQ_NET_TARGET) d->scr_static_net = -1;     // screening shadow: every row of the target net changed
-    d->tgt_rest_synced = true;                                          // soft target update: the nets agree everywhere
+    params_written(d, ParamWrite::TARGET_COPY);
     if (d->bf16())
         XQ_HIP(hipMemcpyAsync(d->params_bf[1], d->params_bf[0], d->nw * sizeof(uint16_t), hipMemcpyDeviceToDevice, d->stream));
     return XQ_OK;
@@ -1330,7 +1363,7 @@ int xq_dqn_set_l0_grad_mode(xq_dqn* d, int mode) {
 
 int xq_dqn_set_refine_stage(xq_dqn* d, int mode) {
     if (!d || mode < -1 || mode > 1) return fail(XQ_ERR_INVALID_ARGUMENT, "xq_dqn_set_refine_stage: -1 (by the screen's counters), 0 (never) or 1 (whenever the launch has room)");
-    d->refine_stage = mode;
+    d->scr.refine_stage = mode;
     return XQ_OK;
 }
 
@@ -1348,23 +1381,22 @@ int xq_dqn_set_exchange_overlap(xq_dqn* d, int mode) {
 
 int xq_dqn_set_qmax_mode(xq_dqn* d, int mode) {
     if (!d || (mode != XQ_QMAX_FULL && mode != XQ_QMAX_SCREENED)) return fail(XQ_ERR_INVALID_ARGUMENT, "bad qmax mode");
-    d->qmax_mode = mode;
-    d->scr_hold = 0;                       // an explicit request starts with the screen switched on again
+    d->scr.set_mode(mode);
     return XQ_OK;
 }
 
 int xq_dqn_qmax_stats(xq_dqn* d, uint64_t stats[4]) {
     if (!d || !stats) return fail(XQ_ERR_INVALID_ARGUMENT, "null");
     unsigned long long h[2] = {0, 0};
-    XQ_TRY(screen_stat_sums(d, h));
-    stats[0] = d->scr_host_steps; stats[1] = d->scr_host_samples; stats[2] = h[0]; stats[3] = h[1];
+    XQ_TRY(d->scr.totals(h));
+    stats[0] = d->scr.host_steps; stats[1] = d->scr.host_samples; stats[2] = h[0]; stats[3] = h[1];
     return XQ_OK;
 }
 
 int xq_dqn_qmax_guard(xq_dqn* d, uint64_t* fallbacks, int* hold_steps_left) {
     if (!d) return fail(XQ_ERR_INVALID_ARGUMENT, "null dqn");
-    if (fallbacks) *fallbacks = d->scr_fallbacks;
-    if (hold_steps_left) *hold_steps_left = d->scr_hold;
+    if (fallbacks) *fallbacks = d->scr.fallbacks;
+    if (hold_steps_left) *hold_steps_left = d->scr.hold;
     return XQ_OK;
 }
 
@@ -1382,7 +1414,7 @@ int xq_dqn_set_precision(xq_dqn* d, int precision) {
         for (auto& p : d->params_bf) XQ_TRY(reserve_zeroed(p, d->nw + pad, d->stream));      // (first call only)
     }
     d->precision = precision;
-    d->params_version += 1;
+    params_written(d, ParamWrite::BF16_SHADOW);
     XQ_TRY(refresh_shadow(d, 0));
     return refresh_shadow(d, 1);
 }
@@ -1499,12 +1531,9 @@ int xq_dqn_backpropagate(xq_dqn* d, const double* states, const double* targets,
     XQ_TRY(bias_grads(d, bj, n));
     SegTable t; memset(&t, 0, sizeof t);
     t.nseg = 1; t.dst[0] = d->params[0]; t.src[0] = d->grads_full; t.len[0] = (long long)(d->nw + d->nb);
-    d->params_version += 1;
+    params_written(d, ParamWrite::ONLINE_WHOLE);       // dense update: every row changes, and the target net, which this never touches, no longer has them
     XQ_TRY(sgd_apply(d, t, lr * grad_scale));
     XQ_TRY(refresh_shadow(d, XQ_NET_ONLINE));          // bf16 Q-net: every later bf16 forward must see the updated weights
-    if (d->scr_static_net == XQ_NET_ONLINE) d->scr_static_net = -1;    // dense update: every output row changed (screening shadow)
-    d->tgt_rest_synced = false;                        // ... and the target net, which this never touches, no longer has them
-    d->sel_invalidate();
     XQ_HIP(hipStreamSynchronize(d->stream));
     return XQ_OK;
 }
@@ -1723,6 +1752,9 @@ static int tail_gradients(xq_dqn* d, int n, float* const* outs, float* G, int mo
 
 // ---- one TD step (td_grads_impl): the stages below, in the order the step runs them -----------------------------------------------
 
+// The screen's part of one TD step, decided at the step's top (Screen::plan): screened at all (else qmax_exact), with screen_top2_kernel for
+// the widths it is built for (else the persistent tile kernel's CM_TOP2 mode), the parity of the wmax slots, the conversion of the shadow
+struct ScreenPlan { bool screened, top2; int parity; ShadowJob shadow; };
 // What the stages of one step share: its inputs, and the shapes and views decided once at its top.
 struct TdStep {
     const int32_t* action_to; const float* reward; const uint8_t* done; SlotSrc slots; const PerOpts* per;
@@ -1730,53 +1762,81 @@ struct TdStep {
     bool big_tiles;              // the max pass's product on 128-row tiles
     int n_partial;               // partial maxima per sample of the max pass's tile kernels
     size_t bias_lds;             // the whole output bias in the persistent column-max kernel's LDS
+    ScreenPlan scr;              // the screened max pass, or not
     float* outs[XQ_MAX_LAYERS]; uint16_t* outs_bf[XQ_MAX_LAYERS];        // s on the online net (kept for the backward pass)
     float* touts[XQ_MAX_LAYERS]; uint16_t* touts_bf[XQ_MAX_LAYERS];      // s' on the selecting net
     float* t2outs[XQ_MAX_LAYERS]; uint16_t* t2outs_bf[XQ_MAX_LAYERS];    // s' on the target net (Double DQN)
     const float* view; long long view_ld; int view_kmax;                 // the online weights that carry the output delta down a layer
 };
 
-// The screening guard of a step that asks for the screened max pass.  The counters queued at one check boundary are evaluated at the NEXT
-// one (32 screened steps later: the copy finished long ago, the wait returns at once) — the step at which a fallback begins is a function
-// of the step count alone, never of how far the host runs ahead of the device.  *screened: whether this step screens.
-static int screen_guard_tick(xq_dqn* d, int n, bool* screened) {
-    XQ_TRY(ensure_screen_capacity(d, n));
-    if (d->scr_guard_pending && d->scr_host_steps % kScreenCheckEvery == 0 && d->scr_host_steps != d->scr_guard_queued_at) {
-        XQ_HIP(hipEventSynchronize(d->scr_guard_ev));
-        d->scr_guard_pending = false;
-        unsigned long long h[2];
-        screen_stat_sums_of(d, d->scr_guard_host, h);
-        const double ds = (double)(d->scr_guard_samples - d->scr_seen[0]);
-        if (ds > 0 && ((double)(h[0] - d->scr_seen[1]) > kScreenMaxPairs * ds || (double)(h[1] - d->scr_seen[2]) > kScreenMaxWhole * ds)) {
-            d->scr_hold = kScreenHoldSteps;
-            d->scr_fallbacks += 1;
-        }
-        if (ds > 0) {                                // whole groups per sample over the window, with hysteresis
-            const double share = (double)(h[1] - d->scr_seen[2]) / ds;
-            if (share > 0.25) d->scr_stage_whole = true; else if (share < 0.10) d->scr_stage_whole = false;
-        }
-        d->scr_seen[0] = d->scr_guard_samples; d->scr_seen[1] = h[0]; d->scr_seen[2] = h[1];
+// The screening guard.  The counters queued at one check boundary (guard_queue) are evaluated at the NEXT one (guard_tick, 32 screened
+// steps later: the copy finished long ago, the wait returns at once) — the step at which a fallback begins is a function of the step
+// count alone, never of how far the host runs ahead of the device.  guard_decide: the rule, on the totals of the copy (no runtime call)
+void Screen::guard_decide(const unsigned long long h[2]) {
+    const double ds = (double)(guard_samples - seen[0]);
+    if (ds > 0 && ((double)(h[0] - seen[1]) > kScreenMaxPairs * ds || (double)(h[1] - seen[2]) > kScreenMaxWhole * ds)) {
+        hold = kScreenHoldSteps;
+        fallbacks += 1;
     }
-    *screened = d->scr_hold == 0;
-    if (d->scr_hold > 0) --d->scr_hold;
+    if (ds > 0) {                                    // whole groups per sample over the window, with hysteresis
+        const double share = (double)(h[1] - seen[2]) / ds;
+        if (share > 0.25) stage_whole = true; else if (share < 0.10) stage_whole = false;
+    }
+    seen[0] = guard_samples; seen[1] = h[0]; seen[2] = h[1];
+}
+// at the top of a step that asks for the screened max pass.  *screened: whether this step screens
+int Screen::guard_tick(bool* screened) {
+    if (guard_pending && host_steps % kScreenCheckEvery == 0 && host_steps != guard_queued_at) {
+        XQ_HIP(hipEventSynchronize(guard_ev));
+        guard_pending = false;
+        unsigned long long h[2];
+        totals_of(guard_host, h);
+        guard_decide(h);
+    }
+    *screened = hold == 0;
+    if (hold > 0) --hold;
+    return XQ_OK;
+}
+// behind the launches of a screened step: count it and, every kScreenCheckEvery steps, queue the copy of the counters
+int Screen::guard_queue(int n, hipStream_t s) {
+    host_steps += 1; host_samples += (unsigned long long)n;
+    if (host_steps % kScreenCheckEvery == 0 && !guard_pending) {
+        XQ_HIP(hipMemcpyAsync(guard_host, stats, (size_t)2 * stat_blocks * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+        XQ_HIP(hipEventRecord(guard_ev, s));
+        guard_pending = true; guard_samples = host_samples; guard_queued_at = host_steps;
+    }
     return XQ_OK;
 }
 
 // bf16 copy + largest row norm / |bias| of the selecting net's output-layer weights.  Only rows 0..95 change under the TD rule: while
-// `scr_static_net` says that rows >= 96 of the shadow (and their maxima, slots [4], [5]) still belong to this net, the shadow pass converts
-// three blocks of 32 rows instead of 254; everything is converted again after set_params / load_model / update_target / a dense
-// backpropagate / a change of the selecting net.  The maxima of rows 0..95 land in the slots of this step's parity, which the refine kernel
-// of the previous screened step zeroed.
-static int screen_shadow_job(xq_dqn* d, int sel_net, int parity, ShadowJob* shadow) {
+// `static_net` says that rows >= 96 of the shadow (and their maxima, slots [4], [5]) still belong to this net, the shadow pass converts
+// three blocks of 32 rows instead of 254; everything is converted again after a write of any other row (params_written) or a change of
+// the selecting net.  The maxima of rows 0..95 land in the slots of this step's parity, which the previous screened step's refine kernel zeroed.
+int Screen::shadow_job(const xq_dqn* d, int sel_net, int parity, hipStream_t s, ShadowJob* shadow) {
     const int NO = d->nout(), nl = d->nl;
-    const bool full = d->scr_static_net != sel_net;
-    if (full) XQ_HIP(hipMemsetAsync(d->scr_wmax + 4, 0, 2 * sizeof(unsigned), d->cur));     // (the maxima of rows >= 96 start again)
+    const bool full = static_net != sel_net;
+    if (full) XQ_HIP(hipMemsetAsync(wmax + 4, 0, 2 * sizeof(unsigned), s));     // (the maxima of rows >= 96 start again)
     memset(shadow, 0, sizeof *shadow);
-    shadow->W = d->wl(sel_net, nl - 1); shadow->bias = d->bl(sel_net, nl - 1); shadow->NO = NO; shadow->K = d->hlast(); shadow->Wb = d->scr_wb;
-    shadow->w_dyn = d->scr_wmax + parity; shadow->b_dyn = d->scr_wmax + 2 + parity;
-    shadow->w_stat = d->scr_wmax + 4; shadow->b_stat = d->scr_wmax + 5;
+    shadow->W = d->wl(sel_net, nl - 1); shadow->bias = d->bl(sel_net, nl - 1); shadow->NO = NO; shadow->K = d->hlast(); shadow->Wb = wb;
+    shadow->w_dyn = wmax + parity; shadow->b_dyn = wmax + 2 + parity;
+    shadow->w_stat = wmax + 4; shadow->b_stat = wmax + 5;
     shadow->nblocks = full ? (NO + kShadowRows - 1) / kShadowRows : std::min((int)kShadowDynBlocks, (NO + kShadowRows - 1) / kShadowRows);
-    d->scr_static_net = sel_net;
+    static_net = sel_net;
+    return XQ_OK;
+}
+
+// This step's part of the screen: the eligibility of its shape, the guard, the parity of its slots and the shadow conversion
+int Screen::plan(xq_dqn* d, const TdStep& s, ScreenPlan* P) {
+    const bool want_screen = mode == XQ_QMAX_SCREENED && !s.bf && !s.dbl && s.big_tiles && (s.Hl % 64) == 0 && s.Hl <= 1024 &&
+                             s.bias_lds <= 40 * 1024 && (s.NO + 127) / 128 * 4 <= 8 * kRefineMaxPerThread;
+    P->screened = false;
+    if (want_screen) {
+        XQ_TRY(reserve(s.NO, s.Hl, s.n, d->params[0].p, d->tacts[0].p));
+        XQ_TRY(guard_tick(&P->screened));
+    }
+    P->parity = (int)(host_steps & 1);
+    P->top2 = P->screened && (s.Hl == 256 || s.Hl == 512);
+    if (P->screened) XQ_TRY(shadow_job(d, s.sel_net, P->parity, d->cur, &P->shadow));
     return XQ_OK;
 }
 
@@ -1809,23 +1869,24 @@ static int colmax_persistent_grid(const xq_dqn* d, GemmArgs& g, int tiles_m, int
 }
 
 // Screened max_a' Q(s', a') of an fp32 net: the bf16 screening product (screen_top2_kernel for the widths it is built for,
-// the persistent tile kernel's CM_TOP2 mode otherwise), the exact fp32 refine of the candidates it leaves, and every kScreenCheckEvery
-// steps the copy of the guard's counters.  *td_fused: the refine kernel did td_delta_kernel's work too.
-static int qmax_screened(xq_dqn* d, const TdStep& s, bool scr_new, int parity, bool* td_fused) {
-    const int n = s.n, NO = s.NO, Hl = s.Hl, nl = s.nl;
+// the persistent tile kernel's CM_TOP2 mode otherwise), the exact fp32 refine of the candidates it leaves, and the guard's count of the step
+// (Screen::guard_queue).  *td_fused: the refine kernel did td_delta_kernel's work too.
+static int qmax_screened(xq_dqn* d, const TdStep& s, bool* td_fused) {
+    const int n = s.n, NO = s.NO, Hl = s.Hl, nl = s.nl, parity = s.scr.parity;
+    const bool top2 = s.scr.top2;  Screen& scr = d->scr;
     const float *W = d->wl(s.sel_net, nl - 1), *bias = d->bl(s.sel_net, nl - 1);
     const int tiles_m = (NO + 127) / 128, total = tiles_m * ((n + 127) / 128);
     // 32-row lane groups: the tile kernel writes all 4 per 128-row tile, screen_top2_kernel only those of 64-row chunks with real rows
-    const int G = scr_new ? 2 * ((NO + 63) / 64) : 4 * tiles_m;
+    const int G = top2 ? 2 * ((NO + 63) / 64) : 4 * tiles_m;
     long long ldp = n;
-    int scr_ranges = 0, scr_gpr = 0;
-    if (scr_new) {
+    int ranges = 0, gpr = 0;
+    if (top2) {
         ScreenArgs a; memset(&a, 0, sizeof a);
-        a.W = d->scr_wb; a.A = d->scr_ab; a.a_frag = 1; a.bias = bias;
-        a.P1 = d->scr_p1; a.P2 = d->scr_p2; a.R = d->scr_R; a.na = d->scr_na;
+        a.W = scr.wb; a.A = scr.ab; a.a_frag = 1; a.bias = bias;
+        a.P1 = scr.p1; a.P2 = scr.p2; a.R = scr.R; a.na = scr.na;
         screen_geometry(NO, n, Hl, d->ncu, a);
         ldp = a.ldp = screen_padded_samples(n, Hl);
-        scr_ranges = a.ranges; scr_gpr = 2 * a.cpr;
+        ranges = a.ranges; gpr = 2 * a.cpr;
         // (bracketed by its own start / stop events: the live figure is the kernel's duration as rocprofv3 reports it)
         ProfScope ps(d, "gemm_qmax_screen", 2.0 * NO * (double)n * Hl, 2.0 * ((double)NO * Hl + (double)n * Hl) + 8.0 * G * n, true);
         XQ_TRY(launch_screen(d, a, SCR_TOP2, ps.start(), ps.stop()));
@@ -1833,9 +1894,9 @@ static int qmax_screened(xq_dqn* d, const TdStep& s, bool scr_new, int parity, b
         GemmArgs g; memset(&g, 0, sizeof g);
         g.M = NO; g.N = n;
         g.K = Hl / 2; g.lda = g.ldb = Hl / 2;
-        g.A = reinterpret_cast<const float*>(d->scr_wb.p); g.B = reinterpret_cast<const float*>(d->scr_ab.p);
+        g.A = reinterpret_cast<const float*>(scr.wb.p); g.B = reinterpret_cast<const float*>(scr.ab.p);
         g.bias = bias;
-        g.partial = d->scr_p1; g.partial2 = d->scr_p2;
+        g.partial = scr.p1; g.partial2 = scr.p2;
         const int grid = colmax_persistent_grid(d, g, tiles_m, total);
         ProfScope ps(d, "gemm_qmax_screen", 2.0 * g.M * g.N * Hl, 2.0 * ((double)g.M * Hl + (double)g.N * Hl) + 8.0 * G * g.N);
         hipLaunchKernelGGL((gemm_colmax_persistent_kernel<2, 2, DT_BF16, CM_TOP2>), dim3(grid), dim3(256), s.bias_lds, d->cur, g, tiles_m, total);
@@ -1847,10 +1908,10 @@ static int qmax_screened(xq_dqn* d, const TdStep& s, bool scr_new, int parity, b
         ProfScope ps(d, "qmax_refine", 2.0 * n * Hl * 3, 12.0 * G * n + 4.0 * n * Hl, true);      // one launch: its own start / stop events
         const dim3 grid((n + kRefineSamples - 1) / kRefineSamples);
         // one block per CU and K = 256: room in LDS for the staged pass of qmax_refine2_kernel (whole groups that many samples ask for)
-        const bool stage = scr_new && Hl == 256 && (int)grid.x <= d->ncu && (d->refine_stage > 0 || (d->refine_stage < 0 && d->scr_stage_whole));
+        const bool stage = top2 && Hl == 256 && (int)grid.x <= d->ncu && (scr.refine_stage > 0 || (scr.refine_stage < 0 && scr.stage_whole));
         const size_t lds = refine_cand_words(G) * sizeof(uint32_t) + refine_wlist_bytes(G) + (stage ? refine_stage_bytes() : 0);
         const float* a_last = s.touts[nl - 2];
-        if (scr_new) {
+        if (top2) {
             TdFused T; memset(&T, 0, sizeof T);
             // the TD target / delta kernel rides in the refine blocks (fp32 net, 256-wide last hidden layer, uniform replay)
             *td_fused = d->td_tail && Hl == 256 && !s.per && !d->bf16_bwd();
@@ -1866,14 +1927,14 @@ static int qmax_screened(xq_dqn* d, const TdStep& s, bool scr_new, int parity, b
             if (*td_fused && d->loss_kind == XQ_LOSS_HUBER) {
                 const auto kern = qmax_refine2_kernel<256, true, HuberLoss>;
                 XQ_TRY(ensure_max_dynamic_lds(kern, 152 * 1024));
-                hipExtLaunchKernelGGL(kern, grid, dim3(256), lds, d->cur, ps.start(), ps.stop(), 0, d->scr_R.p, scr_ranges, scr_gpr, d->scr_p1.p, d->scr_p2.p,
-                                      G, n, ldp, d->scr_na.p, a_last, Hl, W, bias, NO, d->scr_wmax.p, parity, d->zmax.p, d->scr_stats.p, T, whole_mode,
+                hipExtLaunchKernelGGL(kern, grid, dim3(256), lds, d->cur, ps.start(), ps.stop(), 0, scr.R.p, ranges, gpr, scr.p1.p, scr.p2.p,
+                                      G, n, ldp, scr.na.p, a_last, Hl, W, bias, NO, scr.wmax.p, parity, d->zmax.p, scr.stats.p, T, whole_mode,
                                       HuberLoss{d->loss_kappa32});
             } else {
                 const auto kern = *td_fused ? qmax_refine2_kernel<256, true> : Hl == 256 ? qmax_refine2_kernel<256> : qmax_refine2_kernel<512>;
                 XQ_TRY(ensure_max_dynamic_lds(kern, 152 * 1024));     // the staged pass asks for ~145 KB
-                hipExtLaunchKernelGGL(kern, grid, dim3(256), lds, d->cur, ps.start(), ps.stop(), 0, d->scr_R.p, scr_ranges, scr_gpr, d->scr_p1.p, d->scr_p2.p,
-                                      G, n, ldp, d->scr_na.p, a_last, Hl, W, bias, NO, d->scr_wmax.p, parity, d->zmax.p, d->scr_stats.p, T, whole_mode,
+                hipExtLaunchKernelGGL(kern, grid, dim3(256), lds, d->cur, ps.start(), ps.stop(), 0, scr.R.p, ranges, gpr, scr.p1.p, scr.p2.p,
+                                      G, n, ldp, scr.na.p, a_last, Hl, W, bias, NO, scr.wmax.p, parity, d->zmax.p, scr.stats.p, T, whole_mode,
                                       SquaredLoss{});
             }
         } else {
@@ -1881,18 +1942,12 @@ static int qmax_screened(xq_dqn* d, const TdStep& s, bool scr_new, int parity, b
             const auto kern = Hl == 256 ? (small ? qmax_refine_kernel<256, 32> : qmax_refine_kernel<256, 64>)
                             : Hl == 512 ? (small ? qmax_refine_kernel<512, 32> : qmax_refine_kernel<512, 64>)
                                         : (small ? qmax_refine_kernel<0, 32> : qmax_refine_kernel<0, 64>);
-            hipExtLaunchKernelGGL(kern, grid, dim3(256), lds, d->cur, ps.start(), ps.stop(), 0, d->scr_p1.p, d->scr_p2.p, G, n, ldp, a_last, Hl,
-                                  W, bias, NO, d->scr_wmax.p, parity, d->zmax.p, d->scr_stats.p);
+            hipExtLaunchKernelGGL(kern, grid, dim3(256), lds, d->cur, ps.start(), ps.stop(), 0, scr.p1.p, scr.p2.p, G, n, ldp, a_last, Hl,
+                                  W, bias, NO, scr.wmax.p, parity, d->zmax.p, scr.stats.p);
         }
         XQ_HIP(hipGetLastError());
     }
-    d->scr_host_steps += 1; d->scr_host_samples += (unsigned long long)n;
-    if (d->scr_host_steps % kScreenCheckEvery == 0 && !d->scr_guard_pending) {
-        XQ_HIP(hipMemcpyAsync(d->scr_guard_host, d->scr_stats, (size_t)2 * d->scr_stat_blocks * sizeof(unsigned long long), hipMemcpyDeviceToHost, d->cur));
-        XQ_HIP(hipEventRecord(d->scr_guard_ev, d->cur));
-        d->scr_guard_pending = true; d->scr_guard_samples = d->scr_host_samples; d->scr_guard_queued_at = d->scr_host_steps;
-    }
-    return XQ_OK;
+    return scr.guard_queue(n, d->cur);
 }
 
 // Exact max_a' Q(s', a') (+ its row for Double DQN): partial maxima per sample from one of three products — the screen kernel's exact
@@ -2042,22 +2097,15 @@ static int td_grads_impl(xq_dqn* d, const uint32_t* boards, const uint32_t* next
     s.bias_lds = (size_t)((NO + 127) / 128) * 128 * sizeof(float);
     s.view = d->wrest(XQ_NET_ONLINE) + (d->wo[nl - 1] - d->wo[1]);
     s.view_ld = mode == XQ_BACKPROP_REFERENCE ? d->L[nl - 2] : d->L[nl - 1]; s.view_kmax = mode == XQ_BACKPROP_REFERENCE ? d->L[nl - 1] : NO;
-    const bool want_screen = d->qmax_mode == XQ_QMAX_SCREENED && !bf && !dbl && s.big_tiles && (Hl % 64) == 0 && Hl <= 1024 &&
-                             s.bias_lds <= 40 * 1024 && (NO + 127) / 128 * 4 <= 8 * kRefineMaxPerThread;
-    bool screened = false;
-    if (want_screen) XQ_TRY(screen_guard_tick(d, n, &screened));
-    const int parity = (int)(d->scr_host_steps & 1);
-    // screen_top2_kernel (xq_screen.hip.h) for the widths it is built for; the persistent tile kernel's CM_TOP2 mode otherwise
-    const bool scr_new = screened && (Hl == 256 || Hl == 512);
-    ShadowJob shadow;
-    if (screened) XQ_TRY(screen_shadow_job(d, s.sel_net, parity, &shadow));
+    XQ_TRY(d->scr.plan(d, s, &s.scr));
+    const bool screened = s.scr.screened;
     // 1. the forward chains in the same launches (one gather grid, grouped hidden GEMMs): s on the online net with the activations kept
     //    for the backward pass, s' on the net that selects (online, or target for XQ_TD_TARGET_NET) and, for Double DQN, s' on the target
     //    net that evaluates.  bf16 net: the s' chain's last activations feed only the max / arg-max pass; when both that pass and the
     //    forward product run on their own loops (whole tiles), the product writes them in fragment order
     const bool bf_frag = bf && nl >= 3 && (Hl == 256 || Hl == 512) && n >= 1024 && (n % kBgBM) == 0 && (d->L[nl - 2] % kBgBK) == 0;
     ChainJob jobs[3] = {{XQ_NET_ONLINE, boards, s.outs, s.outs_bf, d->gboards, nullptr, false},
-                        {s.sel_net, next_boards, s.touts, s.touts_bf, nullptr, screened ? d->scr_ab : nullptr, scr_new || bf_frag},
+                        {s.sel_net, next_boards, s.touts, s.touts_bf, nullptr, screened ? d->scr.ab : nullptr, s.scr.top2 || bf_frag},
                         {XQ_NET_TARGET, next_boards, s.t2outs, s.t2outs_bf, nullptr, nullptr, false}};
     // The select chain of the trainer starts at the end of the forward product (its stop event, when chain_boards can take it) when
     // max_a' Q(s',a') runs on the bf16 matrix pipe (screening pass of an fp32 net, or the output layer of a bf16 net): its layer-0 gather
@@ -2068,11 +2116,11 @@ static int td_grads_impl(xq_dqn* d, const uint32_t* boards, const uint32_t* next
     // The full fp32 product keeps the chip to itself: there the chain starts behind it (qmax_exact).
     const bool gate_early = (screened || bf) && !d->late_gate;
     hipEvent_t fork = gate_early ? d->ev_qmax : nullptr;
-    XQ_TRY(chain_boards(d, jobs, dbl ? 3 : 2, slots, n, screened ? &shadow : nullptr, &fork));
+    XQ_TRY(chain_boards(d, jobs, dbl ? 3 : 2, slots, n, screened ? &s.scr.shadow : nullptr, &fork));
     if (fork) XQ_HIP(hipEventRecord(fork, d->stream));             // chain_boards did not take the stop event: a marker instead
     // 2. max_a' Q(s', a'); 3. the TD delta, unless the refine kernel did it
     bool td_fused = false;
-    if (screened) XQ_TRY(qmax_screened(d, s, scr_new, parity, &td_fused));
+    if (screened) XQ_TRY(qmax_screened(d, s, &td_fused));
     else XQ_TRY(qmax_exact(d, s, bf_frag, gate_early));
     if (!td_fused) XQ_TRY(td_delta(d, s, screened ? 1 : kReduceParts));
     d->last_n = n;
@@ -2166,9 +2214,7 @@ int xq_dqn_apply_grads(xq_dqn* d, double lr, double grad_scale) {
         ++k;
     });
     t.nseg = k;
-    d->sel_invalidate();                              // W0 / b0 change: the select chain's kept layer-0 sums are stale
-    for (auto& K : d->sel_keep) { K.pays = K.calls >= 2; K.calls = 0; }
-    d->params_version += 1;
+    params_written(d, ParamWrite::TD_SEGMENTS);
     ClipArgs C; memset(&C, 0, sizeof C);
     const bool clip = d->clip_max_norm > 0.0;
     if (clip) XQ_TRY(grad_norm(d, t, grad_scale, &C));
