@@ -23,7 +23,7 @@ struct xq_arena {
     xq::PinnedBuf<int> live_host;
     xq::DevBuf<xq_step_result> results;     // [2 pairs] the last ply's step results
     xq::DevBuf<int16_t> pick;               // [2 pairs] the search players' move indices of the ply (xq_search.hip)
-    hipEvent_t ev_env = nullptr, ev_q[2] = {nullptr, nullptr};
+    xq::Event ev_env, ev_q[2];
 };
 
 namespace xq {
@@ -131,10 +131,7 @@ extern "C" {
 
 int xq_arena_destroy(xq_arena* a) {
     if (!a) return XQ_OK;
-    if (a->env) hipStreamSynchronize(a->env->stream);
-    if (a->ev_env) hipEventDestroy(a->ev_env);
-    for (auto ev : a->ev_q) if (ev) hipEventDestroy(ev);
-    xq_env_destroy(a->env);
+    xq_env_destroy(a->env);             // synchronises the arena's stream: the buffers below go behind it
     delete a;
     return XQ_OK;
 }
@@ -149,8 +146,8 @@ static int arena_init(xq_arena* a, int n_pairs, uint64_t seed, uint32_t first_ga
     XQ_TRY(a->results.alloc(n));
     XQ_TRY(a->pick.alloc(n));
     XQ_TRY(a->live_host.alloc(1));
-    XQ_HIP(hipEventCreateWithFlags(&a->ev_env, stream_event_flags()));
-    for (auto& ev : a->ev_q) XQ_HIP(hipEventCreateWithFlags(&ev, stream_event_flags()));
+    XQ_TRY(a->ev_env.create(stream_event_flags()));
+    for (auto& ev : a->ev_q) XQ_TRY(ev.create(stream_event_flags()));
     return xq_arena_reset(a, 8);
 }
 

@@ -59,7 +59,7 @@ RcclApi& rccl() {
 struct xq_comm {
     ncclComm_t comm = nullptr;
     int rank = 0, world = 1;
-    hipStream_t stream = nullptr;          // stand-alone collectives only (created on first use); the TD step uses its producers' streams
+    xq::Stream stream;                     // stand-alone collectives only (created on first use); the TD step uses its producers' streams
     uint64_t collectives = 0, floats = 0;  // issued so far (tests, bench)
     xq::DevBuf<unsigned long long> scalar; // device scratch of xq_comm_sum_u64
 };
@@ -81,9 +81,8 @@ int comm_allreduce_on(xq_comm* c, float* buf, size_t n_floats, hipStream_t strea
     return XQ_OK;
 }
 int comm_world(const xq_comm* c) { return c->world; }
-static int comm_own_stream(xq_comm* c) {
-    if (!c->stream) XQ_HIP(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-    return XQ_OK;
+static int comm_open_stream(xq_comm* c) {
+    return c->stream ? XQ_OK : c->stream.open_owned(hipStreamNonBlocking);
 }
 
 }  // namespace xq
@@ -161,9 +160,8 @@ int xq_comm_create_from_file(int rank, int world, const char* path, double timeo
 
 int xq_comm_destroy(xq_comm* c) {
     if (!c) return XQ_OK;
-    if (c->stream) hipStreamSynchronize(c->stream);
+    c->stream.close();
     if (c->comm) rccl().CommDestroy(c->comm);
-    if (c->stream) hipStreamDestroy(c->stream);
     delete c;
     return XQ_OK;
 }
@@ -180,7 +178,7 @@ int xq_comm_info(const xq_comm* c, int* rank, int* world, uint64_t* collectives,
 int xq_comm_sum_u64(xq_comm* c, uint64_t* inout_host) {
     if (!c || !inout_host) return fail(XQ_ERR_INVALID_ARGUMENT, "null pointer");
     unsigned long long v = *inout_host;
-    XQ_TRY(comm_own_stream(c));
+    XQ_TRY(comm_open_stream(c));
     XQ_HIP(hipMemcpyAsync(c->scalar, &v, sizeof v, hipMemcpyHostToDevice, c->stream));
     XQ_RCCL(rccl().AllReduce(c->scalar, c->scalar, 1, ncclUint64, ncclSum, c->comm, c->stream));
     XQ_HIP(hipMemcpyAsync(&v, c->scalar, sizeof v, hipMemcpyDeviceToHost, c->stream));
@@ -191,7 +189,7 @@ int xq_comm_sum_u64(xq_comm* c, uint64_t* inout_host) {
 
 int xq_comm_allreduce(xq_comm* c, float* buf_dev, size_t n_floats, void* hip_stream) {
     if (!c || !buf_dev) return fail(XQ_ERR_INVALID_ARGUMENT, "null pointer");
-    if (!hip_stream) XQ_TRY(comm_own_stream(c));
+    if (!hip_stream) XQ_TRY(comm_open_stream(c));
     return comm_allreduce_on(c, buf_dev, n_floats, hip_stream ? (hipStream_t)hip_stream : c->stream);
 }
 

@@ -65,7 +65,7 @@ struct Screen {
     // steps later; a net that leaves the screen too many candidates (outputs all within the bf16 bound of each other) gets the full
     // product for the next kScreenHoldSteps steps
     PinnedBuf<unsigned long long> guard_host;   // pinned copy of stats
-    hipEvent_t guard_ev = nullptr;              // created on first use (reserve)
+    Event guard_ev;                             // created on first use (reserve)
     bool guard_pending = false;
     unsigned long long guard_samples = 0, guard_queued_at = 0;      // host_samples, host_steps when the pending copy was queued
     bool stage_whole = false;                   // the last counter window showed whole groups for many samples: the refine kernel is launched with the LDS of its
@@ -73,7 +73,6 @@ struct Screen {
     unsigned long long seen[3] = {0, 0, 0};     // samples, pairs, whole groups at the last evaluation
     int hold = 0;                               // > 0: that many TD steps still run the full product
     unsigned long long fallbacks = 0;
-    ~Screen() { if (guard_ev) hipEventDestroy(guard_ev); }
     void set_mode(int m) { mode = m; hold = 0; }         // an explicit request starts with the screen switched on again
     void rows_rewritten(int net) { if (static_net == net) static_net = -1; }     // rows >= 96 of `net` are no longer what the shadow holds
     // (defined below the kernel headers, whose constants they use)
@@ -91,17 +90,16 @@ struct xq_dqn {
     size_t wo[XQ_MAX_LAYERS] = {0}, bo[XQ_MAX_LAYERS] = {0};
     double lr = 1e-3, gamma = 0.99;
     uint64_t seed = 0;
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
+    xq::Stream stream;
     // side stream for work that is independent of the main chain inside one TD step (the s-chain forward runs beside the
     // s'-chain + column-max GEMM; the layer-0 gradient beside the other gradient GEMMs); `cur` = stream launches go to (OnStream)
-    hipStream_t side = nullptr;
+    xq::Stream side;
     hipStream_t cur = nullptr;
     int ncu = 256;                              // compute units of the device (persistent-kernel grid = 2 per CU)
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_delta = nullptr;
-    hipEvent_t ev_qmax = nullptr;               // recorded behind the column-max GEMM of the last TD step (trainer: collect starts here)
+    xq::Event ev_fork, ev_join, ev_delta;
+    xq::Event ev_qmax;                          // recorded behind the column-max GEMM of the last TD step (trainer: collect starts here)
     xq::DevBuf<float> params[2];
-    uint64_t params_version = 0;                // ++ whenever an operation that rewrites parameters is queued (params_written; xq_trainer: is ev_params still current?)
+    uint64_t params_version = 0;                // ++ whenever an operation that rewrites parameters is queued (params_written; xq_trainer: is its `params` mark still current?)
     // bf16 Q-net (xq_dqn_set_precision): bf16 shadow of the WEIGHTS of both nets, same element order as params[] (biases stay fp32);
     // forward kernels read the shadow, the backward pass and the SGD step work on the fp32 master copy and refresh the shadow
     int precision = XQ_PRECISION_F32;
@@ -450,7 +448,7 @@ int Screen::reserve(int NO, int Hl, int n, const void* params, const void* acts)
     grew = false;
     XQ_TRY(wmax.reserve(6, &grew));
     if (grew) XQ_HIP(hipMemset(wmax, 0, 6 * sizeof(unsigned)));
-    if (!guard_ev) XQ_HIP(hipEventCreateWithFlags(&guard_ev, hipEventDisableTiming));
+    XQ_TRY(guard_ev.create(hipEventDisableTiming));
     // sample dimension padded to whole blocks of screen_top2_kernel (512): it stores every column of its panels unconditionally
     const size_t rows = (size_t)round_up(n, 512), G = (size_t)4 * ((NO + 127) / 128);
     grew = false;
@@ -1160,7 +1158,7 @@ static void soft_td_segments(const xq_dqn* d, SoftArgs* Z) {
 //   TD_SEGMENTS   apply_grads (fused soft form: the target's     +1              kept (only rows 0..95     dropped, pays/calls  unchanged
 //                 TD segments too)                                               move)                     rolled over
 //   BF16_SHADOW   set_precision rebuilds the shadow              +1              kept                      kept                 unchanged
-// (params_version: is the trainer's ev_params still current?  The kept layer-0 sums are the online net's alone.)
+// (params_version: is the trainer's `params` mark still current?  The kept layer-0 sums are the online net's alone.)
 // Order: what invalidates comes before the write is queued, so a launch that fails leaves the derived state on the conservative side.
 // TARGET_COPY is the one row that asserts something: its site calls behind the copy, once that was queued successfully.
 enum class ParamWrite { ONLINE_WHOLE, TARGET_HOST, TARGET_COPY, TARGET_BLEND, TD_SEGMENTS, BF16_SHADOW };
@@ -1235,19 +1233,15 @@ static int dqn_init(xq_dqn* d, const int* layer_sizes, int n_sizes, double learn
         d->nb += (size_t)d->L[l + 1];
     }
     d->lr = learning_rate; d->gamma = gamma; d->seed = seed;
-    if (hip_stream) d->stream = (hipStream_t)hip_stream;
-    else { XQ_HIP(hipStreamCreate(&d->stream)); d->own_stream = true; }
+    XQ_TRY(d->stream.open(hip_stream));
     d->cur = d->stream;
     {
         hipDeviceProp_t prop; int dev = 0;
         if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
             d->ncu = prop.multiProcessorCount;
     }
-    XQ_HIP(hipStreamCreateWithFlags(&d->side, hipStreamNonBlocking));
-    XQ_HIP(hipEventCreateWithFlags(&d->ev_fork, stream_event_flags()));
-    XQ_HIP(hipEventCreateWithFlags(&d->ev_join, stream_event_flags()));
-    XQ_HIP(hipEventCreateWithFlags(&d->ev_delta, stream_event_flags()));
-    XQ_HIP(hipEventCreateWithFlags(&d->ev_qmax, stream_event_flags()));
+    XQ_TRY(d->side.open_owned(hipStreamNonBlocking));
+    for (Event* ev : {&d->ev_fork, &d->ev_join, &d->ev_delta, &d->ev_qmax}) XQ_TRY(ev->create(stream_event_flags()));
     // + 128 rows of the widest layer: the persistent column-max GEMM reads whole 128-row tiles of W_out (rows beyond the
     // last output are masked in its epilogue, but must be readable)
     int widest = 0;
@@ -1271,25 +1265,17 @@ static int dqn_init(xq_dqn* d, const int* layer_sizes, int n_sizes, double learn
 
 int xq_dqn_destroy(xq_dqn* d) {
     if (!d) return XQ_OK;
-    hipStreamSynchronize(d->stream);
-    if (d->side) hipStreamSynchronize(d->side);
-    retire_stream(d->stream);                                // (synchronised above: nothing queued on it is left to wait for — also when the stream is the caller's, which may destroy it next)
-    if (d->side) retire_stream(d->side);
-    d->prof.collect();
-    if (d->side) hipStreamDestroy(d->side);
+    d->prof.collect();                                       // (waits for its brackets' events: both streams still exist)
+    d->side.close();
+    d->stream.close();
     delete d->tail;
-    if (d->ev_fork) hipEventDestroy(d->ev_fork);
-    if (d->ev_join) hipEventDestroy(d->ev_join);
-    if (d->ev_delta) hipEventDestroy(d->ev_delta);
-    if (d->ev_qmax) hipEventDestroy(d->ev_qmax);
-    if (d->own_stream) hipStreamDestroy(d->stream);
-    delete d;                                                // the buffers go here: behind the synchronises above
+    delete d;                                                // the buffers and events go here: behind the synchronises above
     return XQ_OK;
 }
 
 int xq_dqn_stream(const xq_dqn* d, void** s) {
     if (!d || !s) return fail(XQ_ERR_INVALID_ARGUMENT, "null pointer");
-    *s = (void*)d->stream;
+    *s = (void*)(hipStream_t)d->stream;
     return XQ_OK;
 }
 
@@ -2141,25 +2127,24 @@ int xq_dqn_calibrate_exchange(xq_dqn* d, double threshold_us, double* allreduce_
     // COLLECTIVE: every rank times the same 4 + 20 all-reduces of a scratch buffer of the gradient buffer's size on the handle's stream
     DevBuf<float> scratch;
     XQ_TRY(scratch.alloc(d->n_grads_td));
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    int rc = XQ_OK;
     float ms = 0.f;
     const int reps = 20;
-    do {
-        if (hipMemsetAsync(scratch, 0, d->n_grads_td * sizeof(float), d->stream) != hipSuccess || hipEventCreate(&e0) != hipSuccess ||
-            hipEventCreate(&e1) != hipSuccess) { rc = fail(XQ_ERR_RUNTIME, "xq_dqn_calibrate_exchange: HIP setup failed"); break; }
-        for (int i = 0; i < 4 && rc == XQ_OK; ++i) rc = comm_allreduce_on(d->comm, scratch, d->n_grads_td, d->stream);
-        if (rc != XQ_OK) break;
-        if (hipEventRecord(e0, d->stream) != hipSuccess) { rc = fail(XQ_ERR_RUNTIME, "hipEventRecord failed"); break; }
-        for (int i = 0; i < reps && rc == XQ_OK; ++i) rc = comm_allreduce_on(d->comm, scratch, d->n_grads_td, d->stream);
-        if (rc != XQ_OK) break;
-        if (hipEventRecord(e1, d->stream) != hipSuccess || hipEventSynchronize(e1) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess)
-            rc = fail(XQ_ERR_RUNTIME, "xq_dqn_calibrate_exchange: timing failed");
-    } while (0);
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    (void)hipStreamSynchronize(d->stream);           // (nothing queued reads the scratch buffer when it goes, however this returns)
-    if (rc != XQ_OK) return rc;
+    {
+        struct SyncOnExit {                          // nothing queued reads the scratch buffer when it goes, however this returns
+            hipStream_t s;
+            ~SyncOnExit() { (void)hipStreamSynchronize(s); }
+        } drained{d->stream};
+        Event e0, e1;
+        XQ_HIP(hipMemsetAsync(scratch, 0, d->n_grads_td * sizeof(float), d->stream));
+        XQ_TRY(e0.create(hipEventDefault));
+        XQ_TRY(e1.create(hipEventDefault));
+        for (int i = 0; i < 4; ++i) XQ_TRY(comm_allreduce_on(d->comm, scratch, d->n_grads_td, d->stream));
+        XQ_HIP(hipEventRecord(e0, d->stream));
+        for (int i = 0; i < reps; ++i) XQ_TRY(comm_allreduce_on(d->comm, scratch, d->n_grads_td, d->stream));
+        XQ_HIP(hipEventRecord(e1, d->stream));
+        XQ_HIP(hipEventSynchronize(e1));
+        XQ_HIP(hipEventElapsedTime(&ms, e0, e1));
+    }
     // the ranks must agree (a rank that starts its select chain late while its neighbours start early only wastes what the rule
     // saves): the decision is taken on the MEAN over the ranks, in integer nanoseconds so that every rank computes the same number
     uint64_t ns = (uint64_t)((double)ms * 1e6 / reps + 0.5);

@@ -650,8 +650,7 @@ static int env_init(xq_env* e, int n_games, uint64_t seed, uint32_t first_game_i
     e->n = n_games;
     e->seed = seed;
     e->first_id = first_game_id;
-    if (hip_stream) e->stream = (hipStream_t)hip_stream;
-    else { XQ_HIP(hipStreamCreate(&e->stream)); e->own_stream = true; }
+    XQ_TRY(e->stream.open(hip_stream));
     const size_t n = (size_t)n_games;
     XQ_TRY(e->boards.alloc(n * kBoardWords));
     XQ_TRY(e->meta.alloc(n));
@@ -683,9 +682,7 @@ int xq_env_create(int n_games, uint64_t seed, uint32_t first_game_id, void* hip_
 
 int xq_env_destroy(xq_env* e) {
     if (!e) return XQ_OK;
-    hipStreamSynchronize(e->stream);
-    retire_stream(e->stream);        // synchronised above; unconditional: a caller-owned stream may be destroyed right after this call
-    if (e->own_stream) hipStreamDestroy(e->stream);
+    e->stream.close();
     delete e;
     return XQ_OK;
 }

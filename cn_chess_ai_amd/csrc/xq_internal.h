@@ -4,6 +4,8 @@
 #include "xq_common.h"
 
 #include <algorithm>
+#include <climits>
+#include <utility>
 #include <vector>
 
 namespace xq {
@@ -23,12 +25,91 @@ inline unsigned stream_event_flags() {
     return f;
 }
 
+// ---- the one owner of a HIP event, and of a handle's stream ------------------------------------------------------------------------
+// Event: one hipEvent_t, destroyed by the destructor — a handle's events go with `delete handle`, a scoped one with its scope.  create()
+// leaves an event that exists alone, which is the form the lazily created ones take (first use creates, later uses cost a test).  It
+// converts to hipEvent_t wherever the handle is read.
+struct Event {
+    hipEvent_t ev = nullptr;
+    Event() = default;
+    ~Event() { if (ev) (void)hipEventDestroy(ev); }
+    Event(Event&& o) noexcept : ev(o.ev) { o.ev = nullptr; }
+    Event& operator=(Event&& o) noexcept { std::swap(ev, o.ev); return *this; }
+    Event(const Event&) = delete;
+    Event& operator=(const Event&) = delete;
+    operator hipEvent_t() const { return ev; }
+    int create(unsigned flags) {       // stream_event_flags() for ordering events, hipEventDefault for the ones that time
+        if (!ev) XQ_HIP(hipEventCreateWithFlags(&ev, flags));
+        return XQ_OK;
+    }
+};
+
+void retire_stream(hipStream_t s);     // xq_order.hip: strikes s from every SharedResource (below)
+
+// Stream: the stream a handle runs on — its own, or one the caller lent (the void* hip_stream of every xq_*_create).  close() is the
+// one teardown: synchronise, strike the stream from every SharedResource (nothing queued on it is left to wait for, and the caller
+// may destroy a lent stream right after the handle), destroy it if it is the handle's own.  Closing twice, or closing a stream that
+// was never opened (a handle whose init failed early), does nothing.  What stays with the xq_*_destroy functions is the ORDER: a side
+// or collect stream before the main one, a stream lent to sub-handles after those sub-handles, every stream before `delete handle`
+// frees the buffers its work may touch.  The destructor closes too, as a backstop.
+struct Stream {
+    static constexpr int kNoPriority = INT_MIN;
+    hipStream_t s = nullptr;
+    bool owned = false;
+    Stream() = default;
+    ~Stream() { close(); }
+    Stream(const Stream&) = delete;
+    Stream& operator=(const Stream&) = delete;
+    operator hipStream_t() const { return s; }
+    int open(void* lent) {             // the caller's stream, or a new one when there is none
+        if (lent) { s = (hipStream_t)lent; return XQ_OK; }
+        XQ_HIP(hipStreamCreate(&s));
+        owned = true;
+        return XQ_OK;
+    }
+    int open_owned(unsigned flags, int priority = kNoPriority) {
+        if (priority == kNoPriority) XQ_HIP(hipStreamCreateWithFlags(&s, flags));
+        else XQ_HIP(hipStreamCreateWithPriority(&s, flags, priority));
+        owned = true;
+        return XQ_OK;
+    }
+    void close() {
+        if (!s) return;
+        (void)hipStreamSynchronize(s);
+        retire_stream(s);
+        if (owned) (void)hipStreamDestroy(s);
+        s = nullptr; owned = false;
+    }
+};
+
+// LazyMark: "everything `producer` has queued so far", for another stream to wait behind.  The record is made only when somebody is
+// about to wait (it costs the recording stream ~6 us, and streams run in order, so a record made later still lies behind the work it
+// stands for): touched() says the producer has queued work since the last record, wait() records if so and orders the consumer behind
+// the event.  record() is the eager form, for the one place whose consumers must not see anything queued later.
+struct LazyMark {
+    Event ev;
+    hipStream_t producer = nullptr;
+    bool stale = false;                // the producer has queued work since the last record
+    int open(hipStream_t producer_stream) { producer = producer_stream; return ev.create(stream_event_flags()); }
+    void touched() { stale = true; }
+    int record() {
+        XQ_HIP(hipEventRecord(ev, producer));
+        stale = false;
+        return XQ_OK;
+    }
+    int wait(hipStream_t consumer) {
+        if (stale) XQ_TRY(record());
+        XQ_HIP(hipStreamWaitEvent(consumer, ev, 0));
+        return XQ_OK;
+    }
+};
+
 // One device resource and the streams that touched it last.  read(s) orders s behind the last write; write(s) orders s behind the
 // last write and behind every read since.  The event is recorded LAZILY — on the producer's stream at the moment a consumer on another
 // stream shows up (streams run in order, so a record made later still lies behind the producer's work) — because a record costs the
-// recording stream ~6 us and most producers are never waited for.  Streams the library destroys are struck
-// from every resource first (retire_stream), and every xq_*_destroy strikes the handle's stream — its own or the caller's — after
-// synchronising it; a caller that destroys a lent stream while a handle still uses it gets its entries dropped at the next access
+// recording stream ~6 us and most producers are never waited for.  A stream that goes away is struck from every
+// resource first: Stream::close() (above) does it for every stream a handle holds — its own or the caller's — and xq_stream_destroy
+// for the caller's own; a caller that destroys a lent stream while a handle still uses it gets its entries dropped at the next access
 // (order_behind: a record on a dead stream fails, a dead stream has nothing left to wait for).
 struct SharedResource {
     unsigned cls;
@@ -36,7 +117,7 @@ struct SharedResource {
     hipStream_t writer = nullptr;
     hipStream_t readers[4] = {nullptr, nullptr, nullptr, nullptr};
     int n_readers = 0;
-    hipEvent_t ev = nullptr;
+    Event ev;                          // created by the first order_behind that has to wait
     explicit SharedResource(unsigned c);
     ~SharedResource();
     SharedResource(const SharedResource&) = delete;
@@ -47,7 +128,6 @@ struct SharedResource {
     void forget(hipStream_t s);        // s was synchronised and goes away (caller holds the registry's mutex: retire_stream, order_behind)
     void host_synchronised();          // the whole device was synchronised: nothing left to wait for
 };
-void retire_stream(hipStream_t s);     // after hipStreamSynchronize(s), before hipStreamDestroy(s)
 
 // ---- the one owner of device memory ----------------------------------------------------------------------------------------------
 // DevBuf<T>: n elements of T in device memory (PinnedBuf<T>: in pinned host memory), freed by the destructor — a handle's buffers go
@@ -130,8 +210,7 @@ struct xq_replay {
     uint32_t implicit_call = 0;
     int implicit_size = 0;
     int implicit_start = 0;           // windowed sample: slot = (start + philox % size) % capacity
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
+    xq::Stream stream;
     // Device data of the ring that other handles read or write, possibly on streams of their own — each a SharedResource (above):
     //   contents : boards / next_boards / action_to / reward / done   written by env steps (xq_env_selfplay_step) and push_host,
     //              read by TD steps (xq_dqn_td_grads_replay)
@@ -167,8 +246,7 @@ struct xq_env {
     int n = 0;
     uint64_t seed = 0;
     uint32_t first_id = 0;
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
+    xq::Stream stream;
     xq::DevBuf<uint32_t> boards;       // [n][12]
     xq::DevBuf<uint4> meta;            // [n] {moveCount|player<<16, red|black<<16, plies, episodes}
     xq::DevBuf<uint4> stats;           // [n] {red wins, black wins, captures, explored}
@@ -189,7 +267,7 @@ namespace xq {
 // HIP-event profiler: brackets individual launches on the handle's stream (bench.py roofline leg).  Disabled = free.
 struct Profiler {
     struct Cat { char name[48]; double flops = 0, bytes = 0; int launches = 0; int exact = 0; float ms = 0; };   // exact: launches timed by their own events
-    struct Rec { int cat; hipEvent_t a, b; bool attached; };   // attached: a / b are the start / stop events of the kernel's own launch
+    struct Rec { int cat; Event a, b; bool attached; };   // attached: a / b are the start / stop events of the kernel's own launch
     struct Span { char name[48]; float start_ms, end_ms; };      // relative to the first bracket of the batch (live timeline)
     std::vector<Span> spans;
     bool enabled = false;
@@ -214,16 +292,17 @@ struct Profiler {
     }
     std::vector<Cat> cats;
     std::vector<Rec> recs;
-    std::vector<hipEvent_t> pool;
+    std::vector<Event> pool;
     int cat_id(const char* name) {
         for (size_t i = 0; i < cats.size(); ++i) if (!strcmp(cats[i].name, name)) return (int)i;
         Cat c; memset(c.name, 0, sizeof c.name); strncpy(c.name, name, sizeof c.name - 1);
         cats.push_back(c);
         return (int)cats.size() - 1;
     }
-    hipEvent_t get_event() {
-        if (!pool.empty()) { hipEvent_t e = pool.back(); pool.pop_back(); return e; }
-        hipEvent_t e; (void)hipEventCreate(&e); return e;
+    int get_event(Event* e) {
+        if (pool.empty()) return e->create(hipEventDefault);
+        *e = std::move(pool.back()); pool.pop_back();
+        return XQ_OK;
     }
     // attach: the caller hands recs[h].a / .b to hipExtLaunchKernelGGL as the launch's start / stop events — the elapsed time is then the
     // kernel's own (what rocprofv3 reports), with no marker packets on the stream; otherwise the pair is recorded around the scope
@@ -238,9 +317,11 @@ struct Profiler {
             const int period = sample_period > 1 ? sample_period + o->period_add : 1;
             if (period > 1 && (o->phase++ % period) != 0) return -1;
         }
-        Rec r; r.cat = cat_id(name); r.a = get_event(); r.b = get_event(); r.attached = attach;
+        Rec r;
+        if (get_event(&r.a) != XQ_OK || get_event(&r.b) != XQ_OK) return -1;     // no events: this launch is not bracketed
+        r.cat = cat_id(name); r.attached = attach;
         if (!attach) (void)hipEventRecord(r.a, s);
-        recs.push_back(r);
+        recs.push_back(std::move(r));
         return (int)recs.size() - 1;
     }
     void end(int h, hipStream_t s, double flops, double bytes) {
@@ -263,11 +344,11 @@ struct Profiler {
                 spans.push_back(sp);
             }
         }
-        for (auto& r : recs) { pool.push_back(r.a); pool.push_back(r.b); }
+        for (auto& r : recs) { pool.push_back(std::move(r.a)); pool.push_back(std::move(r.b)); }
         recs.clear();
     }
     void reset() { collect(); cats.clear(); }
-    ~Profiler() { collect(); for (auto e : pool) (void)hipEventDestroy(e); }
+    ~Profiler() { collect(); }
 };
 struct ProfilerOff {                  // while one lives, the profiler brackets nothing
     Profiler& p; bool was;

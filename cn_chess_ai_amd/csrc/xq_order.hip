@@ -21,18 +21,15 @@ SharedResource::SharedResource(unsigned c) : cls(c) {
     registry().push_back(this);
 }
 SharedResource::~SharedResource() {
-    {
-        std::lock_guard<std::mutex> lock(registry_mutex());
-        auto& v = registry();
-        v.erase(std::remove(v.begin(), v.end(), this), v.end());
-    }
-    if (ev) (void)hipEventDestroy(ev);
+    std::lock_guard<std::mutex> lock(registry_mutex());
+    auto& v = registry();
+    v.erase(std::remove(v.begin(), v.end(), this), v.end());
 }
 
 // (callers hold registry_mutex())
 int SharedResource::order_behind(hipStream_t waiter, hipStream_t producer) {
     if (waiter == producer || !(order_mask() & cls)) return XQ_OK;
-    if (!ev) XQ_HIP(hipEventCreateWithFlags(&ev, stream_event_flags()));
+    XQ_TRY(ev.create(stream_event_flags()));
     // lazily: behind everything the producer's stream holds by now.  A record that fails means the producer's stream is gone (a caller
     // destroyed a stream it had lent to a handle without xq_stream_destroy / the handle's destroy, which strike it from here): a
     // destroyed stream has finished its work, so its entry is dropped and there is nothing left to wait for — the error is not kept.
@@ -123,11 +120,10 @@ extern "C" {
 
 int xq_stream_wait_stream(void* waiting_stream, void* producer_stream) {
     if (waiting_stream == producer_stream) return XQ_OK;
-    hipEvent_t ev = nullptr;
-    XQ_HIP(hipEventCreateWithFlags(&ev, stream_event_flags()));
+    Event ev;                                        // (destroyed on return: HIP releases it once the wait has passed)
+    XQ_TRY(ev.create(stream_event_flags()));
     hipError_t e = hipEventRecord(ev, (hipStream_t)producer_stream);
     if (e == hipSuccess) e = hipStreamWaitEvent((hipStream_t)waiting_stream, ev, 0);
-    (void)hipEventDestroy(ev);                       // released once the wait has passed
     if (e != hipSuccess) return fail(XQ_ERR_RUNTIME, "xq_stream_wait_stream: %s", hipGetErrorString(e));
     return XQ_OK;
 }
@@ -214,11 +210,11 @@ int xq_debug_set_stream_ordering(unsigned mask) {
 // the stream a handle runs on (its own when it was created with NULL): what a caller needs for xq_stream_wait_stream
 extern "C" int xq_env_stream(const xq_env* e, void** s) {
     if (!e || !s) return fail(XQ_ERR_INVALID_ARGUMENT, "null pointer");
-    *s = (void*)e->stream;
+    *s = (void*)(hipStream_t)e->stream;
     return XQ_OK;
 }
 extern "C" int xq_replay_stream(const xq_replay* r, void** s) {
     if (!r || !s) return fail(XQ_ERR_INVALID_ARGUMENT, "null pointer");
-    *s = (void*)r->stream;
+    *s = (void*)(hipStream_t)r->stream;
     return XQ_OK;
 }

@@ -274,8 +274,7 @@ int xq_replay_create(int capacity, uint64_t seed, void* hip_stream, xq_replay** 
 
 static int replay_init(xq_replay* r, int capacity, uint64_t seed, void* hip_stream) {
     r->seed = seed;
-    if (hip_stream) r->stream = (hipStream_t)hip_stream;
-    else { XQ_HIP(hipStreamCreate(&r->stream)); r->own_stream = true; }
+    XQ_TRY(r->stream.open(hip_stream));
     const size_t n = (size_t)capacity;
     r->dev.capacity = capacity;
     XQ_TRY(r->boards.alloc(n * kBoardWords));
@@ -295,9 +294,7 @@ static int replay_init(xq_replay* r, int capacity, uint64_t seed, void* hip_stre
 
 int xq_replay_destroy(xq_replay* r) {
     if (!r) return XQ_OK;
-    hipStreamSynchronize(r->stream);
-    retire_stream(r->stream);        // synchronised above; unconditional: a caller-owned stream may be destroyed right after this call
-    if (r->own_stream) hipStreamDestroy(r->stream);
+    r->stream.close();
     delete r;
     return XQ_OK;
 }

@@ -21,31 +21,27 @@
 
 struct xq_trainer {
     xq_trainer_config cfg;
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
+    xq::Stream stream;                      // lent to env, dqn and replay
     xq_env* env = nullptr;
     xq_dqn* dqn = nullptr;
     xq_replay* replay = nullptr;
     uint64_t env_steps = 0, updates = 0;
     uint32_t eps_u32 = 0;
     // overlap_collect
-    hipStream_t cstream = nullptr;          // collect stream
-    hipEvent_t ev_params = nullptr;         // main: parameters of the next iteration are final (after learn_apply)
-    hipEvent_t ev_collect = nullptr;        // cstream: the collects of this iteration are done
-    bool collect_event_stale = false;       // plies queued on cstream since ev_collect was last recorded (recorded when someone waits:
-                                            // a record per ply costs the collect stream ~6 us each, wait_collects())
+    xq::Stream cstream;                     // collect stream
+    // An event record costs the recording stream ~6 us (rocprofv3 trace), so the three marks below are recorded when somebody actually
+    // has to wait for them (xq::LazyMark): `collects` once per iteration instead of once per ply, `params` / `grads` only in the
+    // collect-first or mixed call orders, not on every iteration of the learn_grads -> collect loop
+    xq::LazyMark params;                    // main: parameters of the next iteration are final (after learn_apply)
+    xq::LazyMark collects;                  // cstream: the collects of this iteration are done
     int inflight = 0;                       // ring slots written by collects since the last learn_apply
     bool grads_queued = false;              // learn_grads already queued in this iteration: collect starts behind its big GEMM
     int prepaid_collects = 0;               // collects learn_grads had to run itself (empty ring), owed to the next collect() calls
     int excluded = 0;                       // ring slots the queued learn_grads left out of its minibatch (from write_pos - inflight)
-    hipEvent_t ev_grads = nullptr;          // main: the queued learn_grads has finished reading the ring
+    xq::LazyMark grads;                     // main: the queued learn_grads has finished reading the ring
     bool per_ready = false;                 // prioritized replay: the sum tree holds the ring as of the last learn_apply
-    // an event record costs the recording stream ~6 us (rocprofv3 trace): ev_params / ev_grads are only recorded when a collect
-    // actually has to wait for them (collect-first or mixed call orders), not on every iteration of the learn_grads -> collect loop
-    bool params_event_stale = true;         // ev_params has not been recorded since the last parameter update
-    bool grads_event_stale = true;          // ev_grads has not been recorded since the queued learn_grads
     bool early_collect = false;             // collects_per_update > 1: collects start behind the previous parameter update (see collect_impl)
-    uint64_t params_version = 0;            // dqn_params_version() when ev_params was last recorded: anything that rewrote parameters on the
+    uint64_t params_version = 0;            // dqn_params_version() when `params` was last recorded: anything that rewrote parameters on the
                                             // handle's stream since (set_params on a bf16 net, an apply_grads of the caller's own) lies
                                             // BEHIND that record, and the select chain must not start in front of it
     // versus training: the opponent (vs_on false = self-play), its picks / Q rows of the current phase, and the per-game outcome
@@ -55,7 +51,7 @@ struct xq_trainer {
     xq::DevBuf<int16_t> vs_pick;
     xq::DevBuf<float> vs_q;
     xq::DevBuf<uint4> vs_counts;
-    hipEvent_t vs_ev_env = nullptr, vs_ev_q = nullptr;
+    xq::Event vs_ev_env, vs_ev_q;
 };
 
 using namespace xq;
@@ -63,6 +59,13 @@ using namespace xq;
 extern "C" {
 
 static int trainer_init(xq_trainer* t, const xq_trainer_config* cfg, void* hip_stream);
+
+// records `params` here and now: the select chain may start behind this point as long as nothing rewrites parameters behind it
+static int record_params(xq_trainer* t) {
+    XQ_TRY(t->params.record());
+    t->params_version = dqn_params_version(t->dqn);
+    return XQ_OK;
+}
 
 int xq_trainer_create(const xq_trainer_config* cfg, void* hip_stream, xq_trainer** out) {
     if (!cfg || !out) return fail(XQ_ERR_INVALID_ARGUMENT, "xq_trainer_create: null pointer");
@@ -85,8 +88,7 @@ int xq_trainer_create(const xq_trainer_config* cfg, void* hip_stream, xq_trainer
 
 static int trainer_init(xq_trainer* t, const xq_trainer_config* cfg, void* hip_stream) {
     t->cfg = *cfg;
-    if (hip_stream) t->stream = (hipStream_t)hip_stream;
-    else { XQ_HIP(hipStreamCreate(&t->stream)); t->own_stream = true; }
+    XQ_TRY(t->stream.open(hip_stream));
     XQ_TRY(xq_env_create(cfg->n_games, cfg->seed, cfg->first_game_id, t->stream, &t->env));
     XQ_TRY(xq_dqn_create(cfg->layer_sizes, cfg->n_sizes, cfg->learning_rate, cfg->gamma, cfg->seed ^ 0x9E3779B97F4A7C15ull,
                          t->stream, &t->dqn));
@@ -108,13 +110,11 @@ static int trainer_init(xq_trainer* t, const xq_trainer_config* cfg, void* hip_s
         // 4 x 155 us alone, 375 + 314 us for the two that share the chip with the TD step) => most urgent: 1.096 -> 1.054 ms per step
         // (one ply per update with the select chain most urgent: no difference on the headline bench, -0.5 % on bench --config 5)
         const int prio = cfg->collects_per_update > 1 ? hi : lo;
-        XQ_HIP(hipStreamCreateWithPriority(&t->cstream, hipStreamNonBlocking, prio));
-        XQ_HIP(hipEventCreateWithFlags(&t->ev_params, stream_event_flags()));
-        XQ_HIP(hipEventCreateWithFlags(&t->ev_collect, stream_event_flags()));
-        XQ_HIP(hipEventCreateWithFlags(&t->ev_grads, stream_event_flags()));
-        XQ_HIP(hipEventRecord(t->ev_params, t->stream));      // orders the first collect after the handles' initialisation
-        t->params_event_stale = false;
-        t->params_version = dqn_params_version(t->dqn);
+        XQ_TRY(t->cstream.open_owned(hipStreamNonBlocking, prio));
+        XQ_TRY(t->params.open(t->stream));
+        XQ_TRY(t->collects.open(t->cstream));
+        XQ_TRY(t->grads.open(t->stream));
+        XQ_TRY(record_params(t));                             // orders the first collect after the handles' initialisation
         t->early_collect = cfg->collects_per_update > 1;
     }
     return XQ_OK;
@@ -122,19 +122,11 @@ static int trainer_init(xq_trainer* t, const xq_trainer_config* cfg, void* hip_s
 
 int xq_trainer_destroy(xq_trainer* t) {
     if (!t) return XQ_OK;
-    if (t->cstream) hipStreamSynchronize(t->cstream);
-    hipStreamSynchronize(t->stream);
-    if (t->cstream) { retire_stream(t->cstream); hipStreamDestroy(t->cstream); }
-    if (t->ev_params) hipEventDestroy(t->ev_params);
-    if (t->ev_collect) hipEventDestroy(t->ev_collect);
-    if (t->ev_grads) hipEventDestroy(t->ev_grads);
-    if (t->vs_ev_env) hipEventDestroy(t->vs_ev_env);
-    if (t->vs_ev_q) hipEventDestroy(t->vs_ev_q);
-    retire_stream(t->stream);        // synchronised above; unconditional: a caller-owned stream may be destroyed right after this call
-    xq_env_destroy(t->env);
+    t->cstream.close();              // the collects touch env, Q-net and ring
+    xq_env_destroy(t->env);          // (each synchronises the stream it was lent)
     xq_dqn_destroy(t->dqn);
     xq_replay_destroy(t->replay);
-    if (t->own_stream) hipStreamDestroy(t->stream);
+    t->stream.close();
     delete t;
     return XQ_OK;
 }
@@ -144,11 +136,7 @@ int xq_trainer_dqn(xq_trainer* t, xq_dqn** d) { if (!t || !d) return fail(XQ_ERR
 int xq_trainer_replay(xq_trainer* t, xq_replay** r) { if (!t || !r) return fail(XQ_ERR_INVALID_ARGUMENT, "null"); *r = t->replay; return XQ_OK; }
 
 // the handle's stream waits for every ply queued on the collect stream so far
-static int wait_collects(xq_trainer* t) {
-    if (t->collect_event_stale) { XQ_HIP(hipEventRecord(t->ev_collect, t->cstream)); t->collect_event_stale = false; }
-    XQ_HIP(hipStreamWaitEvent(t->stream, t->ev_collect, 0));
-    return XQ_OK;
-}
+static int wait_collects(xq_trainer* t) { return t->collects.wait(t->stream); }
 
 // The opponent's half-ply of a versus collect (phase 0: the pre-move, 2: the reply) on stream s: its picks, then the env launch
 static int versus_opponent(xq_trainer* t, int phase, hipStream_t s) {
@@ -184,7 +172,7 @@ static int collect_impl(xq_trainer* t) {
     hipStream_t on = nullptr;
     if (t->cstream) {
         on = t->cstream;
-        // has anything rewritten parameters on the handle's stream since ev_params was recorded?  (ORD_TRAINER_PARAMS off: the round-3
+        // has anything rewritten parameters on the handle's stream since `params` was recorded?  (ORD_TRAINER_PARAMS off: the round-3
         // behaviour, for the test that shows the check is needed)
         const bool params_moved = (order_mask() & ORD_TRAINER_PARAMS) && dqn_params_version(t->dqn) != t->params_version;
         if (t->grads_queued && !t->early_collect) {
@@ -195,22 +183,15 @@ static int collect_impl(xq_trainer* t) {
             // before) — it starts behind the previous parameter update, recorded there (learn_apply), and runs beside the whole TD step.
             // If parameters were rewritten behind that record, the event of the queued TD step (behind everything on the handle's
             // stream) takes its place.
-            if (t->inflight == 0 && !t->params_event_stale && !params_moved) XQ_HIP(hipStreamWaitEvent(on, t->ev_params, 0));
+            if (t->inflight == 0 && !t->params.stale && !params_moved) XQ_TRY(t->params.wait(on));
             else if (t->inflight == 0) XQ_HIP(hipStreamWaitEvent(on, dqn_qmax_event(t->dqn), 0));     // (no record yet: first iteration)
         } else if (t->inflight == 0) {
-            if (t->params_event_stale || params_moved) {
-                XQ_HIP(hipEventRecord(t->ev_params, t->stream));
-                t->params_event_stale = false;
-                t->params_version = dqn_params_version(t->dqn);
-            }
-            XQ_HIP(hipStreamWaitEvent(on, t->ev_params, 0));
+            if (t->params.stale || params_moved) XQ_TRY(record_params(t));
+            XQ_TRY(t->params.wait(on));
         }
         // more plies than the queued learn_grads excluded from its minibatch (caller mixed the orders): these slots may be
         // among the ones it samples, so they can only be overwritten once it has read them
-        if (t->grads_queued && t->inflight + t->env->n > t->excluded) {
-            if (t->grads_event_stale) { XQ_HIP(hipEventRecord(t->ev_grads, t->stream)); t->grads_event_stale = false; }
-            XQ_HIP(hipStreamWaitEvent(on, t->ev_grads, 0));
-        }
+        if (t->grads_queued && t->inflight + t->env->n > t->excluded) XQ_TRY(t->grads.wait(on));
     }
     hipStream_t s = on ? on : t->stream;
     if (t->cfg.replay_capacity == 0) {           // on-policy: the ring is exactly one batch, refilled every ply
@@ -234,7 +215,7 @@ static int collect_impl(xq_trainer* t) {
     t->env_steps += (uint64_t)t->env->n;
     if (on) {
         t->inflight += t->env->n;
-        t->collect_event_stale = true;
+        t->collects.touched();
     }
     return XQ_OK;
 }
@@ -279,8 +260,8 @@ int xq_trainer_set_opponent(xq_trainer* t, const xq_arena_player* opp) {
     XQ_TRY(t->vs_counts.reserve(n));                 // (first call only: the env's size is fixed)
     XQ_TRY(t->vs_pick.reserve(n));
     XQ_TRY(t->vs_q.reserve(n * 96));
-    if (!t->vs_ev_env) XQ_HIP(hipEventCreateWithFlags(&t->vs_ev_env, stream_event_flags()));
-    if (!t->vs_ev_q) XQ_HIP(hipEventCreateWithFlags(&t->vs_ev_q, stream_event_flags()));
+    XQ_TRY(t->vs_ev_env.create(stream_event_flags()));
+    XQ_TRY(t->vs_ev_q.create(stream_event_flags()));
     XQ_HIP(hipMemsetAsync(t->vs_counts, 0, n * sizeof(uint4), t->stream));
     XQ_HIP(hipStreamSynchronize(t->stream));
     t->vs = vs;
@@ -304,7 +285,7 @@ int xq_trainer_random_plies(xq_trainer* t, int n_plies) {
     if (!t || n_plies < 0) return fail(XQ_ERR_INVALID_ARGUMENT, "bad argument");
     if (t->inflight > 0 || t->grads_queued) return fail(XQ_ERR_RUNTIME, "xq_trainer_random_plies: call between iterations (after learn_apply)");
     for (int i = 0; i < n_plies; ++i) XQ_TRY(env_selfplay_launch(t->env, nullptr, 0, 0u, nullptr, nullptr, t->stream));
-    t->params_event_stale = true;                // the next collect (own stream) starts behind these plies
+    t->params.touched();                         // the next collect (own stream) starts behind these plies
     return XQ_OK;
 }
 
@@ -328,7 +309,7 @@ static int learn_grads_prioritized(xq_trainer* t) {
     }
     XQ_TRY(replay_per_sample(t->replay, t->cfg.minibatch, t->stream));
     XQ_TRY(xq_dqn_td_grads_replay(t->dqn, t->replay, t->cfg.minibatch, t->cfg.td_net, t->cfg.backprop_mode));
-    t->grads_event_stale = true;
+    t->grads.touched();
     t->grads_queued = true;
     return XQ_OK;
 }
@@ -368,7 +349,7 @@ int xq_trainer_learn_grads(xq_trainer* t) {
         XQ_TRY(replay_sample_implicit(t->replay, batch, start, count));     // no sampling kernel: the consumers recompute the slots
     }
     XQ_TRY(xq_dqn_td_grads_replay(t->dqn, t->replay, batch, t->cfg.td_net, t->cfg.backprop_mode));
-    t->grads_event_stale = true;
+    t->grads.touched();
     t->grads_queued = true;
     return XQ_OK;
 }
@@ -392,12 +373,8 @@ int xq_trainer_learn_apply(xq_trainer* t, int world_size) {
         XQ_TRY(replay_per_rebuild(t->replay, r->write_pos, full ? std::min(m, r->dev.capacity) : 0, t->stream));
         t->per_ready = true;
     }
-    t->params_event_stale = true;
-    if (t->cstream && t->early_collect) {       // the next iteration's collects start here, whatever the caller queues first
-        XQ_HIP(hipEventRecord(t->ev_params, t->stream));
-        t->params_event_stale = false;
-        t->params_version = dqn_params_version(t->dqn);
-    }
+    t->params.touched();
+    if (t->cstream && t->early_collect) XQ_TRY(record_params(t));    // the next iteration's collects start here, whatever the caller queues first
     t->inflight = 0;
     t->grads_queued = false;
     return XQ_OK;
