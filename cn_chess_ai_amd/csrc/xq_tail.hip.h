@@ -461,22 +461,79 @@ __device__ __forceinline__ float vadd(const float a, const float b) { return a +
 __device__ __forceinline__ float4 vadd(const float4 a, const float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
 __device__ __forceinline__ void vzero(float& a) { a = 0.f; }
 __device__ __forceinline__ void vzero(float4& a) { a = make_float4(0.f, 0.f, 0.f, 0.f); }
+// WHEN the terms are loaded is a separate matter from the order: a loop that loads four terms, waits and adds is a chain of n / 4 dependent
+// round trips (17 for the 64 row chunks of the hidden biases), and in a TD step the terms were written a moment ago by other XCDs, so
+// every trip goes out to the Infinity Cache.  OrderedSum therefore takes the terms — p[z * st], 0 <= z < n, n the same in every lane of a
+// wave — in batches of B (a multiple of 4): all B loads of a batch go out before the first wait, into a statically indexed register array,
+// then the terms are added in THE order.
+//   whole(): B live terms, straight-line code.
+//   part():  0 < n < B live terms: the loads past term n - 1 read that term again (never past the end) and only live terms are added, behind
+//            scalar branches.
+// Behind the loads stand a scheduling barrier and an empty asm that every loaded value passes through: without the asm the compiler sinks
+// each load into the branch that adds it, without the barrier it schedules the first adds (and their waits) between the loads — dependent
+// round trips again either way (profiles/NOTES.md, "Ordered sums: every load in flight").
+__device__ __forceinline__ void vpin(float& a) { asm volatile("" : "+v"(a)); }
+__device__ __forceinline__ void vpin(float4& a) { asm volatile("" : "+v"(a.x), "+v"(a.y), "+v"(a.z), "+v"(a.w)); }
+template <typename T>
+struct OrderedSum {
+    T s0, s1, s2, s3;
+    __device__ __forceinline__ OrderedSum() { vzero(s0); vzero(s1); vzero(s2); vzero(s3); }
+    template <int B>
+    __device__ __forceinline__ void whole(const T* __restrict__ p, const long long st) {
+        static_assert(B % 4 == 0, "whole groups of four");
+        T v[B];
+#pragma unroll
+        for (int u = 0; u < B; ++u) v[u] = p[u * st];
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int u = 0; u < B; ++u) vpin(v[u]);
+#pragma unroll
+        for (int u = 0; u < B; u += 4) { s0 = vadd(s0, v[u]); s1 = vadd(s1, v[u + 1]); s2 = vadd(s2, v[u + 2]); s3 = vadd(s3, v[u + 3]); }
+    }
+    template <int B>
+    __device__ __forceinline__ void part(const T* __restrict__ p, const long long st, const int n) {
+        static_assert(B % 4 == 0, "whole groups of four");
+        T v[B];
+#pragma unroll
+        for (int u = 0; u < B; ++u) v[u] = p[min(u, n - 1) * st];
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int u = 0; u < B; ++u) vpin(v[u]);
+#pragma unroll
+        for (int u = 0; u < B; u += 4) {
+            if (u + 3 < n) {
+                s0 = vadd(s0, v[u]); s1 = vadd(s1, v[u + 1]); s2 = vadd(s2, v[u + 2]); s3 = vadd(s3, v[u + 3]);
+            } else if (u < n) {                        // the leftover terms continue chain 0
+                s0 = vadd(s0, v[u]);
+                if (u + 1 < n) s0 = vadd(s0, v[u + 1]);
+                if (u + 2 < n) s0 = vadd(s0, v[u + 2]);
+            }
+        }
+    }
+    // any n: whole batches of B (a multiple of 4 terms each, so the next batch starts on chain 0 as the order asks), then the rest
+    template <int B>
+    __device__ __forceinline__ void run(const T* __restrict__ p, const long long st, int n) {
+        for (; n >= B; n -= B, p += B * st) whole<B>(p, st);
+        if (n > 0) part<B>(p, st, n);
+    }
+    __device__ __forceinline__ T total() const { return vadd(vadd(s0, s1), vadd(s2, s3)); }
+};
+// The slab counts of a TD step at the usual sizes (8, 16, 32) are one whole batch each; every other count goes in batches of 64 single
+// floats or 32 quads (64 quads would be 256 VGPRs): whatever the library produces (up to 64 slabs) is in flight at once, 33 .. 64 slabs
+// of quads in two batches.
 template <typename T>
 __device__ __forceinline__ T slab_sum(const T* __restrict__ s, int nslabs, long long st, long long i) {   // st, i in units of T
-    T s0, s1, s2, s3;
-    vzero(s0); vzero(s1); vzero(s2); vzero(s3);
-    int z = 0;
-    for (; z + 3 < nslabs; z += 4) {
-        s0 = vadd(s0, s[(long long)z * st + i]);
-        s1 = vadd(s1, s[(long long)(z + 1) * st + i]);
-        s2 = vadd(s2, s[(long long)(z + 2) * st + i]);
-        s3 = vadd(s3, s[(long long)(z + 3) * st + i]);
-    }
-    for (; z < nslabs; ++z) s0 = vadd(s0, s[(long long)z * st + i]);
-    return vadd(vadd(s0, s1), vadd(s2, s3));
+    constexpr int kBatch = sizeof(T) > sizeof(float) ? 32 : 64;
+    const T* p = s + i;
+    OrderedSum<T> o;
+    if (nslabs == 8) o.template whole<8>(p, st);
+    else if (nslabs == 16) o.template whole<16>(p, st);
+    else if (kBatch > 32 && nslabs == 32) o.template whole<32>(p, st);
+    else o.template run<kBatch>(p, st, nslabs);
+    return o.total();
 }
 // out[i] = sum_z slabs[z*stride + i], z ascending (deterministic)
-__global__ void reduce_slabs_kernel(const float* __restrict__ slabs, int nslabs, long long stride, long long len, float* __restrict__ out) {
+__global__ __launch_bounds__(256) void reduce_slabs_kernel(const float* __restrict__ slabs, int nslabs, long long stride, long long len, float* __restrict__ out) {
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < len; i += (long long)gridDim.x * blockDim.x)
         out[i] = slab_sum(slabs, nslabs, stride, i);
 }
@@ -576,17 +633,19 @@ __device__ __forceinline__ void segment_loop(const GridX x, const Step& S, float
     T* ms = reinterpret_cast<T*>(m_);
     T* vs = reinterpret_cast<T*>(v_);
     T* tg = reinterpret_cast<T*>(tg_);
+    const bool slabs = SLABS && nslabs > 0;
+    if (slabs && reduce_only) {                   // the parameter is not read
+        for (long long i = x.first; i < len; i += x.stride) d[i] = slab_sum(s, nslabs, st, i);
+        return;
+    }
     for (long long i = x.first; i < len; i += x.stride) {
-        T g;
-        if (SLABS && nslabs > 0) {
-            g = slab_sum(s, nslabs, st, i);
-            if (reduce_only) { d[i] = g; continue; }
-        } else g = s[i];
+        // the element's own loads first: in flight together with the slab loads, not one more round trip behind them
         const T w = d[i];
         T m, v, tv;
         if (Step::kState) { m = ms[i]; v = vs[i]; }
         else { vzero(m); vzero(v); }
-        if (SOFT) tv = tg[i];                     // with the other loads of the element, ahead of the step's arithmetic
+        if (SOFT) tv = tg[i];
+        const T g = slabs ? slab_sum(s, nslabs, st, i) : s[i];
         const T o = step_elems(S, w, g, m, v);
         if (Step::kState) { ms[i] = m; vs[i] = v; }
         d[i] = o;
@@ -629,8 +688,8 @@ struct SgdStep {
     float alpha;
     __device__ __forceinline__ float elem(const float w, const float g, float&, float&) const { return w - alpha * g; }
 };
-__global__ void sgd_segments_kernel(SegTable t, float alpha) { segment_walk<true>(XQ_GRID_X, t, SgdStep{alpha}); }
-__global__ void sgd_segments_soft_kernel(SegTable t, float alpha, SoftArgs Z) { segment_walk<true, true>(XQ_GRID_X, t, SgdStep{alpha}, nullptr, nullptr, &Z); }
+__global__ __launch_bounds__(256) void sgd_segments_kernel(SegTable t, float alpha) { segment_walk<true>(XQ_GRID_X, t, SgdStep{alpha}); }
+__global__ __launch_bounds__(256) void sgd_segments_soft_kernel(SegTable t, float alpha, SoftArgs Z) { segment_walk<true, true>(XQ_GRID_X, t, SgdStep{alpha}, nullptr, nullptr, &Z); }
 
 // Adam (torch.optim.Adam's formula, amsgrad off, no weight decay; DESIGN.md section 4 "Optimizer"):
 //   g' = gs g;  m = b1 m + (1 - b1) g';  v = b2 v + (1 - b2) g'^2;  p -= a m / (sqrt(v) rbc2 + eps)
@@ -658,8 +717,8 @@ struct AdamStep {
     AdamArgs A;
     __device__ __forceinline__ float elem(const float w, const float g, float& m, float& v) const { return adam_elem(A, w, g, m, v); }
 };
-__global__ void adam_segments_kernel(SegTable t, AdamArgs A) { segment_walk<true>(XQ_GRID_X, t, AdamStep{A}, A.m, A.v); }
-__global__ void adam_segments_soft_kernel(SegTable t, AdamArgs A, SoftArgs Z) { segment_walk<true, true>(XQ_GRID_X, t, AdamStep{A}, A.m, A.v, &Z); }
+__global__ __launch_bounds__(256) void adam_segments_kernel(SegTable t, AdamArgs A) { segment_walk<true>(XQ_GRID_X, t, AdamStep{A}, A.m, A.v); }
+__global__ __launch_bounds__(256) void adam_segments_soft_kernel(SegTable t, AdamArgs A, SoftArgs Z) { segment_walk<true, true>(XQ_GRID_X, t, AdamStep{A}, A.m, A.v, &Z); }
 
 // ---- gradient clipping by the global L2 norm (DESIGN.md section 4 "Gradient clipping") ---------------------------------------------
 //   S = sum_i (double)g_i^2;  norm = |grad_scale| sqrt(S);  c = (float)min(1, max_norm / (norm + 1e-6))
