@@ -6,6 +6,7 @@
 #include "xq_internal.h"
 
 #include <algorithm>
+#include <cfloat>
 
 namespace xq {
 
@@ -61,8 +62,8 @@ struct PerTree {
     long long off[8];
 };
 // levels 2.. in one block (they hold <= a few thousand nodes), then the snapshot of the running maximum priority, the number of eligible
-// slots (sum of per_level_kernel's per-wave counts) and — unless a prioritized draw is still waiting for its TD step, which reads the
-// slot — a clean batch-maximum slot for the next draw
+// slots (sum of per_level_kernel's per-wave counts; without them, a one-slot ring, whether leaf 0 is positive) and — unless a prioritized
+// draw is still waiting for its TD step, which reads the slot — a clean batch-maximum slot for the next draw
 __global__ __launch_bounds__(1024) void per_upper_kernel(PerTree T, unsigned* scalars, const unsigned* __restrict__ wave_counts, int n_counts,
                                                          int zero_wmax) {
     __shared__ unsigned csum[16];
@@ -75,7 +76,8 @@ __global__ __launch_bounds__(1024) void per_upper_kernel(PerTree T, unsigned* sc
     if (threadIdx.x == 0) {
         unsigned t = 0;
         for (int w = 0; w < (int)(blockDim.x >> 6); ++w) t += csum[w];
-        if (wave_counts) scalars[3] = t;
+        // (a ring of one slot has no level 1 and so no wave counts: its only leaf is the root)
+        scalars[3] = wave_counts ? t : (T.leaves[0] > 0.f ? 1u : 0u);
         if (zero_wmax) scalars[2] = 0u;
     }
     for (int lv = 2; lv < T.nlv; ++lv) {
@@ -129,7 +131,8 @@ __global__ __launch_bounds__(256) void per_sample_kernel(PerTree T, int batch, u
                 else u = __fsub_rn(u, c[q]);
             }
         }
-        if (pick < 0) { pick = last < 0 ? 0 : last; u = 0.f; }
+        // off the end through rounding: the mass lies at the top of this node's range, so at the top of every node below too
+        if (pick < 0) { pick = last < 0 ? 0 : last; u = FLT_MAX; }
         node = node * 32 + pick;
     }
     // an empty tree (every priority zero) cannot be sampled proportionally: slot 0, weight 1 (callers check the ring is not empty)
@@ -178,7 +181,7 @@ int replay_per_rebuild(xq_replay* r, int retire_start, int retire_count, hipStre
                            r->per.wave_counts, r->per.leaves);
         XQ_HIP(hipGetLastError());
     } else {
-        XQ_HIP(hipMemsetAsync(r->per.scalars + 3, 0, sizeof(unsigned), s));        // (a ring of <= 32 slots: counted by the sampler's callers)
+        // a ring of one slot: the snapshot is the root, and per_upper_kernel counts it as eligible when it is positive
         XQ_HIP(hipMemcpyAsync(r->per.leaves, r->dev.prio, 32 * sizeof(float), hipMemcpyDeviceToDevice, s));
     }
     hipLaunchKernelGGL(per_upper_kernel, dim3(1), dim3(1024), 0, s, T, r->per.scalars, n_counts ? r->per.wave_counts : nullptr, n_counts,

@@ -28,6 +28,7 @@
  */
 #include "xq_oracle.h"
 
+#include <float.h>
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
@@ -232,7 +233,8 @@ float xqo_per_total(const float* tree, int capacity) {
 
 /* descent for one mass u in [0, total): at every node walk the 32 children in index order; child c is taken when
  * u < v[c] (after subtracting the children before it); falling off the end through rounding takes the last child with
- * v > 0 and continues below it with u = 0.  Returns the leaf index. */
+ * v > 0 and stays at the top of the range below it (u = FLT_MAX: the last leaf with v > 0 under the node).  An empty tree
+ * gives leaf 0.  Returns the leaf index. */
 int xqo_per_descend(const float* tree, int capacity, float u) {
     int n[8], p[8];
     const int nlv = xqo_per_levels(capacity, n, p);
@@ -248,14 +250,15 @@ int xqo_per_descend(const float* tree, int capacity, float u) {
             if (u < v[c]) break;
             u -= v[c];
         }
-        if (c == 32) { c = last < 0 ? 0 : last; u = 0.f; }
+        if (c == 32) { c = last < 0 ? 0 : last; u = FLT_MAX; }
         node = node * 32 + c;
     }
     return node;
 }
 
 /* stratified minibatch: u_k = (k + r_k) * (total / B), r_k = (philox(k, 0, call, 2; seed).v[0] >> 8) * 2^-24;
- * slots[k] = leaf, w_raw[k] = (n_eligible * p_leaf / total)^-beta (fp32); returns max_k w_raw (the normaliser) */
+ * slots[k] = leaf, w_raw[k] = (n_eligible * p_leaf / total)^-beta (fp32), 1 where p_leaf = 0 (an empty tree); n_eligible = the
+ * number of leaves > 0, whatever the tree's shape (a one-slot tree included); returns max_k w_raw (the normaliser) */
 float xqo_per_sample(const float* tree, int capacity, int batch, uint64_t seed, uint32_t call, int n_eligible, float beta,
                      int32_t* slots, float* w_raw) {
     const float total = xqo_per_total(tree, capacity);
@@ -269,8 +272,8 @@ float xqo_per_sample(const float* tree, int capacity, int batch, uint64_t seed, 
         const float r = (float)(o[0] >> 8) * (1.0f / 16777216.0f);
         const float u = ((float)k + r) * seg;
         const int leaf = xqo_per_descend(tree, capacity, u);
-        const float prob = tree[leaf] / total;
-        const float wr = powf((float)n_eligible * prob, -beta);
+        const float prob = total > 0.f ? tree[leaf] / total : 0.f;      /* an empty tree: leaf 0 with weight 1 */
+        const float wr = prob > 0.f ? powf((float)n_eligible * prob, -beta) : 1.f;
         slots[k] = leaf;
         w_raw[k] = wr;
         if (wr > wmax) wmax = wr;
