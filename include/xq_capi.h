@@ -263,7 +263,10 @@ enum { XQ_BACKPROP_REFERENCE = 0,  /* bug-compatible hidden delta, dqn.cu:406-42
 enum { XQ_TD_ONLINE_NET = 0,       /* max Q(s') from the ONLINE net — what ChessAI::train does (chessai.cpp:126-127) */
        XQ_TD_TARGET_NET = 1,       /* max Q(s') from the target net — DQN::train (dqn.cpp:166-167) */
        XQ_TD_DOUBLE = 2 };         /* Double DQN (build-defined, BASELINE configs[4]): a* = argmax_k Q_online(s')[k] over all outputs
-                                    * (first maximum), y = r + gamma * Q_target(s')[a*] */
+                                    * (first maximum: from -inf at output 0 with a strict >, so of several equal maxima the lowest
+                                    * output wins, +0 and -0 are equal, +inf wins like any value, a NaN never wins — output 0
+                                    * included — and when nothing wins, all outputs NaN or -inf, a* = 0),
+                                    * y = r + gamma * Q_target(s')[a*] */
 enum { XQ_PRECISION_F32 = 0,       /* fp32 MFMA everywhere (the reference computes in fp64; north_star: fp32, Q within 1e-4) */
        XQ_PRECISION_BF16 = 1,      /* bf16 Q-net (build-defined, BASELINE configs[4]): forward passes on bf16 MFMA — weights and hidden
                                     * activations rounded to bf16 (RNE), fp32 accumulation, biases and outputs fp32; backward and SGD
@@ -559,7 +562,10 @@ int xq_allreduce_grads(xq_dqn* d, xq_comm* comm);
  *   opening  : the first opening_plies plies are uniform-random on the PAIR's Philox stream (ctr = {ply, 0, first_game_id + g mod
  *              n_pairs, 0}), so twins play the same opening with the seats swapped; then game g draws on its own id first_game_id + g;
  *   moves    : each player moves like xq_env_selfplay_step (epsilon-greedy over q[action.to] of the legal list, first maximum wins,
- *              same Philox draws) with an epsilon of its own; a NULL player always takes the uniform-random branch;
+ *              same Philox draws) with an epsilon of its own; a NULL player always takes the uniform-random branch.  First maximum,
+ *              for non-finite values too (dqn.cpp:39-51: maxQ = -inf, bestAction = validActions[0], strict >): of equal maxima the
+ *              first list entry wins, +0 equals -0, denormals compare by value, +inf wins like any value, a NaN never wins, and a
+ *              row whose candidates are all NaN or -inf plays validActions[0];
  *   end      : a game stops on the ply that ends it (a general captured, no legal action for the side to move, the 200-move cap,
  *              chessboard.cpp:286-309) and stays frozen — no reset, no replay write — with its record written on that ply.
  * A player handle is borrowed: the arena runs its forwards through xq_dqn_forward_boards_dev on the handle's stream (no kept

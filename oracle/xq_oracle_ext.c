@@ -128,8 +128,10 @@ int xqo_ext_td_accum(const int* L, int ns, const double* w, const double* b, con
         if (td_rule == 0 || td_rule == 2) xqo_ext_forward(L, ns, w, b, next_state, bf16, NULL, zn);
         if (td_rule == 1 || td_rule == 2) xqo_ext_forward(L, ns, wt, bt, next_state, bf16, NULL, zt);
         const double* sel = td_rule == 1 ? zt : zn;
+        /* first strict maximum from -inf at index 0 (dqn.cpp:40-51): a NaN never wins, output 0 included; nothing wins: 0 */
+        double best = -INFINITY;
         astar = 0;
-        for (int k = 1; k < NO; ++k) if (sel[k] > sel[astar]) astar = k;     /* first strict maximum (dqn.cpp:48) */
+        for (int k = 0; k < NO; ++k) if (sel[k] > best) { best = sel[k]; astar = k; }
         const double* val = td_rule == 0 ? zn : zt;
         y = reward + gamma * tanh(val[astar]);
     }

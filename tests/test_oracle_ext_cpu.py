@@ -36,6 +36,50 @@ def test_ext_oracle_reduces_to_the_reference_restatement(golden_dir):
     assert star == int(np.argmax(zo)) and abs(y - (R[0] + 0.99 * np.tanh(zt[star]))) < 1e-15
 
 
+def test_double_dqn_argmax_is_the_first_maximum_for_non_finite_outputs_too(golden_dir):
+    """a* of the Double-DQN step starts from -inf at output 0 with a strict > (tests/first_max.py): a NaN in output 0 never wins (a
+    loop that starts at `astar = 0` and tests `sel[k] > sel[astar]` keeps it), nor does one elsewhere; of two +inf the lower wins; equal
+    maxima give the lower output; all NaN gives 0.  The outputs are set through the online head's biases (z = bias + ...)."""
+    from first_max import first_max
+    trace = np.load(os.path.join(golden_dir, "ref_trace.npz"))
+    sizes = [1260, 16, 96]
+    S, A, R, D, S2 = transitions(trace, valid_indices(trace, 1, seed=3))
+    w, b = xo.init_weights(sizes, 5)
+    wt, bt = xo.init_weights(sizes, 6)
+    bt[16:] = np.linspace(-1.0, 1.0, 96)                     # the target value names a*
+    x, x2 = xo.state_repr(xo.board_from(S[0])), xo.state_repr(xo.board_from(S2[0]))
+    clean = xo.ext_forward(sizes, w, b, x2)[1]
+    top = int(np.argmax(clean))
+
+    def star(edit):
+        bb = b.copy()
+        edit(bb[16:])
+        gw, gb = np.zeros_like(w), np.zeros_like(b)
+        _, y, a = xo.ext_td_accum(sizes, w, bb, wt, bt, x, x2, 95, 0.0, 0, 0.99, 2, 1, False, 1.0, gw, gb)
+        z = xo.ext_forward(sizes, w, bb, x2)[1]
+        assert a == first_max(z)
+        zt = xo.ext_forward(sizes, wt, bt, x2)[1]
+        assert abs(y - 0.99 * np.tanh(zt[a])) < 1e-15
+        return a
+
+    def put(k, v):
+        def f(h):
+            h[k] = v
+        return f
+
+    assert top not in (0, 95) and star(lambda h: None) == top
+    assert star(put(0, np.nan)) == top                       # NaN at 0: the case the two implementations disagreed on
+    assert star(put(top, np.nan)) != top                     # NaN on the best output: the runner-up (star checks which)
+    assert star(lambda h: h.__setitem__(slice(None), np.nan)) == 0
+    assert star(lambda h: h.__setitem__(slice(None), -np.inf)) == 0
+    assert star(lambda h: h.__setitem__([7, 60], np.inf)) == 7
+
+    head = w[1260 * 16:].reshape(96, 16)                     # an exact tie: two output rows with the same weights and bias
+    head[41] = head[9]
+    assert star(lambda h: h.__setitem__([9, 41], 3.0)) == 9
+    assert star(lambda h: (h.__setitem__([9, 41], 3.0), h.__setitem__(0, np.nan))) == 9
+
+
 def test_bf16_rounding_is_round_to_nearest_even():
     f = xo.lib().xqo_bf16_round
     # 1 + 2^-8 is a tie between 1.0 and 1 + 2^-7: even mantissa (1.0) wins; 1 + 3*2^-8 ties to 1 + 2^-6 (even) not 1 + 2^-7
