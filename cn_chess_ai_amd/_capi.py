@@ -21,6 +21,7 @@ PRECISION_F32, PRECISION_BF16, PRECISION_BF16_FULL = 0, 1, 2
 QMAX_FULL, QMAX_SCREENED = 0, 1
 OPT_SGD, OPT_ADAM = 0, 1
 LOSS_SQUARED, LOSS_HUBER = 0, 1
+MAX_N_STEP = 8
 ORDER_RING_CONTENTS, ORDER_RING_PRIORITIES, ORDER_RING_DRAW, ORDER_TRAINER_PARAMS, ORDER_ALL = 1, 2, 4, 8, 15
 
 STATUS_NAMES = {1: "XQ_ERR_INVALID_ARGUMENT", 2: "XQ_ERR_RUNTIME", 3: "XQ_ERR_NO_DEVICE", 4: "XQ_ERR_IO",
@@ -141,6 +142,9 @@ PROTOTYPES = {
     "xq_replay_set_priorities": [_vp, _i, _i, _pf],
     "xq_replay_get_priorities": [_vp, _i, _i, _pf],
     "xq_replay_per_stats": [_vp, _pf, _pf, _pi],
+    "xq_replay_per_rebuild_hold": [_vp, _i, _i, _i, _i],
+    "xq_replay_set_n_step": [_vp, _i, _i],
+    "xq_replay_get_n_step": [_vp, _pi, _pi],
     "xq_dqn_create": [_pi, _i, _d, _d, _u64, _vp, _pvp],
     "xq_dqn_destroy": [_vp],
     "xq_dqn_set_precision": [_vp, _i],
@@ -171,6 +175,7 @@ PROTOTYPES = {
     "xq_dqn_td_update_host": [_vp, _i, _pu8, _pu8, _pi, _pf, _pu8, _i, _i, _d, _d, _pf, _pf],
     "xq_dqn_last_loss": [_vp, _pd],
     "xq_dqn_last_td_values": [_vp, _i, _pf, _pf],
+    "xq_dqn_last_n_step": [_vp, _i, _pf, _pu8, _pi, _pi, _pi, _pi],
     "xq_dqn_kernel_stats": [_vp, _i, C.POINTER(KernelStat), _i, _pi],
     "xq_dqn_set_fused_apply": [_vp, _i],
     "xq_dqn_set_optimizer": [_vp, _i, _d, _d, _d],
@@ -207,6 +212,7 @@ PROTOTYPES = {
     "xq_trainer_random_plies": [_vp, _i],
     "xq_trainer_set_td_net": [_vp, _i],
     "xq_trainer_set_target_tau": [_vp, _d],
+    "xq_trainer_set_n_step": [_vp, _i],
     "xq_trainer_set_opponent": [_vp, C.POINTER(ArenaPlayer)],
     "xq_trainer_versus_results": [_vp, _pu64],
     "xq_trainer_collect": [_vp],
@@ -236,7 +242,10 @@ LAZY_GRAD_CLIP = frozenset(("xq_dqn_set_grad_clip", "xq_dqn_get_grad_clip", "xq_
 LAZY_TARGET_TAU = frozenset(("xq_dqn_set_target_tau", "xq_dqn_get_target_tau", "xq_dqn_soft_update_target", "xq_trainer_set_target_tau"))
 # ... and the TD loss's
 LAZY_TD_LOSS = frozenset(("xq_dqn_set_td_loss", "xq_dqn_get_td_loss", "xq_dqn_td_error_stats"))
-_LAZY_ALL = LAZY | LAZY_GRAD_CLIP | LAZY_TARGET_TAU | LAZY_TD_LOSS
+# ... and those of the n-step returns
+LAZY_N_STEP = frozenset(("xq_replay_set_n_step", "xq_replay_get_n_step", "xq_replay_per_rebuild_hold", "xq_dqn_last_n_step",
+                         "xq_trainer_set_n_step"))
+_LAZY_ALL = LAZY | LAZY_GRAD_CLIP | LAZY_TARGET_TAU | LAZY_TD_LOSS | LAZY_N_STEP
 _RESTYPES = {"xq_last_error": C.c_char_p, "xq_env_boards_dev": C.c_void_p, "xq_env_meta_dev": C.c_void_p}
 
 _lib = None

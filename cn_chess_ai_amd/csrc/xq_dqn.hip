@@ -188,6 +188,14 @@ struct xq_dqn {
     xq::DevBuf<float> xdense, qfull, tfull;
     xq::DevBuf<uint32_t> hb;                    // host-batch staging: boards, next boards
     xq::DevBuf<int32_t> ha;  xq::DevBuf<float> hr;  xq::DevBuf<uint8_t> hd;
+    // n-step returns (xq_replay_set_n_step): the staging batch nstep_assemble_kernel fills and the TD step then reads with the identity
+    // slot source — boards, next boards, action, n-step reward, done — and per row the chain elements used, the sampled slot and the slot
+    // whose next board was staged.  nstep_rows: rows of the last TD step if it was an n-step one, else 0 (xq_dqn_last_n_step)
+    xq::DevBuf<uint32_t> ns_boards, ns_next;
+    xq::DevBuf<int32_t> ns_action, ns_m, ns_first, ns_last;
+    xq::DevBuf<float> ns_reward;
+    xq::DevBuf<uint8_t> ns_done;
+    int nstep_rows = 0;
     xq::Profiler prof;
     // fused launches of the TD step's tail (td_tail_kernel): while `tail_open`, the launch helpers of the small fp32 GEMMs, the
     // output-layer / layer-0 segmented sums and the bias column sums append their blocks to `tail` instead of launching.  Written by
@@ -273,6 +281,7 @@ struct SmallTiles {
 #include "xq_l0.hip.h"
 #include "xq_tail.hip.h"
 #include "xq_refine.hip.h"
+#include "xq_nstep.hip.h"
 
 namespace xq {
 
@@ -1531,7 +1540,8 @@ struct PerOpts {
     float eps, alpha;
 };
 static int td_grads_impl(xq_dqn* d, const uint32_t* boards, const uint32_t* next_boards, const int32_t* action_to,
-                         const float* reward, const uint8_t* done, SlotSrc slots, int n, int td_net, int mode, const PerOpts* per);
+                         const float* reward, const uint8_t* done, SlotSrc slots, int n, int td_net, int mode, const PerOpts* per,
+                         const float* discount = nullptr);
 
 int xq_dqn_td_grads(xq_dqn* d, const uint32_t* boards, const uint32_t* next_boards, const int32_t* action_to,
                     const float* reward, const uint8_t* done, const int32_t* slots, int n, int td_net, int mode) {
@@ -1744,6 +1754,7 @@ struct ScreenPlan { bool screened, top2; int parity; ShadowJob shadow; };
 // What the stages of one step share: its inputs, and the shapes and views decided once at its top.
 struct TdStep {
     const int32_t* action_to; const float* reward; const uint8_t* done; SlotSrc slots; const PerOpts* per;
+    float gamma;                 // the discount of this step's target: (float)d->gamma, or gamma^n of an n-step batch
     int n, mode, sel_net, nl, Hl, NO; bool dbl, bf;
     bool big_tiles;              // the max pass's product on 128-row tiles
     int n_partial;               // partial maxima per sample of the max pass's tile kernels
@@ -1905,7 +1916,7 @@ static int qmax_screened(xq_dqn* d, const TdStep& s, bool* td_fused) {
                 const int lt = nl - 2;
                 T.src = s.slots; T.action_to = s.action_to; T.reward = s.reward; T.done = s.done;
                 T.a_s = s.outs[lt]; T.w_out = d->wl(XQ_NET_ONLINE, nl - 1); T.b_out = d->bl(XQ_NET_ONLINE, nl - 1);
-                T.view = s.view; T.view_ld = s.view_ld; T.view_kmax = s.view_kmax; T.gamma = (float)d->gamma;
+                T.view = s.view; T.view_ld = s.view_ld; T.view_kmax = s.view_kmax; T.gamma = s.gamma;
                 T.dtop = d->deltas[lt]; T.dsc = d->dsc; T.act = d->act_mb; T.qsa = d->qsa; T.yv = d->yv; T.lossv = d->lossv;
             }
             // whole groups: 2 = the popular ones through LDS when the launch has room for it, 1 = all of them four per round trip
@@ -2007,12 +2018,12 @@ static int td_delta(xq_dqn* d, const TdStep& s, int zparts) {
     if (d->loss_kind == XQ_LOSS_HUBER)
         hipLaunchKernelGGL(td_delta_huber_kernel, dim3((n + 3) / 4), dim3(256), 0, d->cur, n, s.slots, s.action_to, s.reward, s.done,
                            s.outs[lt], Hl, d->wl(XQ_NET_ONLINE, nl - 1), d->bl(XQ_NET_ONLINE, nl - 1), d->zmax, zparts,
-                           (float)d->gamma, s.view, s.view_ld, s.view_kmax, d->deltas[lt], d->dsc, d->act_mb, d->qsa, d->yv, d->lossv, X,
+                           s.gamma, s.view, s.view_ld, s.view_kmax, d->deltas[lt], d->dsc, d->act_mb, d->qsa, d->yv, d->lossv, X,
                            d->loss_kappa32);
     else
         hipLaunchKernelGGL(td_delta_kernel, dim3((n + 3) / 4), dim3(256), 0, d->cur, n, s.slots, s.action_to, s.reward, s.done,
                            s.outs[lt], Hl, d->wl(XQ_NET_ONLINE, nl - 1), d->bl(XQ_NET_ONLINE, nl - 1), d->zmax, zparts,
-                           (float)d->gamma, s.view, s.view_ld, s.view_kmax, d->deltas[lt], d->dsc, d->act_mb, d->qsa, d->yv, d->lossv, X);
+                           s.gamma, s.view, s.view_ld, s.view_kmax, d->deltas[lt], d->dsc, d->act_mb, d->qsa, d->yv, d->lossv, X);
     XQ_HIP(hipGetLastError());
     return XQ_OK;
 }
@@ -2050,7 +2061,8 @@ static int td_gradients_fork(xq_dqn* d, const TdStep& s) {
 }
 
 static int td_grads_impl(xq_dqn* d, const uint32_t* boards, const uint32_t* next_boards, const int32_t* action_to,
-                         const float* reward, const uint8_t* done, SlotSrc slots, int n, int td_net, int mode, const PerOpts* per) {
+                         const float* reward, const uint8_t* done, SlotSrc slots, int n, int td_net, int mode, const PerOpts* per,
+                         const float* discount) {
     if (!d || !boards || !next_boards || !action_to || !reward || !done || n <= 0)
         return fail(XQ_ERR_INVALID_ARGUMENT, "xq_dqn_td_grads: bad argument");
     if (td_net != XQ_TD_ONLINE_NET && td_net != XQ_TD_TARGET_NET && td_net != XQ_TD_DOUBLE) return fail(XQ_ERR_INVALID_ARGUMENT, "bad td_net");
@@ -2072,6 +2084,8 @@ static int td_grads_impl(xq_dqn* d, const uint32_t* boards, const uint32_t* next
     if (bf && (Hl & 1)) return fail(XQ_ERR_INVALID_ARGUMENT, "bf16 Q-net needs even layer widths");
     TdStep s;
     s.action_to = action_to; s.reward = reward; s.done = done; s.slots = slots; s.per = per;
+    s.gamma = discount ? *discount : (float)d->gamma;
+    d->nstep_rows = 0;                               // (xq_dqn_td_grads_replay sets it behind an n-step batch)
     s.n = n; s.mode = mode; s.nl = nl; s.Hl = Hl; s.NO = NO; s.dbl = dbl; s.bf = bf; s.sel_net = td_net == XQ_TD_TARGET_NET ? XQ_NET_TARGET : XQ_NET_ONLINE;
     chain_views(d, d->acts, d->acts_bf, XQ_MAX_LAYERS, true, s.outs, s.outs_bf);
     chain_views(d, d->tacts, d->tacts_bf, 2, !bf, s.touts, s.touts_bf);
@@ -2395,6 +2409,67 @@ int xq_dqn_grad_buffer(xq_dqn* d, float** grads_dev, size_t* n_floats) {
     return XQ_OK;
 }
 
+// A TD step on n-step transitions (xq_replay_set_n_step): one gather assembles them into the handle's staging batch, the step then runs
+// on that batch with the identity slot source and the discount gamma^n; a prioritized draw's priorities go back behind the step
+static int td_grads_nstep(xq_dqn* d, xq_replay* r, SlotSrc src, int batch, int td_net, int mode, const PerOpts* per) {
+    const int cap = r->dev.capacity, n = r->n_step;
+    NStepArgs A; memset(&A, 0, sizeof A);
+    A.boards = r->dev.boards; A.next_boards = r->dev.next_boards; A.action_to = r->dev.action_to; A.reward = r->dev.reward; A.done = r->dev.done;
+    A.cap = cap; A.stride = r->n_stride; A.n = n;
+    if (r->read_count >= 0) { A.first = r->read_first; A.count = r->read_count; }
+    else { A.first = r->size < cap ? 0 : r->write_pos; A.count = r->size; }
+    r->read_count = -1;                              // a narrowed range holds for one step
+    if (A.first < 0 || A.first >= cap || A.count > cap) return fail(XQ_ERR_INVALID_ARGUMENT, "n-step readable range (%d, %d) outside the ring", A.first, A.count);
+    const float gf = (float)d->gamma;
+    float dk[kNStepMax + 1];                         // disc_k: float times float, one fp32 rounding per factor
+    dk[0] = 1.f;
+    for (int k = 1; k <= kNStepMax; ++k) dk[k] = dk[k - 1] * gf;
+    for (int k = 0; k < kNStepMax; ++k) A.disc[k] = dk[k];
+    const float disc_n = dk[n];
+    const size_t rows = (size_t)batch;
+    XQ_TRY(d->ns_boards.reserve(rows * kBoardWords));
+    XQ_TRY(d->ns_next.reserve(rows * kBoardWords));
+    for (DevBuf<int32_t>* b : {&d->ns_action, &d->ns_m, &d->ns_first, &d->ns_last}) XQ_TRY(b->reserve(rows));
+    XQ_TRY(d->ns_reward.reserve(rows));
+    XQ_TRY(d->ns_done.reserve(rows));
+    A.s_boards = d->ns_boards; A.s_next = d->ns_next; A.s_action = d->ns_action; A.s_reward = d->ns_reward; A.s_done = d->ns_done;
+    A.s_m = d->ns_m; A.s_first = d->ns_first; A.s_last = d->ns_last;
+    {
+        // per row: n x 9 B of chain fields and two boards in, two boards and 21 B out
+        ProfScope ps(d, "nstep_assemble", 0.0, (double)batch * (9.0 * n + 4.0 * 48 + 21), true);
+        hipExtLaunchKernelGGL(nstep_assemble_kernel, dim3((batch + 63) / 64), dim3(64), 0, d->cur, ps.start(), ps.stop(), 0, A, src, batch);
+        XQ_HIP(hipGetLastError());
+    }
+    PerOpts step_per;
+    if (per) { step_per = *per; step_per.prio = nullptr; step_per.pmax_live = nullptr; }
+    XQ_TRY(td_grads_impl(d, d->ns_boards, d->ns_next, d->ns_action, d->ns_reward, d->ns_done, explicit_slots(nullptr), batch, td_net, mode,
+                         per ? &step_per : nullptr, &disc_n));
+    d->nstep_rows = batch;
+    if (per) {
+        ProfScope ps(d, "per_writeback", 0.0, (double)batch * 20.0, true);
+        hipExtLaunchKernelGGL(per_writeback_kernel, dim3((batch + 255) / 256), dim3(256), 0, d->cur, ps.start(), ps.stop(), 0, batch,
+                              d->qsa.p, d->yv.p, d->act_mb.p, d->ns_first.p, per->prio, per->pmax_live, per->eps, per->alpha);
+        XQ_HIP(hipGetLastError());
+    }
+    return XQ_OK;
+}
+
+int xq_dqn_last_n_step(xq_dqn* d, int n, float* reward, uint8_t* done, int32_t* steps, int32_t* first_slot, int32_t* last_slot,
+                       int32_t* action) {
+    if (!d) return fail(XQ_ERR_INVALID_ARGUMENT, "null dqn");
+    if (d->nstep_rows <= 0) return fail(XQ_ERR_RUNTIME, "xq_dqn_last_n_step: the last TD step was not an n-step one");
+    if (n < 0 || n > d->nstep_rows) return fail(XQ_ERR_INVALID_ARGUMENT, "xq_dqn_last_n_step: n exceeds the last TD step's %d rows", d->nstep_rows);
+    XQ_HIP(hipStreamSynchronize(d->stream));
+    if (!n) return XQ_OK;
+    if (reward) XQ_HIP(hipMemcpy(reward, d->ns_reward, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
+    if (done) XQ_HIP(hipMemcpy(done, d->ns_done, (size_t)n, hipMemcpyDeviceToHost));
+    if (steps) XQ_HIP(hipMemcpy(steps, d->ns_m, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (first_slot) XQ_HIP(hipMemcpy(first_slot, d->ns_first, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (last_slot) XQ_HIP(hipMemcpy(last_slot, d->ns_last, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (action) XQ_HIP(hipMemcpy(action, d->ns_action, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return XQ_OK;
+}
+
 int xq_dqn_td_grads_replay(xq_dqn* d, xq_replay* r, int batch, int td_net, int mode) {
     if (!d || !r) return fail(XQ_ERR_INVALID_ARGUMENT, "null handle");
     SlotSrc src = explicit_slots(nullptr);
@@ -2422,6 +2497,7 @@ int xq_dqn_td_grads_replay(xq_dqn* d, xq_replay* r, int batch, int td_net, int m
     // ring, slot list and priorities may have been written on other streams (env steps, the draw, a rebuild): this step starts behind
     // them, and whatever touches them next — the next draw overwrites the list, the next env step the slots — behind this step
     XQ_TRY(replay_consumer_begin(r, d->stream, src.slots != nullptr, prioritized));
+    if (r->n_step > 1) return td_grads_nstep(d, r, src, batch, td_net, mode, prioritized ? &per : nullptr);
     return td_grads_impl(d, r->dev.boards, r->dev.next_boards, r->dev.action_to, r->dev.reward, r->dev.done, src, batch, td_net,
                          mode, prioritized ? &per : nullptr);
 }

@@ -210,6 +210,11 @@ struct xq_replay {
     uint32_t implicit_call = 0;
     int implicit_size = 0;
     int implicit_start = 0;           // windowed sample: slot = (start + philox % size) % capacity
+    // n-step returns (xq_replay_set_n_step, DESIGN.md §4 "n-step returns"): chain length (1 = off) and the distance in age order between
+    // successive transitions of one trajectory; read_first / read_count: the readable range of the NEXT xq_dqn_td_grads_replay when its
+    // owner narrowed it (replay_set_readable; read_count < 0: the default — the filled ring in age order), consumed by that step
+    int n_step = 1, n_stride = 1;
+    int read_first = 0, read_count = -1;
     xq::Stream stream;
     // Device data of the ring that other handles read or write, possibly on streams of their own — each a SharedResource (above):
     //   contents : boards / next_boards / action_to / reward / done   written by env steps (xq_env_selfplay_step) and push_host,
@@ -384,7 +389,11 @@ int replay_consumer_begin(xq_replay* r, hipStream_t consumer, bool listed, bool 
 int replay_writer_begin(xq_replay* r, hipStream_t writer);                                      // an env step that writes it
 void replay_advance(xq_replay* r, int n);   // n transitions were written (or queued) from write_pos on: moves write_pos, size and total
 // prioritized replay internals used by the trainer (xq_replay.hip)
-int replay_per_rebuild(xq_replay* r, int retire_start, int retire_count, hipStream_t on);
+// hold: `hold_count` slots from `hold_start` (wrapping) count as priority 0 in the snapshot and the sums only (n-step returns: slots whose
+// chains are not complete yet); the live table keeps their values
+int replay_per_rebuild(xq_replay* r, int retire_start, int retire_count, hipStream_t on, int hold_start = 0, int hold_count = 0);
+// the readable range of the next n-step TD step from this ring: `count` slots in age order from slot `first` (count < 0: the default)
+void replay_set_readable(xq_replay* r, int first, int count);
 int replay_per_sample(xq_replay* r, int batch, hipStream_t on);
 
 // env-side launchers used by the trainer

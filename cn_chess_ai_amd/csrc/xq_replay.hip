@@ -27,8 +27,11 @@ __global__ void replay_sample_kernel(int32_t* slots, int batch, uint32_t start, 
 // parent[i] = ((c[32i] + c[32i+1]) + ...) + c[32i+31]; also counts the non-zero children (eligible slots, level 1 only)
 // `snapshot` (level 1 only): the children are also copied there — the sampler descends through this copy of the priority table,
 // so collects and TD steps may rewrite the live table while a minibatch is being drawn
+// hold (level 1 only, n-step returns): the `hold_count` children from `hold_start` (wrapping at `cap`) enter the snapshot and the sums
+// as 0 — the table they are read from keeps their values; hold_count == 0 changes no value
 __global__ __launch_bounds__(256) void per_level_kernel(const float* __restrict__ child, float* __restrict__ parent, int n_parent,
-                                                        unsigned* __restrict__ count_nonzero, float* __restrict__ snapshot) {
+                                                        unsigned* __restrict__ count_nonzero, float* __restrict__ snapshot,
+                                                        int hold_start, int hold_count, int cap) {
     const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
     int nz = 0;
     if (i < n_parent) {
@@ -36,6 +39,21 @@ __global__ __launch_bounds__(256) void per_level_kernel(const float* __restrict_
         float4 v[8];
 #pragma unroll
         for (int k = 0; k < 8; ++k) v[k] = c[k];
+        if (hold_count > 0) {
+            auto held = [&](int j) {         // (j < 2 cap, hold_start < cap: one conditional add is the whole modulus)
+                int o = j - hold_start;
+                if (o < 0) o += cap;
+                return j < cap && o < hold_count;
+            };
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                const int j = i * 32 + 4 * k;
+                if (held(j)) v[k].x = 0.f;
+                if (held(j + 1)) v[k].y = 0.f;
+                if (held(j + 2)) v[k].z = 0.f;
+                if (held(j + 3)) v[k].w = 0.f;
+            }
+        }
         if (snapshot) {
 #pragma unroll
             for (int k = 0; k < 8; ++k) reinterpret_cast<float4*>(snapshot + (size_t)i * 32)[k] = v[k];
@@ -154,7 +172,7 @@ static PerTree per_tree(const xq_replay* r) {
     return T;
 }
 
-int replay_per_rebuild(xq_replay* r, int retire_start, int retire_count, hipStream_t on) {
+int replay_per_rebuild(xq_replay* r, int retire_start, int retire_count, hipStream_t on, int hold_start, int hold_count) {
     if (!r || !r->per.enabled) return fail(XQ_ERR_INVALID_ARGUMENT, "prioritized replay is not enabled on this ring");
     hipStream_t s = on ? on : r->stream;
     // the batch-maximum slot belongs to the last draw until its TD step has been queued (sample -> rebuild -> td_grads must
@@ -178,11 +196,12 @@ int replay_per_rebuild(xq_replay* r, int retire_start, int retire_count, hipStre
         const int blocks = (T.n[1] + 255) / 256;
         n_counts = blocks * 4;                                       // one count per wave of the level-1 grid
         hipLaunchKernelGGL(per_level_kernel, dim3(blocks), dim3(256), 0, s, r->dev.prio, T.upper + T.off[1], T.n[1],
-                           r->per.wave_counts, r->per.leaves);
+                           r->per.wave_counts, r->per.leaves, hold_start, hold_count, r->dev.capacity);
         XQ_HIP(hipGetLastError());
     } else {
         // a ring of one slot: the snapshot is the root, and per_upper_kernel counts it as eligible when it is positive
         XQ_HIP(hipMemcpyAsync(r->per.leaves, r->dev.prio, 32 * sizeof(float), hipMemcpyDeviceToDevice, s));
+        if (hold_count > 0) XQ_HIP(hipMemsetAsync(r->per.leaves, 0, sizeof(float), s));      // (its one slot is held)
     }
     hipLaunchKernelGGL(per_upper_kernel, dim3(1), dim3(1024), 0, s, T, r->per.scalars, n_counts ? r->per.wave_counts : nullptr, n_counts,
                        zero_wmax ? 1 : 0);
@@ -232,6 +251,8 @@ int replay_writer_begin(xq_replay* r, hipStream_t writer) {
     }
     return XQ_OK;
 }
+
+void replay_set_readable(xq_replay* r, int first, int count) { r->read_first = first; r->read_count = count; }
 
 void replay_advance(xq_replay* r, int n) {
     r->write_pos = (r->write_pos + n) % r->dev.capacity;
@@ -404,10 +425,35 @@ int xq_replay_get_priorities(xq_replay* r, int first, int n, float* prio_host) {
 }
 
 int xq_replay_per_rebuild(xq_replay* r, int retire_start, int retire_count) {
+    return xq_replay_per_rebuild_hold(r, retire_start, retire_count, 0, 0);
+}
+
+int xq_replay_per_rebuild_hold(xq_replay* r, int retire_start, int retire_count, int hold_start, int hold_count) {
     if (!r) return fail(XQ_ERR_INVALID_ARGUMENT, "null replay");
     if (retire_count < 0 || retire_count > r->dev.capacity || retire_start < 0 || retire_start >= r->dev.capacity)
         return fail(XQ_ERR_INVALID_ARGUMENT, "bad retire window");
-    return replay_per_rebuild(r, retire_start, retire_count, nullptr);
+    if (hold_count < 0 || hold_count > r->dev.capacity || hold_start < 0 || hold_start >= r->dev.capacity)
+        return fail(XQ_ERR_INVALID_ARGUMENT, "bad hold window");
+    return replay_per_rebuild(r, retire_start, retire_count, nullptr, hold_start, hold_count);
+}
+
+// ---- n-step returns: C ABI (the kernels are the TD step's: xq_nstep.hip.h) ---------------------------------------------------------
+int xq_replay_set_n_step(xq_replay* r, int n_step, int stride) {
+    if (!r) return fail(XQ_ERR_INVALID_ARGUMENT, "null replay");
+    if (n_step < 1 || n_step > XQ_MAX_N_STEP) return fail(XQ_ERR_INVALID_ARGUMENT, "xq_replay_set_n_step: n_step must be 1..%d", (int)XQ_MAX_N_STEP);
+    if (stride < 1 || stride > r->dev.capacity) return fail(XQ_ERR_INVALID_ARGUMENT, "xq_replay_set_n_step: stride must be 1..capacity (%d)", r->dev.capacity);
+    if ((long long)(n_step - 1) * stride >= (long long)r->dev.capacity)
+        return fail(XQ_ERR_INVALID_ARGUMENT, "xq_replay_set_n_step: a chain of %d steps %d slots apart does not fit a ring of %d", n_step, stride, r->dev.capacity);
+    r->n_step = n_step; r->n_stride = stride;
+    r->read_count = -1;
+    return XQ_OK;
+}
+
+int xq_replay_get_n_step(const xq_replay* r, int* n_step, int* stride) {
+    if (!r) return fail(XQ_ERR_INVALID_ARGUMENT, "null replay");
+    if (n_step) *n_step = r->n_step;
+    if (stride) *stride = r->n_stride;
+    return XQ_OK;
 }
 
 int xq_replay_per_stats(xq_replay* r, float* total, float* max_priority, int* n_eligible) {

@@ -40,6 +40,10 @@ struct xq_trainer {
     int excluded = 0;                       // ring slots the queued learn_grads left out of its minibatch (from write_pos - inflight)
     xq::LazyMark grads;                     // main: the queued learn_grads has finished reading the ring
     bool per_ready = false;                 // prioritized replay: the sum tree holds the ring as of the last learn_apply
+    // n-step returns (xq_trainer_set_n_step; 1 = off).  per_first / per_count: the readable range that goes with the tree of the last
+    // rebuild — the filled ring minus the slots retired there, in age order — of which the newest (n_step - 1) * n_games are held
+    int n_step = 1;
+    int per_first = 0, per_count = 0;
     bool early_collect = false;             // collects_per_update > 1: collects start behind the previous parameter update (see collect_impl)
     uint64_t params_version = 0;            // dqn_params_version() when `params` was last recorded: anything that rewrote parameters on the
                                             // handle's stream since (set_params on a bf16 net, an apply_grads of the caller's own) lies
@@ -238,6 +242,52 @@ int xq_trainer_set_target_tau(xq_trainer* t, double tau) {
     return xq_dqn_set_target_tau(t->dqn, tau);
 }
 
+// The newest (n_step - 1) * n_games slots of the tree's readable range — unless that is all of it (the first iterations of a run): then
+// nothing is held, as the uniform window is sampled uncut, and the rows that reach past the range are dead
+static int held_slots(const xq_trainer* t) {
+    const int h = (t->n_step - 1) * t->cfg.n_games;
+    return t->per_count - h > 0 ? h : 0;
+}
+// the rebuild itself, for the range noted last: `retire_count` slots from write_pos out for good, the held ones out of this tree only
+static int rebuild_held(xq_trainer* t, int retire_count) {
+    xq_replay* r = t->replay;
+    const int hold = held_slots(t);
+    const int hold_start = hold > 0 ? (int)(((long long)t->per_first + t->per_count - hold) % r->dev.capacity) : 0;
+    return replay_per_rebuild(r, r->write_pos, retire_count, t->stream, hold_start, hold);
+}
+
+// Prioritized replay: rebuilds the tree with `retire_count` slots from write_pos retired, notes the readable range that goes with it
+// (what is filled and not retired, in age order) and holds that range's newest (n_step - 1) * n_games slots, whose chains are incomplete
+static int rebuild_tree(xq_trainer* t, int retire_count) {
+    xq_replay* r = t->replay;
+    const int cap = r->dev.capacity;
+    if (retire_count > 0) {          // (only once the ring is full up to the retired window: the rest of it is the whole readable range)
+        t->per_first = (r->write_pos + retire_count) % cap;
+        t->per_count = cap - retire_count;
+    } else {
+        t->per_first = r->size < cap ? 0 : r->write_pos;
+        t->per_count = r->size;
+    }
+    return rebuild_held(t, retire_count);
+}
+
+int xq_trainer_set_n_step(xq_trainer* t, int n_step) {
+    if (!t) return fail(XQ_ERR_INVALID_ARGUMENT, "null trainer");
+    if (t->grads_queued || t->inflight > 0 || t->prepaid_collects > 0)
+        return fail(XQ_ERR_RUNTIME, "xq_trainer_set_n_step: call between iterations (after learn_apply)");
+    const int plies = t->cfg.collects_per_update > 1 ? t->cfg.collects_per_update : 1;
+    if (n_step > 1 && t->cfg.replay_capacity == 0)
+        return fail(XQ_ERR_INVALID_ARGUMENT, "xq_trainer_set_n_step: n-step returns need a replay ring (on-policy keeps one ply)");
+    if (n_step > 1 && n_step <= XQ_MAX_N_STEP && (long long)t->cfg.replay_capacity <= (long long)(n_step - 1 + plies) * t->cfg.n_games)
+        return fail(XQ_ERR_INVALID_ARGUMENT, "xq_trainer_set_n_step: the ring (%d) must exceed (n_step - 1 + collects_per_update) * n_games = %lld",
+                    t->cfg.replay_capacity, (long long)(n_step - 1 + plies) * t->cfg.n_games);
+    XQ_TRY(xq_replay_set_n_step(t->replay, n_step, t->cfg.n_games));
+    t->n_step = n_step;
+    // the tree of the last learn_apply was built for the previous hold: the same tree again (its retired slots are already 0), held anew
+    if (t->cfg.prioritized && t->per_ready) XQ_TRY(rebuild_held(t, 0));
+    return XQ_OK;
+}
+
 int xq_trainer_set_td_net(xq_trainer* t, int td_net) {
     if (!t || (td_net != XQ_TD_ONLINE_NET && td_net != XQ_TD_TARGET_NET && td_net != XQ_TD_DOUBLE)) return fail(XQ_ERR_INVALID_ARGUMENT, "bad td_net");
     if (t->grads_queued) return fail(XQ_ERR_RUNTIME, "xq_trainer_set_td_net: call between iterations (after learn_apply)");
@@ -301,13 +351,14 @@ static int learn_grads_prioritized(xq_trainer* t) {
         }
         if (t->cstream) { XQ_TRY(wait_collects(t)); t->inflight = 0; }
         if (t->replay->size == 0) return fail(XQ_ERR_RUNTIME, "replay is empty");
-        XQ_TRY(replay_per_rebuild(t->replay, 0, 0, t->stream));
+        XQ_TRY(rebuild_tree(t, 0));
         t->per_ready = true;
         t->excluded = 0;
     } else {
         t->excluded = plies * t->cfg.n_games;       // retired at the last learn_apply: the collects may run beside this step
     }
     XQ_TRY(replay_per_sample(t->replay, t->cfg.minibatch, t->stream));
+    if (t->n_step > 1) replay_set_readable(t->replay, t->per_first, t->per_count);
     XQ_TRY(xq_dqn_td_grads_replay(t->dqn, t->replay, t->cfg.minibatch, t->cfg.td_net, t->cfg.backprop_mode));
     t->grads.touched();
     t->grads_queued = true;
@@ -346,6 +397,16 @@ int xq_trainer_learn_grads(xq_trainer* t) {
                 t->excluded = m;
             }
         }
+        if (t->n_step > 1) {
+            // n-step returns: the window in age order (what the chains may read), sampled without its newest (n_step - 1) * n_games
+            // slots, whose chains are not complete — unless that leaves nothing (the first iterations): then the window as it is, and
+            // the rows that reach past it are dead
+            const xq_replay* r = t->replay;
+            if (count < 0) { start = r->size < r->dev.capacity ? 0 : r->write_pos; count = r->size; }
+            replay_set_readable(t->replay, start, count);
+            const int cut = (t->n_step - 1) * t->cfg.n_games;
+            if (count - cut > 0) count -= cut;
+        }
         XQ_TRY(replay_sample_implicit(t->replay, batch, start, count));     // no sampling kernel: the consumers recompute the slots
     }
     XQ_TRY(xq_dqn_td_grads_replay(t->dqn, t->replay, batch, t->cfg.td_net, t->cfg.backprop_mode));
@@ -370,7 +431,7 @@ int xq_trainer_learn_apply(xq_trainer* t, int world_size) {
         const int m = plies * t->cfg.n_games;
         const xq_replay* r = t->replay;
         const bool full = r->size + m > r->dev.capacity;
-        XQ_TRY(replay_per_rebuild(t->replay, r->write_pos, full ? std::min(m, r->dev.capacity) : 0, t->stream));
+        XQ_TRY(rebuild_tree(t, full ? std::min(m, r->dev.capacity) : 0));
         t->per_ready = true;
     }
     t->params.touched();

@@ -182,6 +182,16 @@ class DQN:
         call("xq_dqn_last_td_values", self._h, int(n), _ptr(q, C.c_float), _ptr(y, C.c_float))
         return q, y
 
+    def last_n_step(self, n):
+        """The first n rows of the batch the last td_grads_replay assembled from a ring with n_step > 1: dict of reward (the n-step R),
+        done, steps (chain elements used), first_slot (the sampled slot), last_slot (whose next board was staged) and action (-1: a
+        dead row).  Raises XqError when the last TD step was not an n-step one."""
+        r, d = np.zeros(n, np.float32), np.zeros(n, np.uint8)
+        m, f, l, a = (np.zeros(n, np.int32) for _ in range(4))
+        call("xq_dqn_last_n_step", self._h, int(n), _ptr(r, C.c_float), _ptr(d, C.c_uint8), _ptr(m, C.c_int32), _ptr(f, C.c_int32),
+             _ptr(l, C.c_int32), _ptr(a, C.c_int32))
+        return dict(reward=r, done=d, steps=m, first_slot=f, last_slot=l, action=a)
+
     def kernel_stats(self, enable=-1):
         """Returns the HIP-event timings collected so far; enable: 1 on, 0 off, 2 on + clear, -1 leave."""
         arr = (KernelStat * 64)()
@@ -523,6 +533,11 @@ class Trainer:
         """DQN.set_target_tau on the trainer's network; set target_sync_interval = 0 beside it (both set: both happen).  Call between
         iterations."""
         call("xq_trainer_set_target_tau", self._h, _checked_tau("set_target_tau", tau))
+
+    def set_n_step(self, n_step):
+        """n-step TD returns from the trainer's ring (ReplayBuffer.set_n_step with stride = n_games, and the sample / hold windows that
+        go with it; 1 = off).  Needs a replay ring larger than (n_step - 1 + collects_per_update) * n_games.  Call between iterations."""
+        call("xq_trainer_set_n_step", self._h, int(n_step))
 
     def set_opponent(self, opponent):
         """Train against a fixed opponent from the next collect on (DESIGN.md §4 "Versus training"): None = self-play (the default),

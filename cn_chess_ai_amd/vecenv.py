@@ -111,8 +111,13 @@ class ReplayBuffer:
     def enable_per(self, alpha=0.6, beta=0.4, eps=1e-3):
         call("xq_replay_enable_per", self._h, float(alpha), float(beta), float(eps))
 
-    def per_rebuild(self, retire_start=0, retire_count=0):
-        call("xq_replay_per_rebuild", self._h, int(retire_start), int(retire_count))
+    def per_rebuild(self, retire_start=0, retire_count=0, hold_start=0, hold_count=0):
+        """hold: `hold_count` slots from `hold_start` count as priority 0 in the tree only (never drawn, not eligible); the live table
+        keeps their values.  A hold of 0 is the plain rebuild."""
+        if hold_count == 0 and hold_start == 0:
+            call("xq_replay_per_rebuild", self._h, int(retire_start), int(retire_count))
+        else:
+            call("xq_replay_per_rebuild_hold", self._h, int(retire_start), int(retire_count), int(hold_start), int(hold_count))
 
     def sample_prioritized(self, batch, host=True):
         """(slots, normalised importance weights) of a stratified proportional draw from the tree as of the last rebuild."""
@@ -138,6 +143,19 @@ class ReplayBuffer:
         t, m, k = C.c_float(), C.c_float(), C.c_int32()
         call("xq_replay_per_stats", self._h, C.byref(t), C.byref(m), C.byref(k))
         return dict(total=t.value, max_priority=m.value, n_eligible=k.value)
+
+    # ---- n-step TD returns (build-defined, DESIGN.md §4 "n-step returns") ----
+    def set_n_step(self, n_step, stride=1):
+        """Every DQN.td_grads_replay from this ring learns on n-step transitions: chains of n_step slots `stride` apart in age order
+        (stride = the number of games whose collects fill the ring).  1 = off.  Takes effect at the next td_grads_replay."""
+        call("xq_replay_set_n_step", self._h, int(n_step), int(stride))
+
+    @property
+    def n_step(self):
+        """(n_step, stride) as last set; (1, 1) on a ring that was never asked."""
+        n, s = C.c_int32(), C.c_int32()
+        call("xq_replay_get_n_step", self._h, C.byref(n), C.byref(s))
+        return n.value, s.value
 
     def get(self, slot):
         b, nb = np.zeros(90, np.uint8), np.zeros(90, np.uint8)

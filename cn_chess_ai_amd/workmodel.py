@@ -35,6 +35,8 @@ ROCPROF_NAMES = {
     "l0_grad_segsum": "l0_grad_kernel(",
     "out_grad_segsum": "out_grad_kernel(",
     "bias_grad_colsum": "colsum_partial_kernel(",
+    "nstep_assemble": "nstep_assemble_kernel(",
+    "per_writeback": "per_writeback_kernel(",
 }
 # td_tail_kernel<KINDS, L0MFMA>: KINDS = TAIL_DELTA 1 | TAIL_GRAD 2 | TAIL_OUT 4 | TAIL_COLSUM 8 | TAIL_L0 16 | TAIL_SEL 32 (xq_tail.hip.h)
 TAIL_DELTAS, TAIL_DELTAS_SEL, TAIL_L0 = 7, 39, 30
@@ -117,13 +119,15 @@ def pick_splits(M, N, K):
 
 
 def step_work(layers, minibatch, n_games, plies=1, bf16=False, bf16_bwd=False, td="online", screened=True, derive=True,
-              prioritized=False, l0_mfma=True, optimizer="sgd", grad_clip=False, soft_target=False):
+              prioritized=False, l0_mfma=True, optimizer="sgd", grad_clip=False, soft_target=False, n_step=1):
     """{bracket name: dict(flops, hbm_bytes, bound, peak, peak_unit, what)} for one training step of the given configuration.
     optimizer="adam" (xq_dqn_set_optimizer): adam_apply stands in place of sgd_apply; the default step knows no adam_apply.
     grad_clip=True (xq_dqn_set_grad_clip): grad_norm stands in front of the apply and takes the slab sums over from it; the default
     step knows no grad_norm.
     soft_target=True (xq_dqn_set_target_tau in (0, 1), the target net in step with the online net outside the TD segments): the apply
-    kernel also reads and writes the touched part of the target net (and writes its bf16 shadow); no bracket of its own."""
+    kernel also reads and writes the touched part of the target net (and writes its bf16 shadow); no bracket of its own.
+    n_step > 1 (xq_replay_set_n_step): nstep_assemble stands in front of the step and, on a prioritized draw, per_writeback behind it;
+    the default step knows neither."""
     h = list(layers[1:-1])
     H1, Hl, k = h[0], h[-1], len(h)
     B, n = minibatch, n_games
@@ -289,6 +293,12 @@ def step_work(layers, minibatch, n_games, plies=1, bf16=False, bf16_bwd=False, t
         a["flops"] += 2.0 * touched
         a["hbm_bytes"] += 8 * touched + (2 * touched if bf16 else 0)
         a["what"] += " + soft update of the touched target parameters"
+    if n_step > 1:
+        # per row: action, reward and done of the n chain elements and two boards in, two boards and 21 B of row fields out
+        put("nstep_assemble", 2.0 * B * (n_step - 1), B * (9.0 * n_step + 4 * 48 + 21), "hbm",
+            "gather of the minibatch's n-step transitions into the staging batch the TD step reads")
+        if prioritized:
+            put("per_writeback", 0.0, 20.0 * B, "hbm", "TD-error priorities of a prioritized n-step draw back to the sampled slots")
     nw = STATE * H1 + sum(h[l] * h[l - 1] for l in range(1, k)) + Hl * NO
     nb = sum(h) + NO
     put("target_sync_copy", 0.0, 8.0 * (nw + nb), "hbm", "updateTargetNetwork(): device copy of all parameters")

@@ -364,6 +364,10 @@ public:
         t.actionTo = a; t.done = d != 0;
         return t;
     }
+    // n-step TD returns of every TD step that takes its minibatch from this ring (xq_replay_set_n_step; 1 = off): chains of n transitions
+    // `stride` slots apart in age order
+    void setNStep(int n, int stride) { check(xq_replay_set_n_step(h_, n, stride)); }
+    int nStep() const { int n = 1; check(xq_replay_get_n_step(h_, &n, nullptr)); return n; }
     int size() const { int s = 0; check(xq_replay_size(h_, &s, nullptr, nullptr)); return s; }
     int capacity() const { int c = 0; check(xq_replay_size(h_, nullptr, &c, nullptr)); return c; }
     xq_replay* handle() const { return h_; }
@@ -718,7 +722,8 @@ public:
     struct TrainStats { uint64_t envSteps = 0, updates = 0, episodes = 0; double seconds = 0; uint64_t screenedSteps = 0, guardFallbacks = 0;
                         double candidateGroupsPerSample = 0, wholeGroupsPerSample = 0;      // (sample, 32-output group) pairs the screen left for fp32
                                                                                            // re-evaluation per sample; those re-evaluated as whole groups
-                        uint64_t versus[4] = {0, 0, 0, 0}; };   // with an opponent: the learner's wins, draws, losses, games ended
+                        uint64_t versus[4] = {0, 0, 0, 0};      // with an opponent: the learner's wins, draws, losses, games ended
+                        int nStep = 1; };                       // the n-step setting of the trainer's ring as the run ended (setNStep)
     TrainStats lastTrainStats() const { return stats_; }
     // data-parallel train(): this process is rank comm->rank() of comm->world(); its batched games take the id range
     // [rank * parallelGames, (rank + 1) * parallelGames) and every update all-reduces the gradients over RCCL (nullptr = off)
@@ -734,6 +739,12 @@ public:
     void setTargetTau(double tau) { initializeDQN(); dqn->setTargetTau(tau); }
     // Loss of the batched train(), carried onto the trainer's network like the clip (TdLoss::squared() = the reference's)
     void setTdLoss(const TdLoss& l) { initializeDQN(); dqn->setTdLoss(l); }
+    // n-step TD returns of the batched train() with a replay ring (setReplay): xq_trainer_set_n_step on the trainer (1 = off, the default)
+    void setNStep(int n) {
+        if (n < 1 || n > XQ_MAX_N_STEP) throw std::invalid_argument("setNStep: n must be 1..XQ_MAX_N_STEP");
+        nStep_ = n;
+    }
+    int nStep() const { return nStep_; }
     DQN* network() { return dqn.get(); }
     std::vector<double> getStateRepresentation() {                           // chessai.cpp:268-289 (encoding only)
         std::vector<double> s(90 * 14, 0.0);
@@ -783,6 +794,7 @@ private:
         check(xq_dqn_set_optimizer(td, opt.kind, opt.beta1, opt.beta2, opt.eps));
         check(xq_dqn_set_grad_clip(td, dqn->gradClip()));
         check(xq_trainer_set_target_tau(t, dqn->targetTau()));
+        if (nStep_ > 1) check(xq_trainer_set_n_step(t, nStep_));
         const TdLoss loss = dqn->tdLoss();
         check(xq_dqn_set_td_loss(td, loss.kind, loss.kappa));
         if (comm_) check(xq_trainer_set_comm(t, comm_->handle()));
@@ -826,6 +838,11 @@ private:
         stats_.episodes = eps;
         if (opponent_) check(xq_trainer_versus_results(t, stats_.versus));
         {
+            xq_replay* tr = nullptr;
+            check(xq_trainer_replay(t, &tr));
+            check(xq_replay_get_n_step(tr, &stats_.nStep, nullptr));
+        }
+        {
             uint64_t q[4] = {0, 0, 0, 0}; int hold = 0;
             check(xq_dqn_qmax_stats(td, q));
             check(xq_dqn_qmax_guard(td, &stats_.guardFallbacks, &hold));
@@ -848,6 +865,7 @@ private:
     int replayCapacity_ = 0, replayMinibatch_ = 0;
     int saveInterval_ = 100, savedMark_ = 0;
     bool l0Derive_ = false;
+    int nStep_ = 1;
     int prefillPlies_ = 0;
     std::unique_ptr<Player> opponent_;
     TrainStats stats_;

@@ -251,6 +251,36 @@ int xq_replay_sample_prioritized(xq_replay* r, int batch, int32_t* slots_host /*
 int xq_replay_set_priorities(xq_replay* r, int first, int n, const float* prio_host);
 int xq_replay_get_priorities(xq_replay* r, int first, int n, float* prio_host);
 int xq_replay_per_stats(xq_replay* r, float* total, float* max_priority, int* n_eligible);
+/* xq_replay_per_rebuild with a hold window: the `hold_count` slots from `hold_start` (wrapping) count as priority 0 in the snapshot the
+ * sampler reads and in the sums of the tree ONLY — they are never drawn and are not among n_eligible, while the live priority table
+ * keeps their values, so a later rebuild without them in its hold makes them eligible with the priority they had.  n-step returns hold
+ * the newest (n_step - 1) * stride slots, whose chains are not complete yet.  xq_replay_per_rebuild is this call with a hold of 0:
+ * the same launches, the same bits.  A window outside the ring is XQ_ERR_INVALID_ARGUMENT. */
+int xq_replay_per_rebuild_hold(xq_replay* r, int retire_start, int retire_count, int hold_start, int hold_count);
+/* n-step TD returns (DESIGN.md §4 "n-step returns") — build-defined, off by default.  With n_step > 1 every xq_dqn_td_grads_replay from
+ * this ring first assembles, per minibatch row, the n-step transition that starts at the sampled slot, and then runs the TD step it always
+ * ran on that batch, with the discount gamma^n.
+ *   The ring has capacity `cap`; successive transitions of one trajectory lie `stride` slots apart in age order (xq_env_selfplay_step
+ *   writes game g of a collect to slot write_pos + g: stride = the number of games).  The readable range is `count` slots in age order
+ *   from slot `first`: first = 0 while the ring is not full and the write position once it is, count = the filled size (xq_trainer narrows
+ *   it, see xq_trainer_set_n_step).  For row b with sampled slot s: off0 = (s - first) mod cap; chain element k (0 <= k < n) lives at
+ *   off_k = off0 + k * stride, slot (first + off_k) mod cap, and exists iff off_k < count.
+ *   Arithmetic is fp32, one rounding per operation, no fma: gf = (float)gamma, disc_0 = 1, disc_k = fl32(disc_{k-1} * gf) (host).
+ *   R = r_0, D = done_0, m = 1; for k = 1 .. n-1 while !D: if element k does not exist or its action_to < 0 the row is DEAD and the scan
+ *   stops; otherwise R = fl32(R + fl32(disc_k * r_k)), D = done_k, m = k + 1.  A row whose own action_to < 0 is dead as it is today (no
+ *   scan: m = 1).  A chain that reaches `done` before it would leave the readable range is live.
+ *   Staged transition: board = boards[s], next_board = next_boards[slot_{m-1}], action = dead ? -1 : a_0, reward = R, done = D.  A dead
+ *   row stages s's own two boards; it contributes no gradient and loss 0 and keeps its priority (the rule of an empty slot).
+ *   TD step on the staged batch: y = D ? R : R + disc_n * tanh(max) — !D implies m == n, so this is the n-step target.  A prioritized
+ *   draw gets its importance weights as always; the TD-error priorities go back to the sampled slots behind the step.
+ * n_step == 1 is off: the kernels, launches and bits of a ring that was never asked.  XQ_ERR_INVALID_ARGUMENT for n_step outside
+ * 1..XQ_MAX_N_STEP, stride outside 1..capacity, or (n_step - 1) * stride >= capacity.  Takes effect at the next xq_dqn_td_grads_replay;
+ * xq_dqn_td_grads with raw pointers is never affected.  In self-play the chain follows consecutive plies of one game — both sides'
+ * moves, the one-trajectory view ChessAI::train takes of them (chessai.cpp:121-133); in versus training it is the learner's own
+ * trajectory. */
+enum { XQ_MAX_N_STEP = 8 };
+int xq_replay_set_n_step(xq_replay* r, int n_step, int stride);
+int xq_replay_get_n_step(const xq_replay* r, int* n_step /* optional */, int* stride /* optional */);
 
 /* ------------------------------------------------------------------------------------------------------------
  * xq_dqn — DQN (dqn.h:97-116) = qNetwork + targetNetwork (NeuralNetwork, dqn.h:42-95, dqn.cu), fp32 on MFMA.
@@ -489,6 +519,12 @@ int xq_dqn_last_loss(xq_dqn* d, double* loss);
 /* Q(s,a) and the TD target y of the first n samples of the last xq_dqn_td_grads* (tests / interop; synchronises).  Either pointer
  * may be NULL. */
 int xq_dqn_last_td_values(xq_dqn* d, int n, float* q_sa_host, float* y_host);
+/* The first n rows of the batch the last xq_dqn_td_grads_replay assembled from a ring with n_step > 1 (xq_replay_set_n_step; tests /
+ * interop; synchronises): the n-step reward R, done D, the number of chain elements used m, the sampled slot, the slot whose next board
+ * was staged, and the staged action (-1: a dead row).  All outputs are host pointers, any of which may be NULL.  XQ_ERR_RUNTIME when
+ * the last TD step was not an n-step one. */
+int xq_dqn_last_n_step(xq_dqn* d, int n, float* reward, uint8_t* done, int32_t* steps, int32_t* first_slot, int32_t* last_slot,
+                       int32_t* action);
 /* Per-kernel HIP-event timing on the handle stream, for bench.py (name -> summed ms, launches, algorithmic flops/bytes).
  * enable: -1 leave, 0 off, 1 on, 2 on + clear, 3 on + clear but bracket only the TD step's dominant GEMM (gemm_qmax_rowmax /
  * gemm_qmax_screen) and env_selfplay_step, 4 = 3 with the GEMM bracketed on every 4th launch only (a pair of event records
@@ -675,6 +711,15 @@ int xq_trainer_set_td_net(xq_trainer* t, int td_net);
 /* xq_dqn_set_target_tau on the trainer's network (DQN::updateTargetNetwork, dqn.cpp:71-74, as a soft update inside every learn_apply).
  * target_sync_interval keeps its meaning: a user of tau sets it to 0; if both are set, both happen.  Call between iterations. */
 int xq_trainer_set_target_tau(xq_trainer* t, double tau);
+/* xq_replay_set_n_step(ring, n, n_games) on the trainer's ring, and the windows that go with it (DESIGN.md §4 "n-step returns").
+ * Uniform replay: the minibatch is drawn from the oldest readable slot on, without the slots in flight (as always) and without the
+ * newest (n - 1) * n_games slots in front of them, whose chains are not complete; the chains read the window before that last cut.  If
+ * the cut would leave nothing (the first iterations of a run) the uncut window is sampled and the rows that reach past it are dead.
+ * Prioritized replay: both rebuilds hold the newest (n - 1) * n_games slots (xq_replay_per_rebuild_hold); the chains read the filled
+ * ring minus the slots about to be retired.  Self-play and versus training, any collects_per_update, with and without overlap_collect.
+ * n > 1 needs a replay ring whose capacity exceeds (n - 1 + collects_per_update) * n_games: otherwise, or on-policy, it is
+ * XQ_ERR_INVALID_ARGUMENT.  Call between iterations. */
+int xq_trainer_set_n_step(xq_trainer* t, int n_step);
 /* Versus training (DESIGN.md §4 "Versus training"): from the next collect on, the learner plays against a fixed opponent instead of
  * itself — uniform-random play, the material search (depth 1..3, eps) or a borrowed network (eps; layer_sizes[0] == 1260, >= 90
  * outputs, not the trainer's own).  The learner plays Black in game g iff (first_game_id + g) & 1.  A collect still writes one
