@@ -72,6 +72,7 @@ struct Screen {
                                                 // staged pass (145 KB: otherwise it would keep the select chain's blocks off its CUs for nothing — +3 us per step)
     unsigned long long seen[3] = {0, 0, 0};     // samples, pairs, whole groups at the last evaluation
     int hold = 0;                               // > 0: that many TD steps still run the full product
+    bool rebase = false;                        // a hold began and `seen` has not been re-based since: the next copy decides nothing (guard_queue)
     unsigned long long fallbacks = 0;
     void set_mode(int m) { mode = m; hold = 0; }         // an explicit request starts with the screen switched on again
     void rows_rewritten(int net) { if (static_net == net) static_net = -1; }     // rows >= 96 of `net` are no longer what the shadow holds
@@ -1768,12 +1769,16 @@ struct TdStep {
 
 // The screening guard.  The counters queued at one check boundary (guard_queue) are evaluated at the NEXT one (guard_tick, 32 screened
 // steps later: the copy finished long ago, the wait returns at once) — the step at which a fallback begins is a function of the step
-// count alone, never of how far the host runs ahead of the device.  guard_decide: the rule, on the totals of the copy (no runtime call)
+// count alone, never of how far the host runs ahead of the device.  A decision never counts a step that ran before the end of the last
+// hold: the hold marks `seen` stale (rebase), the first screened step behind it queues a copy at once, and at the next check boundary
+// that copy becomes `seen` without a decision, in front of the boundary's own copy (guard_queue).
+// guard_decide: the rule, on the totals of the copy (no runtime call)
 void Screen::guard_decide(const unsigned long long h[2]) {
     const double ds = (double)(guard_samples - seen[0]);
     if (ds > 0 && ((double)(h[0] - seen[1]) > kScreenMaxPairs * ds || (double)(h[1] - seen[2]) > kScreenMaxWhole * ds)) {
         hold = kScreenHoldSteps;
         fallbacks += 1;
+        rebase = true;                               // (nothing is pending here: the copy just evaluated was)
     }
     if (ds > 0) {                                    // whole groups per sample over the window, with hysteresis
         const double share = (double)(h[1] - seen[2]) / ds;
@@ -1783,7 +1788,7 @@ void Screen::guard_decide(const unsigned long long h[2]) {
 }
 // at the top of a step that asks for the screened max pass.  *screened: whether this step screens
 int Screen::guard_tick(bool* screened) {
-    if (guard_pending && host_steps % kScreenCheckEvery == 0 && host_steps != guard_queued_at) {
+    if (guard_pending && !rebase && host_steps % kScreenCheckEvery == 0 && host_steps != guard_queued_at) {
         XQ_HIP(hipEventSynchronize(guard_ev));
         guard_pending = false;
         unsigned long long h[2];
@@ -1794,10 +1799,20 @@ int Screen::guard_tick(bool* screened) {
     if (hold > 0) --hold;
     return XQ_OK;
 }
-// behind the launches of a screened step: count it and, every kScreenCheckEvery steps, queue the copy of the counters
+// behind the launches of a screened step: count it and, every kScreenCheckEvery steps, queue the copy of the counters.  While `rebase`
+// is set every copy is a re-basing one: queued behind the first screened step that finds none pending (the first behind the hold, or
+// behind a growth of the array that dropped it), taken as `seen` at the next boundary
 int Screen::guard_queue(int n, hipStream_t s) {
     host_steps += 1; host_samples += (unsigned long long)n;
-    if (host_steps % kScreenCheckEvery == 0 && !guard_pending) {
+    const bool boundary = host_steps % kScreenCheckEvery == 0;
+    if (rebase && guard_pending && boundary) {
+        XQ_HIP(hipEventSynchronize(guard_ev));
+        guard_pending = false; rebase = false;
+        unsigned long long h[2];
+        totals_of(guard_host, h);
+        seen[0] = guard_samples; seen[1] = h[0]; seen[2] = h[1];
+    }
+    if ((boundary || rebase) && !guard_pending) {
         XQ_HIP(hipMemcpyAsync(guard_host, stats, (size_t)2 * stat_blocks * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
         XQ_HIP(hipEventRecord(guard_ev, s));
         guard_pending = true; guard_samples = host_samples; guard_queued_at = host_steps;

@@ -200,7 +200,12 @@ typedef struct {
     uint16_t move_count;
     uint8_t winner, reserved;
 } xq_episode_record;
-/* Drains up to max_records finished-episode records (oldest first); *n_out = number written, *total = episodes so far. */
+/* Drains up to max_records finished-episode records (oldest first); *n_out = number written, *total = episodes so far.
+ * The env keeps the newest max(4096, 4 * n_games) records that have not been drained: when more than that finish between two
+ * drains the oldest are dropped (the next drain starts at the oldest record still there) and *total still counts them.  A record is
+ * written at most once: what one call leaves (max_records reached) the next returns.  max_records <= 0 or records_host == NULL: *n_out =
+ * 0 and *total only, and nothing is lost that the ring still holds.  xq_env_reset empties the ring: *total and the episode numbers of
+ * every game slot start again. */
 int xq_env_drain_episodes(xq_env* env, xq_episode_record* records_host, int max_records, int* n_out, uint64_t* total);
 /* totals since create/reset: [0] plies, [1] episodes, [2] red wins, [3] black wins, [4] captures, [5] explored plies */
 int xq_env_counters(xq_env* env, uint64_t counters6_host[6]);
@@ -359,8 +364,24 @@ int xq_dqn_set_refine_stage(xq_dqn* d, int mode);
  * whose last hidden width is a multiple of 64 and whose product is large enough for the persistent GEMM (>= 512 tiles of 128 x 128);
  * every other case silently keeps the full fp32 product.  Guard: every 32 screened steps the candidate counters are read back
  * asynchronously; when the screen leaves more than 24 candidate groups (or 1 whole group) per sample — a net whose outputs all lie
- * within the bf16 bound of each other — the next 512 TD steps run the full product, then the screen is tried again.  stats[4]
- * (xq_dqn_qmax_stats, synchronises): TD steps screened, samples, candidate (sample, 32-output group) pairs re-evaluated in fp32,
+ * within the bf16 bound of each other — the next 512 TD steps run the full product, then the screen is tried again.
+ * The guard in step numbers (S counts screened steps; a step that runs the full product does not count; tests/guard_model.py is this
+ * rule as a program):
+ *   - behind every screened step with S % 32 == 0 the counters are copied back, unless a copy is still pending;
+ *   - a pending copy is evaluated at the top of the first TD step at which S % 32 == 0 again and S is not the S it was queued at, on
+ *     everything counted between the previous evaluation and the copy: the copy of S = 32 at the top of the step behind S = 64 (window
+ *     S = 1..32), that of S = 96 behind S = 128 (window S = 33..96), and so on — one decision per 64 screened steps;
+ *   - over the limit, that TD step and the 511 behind it run the full product;
+ *   - a decision never counts a step that ran before the end of the last hold.  The first screened step behind a hold — whether the
+ *     hold ran out or xq_dqn_set_qmax_mode(XQ_QMAX_SCREENED) ended it, which switches the screen on at once — queues a copy
+ *     whatever S is; that copy decides nothing: at the next S % 32 == 0 it becomes the start of the next window, and that boundary's own
+ *     copy is queued behind it;
+ *   - a larger batch that needs a larger counter array drops the pending copy (the totals are kept); a dropped copy of the kind above is
+ *     queued again behind the next screened step.
+ * So a net the screen cannot handle, asked to screen every step: TD steps 1..64 screen, 65..576 run the full product, 577..640 screen
+ * (S = 65..128: the copy of S = 65 starts the window at S = 96, the copy of S = 96 — window S = 66..96 — is evaluated behind S = 128),
+ * 641..1152 run the full product: 64 screened and 512 full steps per cycle.  A net made harmless during a hold is not held again.
+ * stats[4] (xq_dqn_qmax_stats, synchronises): TD steps screened, samples, candidate (sample, 32-output group) pairs re-evaluated in fp32,
  * pairs whose whole group was re-evaluated. */
 int xq_dqn_set_qmax_mode(xq_dqn* d, int mode);
 int xq_dqn_qmax_stats(xq_dqn* d, uint64_t stats[4]);

@@ -419,3 +419,70 @@ def test_stream_wait_stream_orders_raw_pointer_exchanges(xq, direction):
     check((run_leg(xq, "sync", ALL, 0.0, body, "sync"),
            [run_leg(xq, "ordered", ALL, 0.0001, body, "wait"), run_leg(xq, "ordered", ALL, 0.03, body, "wait")],
            run_leg(xq, "unordered", ALL, 0.05, body, "nothing"), LEG["separate"]))
+
+
+# ----------------------------------------------------------------------------------------------- more reading streams than a resource lists
+class SixNetRig(Rig):
+    """the rig with six Q-nets of the same parameters, each on a stream of its own: a resource lists four reading streams, so the fifth
+    and the sixth reader of the ring each take the place of the fourth (SharedResource::read) and a writer must still end up behind
+    all six.  nets[3] is the first reader to be displaced: the cases gate its stream."""
+
+    def __init__(self, xq, cap):
+        super().__init__(xq, cap=cap)
+        self.nets = [self.d]
+        w, b = self.d.get_params()
+        for _ in range(5):
+            h = C.c_void_p()
+            xq._capi.call("xq_stream_create", 0, 0, C.byref(h))
+            self.streams.append(h)
+            d = xq.DQN(CFG2_NET, 0.001, 0.99, seed=1, stream=h)
+            d.set_params(w, b)
+            d.updateTargetNetwork()
+            d.td_grads_replay(self.rp, N, td_net=0, mode=0)             # allocates, like the rig's own prefill; changes no parameter
+            d.apply_grads(0.0, 1.0)
+            dsync()
+            self.nets.append(d)
+        assert len({self.env.stream(), self.rp.stream()} | {d.stream() for d in self.nets}) == 8
+        if LEG["name"] == "unordered":
+            LEG["separate"] = LEG["separate"] and queues_are_separate(xq, [self.env.stream(), self.rp.stream(), self.nets[3].stream()])
+
+    def close(self):
+        for g in self.gates:
+            g.destroy()
+        self.gates = []
+        dsync()
+        for d in self.nets[1:]:
+            d.close()
+        super().close()
+
+
+def six_readers_then_a_writer(xq, cls, writer):
+    def body(sync):
+        r = SixNetRig(xq, cap=2 * N)                                    # full after the two prefill plies: the next ply writes [0, N)
+        s = (lambda: dsync()) if sync else (lambda: None)
+        r.rp.sample_window(N, 0, N, host=False); s()
+        for k, d in enumerate(r.nets):
+            if k == 3:
+                r.delay(d.stream())                                     # the fourth reader cannot have run when the writer is queued
+            d.td_grads_replay(r.rp, N, td_net=0, mode=0); s()           # reads slots [0, N) through the slot list
+        writer(r); s()
+        for d in r.nets:
+            d.apply_grads(0.05, 1.0 / N); s()
+        dsync()
+        out = [d.get_params() for d in r.nets]
+        r.close()
+        return out
+    res = legs(xq, cls, body)
+    assert all(same(res[0][0], p) for p in res[0][1:])                  # six equal nets on one minibatch
+    check(res)
+
+
+def test_six_td_steps_then_env_step_overwrites_their_slots(xq):
+    """six xq_dqn_td_grads_replay on six streams still reading slots -> the xq_env_selfplay_step that overwrites them: WAR on the ring
+    contents with more readers than the resource lists."""
+    six_readers_then_a_writer(xq, xq._capi.ORDER_RING_CONTENTS, lambda r: r.env.selfplay_step_dev(0, 96, 0.1, replay=r.rp))
+
+
+def test_six_td_steps_then_next_draw_overwrites_their_list(xq):
+    """the same six readers -> the next xq_replay_sample overwrites the slot list they read: WAR on the draw."""
+    six_readers_then_a_writer(xq, xq._capi.ORDER_RING_DRAW, lambda r: r.rp.sample_window(N, N, N, host=False))
