@@ -145,6 +145,8 @@ PROTOTYPES = {
     "xq_replay_per_rebuild_hold": [_vp, _i, _i, _i, _i],
     "xq_replay_set_n_step": [_vp, _i, _i],
     "xq_replay_get_n_step": [_vp, _pi, _pi],
+    "xq_replay_set_mirror": [_vp, _d],
+    "xq_replay_get_mirror": [_vp, _pd, _pu64],
     "xq_dqn_create": [_pi, _i, _d, _d, _u64, _vp, _pvp],
     "xq_dqn_destroy": [_vp],
     "xq_dqn_set_precision": [_vp, _i],
@@ -176,6 +178,7 @@ PROTOTYPES = {
     "xq_dqn_last_loss": [_vp, _pd],
     "xq_dqn_last_td_values": [_vp, _i, _pf, _pf],
     "xq_dqn_last_n_step": [_vp, _i, _pf, _pu8, _pi, _pi, _pi, _pi],
+    "xq_dqn_last_mirror": [_vp, _i, _pu8, _pu8, _pu8, _pi, _pi],
     "xq_dqn_kernel_stats": [_vp, _i, C.POINTER(KernelStat), _i, _pi],
     "xq_dqn_set_fused_apply": [_vp, _i],
     "xq_dqn_set_optimizer": [_vp, _i, _d, _d, _d],
@@ -213,6 +216,7 @@ PROTOTYPES = {
     "xq_trainer_set_td_net": [_vp, _i],
     "xq_trainer_set_target_tau": [_vp, _d],
     "xq_trainer_set_n_step": [_vp, _i],
+    "xq_trainer_set_mirror": [_vp, _d],
     "xq_trainer_set_opponent": [_vp, C.POINTER(ArenaPlayer)],
     "xq_trainer_versus_results": [_vp, _pu64],
     "xq_trainer_collect": [_vp],
@@ -245,7 +249,9 @@ LAZY_TD_LOSS = frozenset(("xq_dqn_set_td_loss", "xq_dqn_get_td_loss", "xq_dqn_td
 # ... and those of the n-step returns
 LAZY_N_STEP = frozenset(("xq_replay_set_n_step", "xq_replay_get_n_step", "xq_replay_per_rebuild_hold", "xq_dqn_last_n_step",
                          "xq_trainer_set_n_step"))
-_LAZY_ALL = LAZY | LAZY_GRAD_CLIP | LAZY_TARGET_TAU | LAZY_TD_LOSS | LAZY_N_STEP
+# ... and those of the mirror augmentation
+LAZY_MIRROR = frozenset(("xq_replay_set_mirror", "xq_replay_get_mirror", "xq_dqn_last_mirror", "xq_trainer_set_mirror"))
+_LAZY_ALL = LAZY | LAZY_GRAD_CLIP | LAZY_TARGET_TAU | LAZY_TD_LOSS | LAZY_N_STEP | LAZY_MIRROR
 _RESTYPES = {"xq_last_error": C.c_char_p, "xq_env_boards_dev": C.c_void_p, "xq_env_meta_dev": C.c_void_p}
 
 _lib = None

@@ -197,6 +197,10 @@ struct xq_dqn {
     xq::DevBuf<float> ns_reward;
     xq::DevBuf<uint8_t> ns_done;
     int nstep_rows = 0;
+    // mirror augmentation (xq_replay_set_mirror): mirror_stage_kernel stages into the same buffers (ns_first: the sampled slot) or
+    // transforms an n-step batch there in place; per row the flag.  mirror_rows: rows of the last TD step if it was a mirror-mode one
+    xq::DevBuf<uint8_t> ns_flag;
+    int mirror_rows = 0;
     xq::Profiler prof;
     // fused launches of the TD step's tail (td_tail_kernel): while `tail_open`, the launch helpers of the small fp32 GEMMs, the
     // output-layer / layer-0 segmented sums and the bias column sums append their blocks to `tail` instead of launching.  Written by
@@ -283,6 +287,7 @@ struct SmallTiles {
 #include "xq_tail.hip.h"
 #include "xq_refine.hip.h"
 #include "xq_nstep.hip.h"
+#include "xq_mirror.hip.h"
 
 namespace xq {
 
@@ -2101,6 +2106,7 @@ static int td_grads_impl(xq_dqn* d, const uint32_t* boards, const uint32_t* next
     s.action_to = action_to; s.reward = reward; s.done = done; s.slots = slots; s.per = per;
     s.gamma = discount ? *discount : (float)d->gamma;
     d->nstep_rows = 0;                               // (xq_dqn_td_grads_replay sets it behind an n-step batch)
+    d->mirror_rows = 0;                              // (... and this one behind a mirror-mode batch)
     s.n = n; s.mode = mode; s.nl = nl; s.Hl = Hl; s.NO = NO; s.dbl = dbl; s.bf = bf; s.sel_net = td_net == XQ_TD_TARGET_NET ? XQ_NET_TARGET : XQ_NET_ONLINE;
     chain_views(d, d->acts, d->acts_bf, XQ_MAX_LAYERS, true, s.outs, s.outs_bf);
     chain_views(d, d->tacts, d->tacts_bf, 2, !bf, s.touts, s.touts_bf);
@@ -2424,8 +2430,71 @@ int xq_dqn_grad_buffer(xq_dqn* d, float** grads_dev, size_t* n_floats) {
     return XQ_OK;
 }
 
+// The TD step on the handle's staging batch (what an n-step assembly or a mirror gather filled): identity slot source, the given discount
+// (nullptr: the handle's gamma).  A prioritized draw keeps its importance weights; the step gets no priority table, and
+// per_writeback_kernel behind it writes the live rows' priorities to the sampled slots recorded in ns_first
+static int td_grads_staged(xq_dqn* d, int batch, int td_net, int mode, const PerOpts* per, const float* discount) {
+    PerOpts step_per;
+    if (per) { step_per = *per; step_per.prio = nullptr; step_per.pmax_live = nullptr; }
+    XQ_TRY(td_grads_impl(d, d->ns_boards, d->ns_next, d->ns_action, d->ns_reward, d->ns_done, explicit_slots(nullptr), batch, td_net, mode,
+                         per ? &step_per : nullptr, discount));
+    if (per) {
+        ProfScope ps(d, "per_writeback", 0.0, (double)batch * 20.0, true);
+        hipExtLaunchKernelGGL(per_writeback_kernel, dim3((batch + 255) / 256), dim3(256), 0, d->cur, ps.start(), ps.stop(), 0, batch,
+                              d->qsa.p, d->yv.p, d->act_mb.p, d->ns_first.p, per->prio, per->pmax_live, per->eps, per->alpha);
+        XQ_HIP(hipGetLastError());
+    }
+    return XQ_OK;
+}
+
+// Mirror augmentation (xq_replay_set_mirror): queues mirror_stage_kernel for the next TD step from ring `r` and counts it.  gather: the
+// minibatch from the ring (through `src`) into the handle's staging batch; otherwise the staging batch an n-step assembly just filled,
+// in place.  Whether row b is reflected is the ring's Philox stream at {b, 0, call, 3}
+static int mirror_stage(xq_dqn* d, xq_replay* r, SlotSrc src, int batch, bool gather) {
+    const size_t rows = (size_t)batch;
+    if (gather) {
+        XQ_TRY(d->ns_boards.reserve(rows * kBoardWords));
+        XQ_TRY(d->ns_next.reserve(rows * kBoardWords));
+        for (DevBuf<int32_t>* b : {&d->ns_action, &d->ns_first}) XQ_TRY(b->reserve(rows));
+        XQ_TRY(d->ns_reward.reserve(rows));
+        XQ_TRY(d->ns_done.reserve(rows));
+    }
+    XQ_TRY(d->ns_flag.reserve(rows));
+    MirrorArgs A; memset(&A, 0, sizeof A);
+    if (gather) {
+        A.boards = r->dev.boards; A.next_boards = r->dev.next_boards; A.action_to = r->dev.action_to; A.reward = r->dev.reward; A.done = r->dev.done;
+    } else {
+        A.boards = d->ns_boards; A.next_boards = d->ns_next; A.action_to = d->ns_action; A.reward = d->ns_reward; A.done = d->ns_done;
+    }
+    A.s_boards = d->ns_boards; A.s_next = d->ns_next; A.s_action = d->ns_action; A.s_reward = d->ns_reward; A.s_done = d->ns_done;
+    A.s_first = d->ns_first; A.s_flag = d->ns_flag;
+    A.thresh = eps_to_u32(r->mirror_prob); A.all = r->mirror_prob >= 1.0 ? 1u : 0u;
+    A.gather = gather ? 1u : 0u;
+    A.call = (uint32_t)r->mirror_calls; A.seed_lo = (uint32_t)r->seed; A.seed_hi = (uint32_t)(r->seed >> 32);
+    r->mirror_calls += 1;
+    {
+        // per row, from the ring: two boards and 9 B in, two boards, 9 B, the slot and the flag out; in place: two boards and the action
+        // in, two boards, the action and the flag out
+        ProfScope ps(d, "mirror_stage", 0.0, (double)batch * (gather ? 215.0 : 201.0), true);
+        hipExtLaunchKernelGGL(mirror_stage_kernel, dim3((batch + 63) / 64), dim3(64), 0, d->cur, ps.start(), ps.stop(), 0, A, src, batch);
+        XQ_HIP(hipGetLastError());
+    }
+    return XQ_OK;
+}
+
+// A TD step on a mirror-augmented batch of one-step transitions (xq_replay_set_mirror on a ring with n_step == 1): one gather stages the
+// minibatch with its flagged rows reflected, the step then runs on that batch with the identity slot source and the handle's discount; a
+// prioritized draw's priorities go back to the sampled slots behind the step (the n-step arrangement)
+static int td_grads_mirror(xq_dqn* d, xq_replay* r, SlotSrc src, int batch, int td_net, int mode, const PerOpts* per) {
+    XQ_TRY(mirror_stage(d, r, src, batch, true));
+    XQ_TRY(td_grads_staged(d, batch, td_net, mode, per, nullptr));
+    d->mirror_rows = batch;
+    return XQ_OK;
+}
+
 // A TD step on n-step transitions (xq_replay_set_n_step): one gather assembles them into the handle's staging batch, the step then runs
-// on that batch with the identity slot source and the discount gamma^n; a prioritized draw's priorities go back behind the step
+// on that batch with the identity slot source and the discount gamma^n; a prioritized draw's priorities go back behind the step.  With
+// mirror augmentation on as well, the assembled batch is transformed in place before the step
 static int td_grads_nstep(xq_dqn* d, xq_replay* r, SlotSrc src, int batch, int td_net, int mode, const PerOpts* per) {
     const int cap = r->dev.capacity, n = r->n_step;
     NStepArgs A; memset(&A, 0, sizeof A);
@@ -2455,17 +2524,11 @@ static int td_grads_nstep(xq_dqn* d, xq_replay* r, SlotSrc src, int batch, int t
         hipExtLaunchKernelGGL(nstep_assemble_kernel, dim3((batch + 63) / 64), dim3(64), 0, d->cur, ps.start(), ps.stop(), 0, A, src, batch);
         XQ_HIP(hipGetLastError());
     }
-    PerOpts step_per;
-    if (per) { step_per = *per; step_per.prio = nullptr; step_per.pmax_live = nullptr; }
-    XQ_TRY(td_grads_impl(d, d->ns_boards, d->ns_next, d->ns_action, d->ns_reward, d->ns_done, explicit_slots(nullptr), batch, td_net, mode,
-                         per ? &step_per : nullptr, &disc_n));
+    const bool mirrored = r->mirror_prob > 0.0;
+    if (mirrored) XQ_TRY(mirror_stage(d, r, src, batch, false));
+    XQ_TRY(td_grads_staged(d, batch, td_net, mode, per, &disc_n));
     d->nstep_rows = batch;
-    if (per) {
-        ProfScope ps(d, "per_writeback", 0.0, (double)batch * 20.0, true);
-        hipExtLaunchKernelGGL(per_writeback_kernel, dim3((batch + 255) / 256), dim3(256), 0, d->cur, ps.start(), ps.stop(), 0, batch,
-                              d->qsa.p, d->yv.p, d->act_mb.p, d->ns_first.p, per->prio, per->pmax_live, per->eps, per->alpha);
-        XQ_HIP(hipGetLastError());
-    }
+    if (mirrored) d->mirror_rows = batch;
     return XQ_OK;
 }
 
@@ -2482,6 +2545,25 @@ int xq_dqn_last_n_step(xq_dqn* d, int n, float* reward, uint8_t* done, int32_t* 
     if (first_slot) XQ_HIP(hipMemcpy(first_slot, d->ns_first, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
     if (last_slot) XQ_HIP(hipMemcpy(last_slot, d->ns_last, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
     if (action) XQ_HIP(hipMemcpy(action, d->ns_action, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return XQ_OK;
+}
+
+int xq_dqn_last_mirror(xq_dqn* d, int n, uint8_t* flags, uint8_t* boards90, uint8_t* next_boards90, int32_t* action_to, int32_t* slot) {
+    if (!d) return fail(XQ_ERR_INVALID_ARGUMENT, "null dqn");
+    if (d->mirror_rows <= 0) return fail(XQ_ERR_RUNTIME, "xq_dqn_last_mirror: the last TD step was not a mirror-mode one");
+    if (n < 0 || n > d->mirror_rows) return fail(XQ_ERR_INVALID_ARGUMENT, "xq_dqn_last_mirror: n exceeds the last TD step's %d rows", d->mirror_rows);
+    XQ_HIP(hipStreamSynchronize(d->stream));
+    if (!n) return XQ_OK;
+    if (flags) XQ_HIP(hipMemcpy(flags, d->ns_flag, (size_t)n, hipMemcpyDeviceToHost));
+    std::vector<uint32_t> w((size_t)n * kBoardWords);
+    const struct { uint8_t* out; const uint32_t* dev; } boards[2] = {{boards90, d->ns_boards}, {next_boards90, d->ns_next}};
+    for (const auto& bd : boards) {
+        if (!bd.out) continue;
+        XQ_HIP(hipMemcpy(w.data(), bd.dev, w.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        for (int i = 0; i < n; ++i) unpack_board(&w[(size_t)i * kBoardWords], bd.out + (size_t)i * 90);
+    }
+    if (action_to) XQ_HIP(hipMemcpy(action_to, d->ns_action, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (slot) XQ_HIP(hipMemcpy(slot, d->ns_first, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
     return XQ_OK;
 }
 
@@ -2513,6 +2595,7 @@ int xq_dqn_td_grads_replay(xq_dqn* d, xq_replay* r, int batch, int td_net, int m
     // them, and whatever touches them next — the next draw overwrites the list, the next env step the slots — behind this step
     XQ_TRY(replay_consumer_begin(r, d->stream, src.slots != nullptr, prioritized));
     if (r->n_step > 1) return td_grads_nstep(d, r, src, batch, td_net, mode, prioritized ? &per : nullptr);
+    if (r->mirror_prob > 0.0) return td_grads_mirror(d, r, src, batch, td_net, mode, prioritized ? &per : nullptr);
     return td_grads_impl(d, r->dev.boards, r->dev.next_boards, r->dev.action_to, r->dev.reward, r->dev.done, src, batch, td_net,
                          mode, prioritized ? &per : nullptr);
 }

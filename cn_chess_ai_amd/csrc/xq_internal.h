@@ -215,6 +215,11 @@ struct xq_replay {
     // owner narrowed it (replay_set_readable; read_count < 0: the default — the filled ring in age order), consumed by that step
     int n_step = 1, n_stride = 1;
     int read_first = 0, read_count = -1;
+    // mirror augmentation (xq_replay_set_mirror, DESIGN.md §4 "Mirror augmentation"): the probability that a minibatch row is reflected
+    // left-right in the staged batch (0 = off), and the number of mirror-mode TD steps queued from this ring so far — the `call` word of
+    // the next one's flag stream
+    double mirror_prob = 0.0;
+    uint64_t mirror_calls = 0;
     xq::Stream stream;
     // Device data of the ring that other handles read or write, possibly on streams of their own — each a SharedResource (above):
     //   contents : boards / next_boards / action_to / reward / done   written by env steps (xq_env_selfplay_step) and push_host,

@@ -242,6 +242,13 @@ int xq_trainer_set_target_tau(xq_trainer* t, double tau) {
     return xq_dqn_set_target_tau(t->dqn, tau);
 }
 
+// mirror augmentation lives on the ring and changes no window: the transform reads what the step read anyway
+int xq_trainer_set_mirror(xq_trainer* t, double prob) {
+    if (!t) return fail(XQ_ERR_INVALID_ARGUMENT, "null trainer");
+    if (t->grads_queued) return fail(XQ_ERR_RUNTIME, "xq_trainer_set_mirror: call between iterations (after learn_apply)");
+    return xq_replay_set_mirror(t->replay, prob);
+}
+
 // The newest (n_step - 1) * n_games slots of the tree's readable range — unless that is all of it (the first iterations of a run): then
 // nothing is held, as the uniform window is sampled uncut, and the rows that reach past the range are dead
 static int held_slots(const xq_trainer* t) {

@@ -192,6 +192,17 @@ class DQN:
              _ptr(l, C.c_int32), _ptr(a, C.c_int32))
         return dict(reward=r, done=d, steps=m, first_slot=f, last_slot=l, action=a)
 
+    def last_mirror(self, n):
+        """The first n rows of the batch the last td_grads_replay staged from a ring with ReplayBuffer.set_mirror(prob > 0): dict of
+        flags (1 = the row was reflected), boards and next_boards ([n, 90] piece codes as staged), action (as staged) and slot (the
+        sampled slot).  Raises XqError when the last TD step was not a mirror-mode one."""
+        f = np.zeros(n, np.uint8)
+        b, nb = np.zeros((n, 90), np.uint8), np.zeros((n, 90), np.uint8)
+        a, s = np.zeros(n, np.int32), np.zeros(n, np.int32)
+        call("xq_dqn_last_mirror", self._h, int(n), _ptr(f, C.c_uint8), _ptr(b, C.c_uint8), _ptr(nb, C.c_uint8), _ptr(a, C.c_int32),
+             _ptr(s, C.c_int32))
+        return dict(flags=f, boards=b, next_boards=nb, action=a, slot=s)
+
     def kernel_stats(self, enable=-1):
         """Returns the HIP-event timings collected so far; enable: 1 on, 0 off, 2 on + clear, -1 leave."""
         arr = (KernelStat * 64)()
@@ -538,6 +549,11 @@ class Trainer:
         """n-step TD returns from the trainer's ring (ReplayBuffer.set_n_step with stride = n_games, and the sample / hold windows that
         go with it; 1 = off).  Needs a replay ring larger than (n_step - 1 + collects_per_update) * n_games.  Call between iterations."""
         call("xq_trainer_set_n_step", self._h, int(n_step))
+
+    def set_mirror(self, prob):
+        """Mirror augmentation of every learn_grads from the trainer's ring (ReplayBuffer.set_mirror; 0 = off): each minibatch row is
+        reflected left-right with probability prob.  Uniform, prioritized and on-policy, any n_step.  Call between iterations."""
+        call("xq_trainer_set_mirror", self._h, float(prob))
 
     def set_opponent(self, opponent):
         """Train against a fixed opponent from the next collect on (DESIGN.md §4 "Versus training"): None = self-play (the default),

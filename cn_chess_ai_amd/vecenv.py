@@ -157,6 +157,21 @@ class ReplayBuffer:
         call("xq_replay_get_n_step", self._h, C.byref(n), C.byref(s))
         return n.value, s.value
 
+    # ---- mirror augmentation (build-defined, DESIGN.md §4 "Mirror augmentation") ----
+    def set_mirror(self, prob):
+        """Every DQN.td_grads_replay from this ring reflects each minibatch row left-right (col -> 8 - col: both boards and the action)
+        with probability prob, in a staged copy of the batch; the ring is never written.  0 = off.  NaN or a value outside [0, 1] is
+        refused.  Takes effect at the next td_grads_replay."""
+        call("xq_replay_set_mirror", self._h, float(prob))
+
+    @property
+    def mirror(self):
+        """(prob, calls): prob as last set (0.0 on a ring that was never asked) and the number of mirror-mode TD steps queued from this
+        ring so far — the call word of the next one's flag stream."""
+        p, c = C.c_double(), C.c_uint64()
+        call("xq_replay_get_mirror", self._h, C.byref(p), C.byref(c))
+        return p.value, c.value
+
     def get(self, slot):
         b, nb = np.zeros(90, np.uint8), np.zeros(90, np.uint8)
         a, r, d = C.c_int32(), C.c_float(), C.c_uint8()

@@ -37,6 +37,7 @@ ROCPROF_NAMES = {
     "bias_grad_colsum": "colsum_partial_kernel(",
     "nstep_assemble": "nstep_assemble_kernel(",
     "per_writeback": "per_writeback_kernel(",
+    "mirror_stage": "mirror_stage_kernel(",
 }
 # td_tail_kernel<KINDS, L0MFMA>: KINDS = TAIL_DELTA 1 | TAIL_GRAD 2 | TAIL_OUT 4 | TAIL_COLSUM 8 | TAIL_L0 16 | TAIL_SEL 32 (xq_tail.hip.h)
 TAIL_DELTAS, TAIL_DELTAS_SEL, TAIL_L0 = 7, 39, 30
@@ -119,7 +120,8 @@ def pick_splits(M, N, K):
 
 
 def step_work(layers, minibatch, n_games, plies=1, bf16=False, bf16_bwd=False, td="online", screened=True, derive=True,
-              prioritized=False, l0_mfma=True, optimizer="sgd", grad_clip=False, soft_target=False, n_step=1):
+              prioritized=False, l0_mfma=True, optimizer="sgd", grad_clip=False, soft_target=False, n_step=1,
+              mirror=False):
     """{bracket name: dict(flops, hbm_bytes, bound, peak, peak_unit, what)} for one training step of the given configuration.
     optimizer="adam" (xq_dqn_set_optimizer): adam_apply stands in place of sgd_apply; the default step knows no adam_apply.
     grad_clip=True (xq_dqn_set_grad_clip): grad_norm stands in front of the apply and takes the slab sums over from it; the default
@@ -127,7 +129,9 @@ def step_work(layers, minibatch, n_games, plies=1, bf16=False, bf16_bwd=False, t
     soft_target=True (xq_dqn_set_target_tau in (0, 1), the target net in step with the online net outside the TD segments): the apply
     kernel also reads and writes the touched part of the target net (and writes its bf16 shadow); no bracket of its own.
     n_step > 1 (xq_replay_set_n_step): nstep_assemble stands in front of the step and, on a prioritized draw, per_writeback behind it;
-    the default step knows neither."""
+    the default step knows neither.
+    mirror=True (xq_replay_set_mirror with prob > 0): mirror_stage stands in front of the step (behind nstep_assemble when n_step > 1)
+    and, on a prioritized draw with n_step == 1, per_writeback behind it; the default step knows no mirror_stage."""
     h = list(layers[1:-1])
     H1, Hl, k = h[0], h[-1], len(h)
     B, n = minibatch, n_games
@@ -299,7 +303,14 @@ def step_work(layers, minibatch, n_games, plies=1, bf16=False, bf16_bwd=False, t
             "gather of the minibatch's n-step transitions into the staging batch the TD step reads")
         if prioritized:
             put("per_writeback", 0.0, 20.0 * B, "hbm", "TD-error priorities of a prioritized n-step draw back to the sampled slots")
-    nw = STATE * H1 + sum(h[l] * h[l - 1] for l in range(1, k)) + Hl * NO
+    if mirror:
+        # per row, from the ring: two boards and 9 B in, two boards, 9 B, the slot and the flag out; in place behind nstep_assemble: two
+        # boards and the action in, two boards, the action and the flag out
+        put("mirror_stage", 0.0, B * (215.0 if n_step == 1 else 201.0), "hbm",
+            "left-right reflection of the flagged minibatch rows in the staging batch the TD step reads")
+        if prioritized and n_step == 1:
+            put("per_writeback", 0.0, 20.0 * B, "hbm", "TD-error priorities of a prioritized mirrored draw back to the sampled slots")
+    nw =STATE * H1 + sum(h[l] * h[l - 1] for l in range(1, k)) + Hl * NO
     nb = sum(h) + NO
     put("target_sync_copy", 0.0, 8.0 * (nw + nb), "hbm", "updateTargetNetwork(): device copy of all parameters")
     # ---- select chain (collect stream): one ply in every game ---------------------------------------------------------------------

@@ -14,6 +14,8 @@
 //   --seed S                      seed of the batched games (default: time, like the reference's srand(time))
 //   adam                          the batched loop's optimizer: Adam (xq::Optimizer::adam(), defaults 0.9 / 0.999 / 1e-8) instead of SGD
 //   clip=<max_norm>               clip the batched loop's gradient by its global L2 norm (xq::ChessAI::setGradClip; inf = measure only)
+//   mirror=<prob>                 mirror augmentation of the batched loop's minibatches: each row reflected left-right with probability
+//                                 prob in [0, 1] (xq::ChessAI::setMirror; 0 = off)
 //   --json                        one JSON line with the loop's counters (bench.py's `facade` leg reads it)
 #include <chrono>
 #include <cstdio>
@@ -29,7 +31,7 @@ int main(int argc, char** argv) {
     std::vector<int> hidden;
     bool derive = false, json = false, adam = false;
     unsigned long long seed = 0;
-    double clip = 0.0;
+    double clip = 0.0, mirror = 0.0;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         auto next = [&]() -> const char* { if (i + 1 >= argc) { std::fprintf(stderr, "%s needs a value\n", a.c_str()); std::exit(2); } return argv[++i]; };
@@ -45,6 +47,11 @@ int main(int argc, char** argv) {
             char* end = nullptr;
             clip = std::strtod(a.c_str() + 5, &end);
             if (end == a.c_str() + 5 || *end || !(clip >= 0.0)) { std::fprintf(stderr, "clip=: expected a max_norm >= 0 or inf, got %s\n", a.c_str() + 5); return 2; }
+        }
+        else if (a.rfind("mirror=", 0) == 0) {
+            char* end = nullptr;
+            mirror = std::strtod(a.c_str() + 7, &end);
+            if (end == a.c_str() + 7 || *end || !(mirror >= 0.0 && mirror <= 1.0)) { std::fprintf(stderr, "mirror=: expected a probability in [0, 1], got %s\n", a.c_str() + 7); return 2; }
         }
         else if (a == "--hidden") {
             for (const char* p = next(); *p;) { hidden.push_back(std::atoi(p)); while (*p && *p != ',') ++p; if (*p == ',') ++p; }
@@ -65,6 +72,7 @@ int main(int argc, char** argv) {
         }
         if (adam) ai.setOptimizer(xq::Optimizer::adam());
         if (clip != 0.0) ai.setGradClip(clip);
+        if (mirror != 0.0) ai.setMirror(mirror);
         if (replay > 0) ai.setReplay(replay, minibatch);
         ai.setSaveInterval(save_every);
         ai.setLayer0Derive(derive);

@@ -368,6 +368,10 @@ public:
     // `stride` slots apart in age order
     void setNStep(int n, int stride) { check(xq_replay_set_n_step(h_, n, stride)); }
     int nStep() const { int n = 1; check(xq_replay_get_n_step(h_, &n, nullptr)); return n; }
+    // mirror augmentation of every TD step that takes its minibatch from this ring (xq_replay_set_mirror; 0 = off): each row reflected
+    // left-right with probability prob, in the staged batch only
+    void setMirror(double prob) { check(xq_replay_set_mirror(h_, prob)); }
+    double mirror() const { double p = 0; check(xq_replay_get_mirror(h_, &p, nullptr)); return p; }
     int size() const { int s = 0; check(xq_replay_size(h_, &s, nullptr, nullptr)); return s; }
     int capacity() const { int c = 0; check(xq_replay_size(h_, nullptr, &c, nullptr)); return c; }
     xq_replay* handle() const { return h_; }
@@ -723,7 +727,8 @@ public:
                         double candidateGroupsPerSample = 0, wholeGroupsPerSample = 0;      // (sample, 32-output group) pairs the screen left for fp32
                                                                                            // re-evaluation per sample; those re-evaluated as whole groups
                         uint64_t versus[4] = {0, 0, 0, 0};      // with an opponent: the learner's wins, draws, losses, games ended
-                        int nStep = 1; };                       // the n-step setting of the trainer's ring as the run ended (setNStep)
+                        int nStep = 1;                          // the n-step setting of the trainer's ring as the run ended (setNStep)
+                        double mirror = 0; };                   // ... and its mirror probability (setMirror)
     TrainStats lastTrainStats() const { return stats_; }
     // data-parallel train(): this process is rank comm->rank() of comm->world(); its batched games take the id range
     // [rank * parallelGames, (rank + 1) * parallelGames) and every update all-reduces the gradients over RCCL (nullptr = off)
@@ -745,6 +750,12 @@ public:
         nStep_ = n;
     }
     int nStep() const { return nStep_; }
+    // mirror augmentation of the batched train(): xq_trainer_set_mirror on the trainer (0 = off, the default); on-policy too
+    void setMirror(double prob) {
+        if (!(prob >= 0.0 && prob <= 1.0)) throw std::invalid_argument("setMirror: prob must be in [0, 1]");
+        mirror_ = prob;
+    }
+    double mirror() const { return mirror_; }
     DQN* network() { return dqn.get(); }
     std::vector<double> getStateRepresentation() {                           // chessai.cpp:268-289 (encoding only)
         std::vector<double> s(90 * 14, 0.0);
@@ -795,6 +806,7 @@ private:
         check(xq_dqn_set_grad_clip(td, dqn->gradClip()));
         check(xq_trainer_set_target_tau(t, dqn->targetTau()));
         if (nStep_ > 1) check(xq_trainer_set_n_step(t, nStep_));
+        if (mirror_ > 0.0) check(xq_trainer_set_mirror(t, mirror_));
         const TdLoss loss = dqn->tdLoss();
         check(xq_dqn_set_td_loss(td, loss.kind, loss.kappa));
         if (comm_) check(xq_trainer_set_comm(t, comm_->handle()));
@@ -841,6 +853,7 @@ private:
             xq_replay* tr = nullptr;
             check(xq_trainer_replay(t, &tr));
             check(xq_replay_get_n_step(tr, &stats_.nStep, nullptr));
+            check(xq_replay_get_mirror(tr, &stats_.mirror, nullptr));
         }
         {
             uint64_t q[4] = {0, 0, 0, 0}; int hold = 0;
@@ -866,6 +879,7 @@ private:
     int saveInterval_ = 100, savedMark_ = 0;
     bool l0Derive_ = false;
     int nStep_ = 1;
+    double mirror_ = 0.0;
     int prefillPlies_ = 0;
     std::unique_ptr<Player> opponent_;
     TrainStats stats_;

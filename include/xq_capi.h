@@ -286,6 +286,27 @@ int xq_replay_per_rebuild_hold(xq_replay* r, int retire_start, int retire_count,
 enum { XQ_MAX_N_STEP = 8 };
 int xq_replay_set_n_step(xq_replay* r, int n_step, int stride);
 int xq_replay_get_n_step(const xq_replay* r, int* n_step /* optional */, int* stride /* optional */);
+/* Mirror augmentation (DESIGN.md §4 "Mirror augmentation") — build-defined, off by default.  Xiangqi is symmetric under the left-right
+ * reflection col -> 8 - col, so the reflection of a played transition is as true as the transition.  While prob > 0 every
+ * xq_dqn_td_grads_replay from this ring stages its minibatch in the handle's staging buffers (the n-step ones) and reflects the rows
+ * whose flag is set; the TD step it always ran then runs on the staged batch.  The ring is never written.
+ *   flag_b = (prob == 1) || philox4x32_10(ctr = {b, 0, call, 3}, key = ring seed).v[0] < floor(prob * 2^32), saturated (the threshold
+ *   rule of the env's epsilon).  Counter word 3 keeps the stream apart from the draw (1) and the stratified draw (2).  `call` counts the
+ *   mirror-mode TD steps queued from this ring since it was created (the first is 0; steps taken while prob == 0 do not count).  The
+ *   flag depends on the row alone: not on the slot, on whether the row is live, or on how the batch was drawn (explicit slots, the
+ *   trainer's implicit draw, the identity of batch = 0, a prioritized draw).
+ *   A flagged row: board'[r * 9 + c] = board[r * 9 + (8 - c)] for s and s' (nibbles 90..95 stay 0); action a' = a - 2 (a mod 9) + 8
+ *   when 0 <= a < 90, any other value (-1: dead or empty, 90..95) as it is; reward and done unchanged.  Dead and empty rows follow the
+ *   same flag rule and still contribute nothing.  An unflagged row is the sampled transition bit for bit.
+ *   The step: identity slot source on the staged batch; with n_step == 1 the discount is (float)gamma as always; a prioritized draw
+ *   gets its importance weights as always and the priorities of its live rows go back to the SAMPLED slots behind the step.  With
+ *   n_step > 1 the n-step batch is assembled first and the flag applies to the assembled transition: s, the staged s' and a_0.
+ * prob == 0 is off: the kernels, launches and bits of a ring that was never asked.  NaN or a value outside [0, 1] is
+ * XQ_ERR_INVALID_ARGUMENT.  Takes effect at the next xq_dqn_td_grads_replay; xq_dqn_td_grads with raw pointers, xq_dqn_td_update_host
+ * and xq_dqn_backpropagate are never affected.  The setting lives on the ring: it survives xq_dqn_set_optimizer, set_params, a model
+ * load, a target update and xq_replay_set_n_step. */
+int xq_replay_set_mirror(xq_replay* r, double prob);
+int xq_replay_get_mirror(const xq_replay* r, double* prob /* optional */, uint64_t* calls /* optional: the `call` the next mirror-mode step will use */);
 
 /* ------------------------------------------------------------------------------------------------------------
  * xq_dqn — DQN (dqn.h:97-116) = qNetwork + targetNetwork (NeuralNetwork, dqn.h:42-95, dqn.cu), fp32 on MFMA.
@@ -543,9 +564,15 @@ int xq_dqn_last_td_values(xq_dqn* d, int n, float* q_sa_host, float* y_host);
 /* The first n rows of the batch the last xq_dqn_td_grads_replay assembled from a ring with n_step > 1 (xq_replay_set_n_step; tests /
  * interop; synchronises): the n-step reward R, done D, the number of chain elements used m, the sampled slot, the slot whose next board
  * was staged, and the staged action (-1: a dead row).  All outputs are host pointers, any of which may be NULL.  XQ_ERR_RUNTIME when
- * the last TD step was not an n-step one. */
+ * the last TD step was not an n-step one.  Behind a step that is both n-step and mirrored (xq_replay_set_mirror) `action` is the
+ * mirrored one of the flagged rows; everything else is what it is without the mirror. */
 int xq_dqn_last_n_step(xq_dqn* d, int n, float* reward, uint8_t* done, int32_t* steps, int32_t* first_slot, int32_t* last_slot,
                        int32_t* action);
+/* The first n rows of the batch the last xq_dqn_td_grads_replay staged in mirror mode (xq_replay_set_mirror; tests / interop;
+ * synchronises): the row's flag (1 = reflected), the two staged boards as 90 piece codes per row, the staged action and the sampled
+ * slot.  All outputs are host pointers, any of which may be NULL.  XQ_ERR_RUNTIME when the last TD step was not a mirror-mode one,
+ * XQ_ERR_INVALID_ARGUMENT for n beyond its rows. */
+int xq_dqn_last_mirror(xq_dqn* d, int n, uint8_t* flags, uint8_t* boards90, uint8_t* next_boards90, int32_t* action_to, int32_t* slot);
 /* Per-kernel HIP-event timing on the handle stream, for bench.py (name -> summed ms, launches, algorithmic flops/bytes).
  * enable: -1 leave, 0 off, 1 on, 2 on + clear, 3 on + clear but bracket only the TD step's dominant GEMM (gemm_qmax_rowmax /
  * gemm_qmax_screen) and env_selfplay_step, 4 = 3 with the GEMM bracketed on every 4th launch only (a pair of event records
@@ -741,6 +768,11 @@ int xq_trainer_set_target_tau(xq_trainer* t, double tau);
  * n > 1 needs a replay ring whose capacity exceeds (n - 1 + collects_per_update) * n_games: otherwise, or on-policy, it is
  * XQ_ERR_INVALID_ARGUMENT.  Call between iterations. */
 int xq_trainer_set_n_step(xq_trainer* t, int n_step);
+/* xq_replay_set_mirror on the trainer's ring (DESIGN.md §4 "Mirror augmentation"): every learn_grads from then on mirrors a random
+ * part of its minibatch — uniform and prioritized replay, on-policy too (the identity batch), with and without overlap_collect, with
+ * any n_step.  No window changes: the transform reads only what the step read anyway.  Call between iterations: XQ_ERR_RUNTIME while a
+ * learn_grads waits for its learn_apply. */
+int xq_trainer_set_mirror(xq_trainer* t, double prob);
 /* Versus training (DESIGN.md §4 "Versus training"): from the next collect on, the learner plays against a fixed opponent instead of
  * itself — uniform-random play, the material search (depth 1..3, eps) or a borrowed network (eps; layer_sizes[0] == 1260, >= 90
  * outputs, not the trainer's own).  The learner plays Black in game g iff (first_game_id + g) & 1.  A collect still writes one
