@@ -21,6 +21,7 @@ PRECISION_F32, PRECISION_BF16, PRECISION_BF16_FULL = 0, 1, 2
 QMAX_FULL, QMAX_SCREENED = 0, 1
 OPT_SGD, OPT_ADAM = 0, 1
 LOSS_SQUARED, LOSS_HUBER = 0, 1
+BOOTSTRAP_ALL, BOOTSTRAP_LEGAL = 0, 1
 MAX_N_STEP = 8
 ORDER_RING_CONTENTS, ORDER_RING_PRIORITIES, ORDER_RING_DRAW, ORDER_TRAINER_PARAMS, ORDER_ALL = 1, 2, 4, 8, 15
 
@@ -179,6 +180,15 @@ PROTOTYPES = {
     "xq_dqn_last_td_values": [_vp, _i, _pf, _pf],
     "xq_dqn_last_n_step": [_vp, _i, _pf, _pu8, _pi, _pi, _pi, _pi],
     "xq_dqn_last_mirror": [_vp, _i, _pu8, _pu8, _pu8, _pi, _pi],
+    "xq_dqn_set_td_bootstrap": [_vp, _i],
+    "xq_dqn_get_td_bootstrap": [_vp, _pi],
+    "xq_dqn_td_grads_sided": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i],
+    "xq_dqn_td_update_host_sided": [_vp, _i, _pu8, _pu8, _pi, _pf, _pu8, _pu8, _i, _i, _d, _d, _pf, _pf],
+    "xq_dqn_last_legal": [_vp, _i, _pi, _pi, _pf, _pf],
+    "xq_replay_track_next_player": [_vp],
+    "xq_replay_push_host_sided": [_vp, _i, _pu8, _pi, _pf, _pu8, _pu8, _pu8],
+    "xq_replay_get_next_player": [_vp, _i, _i, _pu8],
+    "xq_trainer_set_td_bootstrap": [_vp, _i],
     "xq_dqn_kernel_stats": [_vp, _i, C.POINTER(KernelStat), _i, _pi],
     "xq_dqn_set_fused_apply": [_vp, _i],
     "xq_dqn_set_optimizer": [_vp, _i, _d, _d, _d],
@@ -251,7 +261,11 @@ LAZY_N_STEP = frozenset(("xq_replay_set_n_step", "xq_replay_get_n_step", "xq_rep
                          "xq_trainer_set_n_step"))
 # ... and those of the mirror augmentation
 LAZY_MIRROR = frozenset(("xq_replay_set_mirror", "xq_replay_get_mirror", "xq_dqn_last_mirror", "xq_trainer_set_mirror"))
-_LAZY_ALL = LAZY | LAZY_GRAD_CLIP | LAZY_TARGET_TAU | LAZY_TD_LOSS | LAZY_N_STEP | LAZY_MIRROR
+# ... and those of the legal-move bootstrap
+LAZY_LEGAL = frozenset(("xq_dqn_set_td_bootstrap", "xq_dqn_get_td_bootstrap", "xq_dqn_td_grads_sided", "xq_dqn_td_update_host_sided",
+                        "xq_dqn_last_legal", "xq_replay_track_next_player", "xq_replay_push_host_sided", "xq_replay_get_next_player",
+                        "xq_trainer_set_td_bootstrap"))
+_LAZY_ALL = LAZY | LAZY_GRAD_CLIP | LAZY_TARGET_TAU | LAZY_TD_LOSS | LAZY_N_STEP | LAZY_MIRROR | LAZY_LEGAL
 _RESTYPES = {"xq_last_error": C.c_char_p, "xq_env_boards_dev": C.c_void_p, "xq_env_meta_dev": C.c_void_p}
 
 _lib = None

@@ -24,7 +24,8 @@
 // the one place that touches params_version, the screen's kept rows, the select chain's kept sums and tgt_rest_synced.
 // This file = the handle (struct xq_dqn) + host orchestration + the C ABI; the kernels live in xq_l0.hip.h (layer-0 gathers and
 // segmented sums), xq_tail.hip.h (TD delta, gradient sums, fused launches, SGD), xq_refine.hip.h (screening pass 2), xq_l0grad.hip.h
-// (layer-0 gradient on the matrix pipe), xq_gemm*.hip.h and xq_screen.hip.h (matrix-pipe products).
+// (layer-0 gradient on the matrix pipe), xq_gemm*.hip.h and xq_screen.hip.h (matrix-pipe products), xq_nstep.hip.h and xq_mirror.hip.h
+// (staging of n-step and mirrored batches), xq_legal.hip.h (the legal-move bootstrap, on the rules engine of xq_rules.hip.h).
 #include "xq_internal.h"
 #include <hip/hip_ext.h>
 #include "xq_gemm.hip.h"
@@ -201,6 +202,14 @@ struct xq_dqn {
     // transforms an n-step batch there in place; per row the flag.  mirror_rows: rows of the last TD step if it was a mirror-mode one
     xq::DevBuf<uint8_t> ns_flag;
     int mirror_rows = 0;
+    // legal-move bootstrap (xq_dqn_set_td_bootstrap): the k-slabs of the 96-row head product of s' (the selecting net's, then the target
+    // net's of a Double-DQN step), the pre-activations legal_qmax_kernel leaves of them, the move count per row, the host batch's side
+    // bytes.  legal_rows: rows of the last TD step if it was a legal one, else 0 (xq_dqn_last_legal)
+    int bootstrap = XQ_BOOTSTRAP_ALL;
+    xq::DevBuf<float> z96, z96_slabs;
+    xq::DevBuf<int> legal_nmoves;
+    xq::DevBuf<uint8_t> hside, ns_side;         // side bytes of the host batch / of the staged (n-step, mirror) batch
+    int legal_rows = 0;
     xq::Profiler prof;
     // fused launches of the TD step's tail (td_tail_kernel): while `tail_open`, the launch helpers of the small fp32 GEMMs, the
     // output-layer / layer-0 segmented sums and the bias column sums append their blocks to `tail` instead of launching.  Written by
@@ -288,6 +297,7 @@ struct SmallTiles {
 #include "xq_refine.hip.h"
 #include "xq_nstep.hip.h"
 #include "xq_mirror.hip.h"
+#include "xq_legal.hip.h"
 
 namespace xq {
 
@@ -1547,11 +1557,16 @@ struct PerOpts {
 };
 static int td_grads_impl(xq_dqn* d, const uint32_t* boards, const uint32_t* next_boards, const int32_t* action_to,
                          const float* reward, const uint8_t* done, SlotSrc slots, int n, int td_net, int mode, const PerOpts* per,
-                         const float* discount = nullptr);
+                         const float* discount = nullptr, const uint8_t* next_player = nullptr);
 
 int xq_dqn_td_grads(xq_dqn* d, const uint32_t* boards, const uint32_t* next_boards, const int32_t* action_to,
                     const float* reward, const uint8_t* done, const int32_t* slots, int n, int td_net, int mode) {
     return td_grads_impl(d, boards, next_boards, action_to, reward, done, explicit_slots(slots), n, td_net, mode, nullptr);
+}
+int xq_dqn_td_grads_sided(xq_dqn* d, const uint32_t* boards, const uint32_t* next_boards, const int32_t* action_to,
+                          const float* reward, const uint8_t* done, const uint8_t* next_player, const int32_t* slots, int n, int td_net, int mode) {
+    if (!next_player) return fail(XQ_ERR_INVALID_ARGUMENT, "xq_dqn_td_grads_sided: null next_player");
+    return td_grads_impl(d, boards, next_boards, action_to, reward, done, explicit_slots(slots), n, td_net, mode, nullptr, nullptr, next_player);
 }
 
 // ---- the gradient half of a TD step: one description of each gradient, emitted in two orders -----------------------------------
@@ -1760,6 +1775,7 @@ struct ScreenPlan { bool screened, top2; int parity; ShadowJob shadow; };
 // What the stages of one step share: its inputs, and the shapes and views decided once at its top.
 struct TdStep {
     const int32_t* action_to; const float* reward; const uint8_t* done; SlotSrc slots; const PerOpts* per;
+    const uint32_t* next_boards; const uint8_t* next_player; bool legal;       // the legal-move bootstrap: s', its side to move (by slot)
     float gamma;                 // the discount of this step's target: (float)d->gamma, or gamma^n of an n-step batch
     int n, mode, sel_net, nl, Hl, NO; bool dbl, bf;
     bool big_tiles;              // the max pass's product on 128-row tiles
@@ -1844,7 +1860,7 @@ int Screen::shadow_job(const xq_dqn* d, int sel_net, int parity, hipStream_t s, 
 
 // This step's part of the screen: the eligibility of its shape, the guard, the parity of its slots and the shadow conversion
 int Screen::plan(xq_dqn* d, const TdStep& s, ScreenPlan* P) {
-    const bool want_screen = mode == XQ_QMAX_SCREENED && !s.bf && !s.dbl && s.big_tiles && (s.Hl % 64) == 0 && s.Hl <= 1024 &&
+    const bool want_screen = mode == XQ_QMAX_SCREENED && !s.legal && !s.bf && !s.dbl && s.big_tiles && (s.Hl % 64) == 0 && s.Hl <= 1024 &&
                              s.bias_lds <= 40 * 1024 && (s.NO + 127) / 128 * 4 <= 8 * kRefineMaxPerThread;
     P->screened = false;
     if (want_screen) {
@@ -2016,6 +2032,43 @@ static int qmax_exact(xq_dqn* d, const TdStep& s, bool bf_frag, bool gate_early)
     return XQ_OK;
 }
 
+// Legal-move bootstrap (xq_dqn_set_td_bootstrap): the 96-row head product of s' on the selecting net as k-slabs (q_head's
+// split: four blocks per CU instead of one walking all of K) and legal_qmax_kernel, which sums them, generates the moves of the side to
+// move in s' and leaves in zmax the pre-activation of the env kernel's greedy pick.  Double DQN: the same product on the target net's s'
+// chain as well; the kernel picks on the online values and leaves the target net's value of that output, so td_delta runs its one-net
+// form (its own Double path has no way to give a row without a move y = r).
+static int qmax_legal(xq_dqn* d, const TdStep& s, bool gate_early) {
+    const int n = s.n, nl = s.nl, Hl = s.Hl;
+    const int want = (n >= 2048 && (Hl % 128) == 0) ? std::min(Hl / 64, (int)kLegalMaxSlabs) : 1;
+    const int nets = s.dbl ? 2 : 1;
+    const long long slab_stride = (long long)n * 96;
+    XQ_TRY(d->z96_slabs.reserve((size_t)nets * want * slab_stride));
+    XQ_TRY(d->z96.reserve((size_t)slab_stride));
+    XQ_TRY(d->legal_nmoves.reserve((size_t)n));
+    int used[2] = {want, want};
+    for (int k = 0; k < nets; ++k) {
+        GemmArgs g; memset(&g, 0, sizeof g);
+        g.M = n; g.N = 96; g.K = Hl;
+        g.A = k == 0 ? s.touts[nl - 2] : s.t2outs[nl - 2]; g.lda = Hl;
+        g.B = d->wl(k == 0 ? s.sel_net : XQ_NET_TARGET, nl - 1); g.ldb = Hl;
+        g.C = d->z96_slabs + (size_t)k * want * slab_stride; g.ldc = 96; g.slab_stride = slab_stride;
+        XQ_TRY((launch_gemm<L_KCONTIG, L_KCONTIG, EPI_STORE>(d, g, want, "gemm_legal_head", &used[k], true)));
+    }
+    if (used[0] < 1 || used[0] > want || (s.dbl && used[1] != used[0])) return fail(XQ_ERR_RUNTIME, "legal head: %d k-slabs for %d asked", used[0], want);
+    LegalArgs A; memset(&A, 0, sizeof A);
+    A.next_boards = s.next_boards; A.action_to = s.action_to; A.done = s.done; A.side = s.next_player;
+    A.sel_slabs = d->z96_slabs; A.sel_bias = d->bl(s.sel_net, nl - 1);
+    if (s.dbl) { A.ev_slabs = d->z96_slabs + (size_t)want * slab_stride; A.ev_bias = d->bl(XQ_NET_TARGET, nl - 1); }
+    A.slab_stride = slab_stride; A.nslabs = used[0];
+    A.z96 = d->z96; A.zmax = d->zmax; A.zidx = d->zidx; A.n_moves = d->legal_nmoves;
+    // per row: the board, 6 B of fields, nets x nslabs x 96 slab values in, 96 values and 12 B out
+    ProfScope ps(d, "legal_qmax", 0.0, (double)n * (48 + 6 + 384.0 * nets * used[0] + 384 + 12), true);
+    hipExtLaunchKernelGGL(legal_qmax_kernel, dim3((n + 3) / 4), dim3(256), 0, d->cur, ps.start(), ps.stop(), 0, A, s.slots, n);
+    XQ_HIP(hipGetLastError());
+    if (!d->late_gate && !gate_early) XQ_HIP(hipEventRecord(d->ev_qmax, d->stream));    // (not reached: a legal step gates early)
+    return XQ_OK;
+}
+
 // Q(s, a), target, the scalar output delta and the delta of the last hidden layer (one launch, no GEMM); zparts = maxima per sample in zmax
 static int td_delta(xq_dqn* d, const TdStep& s, int zparts) {
     const int n = s.n, nl = s.nl, Hl = s.Hl;
@@ -2023,7 +2076,7 @@ static int td_delta(xq_dqn* d, const TdStep& s, int zparts) {
     ProfScope ps(d, "td_target_delta", 4.0 * n * Hl, (double)n * (Hl * 16 + s.n_partial * 4));
     TdExtra X; memset(&X, 0, sizeof X);
     X.nout = s.NO;
-    if (s.dbl) {
+    if (s.dbl && !s.legal) {             // (legal bootstrap: zmax already holds the target net's value of the online pick)
         X.double_dqn = 1; X.partial_idx = d->zidx;
         X.bout_t = d->bl(XQ_NET_TARGET, nl - 1);
         if (s.bf) { X.wout_t_bf = d->wl_bf(XQ_NET_TARGET, nl - 1); X.alast_t_bf = s.t2outs_bf[lt]; }
@@ -2082,7 +2135,7 @@ static int td_gradients_fork(xq_dqn* d, const TdStep& s) {
 
 static int td_grads_impl(xq_dqn* d, const uint32_t* boards, const uint32_t* next_boards, const int32_t* action_to,
                          const float* reward, const uint8_t* done, SlotSrc slots, int n, int td_net, int mode, const PerOpts* per,
-                         const float* discount) {
+                         const float* discount, const uint8_t* next_player) {
     if (!d || !boards || !next_boards || !action_to || !reward || !done || n <= 0)
         return fail(XQ_ERR_INVALID_ARGUMENT, "xq_dqn_td_grads: bad argument");
     if (td_net != XQ_TD_ONLINE_NET && td_net != XQ_TD_TARGET_NET && td_net != XQ_TD_DOUBLE) return fail(XQ_ERR_INVALID_ARGUMENT, "bad td_net");
@@ -2090,6 +2143,11 @@ static int td_grads_impl(xq_dqn* d, const uint32_t* boards, const uint32_t* next
     if (d->nout() < 96) return fail(XQ_ERR_INVALID_ARGUMENT, "TD path needs >= 96 outputs (action.to indexes outputs 0..89)");
     if (mode == XQ_BACKPROP_REFERENCE) XQ_TRY(check_reference_topology(d));
     const bool dbl = td_net == XQ_TD_DOUBLE, bf = d->bf16();
+    const bool legal = d->bootstrap == XQ_BOOTSTRAP_LEGAL;
+    if (legal && bf) return fail(XQ_ERR_INVALID_ARGUMENT, "the legal-move bootstrap needs an fp32 net (xq_dqn_set_precision)");
+    if (legal && !next_player)
+        return fail(XQ_ERR_INVALID_ARGUMENT, "the legal-move bootstrap needs the side to move in s': use xq_dqn_td_grads_sided / xq_dqn_td_update_host_sided");
+    d->legal_rows = 0;
     d->l0_split_done = d->l0_sel_done = false;       // (set by this step's launches, consumed by l0_gradient)
     // Data-parallel step with more than one rank: the trainer's select chain (it waits for ev_qmax) starts behind the GRADIENTS
     // instead of behind the max pass, so that it runs beside the all-reduce — the exchange is then hidden behind work the step has to
@@ -2104,6 +2162,7 @@ static int td_grads_impl(xq_dqn* d, const uint32_t* boards, const uint32_t* next
     if (bf && (Hl & 1)) return fail(XQ_ERR_INVALID_ARGUMENT, "bf16 Q-net needs even layer widths");
     TdStep s;
     s.action_to = action_to; s.reward = reward; s.done = done; s.slots = slots; s.per = per;
+    s.next_boards = next_boards; s.next_player = next_player; s.legal = legal;
     s.gamma = discount ? *discount : (float)d->gamma;
     d->nstep_rows = 0;                               // (xq_dqn_td_grads_replay sets it behind an n-step batch)
     d->mirror_rows = 0;                              // (... and this one behind a mirror-mode batch)
@@ -2135,16 +2194,22 @@ static int td_grads_impl(xq_dqn* d, const uint32_t* boards, const uint32_t* next
     // 0.1946-0.1969 ms, here 0.1888-0.1937; behind the layer-0 gather of this step 0.1886-0.1896 against 0.1914-0.1921; at the very top of
     // the step no difference; --config 4 / 5 -0.3 % / -0.9 %.  The product's stop event rather than a marker behind it: 0.1740 -> 0.1728 ms.
     // The full fp32 product keeps the chip to itself: there the chain starts behind it (qmax_exact).
-    const bool gate_early = (screened || bf) && !d->late_gate;
+    // A legal step starts it there too: behind legal_qmax_kernel the chain ran beside the fused gradient launches and the step came out
+    // slower than the screened one (0.169-0.176 against 0.163-0.165 ms through the trainer, profiles/NOTES.md "Legal-move bootstrap").  What
+    // runs behind the early gate reads ring slots (legal_qmax_kernel, td_delta) exactly as the refine kernel with the TD delta inside does:
+    // the trainer's collect writes only slots its windowed draw left out.
+    const bool gate_early = (screened || bf || legal) && !d->late_gate;
     hipEvent_t fork = gate_early ? d->ev_qmax : nullptr;
     XQ_TRY(chain_boards(d, jobs, dbl ? 3 : 2, slots, n, screened ? &s.scr.shadow : nullptr, &fork));
     if (fork) XQ_HIP(hipEventRecord(fork, d->stream));             // chain_boards did not take the stop event: a marker instead
     // 2. max_a' Q(s', a'); 3. the TD delta, unless the refine kernel did it
     bool td_fused = false;
-    if (screened) XQ_TRY(qmax_screened(d, s, &td_fused));
+    if (legal) XQ_TRY(qmax_legal(d, s, gate_early));
+    else if (screened) XQ_TRY(qmax_screened(d, s, &td_fused));
     else XQ_TRY(qmax_exact(d, s, bf_frag, gate_early));
-    if (!td_fused) XQ_TRY(td_delta(d, s, screened ? 1 : kReduceParts));
+    if (!td_fused) XQ_TRY(td_delta(d, s, legal || screened ? 1 : kReduceParts));
     d->last_n = n;
+    if (legal) d->legal_rows = n;
     // 4. the gradients
     if (tail_eligible(d, n)) return tail_gradients(d, n, s.outs, d->grads_td, mode);
     return td_gradients_fork(d, s);
@@ -2433,11 +2498,22 @@ int xq_dqn_grad_buffer(xq_dqn* d, float** grads_dev, size_t* n_floats) {
 // The TD step on the handle's staging batch (what an n-step assembly or a mirror gather filled): identity slot source, the given discount
 // (nullptr: the handle's gamma).  A prioritized draw keeps its importance weights; the step gets no priority table, and
 // per_writeback_kernel behind it writes the live rows' priorities to the sampled slots recorded in ns_first
-static int td_grads_staged(xq_dqn* d, int batch, int td_net, int mode, const PerOpts* per, const float* discount) {
+// Under the legal-move bootstrap the staged rows' side bytes come from the ring's column at row_slot[b] (legal_side_stage_kernel)
+static int td_grads_staged(xq_dqn* d, xq_replay* r, const int32_t* row_slot, int batch, int td_net, int mode, const PerOpts* per,
+                           const float* discount) {
     PerOpts step_per;
     if (per) { step_per = *per; step_per.prio = nullptr; step_per.pmax_live = nullptr; }
+    const uint8_t* side = nullptr;
+    if (d->bootstrap == XQ_BOOTSTRAP_LEGAL) {
+        XQ_TRY(d->ns_side.reserve((size_t)batch));
+        ProfScope ps(d, "legal_side_stage", 0.0, (double)batch * 6.0, true);
+        hipExtLaunchKernelGGL(legal_side_stage_kernel, dim3((batch + 255) / 256), dim3(256), 0, d->cur, ps.start(), ps.stop(), 0,
+                              r->dev.next_player, row_slot, d->ns_side.p, batch, r->dev.capacity);
+        XQ_HIP(hipGetLastError());
+        side = d->ns_side;
+    }
     XQ_TRY(td_grads_impl(d, d->ns_boards, d->ns_next, d->ns_action, d->ns_reward, d->ns_done, explicit_slots(nullptr), batch, td_net, mode,
-                         per ? &step_per : nullptr, discount));
+                         per ? &step_per : nullptr, discount, side));
     if (per) {
         ProfScope ps(d, "per_writeback", 0.0, (double)batch * 20.0, true);
         hipExtLaunchKernelGGL(per_writeback_kernel, dim3((batch + 255) / 256), dim3(256), 0, d->cur, ps.start(), ps.stop(), 0, batch,
@@ -2487,7 +2563,7 @@ static int mirror_stage(xq_dqn* d, xq_replay* r, SlotSrc src, int batch, bool ga
 // prioritized draw's priorities go back to the sampled slots behind the step (the n-step arrangement)
 static int td_grads_mirror(xq_dqn* d, xq_replay* r, SlotSrc src, int batch, int td_net, int mode, const PerOpts* per) {
     XQ_TRY(mirror_stage(d, r, src, batch, true));
-    XQ_TRY(td_grads_staged(d, batch, td_net, mode, per, nullptr));
+    XQ_TRY(td_grads_staged(d, r, d->ns_first, batch, td_net, mode, per, nullptr));
     d->mirror_rows = batch;
     return XQ_OK;
 }
@@ -2526,7 +2602,7 @@ static int td_grads_nstep(xq_dqn* d, xq_replay* r, SlotSrc src, int batch, int t
     }
     const bool mirrored = r->mirror_prob > 0.0;
     if (mirrored) XQ_TRY(mirror_stage(d, r, src, batch, false));
-    XQ_TRY(td_grads_staged(d, batch, td_net, mode, per, &disc_n));
+    XQ_TRY(td_grads_staged(d, r, d->ns_last, batch, td_net, mode, per, &disc_n));
     d->nstep_rows = batch;
     if (mirrored) d->mirror_rows = batch;
     return XQ_OK;
@@ -2584,6 +2660,8 @@ int xq_dqn_td_grads_replay(xq_dqn* d, xq_replay* r, int batch, int td_net, int m
         batch = r->size;       // identity over the filled part of the ring (on-policy use)
     }
     if (batch <= 0) return fail(XQ_ERR_RUNTIME, "replay is empty");
+    if (d->bootstrap == XQ_BOOTSTRAP_LEGAL && !r->dev.next_player)
+        return fail(XQ_ERR_INVALID_ARGUMENT, "the legal-move bootstrap needs the side to move in s': this ring does not track it (xq_replay_track_next_player)");
     PerOpts per; memset(&per, 0, sizeof per);
     const bool prioritized = r->per.enabled && r->per.last_prioritized && !r->implicit && src.slots != nullptr;
     if (prioritized) {        // importance weights in, TD-error priorities out (xq_replay_sample_prioritized drew the slots)
@@ -2597,14 +2675,22 @@ int xq_dqn_td_grads_replay(xq_dqn* d, xq_replay* r, int batch, int td_net, int m
     if (r->n_step > 1) return td_grads_nstep(d, r, src, batch, td_net, mode, prioritized ? &per : nullptr);
     if (r->mirror_prob > 0.0) return td_grads_mirror(d, r, src, batch, td_net, mode, prioritized ? &per : nullptr);
     return td_grads_impl(d, r->dev.boards, r->dev.next_boards, r->dev.action_to, r->dev.reward, r->dev.done, src, batch, td_net,
-                         mode, prioritized ? &per : nullptr);
+                         mode, prioritized ? &per : nullptr, nullptr, r->dev.next_player);
 }
 
-int xq_dqn_td_update_host(xq_dqn* d, int n, const uint8_t* boards90, const uint8_t* next_boards90, const int32_t* action_to,
-                          const float* reward, const uint8_t* done, int td_net, int mode, double lr, double grad_scale,
-                          float* q_sa_out, float* y_out) {
+static int td_update_host_impl(xq_dqn* d, int n, const uint8_t* boards90, const uint8_t* next_boards90, const int32_t* action_to,
+                               const float* reward, const uint8_t* done, const uint8_t* next_player, int td_net, int mode, double lr,
+                               double grad_scale, float* q_sa_out, float* y_out) {
     if (!d || n <= 0 || !boards90 || !next_boards90 || !action_to || !reward || !done)
         return fail(XQ_ERR_INVALID_ARGUMENT, "xq_dqn_td_update_host: bad argument");
+    if (next_player) {
+        for (int i = 0; i < n; ++i) {
+            if (next_player[i] > 1) return fail(XQ_ERR_INVALID_ARGUMENT, "next_player[%d] = %d: 0 (Red) or 1 (Black)", i, (int)next_player[i]);
+            // (move generation ranks a side's pieces into a 16-entry table)
+            if (const char* why = board_fault(next_boards90 + (size_t)i * 90)) return fail(XQ_ERR_INVALID_ARGUMENT, "next board %d: %s", i, why);
+        }
+        XQ_TRY(d->hside.reserve((size_t)n));
+    }
     for (size_t i = 0; i < (size_t)n * 90; ++i)       // code 15 would index one-hot plane 14 of 14 in the layer-0 kernels
         if (boards90[i] > 14 || next_boards90[i] > 14) return fail(XQ_ERR_INVALID_ARGUMENT, "piece code > 14");
     XQ_TRY(d->hb.reserve((size_t)n * 2 * kBoardWords));
@@ -2621,11 +2707,49 @@ int xq_dqn_td_update_host(xq_dqn* d, int n, const uint8_t* boards90, const uint8
     XQ_HIP(hipMemcpy(d->ha, action_to, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice));
     XQ_HIP(hipMemcpy(d->hr, reward, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
     XQ_HIP(hipMemcpy(d->hd, done, (size_t)n, hipMemcpyHostToDevice));
-    XQ_TRY(xq_dqn_td_grads(d, d->hb, d->hb + (size_t)n * kBoardWords, d->ha, d->hr, d->hd, nullptr, n, td_net, mode));
+    if (next_player) XQ_HIP(hipMemcpy(d->hside, next_player, (size_t)n, hipMemcpyHostToDevice));
+    XQ_TRY(td_grads_impl(d, d->hb, d->hb + (size_t)n * kBoardWords, d->ha, d->hr, d->hd, explicit_slots(nullptr), n, td_net, mode, nullptr, nullptr,
+                         next_player ? d->hside.p : nullptr));
     XQ_TRY(xq_dqn_apply_grads(d, lr, grad_scale));
     XQ_HIP(hipStreamSynchronize(d->stream));
     if (q_sa_out) XQ_HIP(hipMemcpy(q_sa_out, d->qsa, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
     if (y_out) XQ_HIP(hipMemcpy(y_out, d->yv, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
+    return XQ_OK;
+}
+int xq_dqn_td_update_host(xq_dqn* d, int n, const uint8_t* boards90, const uint8_t* next_boards90, const int32_t* action_to,
+                          const float* reward, const uint8_t* done, int td_net, int mode, double lr, double grad_scale,
+                          float* q_sa_out, float* y_out) {
+    return td_update_host_impl(d, n, boards90, next_boards90, action_to, reward, done, nullptr, td_net, mode, lr, grad_scale, q_sa_out, y_out);
+}
+int xq_dqn_td_update_host_sided(xq_dqn* d, int n, const uint8_t* boards90, const uint8_t* next_boards90, const int32_t* action_to,
+                                const float* reward, const uint8_t* done, const uint8_t* next_player, int td_net, int mode, double lr,
+                                double grad_scale, float* q_sa_out, float* y_out) {
+    if (!next_player) return fail(XQ_ERR_INVALID_ARGUMENT, "xq_dqn_td_update_host_sided: null next_player");
+    return td_update_host_impl(d, n, boards90, next_boards90, action_to, reward, done, next_player, td_net, mode, lr, grad_scale, q_sa_out, y_out);
+}
+
+int xq_dqn_set_td_bootstrap(xq_dqn* d, int kind) {
+    if (!d) return fail(XQ_ERR_INVALID_ARGUMENT, "null dqn");
+    if (kind != XQ_BOOTSTRAP_ALL && kind != XQ_BOOTSTRAP_LEGAL) return fail(XQ_ERR_INVALID_ARGUMENT, "unknown TD bootstrap %d", kind);
+    if (kind == XQ_BOOTSTRAP_LEGAL && d->nout() < 96) return fail(XQ_ERR_INVALID_ARGUMENT, "the legal-move bootstrap needs >= 96 outputs");
+    d->bootstrap = kind;
+    return XQ_OK;
+}
+int xq_dqn_get_td_bootstrap(const xq_dqn* d, int* kind) {
+    if (!d || !kind) return fail(XQ_ERR_INVALID_ARGUMENT, "null pointer");
+    *kind = d->bootstrap;
+    return XQ_OK;
+}
+int xq_dqn_last_legal(xq_dqn* d, int n, int32_t* n_moves, int32_t* a_star, float* zmax, float* z96) {
+    if (!d) return fail(XQ_ERR_INVALID_ARGUMENT, "null dqn");
+    if (d->legal_rows <= 0) return fail(XQ_ERR_RUNTIME, "xq_dqn_last_legal: the last TD step was not a legal-bootstrap one");
+    if (n < 0 || n > d->legal_rows) return fail(XQ_ERR_INVALID_ARGUMENT, "xq_dqn_last_legal: n exceeds the last TD step's %d rows", d->legal_rows);
+    XQ_HIP(hipStreamSynchronize(d->stream));
+    if (!n) return XQ_OK;
+    if (n_moves) XQ_HIP(hipMemcpy(n_moves, d->legal_nmoves, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (a_star) XQ_HIP(hipMemcpy(a_star, d->zidx, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (zmax) XQ_HIP(hipMemcpy(zmax, d->zmax, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
+    if (z96) XQ_HIP(hipMemcpy(z96, d->z96, (size_t)n * 96 * sizeof(float), hipMemcpyDeviceToHost));
     return XQ_OK;
 }
 

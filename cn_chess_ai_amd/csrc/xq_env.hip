@@ -344,6 +344,7 @@ __global__ __launch_bounds__(256) void env_kernel(EnvParams P) {
             P.rp.action_to[slot] = have_action ? to : -1;
             P.rp.reward[slot] = (float)reward;
             P.rp.done[slot] = done ? 1 : 0;
+            if (P.rp.next_player != nullptr) P.rp.next_player[slot] = (uint8_t)(1 - mover);       // the side to move in s'
             // prioritized replay: a new transition enters with the largest priority assigned so far (an empty one never gets sampled)
             if (P.rp.prio != nullptr) P.rp.prio[slot] = have_action ? __uint_as_float(*P.rp.pmax_snap) : 0.f;
         }
@@ -368,6 +369,7 @@ __global__ __launch_bounds__(256) void env_kernel(EnvParams P) {
             if (s2_now) {
                 P.rp.reward[slot] = ph == 0 ? 0.f : (float)reward;
                 P.rp.done[slot] = ph == 0 || done ? 1 : 0;
+                if (P.rp.next_player != nullptr) P.rp.next_player[slot] = (uint8_t)vs_learner;    // s' is the learner's to move
                 if (P.rp.prio != nullptr) P.rp.prio[slot] = learner_moved ? __uint_as_float(*P.rp.pmax_snap) : 0.f;
             }
         }

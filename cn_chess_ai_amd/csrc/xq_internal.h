@@ -186,6 +186,7 @@ struct ReplayDev {
     int32_t* action_to = nullptr;     // [capacity]   action.to (0..89), -1 = empty slot (contributes no gradient)
     float* reward = nullptr;          // [capacity]
     uint8_t* done = nullptr;          // [capacity]
+    uint8_t* next_player = nullptr;   // [capacity]   side to move in next_boards (0 Red, 1 Black); nullptr until xq_replay_track_next_player
     int capacity = 0;
     // prioritized replay (xq_replay_enable_per; nullptr = uniform): priority of every slot = leaves of the sum tree, and the
     // largest priority assigned so far as it stood at the last rebuild (what a new transition enters with), as float bits
@@ -198,7 +199,7 @@ struct xq_replay {
     xq::DevBuf<uint32_t> boards, next_boards;     // what `dev` points into
     xq::DevBuf<int32_t> action_to;
     xq::DevBuf<float> reward, prio;
-    xq::DevBuf<uint8_t> done;
+    xq::DevBuf<uint8_t> done, next_player;
     int size = 0;
     int write_pos = 0;
     uint64_t total = 0;

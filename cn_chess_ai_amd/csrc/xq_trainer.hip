@@ -243,6 +243,15 @@ int xq_trainer_set_target_tau(xq_trainer* t, double tau) {
 }
 
 // mirror augmentation lives on the ring and changes no window: the transform reads what the step read anyway
+// The legal-move bootstrap on the trainer's Q-net; `legal` first makes the trainer's ring record the side to move in s' (possible only
+// while the ring is empty: XQ_ERR_RUNTIME once it holds a transition, unless it tracks already).  Back to `all` the column stays written.
+int xq_trainer_set_td_bootstrap(xq_trainer* t, int kind) {
+    if (!t) return fail(XQ_ERR_INVALID_ARGUMENT, "null trainer");
+    if (t->grads_queued) return fail(XQ_ERR_RUNTIME, "xq_trainer_set_td_bootstrap: call between iterations (after learn_apply)");
+    if (kind == XQ_BOOTSTRAP_LEGAL) XQ_TRY(xq_replay_track_next_player(t->replay));
+    return xq_dqn_set_td_bootstrap(t->dqn, kind);
+}
+
 int xq_trainer_set_mirror(xq_trainer* t, double prob) {
     if (!t) return fail(XQ_ERR_INVALID_ARGUMENT, "null trainer");
     if (t->grads_queued) return fail(XQ_ERR_RUNTIME, "xq_trainer_set_mirror: call between iterations (after learn_apply)");

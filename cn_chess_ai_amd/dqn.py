@@ -125,7 +125,9 @@ class DQN:
 
     # ---- batched device-side TD step on packed boards ----
     def td_update(self, boards, next_boards, action_to, reward, done, td_net=_capi.TD_ONLINE_NET,
-                  mode=_capi.BACKPROP_REFERENCE, learning_rate=None, grad_scale=1.0):
+                  mode=_capi.BACKPROP_REFERENCE, learning_rate=None, grad_scale=1.0, next_player=None):
+        """One TD update on host transitions; returns (Q(s,a), y).  next_player: the side to move in each next board (0 = Red,
+        1 = Black) — what set_td_bootstrap("legal") needs; without it the unsided entry point is called."""
         b = np.ascontiguousarray(boards, dtype=np.uint8).reshape(-1, 90)
         nb = np.ascontiguousarray(next_boards, dtype=np.uint8).reshape(-1, 90)
         n = len(b)
@@ -134,6 +136,12 @@ class DQN:
         d = np.ascontiguousarray(done, dtype=np.uint8).reshape(n)
         qsa, y = np.zeros(n, np.float32), np.zeros(n, np.float32)
         lr = self.learning_rate if learning_rate is None else learning_rate
+        if next_player is not None:
+            p = np.ascontiguousarray(next_player, dtype=np.uint8).reshape(n)
+            call("xq_dqn_td_update_host_sided", self._h, n, _ptr(b, C.c_uint8), _ptr(nb, C.c_uint8), _ptr(a, C.c_int32),
+                 _ptr(r, C.c_float), _ptr(d, C.c_uint8), _ptr(p, C.c_uint8), int(td_net), int(mode), float(lr), float(grad_scale),
+                 _ptr(qsa, C.c_float), _ptr(y, C.c_float))
+            return qsa, y
         call("xq_dqn_td_update_host", self._h, n, _ptr(b, C.c_uint8), _ptr(nb, C.c_uint8), _ptr(a, C.c_int32),
              _ptr(r, C.c_float), _ptr(d, C.c_uint8), int(td_net), int(mode), float(lr), float(grad_scale),
              _ptr(qsa, C.c_float), _ptr(y, C.c_float))
@@ -444,6 +452,47 @@ DQN.td_loss = _td_loss
 DQN.td_error_stats = _td_error_stats
 
 
+_BOOTSTRAPS = {"all": _capi.BOOTSTRAP_ALL, "legal": _capi.BOOTSTRAP_LEGAL}
+
+
+def _set_td_bootstrap(self, kind="all"):
+    """What the TD target bootstraps from: "all" (default) = the maximum over all outputs of the net, "legal" = the maximum over the
+    moves the side to move can play in s' (the move the epsilon = 0 policy would play there; y = r where it has none).  "legal" needs
+    the side to move per transition — td_update(..., next_player=...) — and an fp32 net; the unsided entry points and td_grads_replay from a ring without
+    ReplayBuffer.track_next_player() raise XqError while it is in force (Trainer.set_td_bootstrap sets both up)."""
+    if kind not in _BOOTSTRAPS:
+        raise ValueError(f"set_td_bootstrap: expected 'all' or 'legal', got {kind!r}")
+    call("xq_dqn_set_td_bootstrap", self._h, _BOOTSTRAPS[kind])
+
+
+def _td_bootstrap(self):
+    """"all" or "legal": the bootstrap in force."""
+    k = C.c_int32()
+    call("xq_dqn_get_td_bootstrap", self._h, C.byref(k))
+    return {v: n for n, v in _BOOTSTRAPS.items()}[k.value]
+
+
+def _last_legal(self, n, z96=True):
+    """The first n rows of the last TD step if it ran under set_td_bootstrap("legal"): dict of n_moves (length of the row's move list;
+    -1 on done and dead rows), a_star (the winning `to`, -1 without a winner), zmax (the pre-activation the target took, 0 where y = r)
+    and z96 ([n, 96] pre-activations of the selecting net; omitted with z96=False).  Raises XqError when the last TD step was not a
+    legal one."""
+    nm, a = np.zeros(n, np.int32), np.zeros(n, np.int32)
+    zm = np.zeros(n, np.float32)
+    z = np.zeros((n, 96), np.float32) if z96 else None
+    call("xq_dqn_last_legal", self._h, int(n), _ptr(nm, C.c_int32), _ptr(a, C.c_int32), _ptr(zm, C.c_float),
+         _ptr(z, C.c_float) if z96 else None)
+    out = dict(n_moves=nm, a_star=a, zmax=zm)
+    if z96:
+        out["z96"] = z
+    return out
+
+
+DQN.set_td_bootstrap = _set_td_bootstrap
+DQN.td_bootstrap = _td_bootstrap
+DQN.last_legal = _last_legal
+
+
 def _checked_tau(who, tau):
     tau = float(tau)
     if not 0.0 <= tau <= 1.0:
@@ -554,6 +603,13 @@ class Trainer:
         """Mirror augmentation of every learn_grads from the trainer's ring (ReplayBuffer.set_mirror; 0 = off): each minibatch row is
         reflected left-right with probability prob.  Uniform, prioritized and on-policy, any n_step.  Call between iterations."""
         call("xq_trainer_set_mirror", self._h, float(prob))
+
+    def set_td_bootstrap(self, kind):
+        """DQN.set_td_bootstrap on the trainer's net; "legal" first makes the trainer's ring record the side to move in s', so call it
+        before the first collect (XqError once the ring holds a transition).  Back to "all" between iterations."""
+        if kind not in _BOOTSTRAPS:
+            raise ValueError(f"set_td_bootstrap: expected 'all' or 'legal', got {kind!r}")
+        call("xq_trainer_set_td_bootstrap", self._h, _BOOTSTRAPS[kind])
 
     def set_opponent(self, opponent):
         """Train against a fixed opponent from the next collect on (DESIGN.md §4 "Versus training"): None = self-play (the default),

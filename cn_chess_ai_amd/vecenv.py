@@ -79,13 +79,30 @@ class ReplayBuffer:
     def __len__(self):
         return self.stats()[0]
 
-    def push(self, boards, action_to, reward, done, next_boards):
+    def track_next_player(self):
+        """Make the ring record the side to move in every stored next board (what DQN.set_td_bootstrap("legal") reads).  While the
+        ring is empty; afterwards push() needs next_player."""
+        call("xq_replay_track_next_player", self._h)
+
+    def next_player(self, first=0, n=None):
+        """the side bytes of slots [first, first + n) of a tracking ring (0 = Red, 1 = Black)"""
+        n = self.stats()[1] - first if n is None else n
+        out = np.zeros(n, dtype=np.uint8)
+        call("xq_replay_get_next_player", self._h, int(first), int(n), _ptr(out, C.c_uint8))
+        return out
+
+    def push(self, boards, action_to, reward, done, next_boards, next_player=None):
         boards = np.ascontiguousarray(boards, dtype=np.uint8).reshape(-1, 90)
         next_boards = np.ascontiguousarray(next_boards, dtype=np.uint8).reshape(-1, 90)
         n = len(boards)
         a = np.ascontiguousarray(action_to, dtype=np.int32).reshape(n)
         r = np.ascontiguousarray(reward, dtype=np.float32).reshape(n)
         d = np.ascontiguousarray(done, dtype=np.uint8).reshape(n)
+        if next_player is not None:
+            p = np.ascontiguousarray(next_player, dtype=np.uint8).reshape(n)
+            call("xq_replay_push_host_sided", self._h, n, _ptr(boards, C.c_uint8), _ptr(a, C.c_int32), _ptr(r, C.c_float),
+                 _ptr(d, C.c_uint8), _ptr(next_boards, C.c_uint8), _ptr(p, C.c_uint8))
+            return
         call("xq_replay_push_host", self._h, n, _ptr(boards, C.c_uint8), _ptr(a, C.c_int32), _ptr(r, C.c_float),
              _ptr(d, C.c_uint8), _ptr(next_boards, C.c_uint8))
 

@@ -38,6 +38,9 @@ ROCPROF_NAMES = {
     "nstep_assemble": "nstep_assemble_kernel(",
     "per_writeback": "per_writeback_kernel(",
     "mirror_stage": "mirror_stage_kernel(",
+    "legal_qmax": "legal_qmax_kernel(",
+    "legal_side_stage": "legal_side_stage_kernel(",
+    "gemm_legal_head": "gemm_f32_kernel<0, 0, 0, 1, 1, 0>(",
 }
 # td_tail_kernel<KINDS, L0MFMA>: KINDS = TAIL_DELTA 1 | TAIL_GRAD 2 | TAIL_OUT 4 | TAIL_COLSUM 8 | TAIL_L0 16 | TAIL_SEL 32 (xq_tail.hip.h)
 TAIL_DELTAS, TAIL_DELTAS_SEL, TAIL_L0 = 7, 39, 30
@@ -121,7 +124,7 @@ def pick_splits(M, N, K):
 
 def step_work(layers, minibatch, n_games, plies=1, bf16=False, bf16_bwd=False, td="online", screened=True, derive=True,
               prioritized=False, l0_mfma=True, optimizer="sgd", grad_clip=False, soft_target=False, n_step=1,
-              mirror=False):
+              mirror=False, bootstrap="all"):
     """{bracket name: dict(flops, hbm_bytes, bound, peak, peak_unit, what)} for one training step of the given configuration.
     optimizer="adam" (xq_dqn_set_optimizer): adam_apply stands in place of sgd_apply; the default step knows no adam_apply.
     grad_clip=True (xq_dqn_set_grad_clip): grad_norm stands in front of the apply and takes the slab sums over from it; the default
@@ -131,7 +134,16 @@ def step_work(layers, minibatch, n_games, plies=1, bf16=False, bf16_bwd=False, t
     n_step > 1 (xq_replay_set_n_step): nstep_assemble stands in front of the step and, on a prioritized draw, per_writeback behind it;
     the default step knows neither.
     mirror=True (xq_replay_set_mirror with prob > 0): mirror_stage stands in front of the step (behind nstep_assemble when n_step > 1)
-    and, on a prioritized draw with n_step == 1, per_writeback behind it; the default step knows no mirror_stage."""
+    and, on a prioritized draw with n_step == 1, per_writeback behind it; the default step knows no mirror_stage.
+    bootstrap="legal" (xq_dqn_set_td_bootstrap, fp32 nets): gemm_legal_head and legal_qmax stand in place of the max pass over the 8100
+    outputs (never screened), td_target_delta behind them, and legal_side_stage in front of a staged (n-step, mirror) batch; the default
+    step knows none of them."""
+    if bootstrap not in ("all", "legal"):
+        raise ValueError("bootstrap: 'all' or 'legal'")
+    legal = bootstrap == "legal"
+    if legal and bf16:
+        raise ValueError("bootstrap='legal' needs an fp32 net")
+    screened = screened and not legal
     h = list(layers[1:-1])
     H1, Hl, k = h[0], h[-1], len(h)
     B, n = minibatch, n_games
@@ -169,7 +181,17 @@ def step_work(layers, minibatch, n_games, plies=1, bf16=False, bf16_bwd=False, t
         put("gemm_hidden_fwd", fl / (k - 1), by / (k - 1), "mfma",
             "hidden products of the %d forward chains grouped in one launch per layer, bias + tanh epilogue" % chains)
     G = 2 * ((NO + 63) // 64)
-    if screened:
+    if legal:
+        # the 96-row head of s' as k-slabs (q_head's split), once per net a Double-DQN step asks (online selects, target evaluates);
+        # per row of legal_qmax: the board and 6 B of fields, the slabs of both heads, the 96 pre-activations and 12 B out
+        nets = 2 if dbl else 1
+        nslabs = min(Hl // 64, 8) if B >= 2048 and Hl % 128 == 0 else 1
+        put("gemm_legal_head", 2.0 * B * 96 * Hl, B * Hl * 4 + 96 * Hl * 4 + nslabs * B * 96 * 4, "mfma",
+            "pre-activations of outputs 0..95 for s' as k-slabs, per launch (%d per step)" % nets)
+        put("legal_qmax", 0.0, B * (48 + 6 + 384.0 * nets * nslabs + 384 + 12), "hbm",
+            "move generation for the side to move in s' and the greedy pick over z[to] of its moves: the legal-move bootstrap")
+        put("td_target_delta", 4.0 * B * Hl, 2 * B * Hl * 4 + 32 * B, "hbm", "Q(s,a), y, output delta, top hidden delta")
+    elif screened:
         put("gemm_qmax_screen", 2.0 * NO * B * Hl, NO * Hl * 2 + B * Hl * 2 + 2 * G * B * 4 + 16 * B * 4 + B * 4, "mfma",
             "exact screen of max_a' Q(s'): all 8100 outputs once on bf16 MFMA, top-2 per 32-output group", PEAK_BF16_MFMA_TFLOPS)
         td_in_refine = Hl == 256 and not prioritized and not bf16_bwd
@@ -310,6 +332,9 @@ def step_work(layers, minibatch, n_games, plies=1, bf16=False, bf16_bwd=False, t
             "left-right reflection of the flagged minibatch rows in the staging batch the TD step reads")
         if prioritized and n_step == 1:
             put("per_writeback", 0.0, 20.0 * B, "hbm", "TD-error priorities of a prioritized mirrored draw back to the sampled slots")
+    if legal and (n_step > 1 or mirror):
+        # per staged row: the slot whose side it takes (4 B), the ring's byte, the staged byte
+        put("legal_side_stage", 0.0, 6.0 * B, "hbm", "side to move in s' of every staged row, from the ring's column (legal-move bootstrap)")
     nw =STATE * H1 + sum(h[l] * h[l - 1] for l in range(1, k)) + Hl * NO
     nb = sum(h) + NO
     put("target_sync_copy", 0.0, 8.0 * (nw + nb), "hbm", "updateTargetNetwork(): device copy of all parameters")

@@ -16,6 +16,8 @@
 //   clip=<max_norm>               clip the batched loop's gradient by its global L2 norm (xq::ChessAI::setGradClip; inf = measure only)
 //   mirror=<prob>                 mirror augmentation of the batched loop's minibatches: each row reflected left-right with probability
 //                                 prob in [0, 1] (xq::ChessAI::setMirror; 0 = off)
+//   bootstrap=all|legal           target of the batched loop's TD step: the maximum over all outputs (default, chessai.cpp:126) or over the
+//                                 moves the side to move can play in s' (xq::ChessAI::setTdBootstrap)
 //   --json                        one JSON line with the loop's counters (bench.py's `facade` leg reads it)
 #include <chrono>
 #include <cstdio>
@@ -29,7 +31,7 @@ int main(int argc, char** argv) {
     int episodes = 1000, parallel = 8192, replay = 0, minibatch = 0, save_every = 100, prefill = 0, npos = 0;
     const char* file = "model.bin";
     std::vector<int> hidden;
-    bool derive = false, json = false, adam = false;
+    bool derive = false, json = false, adam = false, legal = false;
     unsigned long long seed = 0;
     double clip = 0.0, mirror = 0.0;
     for (int i = 1; i < argc; ++i) {
@@ -47,6 +49,11 @@ int main(int argc, char** argv) {
             char* end = nullptr;
             clip = std::strtod(a.c_str() + 5, &end);
             if (end == a.c_str() + 5 || *end || !(clip >= 0.0)) { std::fprintf(stderr, "clip=: expected a max_norm >= 0 or inf, got %s\n", a.c_str() + 5); return 2; }
+        }
+        else if (a.rfind("bootstrap=", 0) == 0) {
+            const std::string v = a.substr(10);
+            if (v != "all" && v != "legal") { std::fprintf(stderr, "bootstrap=: expected all or legal, got %s\n", v.c_str()); return 2; }
+            legal = v == "legal";
         }
         else if (a.rfind("mirror=", 0) == 0) {
             char* end = nullptr;
@@ -73,6 +80,7 @@ int main(int argc, char** argv) {
         if (adam) ai.setOptimizer(xq::Optimizer::adam());
         if (clip != 0.0) ai.setGradClip(clip);
         if (mirror != 0.0) ai.setMirror(mirror);
+        if (legal) ai.setTdBootstrap(xq::TdBootstrap::legal());
         if (replay > 0) ai.setReplay(replay, minibatch);
         ai.setSaveInterval(save_every);
         ai.setLayer0Derive(derive);

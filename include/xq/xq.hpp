@@ -213,6 +213,18 @@ struct TdLoss {
     }
 };
 
+// What the batched TD step's target bootstraps from (xq_dqn_set_td_bootstrap; no upstream analogue): all() is the reference's maximum over
+// every output (chessai.cpp:126), legal() the maximum over the moves the side to move can play in s' (fp32 nets; the step then needs the
+// side to move per transition: xq_dqn_td_grads_sided / xq_dqn_td_update_host_sided, or a ring that tracks it — ChessAI::setTdBootstrap).
+struct TdBootstrap {
+    int kind = XQ_BOOTSTRAP_ALL;
+    static TdBootstrap all() { return TdBootstrap(); }
+    static TdBootstrap legal() {
+        TdBootstrap b; b.kind = XQ_BOOTSTRAP_LEGAL;
+        return b;
+    }
+};
+
 // ---- DQN, dqn.h:97-116 ----------------------------------------------------------------------------------------------
 class DQN {
 public:
@@ -316,6 +328,13 @@ public:
         TdLoss l;
         check(xq_dqn_get_td_loss(h_, &l.kind, &l.kappa));
         return l;
+    }
+    // target of the batched TD step (xq_dqn_set_td_bootstrap): TdBootstrap::all() (default) or TdBootstrap::legal()
+    void setTdBootstrap(const TdBootstrap& b) { check(xq_dqn_set_td_bootstrap(h_, b.kind)); }
+    TdBootstrap tdBootstrap() const {
+        TdBootstrap b;
+        check(xq_dqn_get_td_bootstrap(h_, &b.kind));
+        return b;
     }
     // TD errors e = Q(s,a) - y of the last batched TD step's live samples: linear = those with |e| > kappa (0 under the squared loss)
     struct TdErrorStats { uint64_t live = 0; double meanAbs = 0.0, maxAbs = 0.0, meanLoss = 0.0; uint64_t linear = 0; };
@@ -756,6 +775,9 @@ public:
         mirror_ = prob;
     }
     double mirror() const { return mirror_; }
+    // Target of the batched train(), carried onto the trainer's network like the loss: TdBootstrap::legal() makes the trainer's ring
+    // record the side to move in s' (xq_trainer_set_td_bootstrap, before the first collect).  fp32 nets; the sequential loop is unaffected.
+    void setTdBootstrap(const TdBootstrap& b) { initializeDQN(); dqn->setTdBootstrap(b); }
     DQN* network() { return dqn.get(); }
     std::vector<double> getStateRepresentation() {                           // chessai.cpp:268-289 (encoding only)
         std::vector<double> s(90 * 14, 0.0);
@@ -795,6 +817,7 @@ private:
         struct Guard { xq_trainer* t; ~Guard() { xq_trainer_destroy(t); } } guard{t};   // released on every path, also when check() throws
         xq_dqn* td = nullptr; xq_env* te = nullptr;
         check(xq_trainer_dqn(t, &td)); check(xq_trainer_env(t, &te));
+        if (dqn->tdBootstrap().kind != XQ_BOOTSTRAP_ALL) check(xq_trainer_set_td_bootstrap(t, dqn->tdBootstrap().kind));   // (the ring is empty)
         std::vector<double> w, b;
         dqn->getParameters(w, b);                // continue from this agent's weights
         check(xq_dqn_set_params(td, XQ_NET_ONLINE, w.data(), b.data()));

@@ -573,6 +573,57 @@ int xq_dqn_last_n_step(xq_dqn* d, int n, float* reward, uint8_t* done, int32_t* 
  * slot.  All outputs are host pointers, any of which may be NULL.  XQ_ERR_RUNTIME when the last TD step was not a mirror-mode one,
  * XQ_ERR_INVALID_ARGUMENT for n beyond its rows. */
 int xq_dqn_last_mirror(xq_dqn* d, int n, uint8_t* flags, uint8_t* boards90, uint8_t* next_boards90, int32_t* action_to, int32_t* slot);
+/* What the TD target bootstraps from (no upstream analogue: chessai.cpp:126 takes the maximum over all outputs).  XQ_BOOTSTRAP_ALL
+ * (default): y = done ? r : r + gamma * max_k Q_net(s')[k] over ALL outputs — the kernels, launches and bits of a handle that was never
+ * asked.  XQ_BOOTSTRAP_LEGAL: the maximum over the moves that can be played in s',
+ *   y = done ? r : r + gamma * tanh(max over k of z(s')[to_k])
+ * where (from_k, to_k) runs over getAllValidActions(s', side) in the canonical order (at most XQ_MAX_MOVES: a longer list is its first
+ * 128), z is the output layer's pre-activation on the selecting net and the winner is chosen as everywhere (first maximum in list order,
+ * a NaN never wins, nothing wins: entry 0 of the list) — the move xq_env_selfplay_step plays on the same values at epsilon 0.  A row whose
+ * side has no move in s' takes y = r.  XQ_TD_ONLINE_NET / XQ_TD_TARGET_NET select and evaluate on one net; XQ_TD_DOUBLE selects on the
+ * online net and takes the target net's pre-activation of the selected output.  The step then runs one 96-row product and one kernel
+ * (legal_qmax_kernel: move generation, one wavefront per row) in place of the 8100-row maximum; xq_dqn_set_qmax_mode has no effect on
+ * it (a legal step is never screened: the counters and the guard stand still), everything behind the target — loss, importance weights,
+ * priorities, gradients, optimizers — is unchanged.
+ * The side to move in s' cannot be recovered from (s, a, s') and is an input: xq_dqn_td_grads_sided / xq_dqn_td_update_host_sided take
+ * it per transition (0 = Red, 1 = Black), and a replay ring records it once xq_replay_track_next_player was called: xq_dqn_td_grads_replay
+ * then reads the ring's column — the sampled slot's byte; for an n-step batch the byte of the slot whose next board was staged; for a
+ * mirrored batch the sampled slot's (a reflection does not change the side); one small gather (legal_side_stage_kernel) stages them.
+ * While XQ_BOOTSTRAP_LEGAL is in force the step is XQ_ERR_INVALID_ARGUMENT through every entry that has no side — xq_dqn_td_grads,
+ * xq_dqn_td_update_host, xq_dqn_td_grads_replay from a ring that does not track it — and on a bf16 precision (fp32 nets only).  An unknown kind, or XQ_BOOTSTRAP_LEGAL on a net with fewer than 96 outputs, is
+ * XQ_ERR_INVALID_ARGUMENT.  The setting may change between any two steps and survives every other setter. */
+enum { XQ_BOOTSTRAP_ALL = 0, XQ_BOOTSTRAP_LEGAL = 1 };
+int xq_dqn_set_td_bootstrap(xq_dqn* d, int kind);
+int xq_dqn_get_td_bootstrap(const xq_dqn* d, int* kind);
+/* xq_dqn_td_grads with the side to move in each next board: next_player_dev is [rows] u8 (0 = Red, 1 = Black; not validated on the
+ * device, where any non-zero byte is taken as Black), read through
+ * slots_dev like done_dev.  Under XQ_BOOTSTRAP_ALL the side bytes are not read and the step is xq_dqn_td_grads.  Boards must satisfy
+ * what xq_env_set_state asks (piece codes <= 14, at most 16 pieces of one colour). */
+int xq_dqn_td_grads_sided(xq_dqn* d, const uint32_t* boards_dev, const uint32_t* next_boards_dev, const int32_t* action_to_dev,
+                          const float* reward_dev, const uint8_t* done_dev, const uint8_t* next_player_dev, const int32_t* slots_dev,
+                          int n, int td_net, int mode);
+/* xq_dqn_td_update_host with next_player[n] (0 or 1; anything else, or a next board with more than 16 pieces of one colour, is
+ * XQ_ERR_INVALID_ARGUMENT). */
+int xq_dqn_td_update_host_sided(xq_dqn* d, int n, const uint8_t* boards90, const uint8_t* next_boards90, const int32_t* action_to,
+                                const float* reward, const uint8_t* done, const uint8_t* next_player, int td_net, int mode,
+                                double learning_rate, double grad_scale, float* q_sa_out, float* y_out);
+/* The first n rows of the last TD step if it ran under XQ_BOOTSTRAP_LEGAL (tests / interop; synchronises): the length of the row's move
+ * list (0: no move; -1: a done row or a dead one, action < 0, for which no list was generated), the winning `to` (-1 where there is no
+ * winner), the pre-activation the target took (0 where y = r) and, optionally, the selecting net's 96 pre-activations per row, [n][96].
+ * All outputs are host pointers, any of which may be NULL.  XQ_ERR_RUNTIME when the last TD step was not a legal one,
+ * XQ_ERR_INVALID_ARGUMENT for n beyond its rows. */
+int xq_dqn_last_legal(xq_dqn* d, int n, int32_t* n_moves, int32_t* a_star, float* zmax, float* z96);
+/* The ring's side-to-move column (for XQ_BOOTSTRAP_LEGAL): one byte per slot, the side to move in the stored next board.  The column is
+ * allocated by xq_replay_track_next_player, which must come while the ring is empty (XQ_ERR_RUNTIME otherwise; a second call is a
+ * no-op); a ring that never tracked is the ring of before, array for array.  On a tracking ring every transition written by
+ * xq_env_selfplay_step carries 1 - mover, every one written by versus training the learner's colour; xq_replay_push_host is
+ * XQ_ERR_INVALID_ARGUMENT and xq_replay_push_host_sided pushes with next_player[n] (0 or 1).  xq_replay_get_next_player copies slots
+ * [first, first + n) to the host (tests; synchronises; XQ_ERR_RUNTIME on a ring that does not track).  The column belongs to
+ * XQ_ORDER_RING_CONTENTS. */
+int xq_replay_track_next_player(xq_replay* r);
+int xq_replay_push_host_sided(xq_replay* r, int n, const uint8_t* boards90, const int32_t* action_to, const float* reward,
+                              const uint8_t* done, const uint8_t* next_boards90, const uint8_t* next_player);
+int xq_replay_get_next_player(xq_replay* r, int first, int n, uint8_t* out);
 /* Per-kernel HIP-event timing on the handle stream, for bench.py (name -> summed ms, launches, algorithmic flops/bytes).
  * enable: -1 leave, 0 off, 1 on, 2 on + clear, 3 on + clear but bracket only the TD step's dominant GEMM (gemm_qmax_rowmax /
  * gemm_qmax_screen) and env_selfplay_step, 4 = 3 with the GEMM bracketed on every 4th launch only (a pair of event records
@@ -773,6 +824,11 @@ int xq_trainer_set_n_step(xq_trainer* t, int n_step);
  * any n_step.  No window changes: the transform reads only what the step read anyway.  Call between iterations: XQ_ERR_RUNTIME while a
  * learn_grads waits for its learn_apply. */
 int xq_trainer_set_mirror(xq_trainer* t, double prob);
+/* xq_dqn_set_td_bootstrap on the trainer's Q-net.  XQ_BOOTSTRAP_LEGAL first turns tracking on for the trainer's ring, so call it before
+ * the first collect: XQ_ERR_RUNTIME once the ring holds a transition (unless it tracks already).  Back to XQ_BOOTSTRAP_ALL is allowed
+ * between iterations (XQ_ERR_RUNTIME while a learn_grads waits for its learn_apply); the column keeps being written.  Uniform,
+ * prioritized and on-policy rings, overlap_collect 0 and 1, self-play and versus. */
+int xq_trainer_set_td_bootstrap(xq_trainer* t, int kind);
 /* Versus training (DESIGN.md §4 "Versus training"): from the next collect on, the learner plays against a fixed opponent instead of
  * itself — uniform-random play, the material search (depth 1..3, eps) or a borrowed network (eps; layer_sizes[0] == 1260, >= 90
  * outputs, not the trainer's own).  The learner plays Black in game g iff (first_game_id + g) & 1.  A collect still writes one
