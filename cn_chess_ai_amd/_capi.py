@@ -22,6 +22,7 @@ QMAX_FULL, QMAX_SCREENED = 0, 1
 OPT_SGD, OPT_ADAM = 0, 1
 LOSS_SQUARED, LOSS_HUBER = 0, 1
 BOOTSTRAP_ALL, BOOTSTRAP_LEGAL = 0, 1
+REWARD_EVALUATE, REWARD_DELTA = 0, 1
 MAX_N_STEP = 8
 ORDER_RING_CONTENTS, ORDER_RING_PRIORITIES, ORDER_RING_DRAW, ORDER_TRAINER_PARAMS, ORDER_ALL = 1, 2, 4, 8, 15
 
@@ -189,6 +190,9 @@ PROTOTYPES = {
     "xq_replay_push_host_sided": [_vp, _i, _pu8, _pi, _pf, _pu8, _pu8, _pu8],
     "xq_replay_get_next_player": [_vp, _i, _i, _pu8],
     "xq_trainer_set_td_bootstrap": [_vp, _i],
+    "xq_env_set_reward": [_vp, _i, _d, _d, _d],
+    "xq_env_get_reward": [_vp, _pi, _pd, _pd, _pd],
+    "xq_trainer_set_reward": [_vp, _i, _d, _d, _d],
     "xq_dqn_kernel_stats": [_vp, _i, C.POINTER(KernelStat), _i, _pi],
     "xq_dqn_set_fused_apply": [_vp, _i],
     "xq_dqn_set_optimizer": [_vp, _i, _d, _d, _d],
@@ -265,7 +269,9 @@ LAZY_MIRROR = frozenset(("xq_replay_set_mirror", "xq_replay_get_mirror", "xq_dqn
 LAZY_LEGAL = frozenset(("xq_dqn_set_td_bootstrap", "xq_dqn_get_td_bootstrap", "xq_dqn_td_grads_sided", "xq_dqn_td_update_host_sided",
                         "xq_dqn_last_legal", "xq_replay_track_next_player", "xq_replay_push_host_sided", "xq_replay_get_next_player",
                         "xq_trainer_set_td_bootstrap"))
-_LAZY_ALL = LAZY | LAZY_GRAD_CLIP | LAZY_TARGET_TAU | LAZY_TD_LOSS | LAZY_N_STEP | LAZY_MIRROR | LAZY_LEGAL
+# ... and those of the reward rule
+LAZY_REWARD = frozenset(("xq_env_set_reward", "xq_env_get_reward", "xq_trainer_set_reward"))
+_LAZY_ALL = LAZY | LAZY_GRAD_CLIP | LAZY_TARGET_TAU | LAZY_TD_LOSS | LAZY_N_STEP | LAZY_MIRROR | LAZY_LEGAL | LAZY_REWARD
 _RESTYPES = {"xq_last_error": C.c_char_p, "xq_env_boards_dev": C.c_void_p, "xq_env_meta_dev": C.c_void_p}
 
 _lib = None

@@ -60,6 +60,10 @@ struct EnvParams {
     int vs_phase;
     const int16_t* vs_pick;
     uint4* vs_counts;
+    // the reward the ring gets (xq_env_set_reward, DESIGN.md §4 "Reward rule"): XQ_REWARD_EVALUATE = evaluateBoard as the reference, or
+    // XQ_REWARD_DELTA = delta_reward() of the transition's change of material balance; xq_step_result.reward is evaluateBoard always
+    int rw_kind;
+    float rw_scale, rw_cost, rw_bound;
 };
 
 __constant__ uint32_t c_start_words[kBoardWords];
@@ -75,6 +79,16 @@ enum : uint32_t { META_TRACKED = 1u << 17, META_RED_GENERAL = 1u << 18, META_BLA
                   META_FROZEN = kMetaFrozen,       // MODE_ARENA: the game has ended and is never stepped again
                   META_VS_DONE = kMetaVsDone };    // MODE_VERSUS: this collect's slot is written, the game sits out the later phases
 constexpr int kSideMaterial = 1000 + 2 * 20 + 2 * 20 + 2 * 40 + 2 * 90 + 2 * 45 + 5 * 10;      // 1480, chessboard.h:23-31
+
+// XQ_REWARD_DELTA: clamp(fl32(fl32(delta * scale) - cost), -bound, bound) — a product and a difference rounded once each.  This file is
+// built with -ffp-contract=off and the pragma says it again for this function: a product that feeds a sum is what hipcc contracts into
+// one fma under its default (profiles/NOTES.md, n-step returns), and tests/reward_ref.py holds the two roundings bit for bit.
+__device__ __forceinline__ float delta_reward(int delta, float scale, float cost, float bound) {
+#pragma clang fp contract(off)
+    const float prod = (float)delta * scale;
+    const float r = prod - cost;
+    return fminf(fmaxf(r, -bound), bound);
+}
 
 template <int MODE>
 __global__ __launch_bounds__(256) void env_kernel(EnvParams P) {
@@ -95,10 +109,19 @@ __global__ __launch_bounds__(256) void env_kernel(EnvParams P) {
     // (last hidden width <= 512), two outputs per lane (lane, 64 + lane < 90).
     float qpre[2][8];
     float qbias[2] = {0.f, 0.f};
+    // versus under the delta rule: what the learner took in phase (b) waits in this collect's ring slot as an exact integer; the reply
+    // phase asks for it here, beside the board and meta loads, and not behind move generation
+    const bool rw_carry = MODE == MODE_VERSUS && P.rw_kind == XQ_REWARD_DELTA && P.vs_phase == 2;
+    float carried = 0.f;
     const bool q_from_slabs = (MODE == MODE_SELFPLAY || MODE == MODE_VERSUS) && P.q_slabs != nullptr && P.q_nslabs <= 8;
     if (active) {
         if (lane < kBoardWords) word = P.boards[(size_t)g * kBoardWords + lane];
         m = P.meta[g];
+        if (rw_carry) {
+            int slot = P.rp_write_base + g;
+            slot -= (slot >= P.rp.capacity) ? P.rp.capacity : 0;
+            carried = P.rp.reward[slot];
+        }
         if (q_from_slabs) {
             const float* p0 = P.q_slabs + (size_t)g * 96 + lane;
             const float* p1 = P.q_slabs + (size_t)g * 96 + 64 + (lane < 26 ? lane : 0);
@@ -260,7 +283,7 @@ __global__ __launch_bounds__(256) void env_kernel(EnvParams P) {
     }
 
     // ---- movePiece (chessboard.cpp:38-64) -------------------------------------------------------------------
-    int captured = 0;
+    int captured = 0, gain = 0;                                     // gain: the value of the piece this ply took
     if (valid) {
         const int moving = __builtin_amdgcn_readfirstlane((int)S.sq[from]);
         captured = __builtin_amdgcn_readfirstlane((int)S.sq[to]);
@@ -272,6 +295,7 @@ __global__ __launch_bounds__(256) void env_kernel(EnvParams P) {
         wave_sync();
         if (captured != 0) {
             const int sc = piece_value(captured);
+            gain = sc;
             if (captured <= 7) black += sc; else red += sc;        // credited by the VICTIM's colour (:51-58)
             if (captured == 1) flags &= ~META_RED_GENERAL;
             if (captured == 8) flags &= ~META_BLACK_GENERAL;
@@ -342,7 +366,8 @@ __global__ __launch_bounds__(256) void env_kernel(EnvParams P) {
         }
         if (lane == 0) {
             P.rp.action_to[slot] = have_action ? to : -1;
-            P.rp.reward[slot] = (float)reward;
+            // delta rule: the mover's change of balance over the ply is the value of what it took
+            P.rp.reward[slot] = P.rw_kind == XQ_REWARD_DELTA ? delta_reward(gain, P.rw_scale, P.rw_cost, P.rw_bound) : (float)reward;
             P.rp.done[slot] = done ? 1 : 0;
             if (P.rp.next_player != nullptr) P.rp.next_player[slot] = (uint8_t)(1 - mover);       // the side to move in s'
             // prioritized replay: a new transition enters with the largest priority assigned so far (an empty one never gets sampled)
@@ -366,8 +391,13 @@ __global__ __launch_bounds__(256) void env_kernel(EnvParams P) {
             const bool learner_moved = ph == 2 || (ph == 1 && have_action);
             if (ph == 0 && ended_now) P.rp.action_to[slot] = -1;
             if (ph == 1) P.rp.action_to[slot] = have_action ? to : -1;
+            // delta rule: the learner's change of balance over the whole transition — what it took in (b), carried to (c) in the slot's own
+            // reward word (the slot is in flight until the collect's last phase and never sampled), minus what the reply took
+            const bool rw_delta = P.rw_kind == XQ_REWARD_DELTA;
+            if (rw_delta && ph == 1 && !s2_now) P.rp.reward[slot] = (float)gain;
             if (s2_now) {
-                P.rp.reward[slot] = ph == 0 ? 0.f : (float)reward;
+                const int delta = ph == 1 ? gain : __builtin_amdgcn_readfirstlane((int)carried) - gain;
+                P.rp.reward[slot] = ph == 0 ? 0.f : rw_delta ? delta_reward(delta, P.rw_scale, P.rw_cost, P.rw_bound) : (float)reward;
                 P.rp.done[slot] = ph == 0 || done ? 1 : 0;
                 if (P.rp.next_player != nullptr) P.rp.next_player[slot] = (uint8_t)vs_learner;    // s' is the learner's to move
                 if (P.rp.prio != nullptr) P.rp.prio[slot] = learner_moved ? __uint_as_float(*P.rp.pmax_snap) : 0.f;
@@ -523,6 +553,8 @@ static EnvParams base_params(xq_env* e) {
     P.ep_ring = e->ep_ring;
     P.ep_cap = e->ep_cap;
     P.ep_head = e->ep_head;
+    P.rw_kind = e->rw_kind;
+    P.rw_scale = (float)e->rw_scale; P.rw_cost = (float)e->rw_cost; P.rw_bound = (float)e->rw_bound;
     return P;
 }
 
@@ -873,6 +905,28 @@ int xq_env_selfplay_step_host(xq_env* e, const float* q90_host, uint32_t eps_u32
     if (results_host)
         XQ_HIP(hipMemcpyAsync(results_host, e->results, (size_t)e->n * sizeof(xq_step_result), hipMemcpyDeviceToHost, e->stream));
     XQ_HIP(hipStreamSynchronize(e->stream));
+    return XQ_OK;
+}
+
+int xq_env_set_reward(xq_env* e, int kind, double scale, double ply_cost, double bound) {
+    if (!e) return fail(XQ_ERR_INVALID_ARGUMENT, "null env");
+    if (kind != XQ_REWARD_EVALUATE && kind != XQ_REWARD_DELTA) return fail(XQ_ERR_INVALID_ARGUMENT, "xq_env_set_reward: unknown kind %d", kind);
+    // held on the fp32 values the kernel computes with; every comparison is false for a NaN
+    const float s = (float)scale, c = (float)ply_cost, b = (float)bound;
+    if (!(s > 0.f && s < __builtin_inff())) return fail(XQ_ERR_INVALID_ARGUMENT, "xq_env_set_reward: scale must be finite and > 0 in fp32");
+    if (!(c >= 0.f && c < __builtin_inff())) return fail(XQ_ERR_INVALID_ARGUMENT, "xq_env_set_reward: ply_cost must be finite and >= 0");
+    if (!(b > 0.f)) return fail(XQ_ERR_INVALID_ARGUMENT, "xq_env_set_reward: bound must be > 0 (+inf: no clamp)");
+    e->rw_kind = kind;
+    e->rw_scale = scale; e->rw_cost = ply_cost; e->rw_bound = bound;
+    return XQ_OK;
+}
+
+int xq_env_get_reward(const xq_env* e, int* kind, double* scale, double* ply_cost, double* bound) {
+    if (!e) return fail(XQ_ERR_INVALID_ARGUMENT, "null env");
+    if (kind) *kind = e->rw_kind;
+    if (scale) *scale = e->rw_scale;
+    if (ply_cost) *ply_cost = e->rw_cost;
+    if (bound) *bound = e->rw_bound;
     return XQ_OK;
 }
 

@@ -271,6 +271,9 @@ struct xq_env {
     int ep_cap = 0;
     xq::DevBuf<unsigned long long> ep_head;  // device counter of finished episodes
     uint64_t ep_drained = 0;
+    // the reward the env kernel writes into a ring (xq_env_set_reward), as given; the launches carry the fp32 values
+    int rw_kind = XQ_REWARD_EVALUATE;
+    double rw_scale = 1e-3, rw_cost = 0.0, rw_bound = 1.0;
 };
 
 namespace xq {

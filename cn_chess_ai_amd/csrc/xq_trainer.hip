@@ -252,6 +252,13 @@ int xq_trainer_set_td_bootstrap(xq_trainer* t, int kind) {
     return xq_dqn_set_td_bootstrap(t->dqn, kind);
 }
 
+// the reward rule of the trainer's env: the next collect writes it, slots already in the ring keep theirs
+int xq_trainer_set_reward(xq_trainer* t, int kind, double scale, double ply_cost, double bound) {
+    if (!t) return fail(XQ_ERR_INVALID_ARGUMENT, "null trainer");
+    if (t->grads_queued) return fail(XQ_ERR_RUNTIME, "xq_trainer_set_reward: call between iterations (after learn_apply)");
+    return xq_env_set_reward(t->env, kind, scale, ply_cost, bound);
+}
+
 int xq_trainer_set_mirror(xq_trainer* t, double prob) {
     if (!t) return fail(XQ_ERR_INVALID_ARGUMENT, "null trainer");
     if (t->grads_queued) return fail(XQ_ERR_RUNTIME, "xq_trainer_set_mirror: call between iterations (after learn_apply)");

@@ -9,7 +9,7 @@ import numpy as np
 
 from . import _capi
 from ._capi import call, KernelStat, KernelSpan, TrainerConfig as _CConfig
-from .vecenv import VecEnv, ReplayBuffer, _ptr
+from .vecenv import VecEnv, ReplayBuffer, _ptr, reward_kind
 from .arena import Search, player
 
 REFERENCE_LAYERS = (1260, 128, 8100)     # ChessAI::initializeDQN, chessai.cpp:395-404
@@ -610,6 +610,12 @@ class Trainer:
         if kind not in _BOOTSTRAPS:
             raise ValueError(f"set_td_bootstrap: expected 'all' or 'legal', got {kind!r}")
         call("xq_trainer_set_td_bootstrap", self._h, _BOOTSTRAPS[kind])
+
+    def set_reward(self, kind, scale=1e-3, ply_cost=0.0, bound=1.0):
+        """VecEnv.set_reward on the trainer's env (DESIGN.md §4 "Reward rule"): "evaluate" (the reference's evaluateBoard, the default)
+        or "delta" (the transition's change of material balance, scaled, less ply_cost, clamped to +-bound).  The next collect writes
+        it; slots already in the ring keep theirs.  Call between iterations."""
+        call("xq_trainer_set_reward", self._h, reward_kind(kind), float(scale), float(ply_cost), float(bound))
 
     def set_opponent(self, opponent):
         """Train against a fixed opponent from the next collect on (DESIGN.md §4 "Versus training"): None = self-play (the default),

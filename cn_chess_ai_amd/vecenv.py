@@ -39,6 +39,18 @@ def _ptr(a, ctype):
     return a.ctypes.data_as(C.POINTER(ctype))
 
 
+REWARD_KINDS = {"evaluate": _capi.REWARD_EVALUATE, "delta": _capi.REWARD_DELTA}
+
+
+def reward_kind(kind):
+    """"evaluate" / "delta" -> XQ_REWARD_*; an int passes as it is (the library refuses an unknown one)."""
+    if isinstance(kind, str):
+        if kind not in REWARD_KINDS:
+            raise ValueError(f"set_reward: expected 'evaluate' or 'delta', got {kind!r}")
+        return REWARD_KINDS[kind]
+    return int(kind)
+
+
 class ReplayBuffer:
     """ReplayBuffer{capacity; push(s,a,r,s',done); sample(B)} — element = the 5-tuple of DQN::train (dqn.cpp:157)."""
 
@@ -309,6 +321,22 @@ class VecEnv:
         """Asynchronous, device pointers only (ints): the hot-loop form."""
         call("xq_env_selfplay_step", self._h, C.c_void_p(q90_dev) if q90_dev else None, int(q_stride), eps_to_u32(eps),
              C.c_void_p(results_dev) if results_dev else None, replay.handle if replay is not None else None)
+
+    # ---- reward rule (build-defined, DESIGN.md §4 "Reward rule") ----
+    def set_reward(self, kind, scale=1e-3, ply_cost=0.0, bound=1.0):
+        """What the env kernel writes into a replay ring as the reward: "evaluate" = evaluateBoard as the reference (the default), or
+        "delta" = clamp(fl32(fl32(delta * scale) - ply_cost), -bound, bound) in fp32, delta = the change of the mover's (versus: the
+        learner's) material balance over the transition.  scale finite > 0, ply_cost finite >= 0, bound > 0 (inf: no clamp).  Takes
+        effect at the next ply that writes a ring; the reward field of a step result stays evaluateBoard."""
+        call("xq_env_set_reward", self._h, reward_kind(kind), float(scale), float(ply_cost), float(bound))
+
+    @property
+    def reward(self):
+        """(kind, scale, ply_cost, bound) as last set; ("evaluate", 1e-3, 0.0, 1.0) on an env that was never asked."""
+        k, s, c, b = C.c_int32(), C.c_double(), C.c_double(), C.c_double()
+        call("xq_env_get_reward", self._h, C.byref(k), C.byref(s), C.byref(c), C.byref(b))
+        names = {v: n for n, v in REWARD_KINDS.items()}
+        return names[k.value], s.value, c.value, b.value
 
     def drain_episodes(self, max_records=65536):
         rec = np.zeros(max_records, dtype=EPISODE_DTYPE)

@@ -18,6 +18,10 @@
 //                                 prob in [0, 1] (xq::ChessAI::setMirror; 0 = off)
 //   bootstrap=all|legal           target of the batched loop's TD step: the maximum over all outputs (default, chessai.cpp:126) or over the
 //                                 moves the side to move can play in s' (xq::ChessAI::setTdBootstrap)
+//   reward=evaluate|delta[:scale[:cost[:bound]]]
+//                                 what the batched loop's plies write into the ring: evaluateBoard (default, chessai.cpp:115) or the
+//                                 transition's change of material balance, scaled (1e-3), less a cost per ply (0), clamped to +-bound (1)
+//                                 (xq::ChessAI::setReward; the sequential loop, parallel_games = 1, refuses delta)
 //   --json                        one JSON line with the loop's counters (bench.py's `facade` leg reads it)
 #include <chrono>
 #include <cstdio>
@@ -34,6 +38,7 @@ int main(int argc, char** argv) {
     bool derive = false, json = false, adam = false, legal = false;
     unsigned long long seed = 0;
     double clip = 0.0, mirror = 0.0;
+    xq::Reward reward;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         auto next = [&]() -> const char* { if (i + 1 >= argc) { std::fprintf(stderr, "%s needs a value\n", a.c_str()); std::exit(2); } return argv[++i]; };
@@ -54,6 +59,23 @@ int main(int argc, char** argv) {
             const std::string v = a.substr(10);
             if (v != "all" && v != "legal") { std::fprintf(stderr, "bootstrap=: expected all or legal, got %s\n", v.c_str()); return 2; }
             legal = v == "legal";
+        }
+        else if (a.rfind("reward=", 0) == 0) {
+            // evaluate | delta[:scale[:cost[:bound]]]; the values are checked by ChessAI::setReward
+            const std::string v = a.substr(7);
+            if (v == "evaluate") reward = xq::Reward::evaluate();
+            else if (v.rfind("delta", 0) == 0 && (v.size() == 5 || v[5] == ':')) {
+                double p[3] = {1e-3, 0.0, 1.0};
+                const char* s = v.c_str() + 5;
+                for (int k = 0; k < 3 && *s == ':'; ++k) {
+                    char* end = nullptr;
+                    p[k] = std::strtod(s + 1, &end);
+                    if (end == s + 1) { std::fprintf(stderr, "reward=: expected a number after ':', got %s\n", s + 1); return 2; }
+                    s = end;
+                }
+                if (*s) { std::fprintf(stderr, "reward=: expected delta[:scale[:cost[:bound]]], got %s\n", v.c_str()); return 2; }
+                reward = xq::Reward::delta(p[0], p[1], p[2]);
+            } else { std::fprintf(stderr, "reward=: expected evaluate or delta[:scale[:cost[:bound]]], got %s\n", v.c_str()); return 2; }
         }
         else if (a.rfind("mirror=", 0) == 0) {
             char* end = nullptr;
@@ -81,6 +103,7 @@ int main(int argc, char** argv) {
         if (clip != 0.0) ai.setGradClip(clip);
         if (mirror != 0.0) ai.setMirror(mirror);
         if (legal) ai.setTdBootstrap(xq::TdBootstrap::legal());
+        ai.setReward(reward);
         if (replay > 0) ai.setReplay(replay, minibatch);
         ai.setSaveInterval(save_every);
         ai.setLayer0Derive(derive);

@@ -225,6 +225,19 @@ struct TdBootstrap {
     }
 };
 
+// The reward the env kernel writes into a replay ring (xq_env_set_reward, DESIGN.md §4 "Reward rule"; no upstream analogue): evaluate() is
+// the reference's evaluateBoard(mover, moveCount); delta() the transition's change of material balance, in fp32
+// min(max(delta * scale - plyCost, -bound), bound) with scale finite > 0, plyCost finite >= 0, bound > 0 (+inf: no clamp).
+struct Reward {
+    int kind = XQ_REWARD_EVALUATE;
+    double scale = 1e-3, plyCost = 0.0, bound = 1.0;
+    static Reward evaluate() { return Reward(); }
+    static Reward delta(double scale = 1e-3, double plyCost = 0.0, double bound = 1.0) {
+        Reward r; r.kind = XQ_REWARD_DELTA; r.scale = scale; r.plyCost = plyCost; r.bound = bound;
+        return r;
+    }
+};
+
 // ---- DQN, dqn.h:97-116 ----------------------------------------------------------------------------------------------
 class DQN {
 public:
@@ -427,6 +440,13 @@ public:
         check(xq_env_search(h_, depth, r.values.data(), r.counts.data(), r.best.data()));
         return r;
     }
+    // what this env's plies write into a replay ring as the reward (xq_env_set_reward); step results keep evaluateBoard
+    void setReward(const Reward& r) { check(xq_env_set_reward(h_, r.kind, r.scale, r.plyCost, r.bound)); }
+    Reward reward() const {
+        Reward r;
+        check(xq_env_get_reward(h_, &r.kind, &r.scale, &r.plyCost, &r.bound));
+        return r;
+    }
     xq_env* handle() const { return h_; }
 private:
     xq_env* h_ = nullptr;
@@ -623,9 +643,15 @@ public:
     }
 
     // One ply of the loop body chessai.cpp:96-143.  Returns false when the episode is over (nothing was played).
-    bool trainStep() { return ply(true); }
+    bool trainStep() { parityLoopReward("trainStep"); return ply(true); }
 
 private:
+    // the single-board loops are the reference's: they learn on evaluateBoard and never silently on another reward
+    void parityLoopReward(const char* who) const {
+        if (reward_.kind != XQ_REWARD_EVALUATE)
+            throw std::invalid_argument(std::string("ChessAI::") + who + ": Reward::delta needs the batched loop (setParallelGames(n > 1)); "
+                                        "the single-board loops keep the reference's evaluateBoard");
+    }
     // trainLoop = true: ChessAI::train (local 200-ply cap, done includes moveCount+1 >= 200, :96/:119);
     // trainLoop = false: ChessAI::startSelfPlay (no local cap, done = checkGameOver(), :197/:227).
     bool ply(bool trainLoop) {
@@ -658,6 +684,7 @@ private:
 public:
     // One episode = one iteration of the `for episode` loop, chessai.cpp:90-167 (minus the periodic save).
     int trainEpisode() {
+        parityLoopReward("trainEpisode");
         initializeDQN();
         beginEpisode();
         int plies = 0;
@@ -677,6 +704,7 @@ public:
     void train(int numEpisodes) {
         if (parallelGames_ <= 1 && opponent_)
             throw std::logic_error("ChessAI::train: an opponent (setOpponent) needs the batched loop (setParallelGames(n > 1))");
+        if (parallelGames_ <= 1) parityLoopReward("train");
         initializeDQN();
         if (parallelGames_ <= 1) {
             for (int e = 0; e < numEpisodes; ++e) {
@@ -693,6 +721,7 @@ public:
     }
     // chessai.cpp:191-266: same loop driven by board->getCurrentPlayer(), no local 200-ply cap (the board's own cap ends it)
     void startSelfPlay(int numGames) {
+        parityLoopReward("startSelfPlay");
         initializeDQN();
         for (int i = 0; i < numGames; ++i) {
             board->reset();
@@ -747,7 +776,8 @@ public:
                                                                                            // re-evaluation per sample; those re-evaluated as whole groups
                         uint64_t versus[4] = {0, 0, 0, 0};      // with an opponent: the learner's wins, draws, losses, games ended
                         int nStep = 1;                          // the n-step setting of the trainer's ring as the run ended (setNStep)
-                        double mirror = 0; };                   // ... and its mirror probability (setMirror)
+                        double mirror = 0;                      // ... and its mirror probability (setMirror)
+                        Reward reward; };                       // the reward rule of the trainer's env as the run ended (setReward)
     TrainStats lastTrainStats() const { return stats_; }
     // data-parallel train(): this process is rank comm->rank() of comm->world(); its batched games take the id range
     // [rank * parallelGames, (rank + 1) * parallelGames) and every update all-reduces the gradients over RCCL (nullptr = off)
@@ -775,6 +805,17 @@ public:
         mirror_ = prob;
     }
     double mirror() const { return mirror_; }
+    // Reward of the batched train(): xq_trainer_set_reward on the trainer (Reward::evaluate() = the reference's, the default).  The
+    // single-board loops (trainEpisode, trainStep, startSelfPlay, train with parallelGames == 1) stay the reference's and throw
+    // std::invalid_argument when asked for Reward::delta.
+    void setReward(const Reward& r) {
+        if (r.kind != XQ_REWARD_EVALUATE && r.kind != XQ_REWARD_DELTA) throw std::invalid_argument("setReward: unknown kind");
+        const float s = (float)r.scale, c = (float)r.plyCost, b = (float)r.bound;
+        if (!(s > 0.f && s <= std::numeric_limits<float>::max()) || !(c >= 0.f && c <= std::numeric_limits<float>::max()) || !(b > 0.f))
+            throw std::invalid_argument("setReward: scale must be finite and > 0, plyCost finite and >= 0, bound > 0");
+        reward_ = r;
+    }
+    Reward reward() const { return reward_; }
     // Target of the batched train(), carried onto the trainer's network like the loss: TdBootstrap::legal() makes the trainer's ring
     // record the side to move in s' (xq_trainer_set_td_bootstrap, before the first collect).  fp32 nets; the sequential loop is unaffected.
     void setTdBootstrap(const TdBootstrap& b) { initializeDQN(); dqn->setTdBootstrap(b); }
@@ -830,6 +871,7 @@ private:
         check(xq_trainer_set_target_tau(t, dqn->targetTau()));
         if (nStep_ > 1) check(xq_trainer_set_n_step(t, nStep_));
         if (mirror_ > 0.0) check(xq_trainer_set_mirror(t, mirror_));
+        if (reward_.kind != XQ_REWARD_EVALUATE) check(xq_trainer_set_reward(t, reward_.kind, reward_.scale, reward_.plyCost, reward_.bound));
         const TdLoss loss = dqn->tdLoss();
         check(xq_dqn_set_td_loss(td, loss.kind, loss.kappa));
         if (comm_) check(xq_trainer_set_comm(t, comm_->handle()));
@@ -877,6 +919,7 @@ private:
             check(xq_trainer_replay(t, &tr));
             check(xq_replay_get_n_step(tr, &stats_.nStep, nullptr));
             check(xq_replay_get_mirror(tr, &stats_.mirror, nullptr));
+            check(xq_env_get_reward(te, &stats_.reward.kind, &stats_.reward.scale, &stats_.reward.plyCost, &stats_.reward.bound));
         }
         {
             uint64_t q[4] = {0, 0, 0, 0}; int hold = 0;
@@ -903,6 +946,7 @@ private:
     bool l0Derive_ = false;
     int nStep_ = 1;
     double mirror_ = 0.0;
+    Reward reward_;
     int prefillPlies_ = 0;
     std::unique_ptr<Player> opponent_;
     TrainStats stats_;

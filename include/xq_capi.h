@@ -164,7 +164,8 @@ typedef struct {
     int32_t action;      /* action code played, -1 if the side to move had no action (chessai.cpp:100-103) */
     int32_t n_moves;     /* size of the legal list the action was chosen from (0 for xq_env_step) */
     int32_t reward;      /* evaluateBoard(mover, post-move count), chessai.cpp:311-345; where no move was made (action -1, or a
-                          * rejected move of xq_env_step) it is evaluateBoard(side to move, the unchanged count) of the untouched board */
+                          * rejected move of xq_env_step) it is evaluateBoard(side to move, the unchanged count) of the untouched board.
+                          * Always evaluateBoard, part of the ABI: xq_env_set_reward changes what a replay ring gets, never this field */
     uint8_t captured;    /* piece code movePiece() returned (chessboard.cpp:38-64); 0 = none or invalid move */
     uint8_t valid;       /* 0: movePiece() rejected the move — no state change */
     uint8_t done;        /* checkGameOver() || moveCount+1 >= 200 (chessai.cpp:119) */
@@ -192,6 +193,28 @@ int xq_env_selfplay_step(xq_env* env, const float* q90_dev, int q_stride, uint32
                          xq_step_result* results_dev, xq_replay* replay);
 /* Convenience for tests: same, copying results to the host. */
 int xq_env_selfplay_step_host(xq_env* env, const float* q90_host, uint32_t eps_u32, xq_step_result* results_host);
+
+/* The reward the env kernel writes into a replay ring (DESIGN.md §4 "Reward rule") — build-defined; the default is the reference's.
+ *   XQ_REWARD_EVALUATE : evaluateBoard(mover, moveCount) (chessai.cpp:115, :311-345; versus training: from the learner's side): the
+ *                        absolute material balance, up to +-1480, minus a truncated 0.1 moveCount.  Same launches and bits as an env that
+ *                        was never asked; scale, ply_cost and bound are checked, kept and not used.
+ *   XQ_REWARD_DELTA    : the change of material balance over the transition, scaled, less a cost per ply, clamped.  With B(board, side) =
+ *                        the PieceScore sum of side's pieces minus the other side's (general 1000; evaluateBoard's material sum):
+ *                          self-play: delta = B(s', mover) - B(s, mover)      = the value of the piece this ply took (>= 0)
+ *                          versus   : delta = B(s', learner) - B(s, learner)  = what the learner took minus what the reply took, over the
+ *                                     whole learner transition; the game ended by the learner's move: its part only; the empty slot of
+ *                                     an opponent's pre-move that ended the game keeps reward 0
+ *                          r = min(max(fl32(fl32((float)delta * (float)scale) - (float)ply_cost), -(float)bound), (float)bound)
+ *                        in fp32, one rounding per operation.  A row without an action (action_to -1) stays an empty row: delta = 0 there.
+ *                        The gain is the captured piece's value, not a difference of tracked scores, so boards from xq_env_set_state
+ *                        follow the same rule.
+ * As fp32 values: scale finite and > 0, ply_cost finite and >= 0, bound > 0 (+inf: no clamp); anything else, NaN included, or an unknown
+ * kind: XQ_ERR_INVALID_ARGUMENT and nothing changes.  Takes effect at the next launch that writes a ring (xq_env_selfplay_step with a
+ * replay, a trainer's collect); slots already written keep their values.  xq_step_result.reward, host pushes and the arena are untouched.
+ * xq_env_get_reward: the values as last given — on an env that was never asked XQ_REWARD_EVALUATE, 1e-3, 0, 1.  Outputs may be NULL. */
+enum { XQ_REWARD_EVALUATE = 0, XQ_REWARD_DELTA = 1 };
+int xq_env_set_reward(xq_env* env, int kind, double scale, double ply_cost, double bound);
+int xq_env_get_reward(const xq_env* env, int* kind, double* scale, double* ply_cost, double* bound);
 
 /* Episode reporting — the gameCompleted(game, redScore, blackScore) signal (chessai.h:35, chessai.cpp:162). */
 typedef struct {
@@ -824,6 +847,11 @@ int xq_trainer_set_n_step(xq_trainer* t, int n_step);
  * any n_step.  No window changes: the transform reads only what the step read anyway.  Call between iterations: XQ_ERR_RUNTIME while a
  * learn_grads waits for its learn_apply. */
 int xq_trainer_set_mirror(xq_trainer* t, double prob);
+/* xq_env_set_reward on the trainer's env (DESIGN.md §4 "Reward rule"): the next collect writes the new reward, slots already in the ring
+ * keep theirs.  Uniform, prioritized and on-policy rings, overlap_collect 0 and 1, self-play and versus; n-step returns, the mirror,
+ * prioritized replay and both bootstraps read the ring's reward column as before.  Call between iterations: XQ_ERR_RUNTIME while a
+ * learn_grads waits for its learn_apply. */
+int xq_trainer_set_reward(xq_trainer* t, int kind, double scale, double ply_cost, double bound);
 /* xq_dqn_set_td_bootstrap on the trainer's Q-net.  XQ_BOOTSTRAP_LEGAL first turns tracking on for the trainer's ring, so call it before
  * the first collect: XQ_ERR_RUNTIME once the ring holds a transition (unless it tracks already).  Back to XQ_BOOTSTRAP_ALL is allowed
  * between iterations (XQ_ERR_RUNTIME while a learn_grads waits for its learn_apply); the column keeps being written.  Uniform,
