@@ -149,6 +149,8 @@ PROTOTYPES = {
     "xq_replay_get_n_step": [_vp, _pi, _pi],
     "xq_replay_set_mirror": [_vp, _d],
     "xq_replay_get_mirror": [_vp, _pd, _pu64],
+    "xq_replay_set_colour_swap": [_vp, _d],
+    "xq_replay_get_colour_swap": [_vp, _pd, _pu64],
     "xq_dqn_create": [_pi, _i, _d, _d, _u64, _vp, _pvp],
     "xq_dqn_destroy": [_vp],
     "xq_dqn_set_precision": [_vp, _i],
@@ -181,6 +183,7 @@ PROTOTYPES = {
     "xq_dqn_last_td_values": [_vp, _i, _pf, _pf],
     "xq_dqn_last_n_step": [_vp, _i, _pf, _pu8, _pi, _pi, _pi, _pi],
     "xq_dqn_last_mirror": [_vp, _i, _pu8, _pu8, _pu8, _pi, _pi],
+    "xq_dqn_last_colour_swap": [_vp, _i, _pu8, _pu8, _pu8, _pi, _pu8, _pi],
     "xq_dqn_set_td_bootstrap": [_vp, _i],
     "xq_dqn_get_td_bootstrap": [_vp, _pi],
     "xq_dqn_td_grads_sided": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i],
@@ -231,6 +234,7 @@ PROTOTYPES = {
     "xq_trainer_set_target_tau": [_vp, _d],
     "xq_trainer_set_n_step": [_vp, _i],
     "xq_trainer_set_mirror": [_vp, _d],
+    "xq_trainer_set_colour_swap": [_vp, _d],
     "xq_trainer_set_opponent": [_vp, C.POINTER(ArenaPlayer)],
     "xq_trainer_versus_results": [_vp, _pu64],
     "xq_trainer_collect": [_vp],
@@ -271,7 +275,11 @@ LAZY_LEGAL = frozenset(("xq_dqn_set_td_bootstrap", "xq_dqn_get_td_bootstrap", "x
                         "xq_trainer_set_td_bootstrap"))
 # ... and those of the reward rule
 LAZY_REWARD = frozenset(("xq_env_set_reward", "xq_env_get_reward", "xq_trainer_set_reward"))
-_LAZY_ALL = LAZY | LAZY_GRAD_CLIP | LAZY_TARGET_TAU | LAZY_TD_LOSS | LAZY_N_STEP | LAZY_MIRROR | LAZY_LEGAL | LAZY_REWARD
+# ... and those of the colour-swap augmentation
+LAZY_COLOUR_SWAP = frozenset(("xq_replay_set_colour_swap", "xq_replay_get_colour_swap", "xq_dqn_last_colour_swap",
+                              "xq_trainer_set_colour_swap"))
+_LAZY_ALL = (LAZY | LAZY_GRAD_CLIP | LAZY_TARGET_TAU | LAZY_TD_LOSS | LAZY_N_STEP | LAZY_MIRROR | LAZY_LEGAL | LAZY_REWARD
+             | LAZY_COLOUR_SWAP)
 _RESTYPES = {"xq_last_error": C.c_char_p, "xq_env_boards_dev": C.c_void_p, "xq_env_meta_dev": C.c_void_p}
 
 _lib = None

@@ -24,8 +24,8 @@
 // the one place that touches params_version, the screen's kept rows, the select chain's kept sums and tgt_rest_synced.
 // This file = the handle (struct xq_dqn) + host orchestration + the C ABI; the kernels live in xq_l0.hip.h (layer-0 gathers and
 // segmented sums), xq_tail.hip.h (TD delta, gradient sums, fused launches, SGD), xq_refine.hip.h (screening pass 2), xq_l0grad.hip.h
-// (layer-0 gradient on the matrix pipe), xq_gemm*.hip.h and xq_screen.hip.h (matrix-pipe products), xq_nstep.hip.h and xq_mirror.hip.h
-// (staging of n-step and mirrored batches), xq_legal.hip.h (the legal-move bootstrap, on the rules engine of xq_rules.hip.h).
+// (layer-0 gradient on the matrix pipe), xq_gemm*.hip.h and xq_screen.hip.h (matrix-pipe products), xq_nstep.hip.h, xq_mirror.hip.h and
+// xq_colour_swap.hip.h (staging of n-step, mirrored and colour-swapped batches), xq_legal.hip.h (the legal-move bootstrap, on the rules engine of xq_rules.hip.h).
 #include "xq_internal.h"
 #include <hip/hip_ext.h>
 #include "xq_gemm.hip.h"
@@ -202,6 +202,12 @@ struct xq_dqn {
     // transforms an n-step batch there in place; per row the flag.  mirror_rows: rows of the last TD step if it was a mirror-mode one
     xq::DevBuf<uint8_t> ns_flag;
     int mirror_rows = 0;
+    // colour-swap augmentation (xq_replay_set_colour_swap): colour_swap_stage_kernel does the same, as the first staging transform or in
+    // place behind the n-step assembly and / or the mirror; per row its own flag.  colour_swap_rows: rows of the last TD step if it was a
+    // colour-swap-mode one; colour_swap_sided: that step staged the side bytes too (it ran under the legal-move bootstrap)
+    xq::DevBuf<uint8_t> ns_cflag;
+    int colour_swap_rows = 0;
+    bool colour_swap_sided = false;
     // legal-move bootstrap (xq_dqn_set_td_bootstrap): the k-slabs of the 96-row head product of s' (the selecting net's, then the target
     // net's of a Double-DQN step), the pre-activations legal_qmax_kernel leaves of them, the move count per row, the host batch's side
     // bytes.  legal_rows: rows of the last TD step if it was a legal one, else 0 (xq_dqn_last_legal)
@@ -297,6 +303,7 @@ struct SmallTiles {
 #include "xq_refine.hip.h"
 #include "xq_nstep.hip.h"
 #include "xq_mirror.hip.h"
+#include "xq_colour_swap.hip.h"
 #include "xq_legal.hip.h"
 
 namespace xq {
@@ -2166,6 +2173,7 @@ static int td_grads_impl(xq_dqn* d, const uint32_t* boards, const uint32_t* next
     s.gamma = discount ? *discount : (float)d->gamma;
     d->nstep_rows = 0;                               // (xq_dqn_td_grads_replay sets it behind an n-step batch)
     d->mirror_rows = 0;                              // (... and this one behind a mirror-mode batch)
+    d->colour_swap_rows = 0;                         // (... and this one behind a colour-swap-mode batch)
     s.n = n; s.mode = mode; s.nl = nl; s.Hl = Hl; s.NO = NO; s.dbl = dbl; s.bf = bf; s.sel_net = td_net == XQ_TD_TARGET_NET ? XQ_NET_TARGET : XQ_NET_ONLINE;
     chain_views(d, d->acts, d->acts_bf, XQ_MAX_LAYERS, true, s.outs, s.outs_bf);
     chain_views(d, d->tacts, d->tacts_bf, 2, !bf, s.touts, s.touts_bf);
@@ -2498,13 +2506,16 @@ int xq_dqn_grad_buffer(xq_dqn* d, float** grads_dev, size_t* n_floats) {
 // The TD step on the handle's staging batch (what an n-step assembly or a mirror gather filled): identity slot source, the given discount
 // (nullptr: the handle's gamma).  A prioritized draw keeps its importance weights; the step gets no priority table, and
 // per_writeback_kernel behind it writes the live rows' priorities to the sampled slots recorded in ns_first
-// Under the legal-move bootstrap the staged rows' side bytes come from the ring's column at row_slot[b] (legal_side_stage_kernel)
+// Under the legal-move bootstrap the staged rows' side bytes come from the ring's column at row_slot[b] (legal_side_stage_kernel) —
+// unless colour_swap_stage_kernel has staged them already (side_staged: it flips the flagged rows' bytes as it goes)
 static int td_grads_staged(xq_dqn* d, xq_replay* r, const int32_t* row_slot, int batch, int td_net, int mode, const PerOpts* per,
-                           const float* discount) {
+                           const float* discount, bool side_staged = false) {
     PerOpts step_per;
     if (per) { step_per = *per; step_per.prio = nullptr; step_per.pmax_live = nullptr; }
     const uint8_t* side = nullptr;
-    if (d->bootstrap == XQ_BOOTSTRAP_LEGAL) {
+    if (d->bootstrap == XQ_BOOTSTRAP_LEGAL && side_staged) {
+        side = d->ns_side;
+    } else if (d->bootstrap == XQ_BOOTSTRAP_LEGAL) {
         XQ_TRY(d->ns_side.reserve((size_t)batch));
         ProfScope ps(d, "legal_side_stage", 0.0, (double)batch * 6.0, true);
         hipExtLaunchKernelGGL(legal_side_stage_kernel, dim3((batch + 255) / 256), dim3(256), 0, d->cur, ps.start(), ps.stop(), 0,
@@ -2568,9 +2579,65 @@ static int td_grads_mirror(xq_dqn* d, xq_replay* r, SlotSrc src, int batch, int 
     return XQ_OK;
 }
 
+// Colour-swap augmentation (xq_replay_set_colour_swap): queues colour_swap_stage_kernel for the next TD step from ring `r` and counts
+// it.  gather: the minibatch from the ring (through `src`) into the handle's staging batch; otherwise the staging batch an n-step
+// assembly and / or a mirror gather just filled, in place.  Whether row b is swapped is the ring's Philox stream at {b, 0, call, 4}.
+// Under the legal-move bootstrap the kernel also stages the side bytes, from the ring's column at row_slot[b] (gather: at the sampled
+// slot; row_slot is not read), flipped on the flagged rows: td_grads_staged then launches no legal_side_stage_kernel
+static int colour_swap_stage(xq_dqn* d, xq_replay* r, SlotSrc src, int batch, bool gather, const int32_t* row_slot) {
+    const size_t rows = (size_t)batch;
+    const bool sided = d->bootstrap == XQ_BOOTSTRAP_LEGAL;
+    if (gather) {
+        XQ_TRY(d->ns_boards.reserve(rows * kBoardWords));
+        XQ_TRY(d->ns_next.reserve(rows * kBoardWords));
+        for (DevBuf<int32_t>* b : {&d->ns_action, &d->ns_first}) XQ_TRY(b->reserve(rows));
+        XQ_TRY(d->ns_reward.reserve(rows));
+        XQ_TRY(d->ns_done.reserve(rows));
+    }
+    XQ_TRY(d->ns_cflag.reserve(rows));
+    if (sided) XQ_TRY(d->ns_side.reserve(rows));
+    ColourSwapArgs A; memset(&A, 0, sizeof A);
+    if (gather) {
+        A.boards = r->dev.boards; A.next_boards = r->dev.next_boards; A.action_to = r->dev.action_to; A.reward = r->dev.reward; A.done = r->dev.done;
+    } else {
+        A.boards = d->ns_boards; A.next_boards = d->ns_next; A.action_to = d->ns_action; A.reward = d->ns_reward; A.done = d->ns_done;
+    }
+    A.s_boards = d->ns_boards; A.s_next = d->ns_next; A.s_action = d->ns_action; A.s_reward = d->ns_reward; A.s_done = d->ns_done;
+    A.s_first = d->ns_first; A.s_flag = d->ns_cflag;
+    if (sided) { A.ring_side = r->dev.next_player; A.row_slot = gather ? nullptr : row_slot; A.s_side = d->ns_side; }
+    A.cap = r->dev.capacity;
+    A.thresh = eps_to_u32(r->colour_swap_prob); A.all = r->colour_swap_prob >= 1.0 ? 1u : 0u;
+    A.gather = gather ? 1u : 0u;
+    A.call = (uint32_t)r->colour_swap_calls; A.seed_lo = (uint32_t)r->seed; A.seed_hi = (uint32_t)(r->seed >> 32);
+    r->colour_swap_calls += 1;
+    {
+        // per row: the mirror's bytes (from the ring 215, in place 201); under the legal bootstrap the ring's side byte in and the staged
+        // one out, in place also the 4 B of the slot it is read at
+        const double side_bytes = sided ? (gather ? 2.0 : 6.0) : 0.0;
+        ProfScope ps(d, "colour_swap_stage", 0.0, (double)batch * ((gather ? 215.0 : 201.0) + side_bytes), true);
+        hipExtLaunchKernelGGL(colour_swap_stage_kernel, dim3((batch + 63) / 64), dim3(64), 0, d->cur, ps.start(), ps.stop(), 0, A, src, batch);
+        XQ_HIP(hipGetLastError());
+    }
+    return XQ_OK;
+}
+
+// A TD step on a colour-swapped batch of one-step transitions (xq_replay_set_colour_swap on a ring with n_step == 1), with or without
+// the mirror: the first transform on gathers the minibatch from the ring, the colour swap behind the mirror works in place (the two
+// commute: one acts on columns, the other on rows and codes); the step then runs as behind the mirror alone
+static int td_grads_colour_swap(xq_dqn* d, xq_replay* r, SlotSrc src, int batch, int td_net, int mode, const PerOpts* per) {
+    const bool mirrored = r->mirror_prob > 0.0;
+    if (mirrored) XQ_TRY(mirror_stage(d, r, src, batch, true));
+    XQ_TRY(colour_swap_stage(d, r, src, batch, !mirrored, d->ns_first));
+    XQ_TRY(td_grads_staged(d, r, d->ns_first, batch, td_net, mode, per, nullptr, true));
+    if (mirrored) d->mirror_rows = batch;
+    d->colour_swap_rows = batch;
+    d->colour_swap_sided = d->bootstrap == XQ_BOOTSTRAP_LEGAL;
+    return XQ_OK;
+}
+
 // A TD step on n-step transitions (xq_replay_set_n_step): one gather assembles them into the handle's staging batch, the step then runs
 // on that batch with the identity slot source and the discount gamma^n; a prioritized draw's priorities go back behind the step.  With
-// mirror augmentation on as well, the assembled batch is transformed in place before the step
+// mirror and / or colour-swap augmentation on as well, the assembled batch is transformed in place before the step
 static int td_grads_nstep(xq_dqn* d, xq_replay* r, SlotSrc src, int batch, int td_net, int mode, const PerOpts* per) {
     const int cap = r->dev.capacity, n = r->n_step;
     NStepArgs A; memset(&A, 0, sizeof A);
@@ -2602,9 +2669,12 @@ static int td_grads_nstep(xq_dqn* d, xq_replay* r, SlotSrc src, int batch, int t
     }
     const bool mirrored = r->mirror_prob > 0.0;
     if (mirrored) XQ_TRY(mirror_stage(d, r, src, batch, false));
-    XQ_TRY(td_grads_staged(d, r, d->ns_last, batch, td_net, mode, per, &disc_n));
+    const bool swapped = r->colour_swap_prob > 0.0;
+    if (swapped) XQ_TRY(colour_swap_stage(d, r, src, batch, false, d->ns_last));
+    XQ_TRY(td_grads_staged(d, r, d->ns_last, batch, td_net, mode, per, &disc_n, swapped));
     d->nstep_rows = batch;
     if (mirrored) d->mirror_rows = batch;
+    if (swapped) { d->colour_swap_rows = batch; d->colour_swap_sided = d->bootstrap == XQ_BOOTSTRAP_LEGAL; }
     return XQ_OK;
 }
 
@@ -2643,6 +2713,30 @@ int xq_dqn_last_mirror(xq_dqn* d, int n, uint8_t* flags, uint8_t* boards90, uint
     return XQ_OK;
 }
 
+int xq_dqn_last_colour_swap(xq_dqn* d, int n, uint8_t* flags, uint8_t* boards90, uint8_t* next_boards90, int32_t* action_to,
+                            uint8_t* next_player, int32_t* slot) {
+    if (!d) return fail(XQ_ERR_INVALID_ARGUMENT, "null dqn");
+    if (d->colour_swap_rows <= 0) return fail(XQ_ERR_RUNTIME, "xq_dqn_last_colour_swap: the last TD step was not a colour-swap-mode one");
+    if (n < 0 || n > d->colour_swap_rows)
+        return fail(XQ_ERR_INVALID_ARGUMENT, "xq_dqn_last_colour_swap: n exceeds the last TD step's %d rows", d->colour_swap_rows);
+    if (next_player && !d->colour_swap_sided)
+        return fail(XQ_ERR_INVALID_ARGUMENT, "xq_dqn_last_colour_swap: next_player asked, but the last TD step was not under the legal-move bootstrap");
+    XQ_HIP(hipStreamSynchronize(d->stream));
+    if (!n) return XQ_OK;
+    if (flags) XQ_HIP(hipMemcpy(flags, d->ns_cflag, (size_t)n, hipMemcpyDeviceToHost));
+    std::vector<uint32_t> w((size_t)n * kBoardWords);
+    const struct { uint8_t* out; const uint32_t* dev; } boards[2] = {{boards90, d->ns_boards}, {next_boards90, d->ns_next}};
+    for (const auto& bd : boards) {
+        if (!bd.out) continue;
+        XQ_HIP(hipMemcpy(w.data(), bd.dev, w.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        for (int i = 0; i < n; ++i) unpack_board(&w[(size_t)i * kBoardWords], bd.out + (size_t)i * 90);
+    }
+    if (action_to) XQ_HIP(hipMemcpy(action_to, d->ns_action, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (next_player) XQ_HIP(hipMemcpy(next_player, d->ns_side, (size_t)n, hipMemcpyDeviceToHost));
+    if (slot) XQ_HIP(hipMemcpy(slot, d->ns_first, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return XQ_OK;
+}
+
 int xq_dqn_td_grads_replay(xq_dqn* d, xq_replay* r, int batch, int td_net, int mode) {
     if (!d || !r) return fail(XQ_ERR_INVALID_ARGUMENT, "null handle");
     SlotSrc src = explicit_slots(nullptr);
@@ -2673,6 +2767,7 @@ int xq_dqn_td_grads_replay(xq_dqn* d, xq_replay* r, int batch, int td_net, int m
     // them, and whatever touches them next — the next draw overwrites the list, the next env step the slots — behind this step
     XQ_TRY(replay_consumer_begin(r, d->stream, src.slots != nullptr, prioritized));
     if (r->n_step > 1) return td_grads_nstep(d, r, src, batch, td_net, mode, prioritized ? &per : nullptr);
+    if (r->colour_swap_prob > 0.0) return td_grads_colour_swap(d, r, src, batch, td_net, mode, prioritized ? &per : nullptr);
     if (r->mirror_prob > 0.0) return td_grads_mirror(d, r, src, batch, td_net, mode, prioritized ? &per : nullptr);
     return td_grads_impl(d, r->dev.boards, r->dev.next_boards, r->dev.action_to, r->dev.reward, r->dev.done, src, batch, td_net,
                          mode, prioritized ? &per : nullptr, nullptr, r->dev.next_player);

@@ -221,6 +221,10 @@ struct xq_replay {
     // the next one's flag stream
     double mirror_prob = 0.0;
     uint64_t mirror_calls = 0;
+    // colour-swap augmentation (xq_replay_set_colour_swap, DESIGN.md §4 "Colour-swap augmentation"): the same pair for the exchange of
+    // the colours with row -> 9 - row; a counter of its own (the mirror's is untouched)
+    double colour_swap_prob = 0.0;
+    uint64_t colour_swap_calls = 0;
     xq::Stream stream;
     // Device data of the ring that other handles read or write, possibly on streams of their own — each a SharedResource (above):
     //   contents : boards / next_boards / action_to / reward / done   written by env steps (xq_env_selfplay_step) and push_host,

@@ -508,6 +508,21 @@ int xq_replay_get_mirror(const xq_replay* r, double* prob, uint64_t* calls) {
     return XQ_OK;
 }
 
+// ---- colour-swap augmentation: C ABI (the kernel is the TD step's: xq_colour_swap.hip.h) ---------------------------------------------
+int xq_replay_set_colour_swap(xq_replay* r, double prob) {
+    if (!r) return fail(XQ_ERR_INVALID_ARGUMENT, "null replay");
+    if (!(prob >= 0.0 && prob <= 1.0)) return fail(XQ_ERR_INVALID_ARGUMENT, "xq_replay_set_colour_swap: prob must be in [0, 1]");     // (NaN too)
+    r->colour_swap_prob = prob;
+    return XQ_OK;
+}
+
+int xq_replay_get_colour_swap(const xq_replay* r, double* prob, uint64_t* calls) {
+    if (!r) return fail(XQ_ERR_INVALID_ARGUMENT, "null replay");
+    if (prob) *prob = r->colour_swap_prob;
+    if (calls) *calls = r->colour_swap_calls;
+    return XQ_OK;
+}
+
 int xq_replay_per_stats(xq_replay* r, float* total, float* max_priority, int* n_eligible) {
     if (!r || !r->per.enabled) return fail(XQ_ERR_INVALID_ARGUMENT, "prioritized replay is not enabled on this ring");
     XQ_HIP(hipDeviceSynchronize());

@@ -265,6 +265,13 @@ int xq_trainer_set_mirror(xq_trainer* t, double prob) {
     return xq_replay_set_mirror(t->replay, prob);
 }
 
+// ... and so does the colour swap (the side byte it flips is read at the slot the step reads it at anyway)
+int xq_trainer_set_colour_swap(xq_trainer* t, double prob) {
+    if (!t) return fail(XQ_ERR_INVALID_ARGUMENT, "null trainer");
+    if (t->grads_queued) return fail(XQ_ERR_RUNTIME, "xq_trainer_set_colour_swap: call between iterations (after learn_apply)");
+    return xq_replay_set_colour_swap(t->replay, prob);
+}
+
 // The newest (n_step - 1) * n_games slots of the tree's readable range — unless that is all of it (the first iterations of a run): then
 // nothing is held, as the uniform window is sampled uncut, and the rows that reach past the range are dead
 static int held_slots(const xq_trainer* t) {

@@ -211,6 +211,23 @@ class DQN:
              _ptr(s, C.c_int32))
         return dict(flags=f, boards=b, next_boards=nb, action=a, slot=s)
 
+    def last_colour_swap(self, n, next_player=False):
+        """The first n rows of the batch the last td_grads_replay staged from a ring with ReplayBuffer.set_colour_swap(prob > 0): dict
+        of flags (1 = the row's colours were exchanged), boards and next_boards ([n, 90] piece codes as staged), action (as staged) and
+        slot (the sampled slot); with next_player=True also next_player (the staged side bytes: only behind a step under the legal-move
+        bootstrap).  With the mirror on as well this is the same staged batch last_mirror reports, with this transform's flags.  Raises
+        XqError when the last TD step was not a colour-swap-mode one."""
+        f = np.zeros(n, np.uint8)
+        b, nb = np.zeros((n, 90), np.uint8), np.zeros((n, 90), np.uint8)
+        a, s = np.zeros(n, np.int32), np.zeros(n, np.int32)
+        p = np.zeros(n, np.uint8) if next_player else None
+        call("xq_dqn_last_colour_swap", self._h, int(n), _ptr(f, C.c_uint8), _ptr(b, C.c_uint8), _ptr(nb, C.c_uint8), _ptr(a, C.c_int32),
+             _ptr(p, C.c_uint8) if next_player else None, _ptr(s, C.c_int32))
+        out = dict(flags=f, boards=b, next_boards=nb, action=a, slot=s)
+        if next_player:
+            out["next_player"] = p
+        return out
+
     def kernel_stats(self, enable=-1):
         """Returns the HIP-event timings collected so far; enable: 1 on, 0 off, 2 on + clear, -1 leave."""
         arr = (KernelStat * 64)()
@@ -603,6 +620,12 @@ class Trainer:
         """Mirror augmentation of every learn_grads from the trainer's ring (ReplayBuffer.set_mirror; 0 = off): each minibatch row is
         reflected left-right with probability prob.  Uniform, prioritized and on-policy, any n_step.  Call between iterations."""
         call("xq_trainer_set_mirror", self._h, float(prob))
+
+    def set_colour_swap(self, prob):
+        """Colour-swap augmentation of every learn_grads from the trainer's ring (ReplayBuffer.set_colour_swap; 0 = off): each minibatch
+        row has its colours exchanged with probability prob.  Uniform, prioritized and on-policy, any n_step, self-play and versus, with
+        or without the mirror.  Call between iterations."""
+        call("xq_trainer_set_colour_swap", self._h, float(prob))
 
     def set_td_bootstrap(self, kind):
         """DQN.set_td_bootstrap on the trainer's net; "legal" first makes the trainer's ring record the side to move in s', so call it

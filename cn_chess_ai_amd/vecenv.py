@@ -201,6 +201,21 @@ class ReplayBuffer:
         call("xq_replay_get_mirror", self._h, C.byref(p), C.byref(c))
         return p.value, c.value
 
+    # ---- colour-swap augmentation (build-defined, DESIGN.md §4 "Colour-swap augmentation") ----
+    def set_colour_swap(self, prob):
+        """Every DQN.td_grads_replay from this ring exchanges the colours of each minibatch row with probability prob (row -> 9 - row
+        and Red <-> Black on both boards, the action's square, and 1 - side under the legal-move bootstrap), in a staged copy of the
+        batch; the ring is never written.  0 = off.  NaN or a value outside [0, 1] is refused.  Takes effect at the next
+        td_grads_replay; composes with set_mirror and set_n_step."""
+        call("xq_replay_set_colour_swap", self._h, float(prob))
+
+    def colour_swap(self):
+        """(prob, calls): prob as last set (0.0 on a ring that was never asked) and the number of colour-swap-mode TD steps queued from
+        this ring so far — the call word of the next one's flag stream (a counter of its own, apart from the mirror's)."""
+        p, c = C.c_double(), C.c_uint64()
+        call("xq_replay_get_colour_swap", self._h, C.byref(p), C.byref(c))
+        return p.value, c.value
+
     def get(self, slot):
         b, nb = np.zeros(90, np.uint8), np.zeros(90, np.uint8)
         a, r, d = C.c_int32(), C.c_float(), C.c_uint8()

@@ -38,6 +38,7 @@ ROCPROF_NAMES = {
     "nstep_assemble": "nstep_assemble_kernel(",
     "per_writeback": "per_writeback_kernel(",
     "mirror_stage": "mirror_stage_kernel(",
+    "colour_swap_stage": "colour_swap_stage_kernel(",
     "legal_qmax": "legal_qmax_kernel(",
     "legal_side_stage": "legal_side_stage_kernel(",
     "gemm_legal_head": "gemm_f32_kernel<0, 0, 0, 1, 1, 0>(",
@@ -124,7 +125,7 @@ def pick_splits(M, N, K):
 
 def step_work(layers, minibatch, n_games, plies=1, bf16=False, bf16_bwd=False, td="online", screened=True, derive=True,
               prioritized=False, l0_mfma=True, optimizer="sgd", grad_clip=False, soft_target=False, n_step=1,
-              mirror=False, bootstrap="all"):
+              mirror=False, bootstrap="all", colour_swap=False):
     """{bracket name: dict(flops, hbm_bytes, bound, peak, peak_unit, what)} for one training step of the given configuration.
     optimizer="adam" (xq_dqn_set_optimizer): adam_apply stands in place of sgd_apply; the default step knows no adam_apply.
     grad_clip=True (xq_dqn_set_grad_clip): grad_norm stands in front of the apply and takes the slab sums over from it; the default
@@ -137,7 +138,10 @@ def step_work(layers, minibatch, n_games, plies=1, bf16=False, bf16_bwd=False, t
     and, on a prioritized draw with n_step == 1, per_writeback behind it; the default step knows no mirror_stage.
     bootstrap="legal" (xq_dqn_set_td_bootstrap, fp32 nets): gemm_legal_head and legal_qmax stand in place of the max pass over the 8100
     outputs (never screened), td_target_delta behind them, and legal_side_stage in front of a staged (n-step, mirror) batch; the default
-    step knows none of them."""
+    step knows none of them.
+    colour_swap=True (xq_replay_set_colour_swap with prob > 0): colour_swap_stage stands in front of the step (behind nstep_assemble and
+    mirror_stage when they are on) and, on a prioritized draw that nothing else stages, per_writeback behind it; under
+    bootstrap="legal" it stages the side bytes too and legal_side_stage is not launched; the default step knows no colour_swap_stage."""
     if bootstrap not in ("all", "legal"):
         raise ValueError("bootstrap: 'all' or 'legal'")
     legal = bootstrap == "legal"
@@ -332,7 +336,16 @@ def step_work(layers, minibatch, n_games, plies=1, bf16=False, bf16_bwd=False, t
             "left-right reflection of the flagged minibatch rows in the staging batch the TD step reads")
         if prioritized and n_step == 1:
             put("per_writeback", 0.0, 20.0 * B, "hbm", "TD-error priorities of a prioritized mirrored draw back to the sampled slots")
-    if legal and (n_step > 1 or mirror):
+    if colour_swap:
+        # per row: the mirror's bytes — from the ring when it is the first staging transform, in place behind nstep_assemble or
+        # mirror_stage; under the legal bootstrap also the side byte: the ring's byte in and the staged one out, in place the 4 B of the
+        # slot it is read at as well (legal_side_stage is then not launched)
+        first = n_step == 1 and not mirror
+        put("colour_swap_stage", 0.0, B * ((215.0 if first else 201.0) + ((2.0 if first else 6.0) if legal else 0.0)), "hbm",
+            "exchange of the colours (row -> 9 - row, Red <-> Black) of the flagged minibatch rows in the staging batch the TD step reads")
+        if prioritized and first:
+            put("per_writeback", 0.0, 20.0 * B, "hbm", "TD-error priorities of a prioritized colour-swapped draw back to the sampled slots")
+    if legal and (n_step > 1 or mirror) and not colour_swap:
         # per staged row: the slot whose side it takes (4 B), the ring's byte, the staged byte
         put("legal_side_stage", 0.0, 6.0 * B, "hbm", "side to move in s' of every staged row, from the ring's column (legal-move bootstrap)")
     nw =STATE * H1 + sum(h[l] * h[l - 1] for l in range(1, k)) + Hl * NO

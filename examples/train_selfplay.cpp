@@ -16,7 +16,9 @@
 //   clip=<max_norm>               clip the batched loop's gradient by its global L2 norm (xq::ChessAI::setGradClip; inf = measure only)
 //   mirror=<prob>                 mirror augmentation of the batched loop's minibatches: each row reflected left-right with probability
 //                                 prob in [0, 1] (xq::ChessAI::setMirror; 0 = off)
-//   bootstrap=all|legal           target of the batched loop's TD step: the maximum over all outputs (default, chessai.cpp:126) or over the
+//   swap=<prob>                   colour-swap augmentation of the batched loop's minibatches: each row's colours exchanged (row -> 9 - row,
+//                                 Red <-> Black) with probability prob in [0, 1] (xq::ChessAI::setColourSwap; 0 = off)
+//   bootstrap=all|legal         target of the batched loop's TD step: the maximum over all outputs (default, chessai.cpp:126) or over the
 //                                 moves the side to move can play in s' (xq::ChessAI::setTdBootstrap)
 //   reward=evaluate|delta[:scale[:cost[:bound]]]
 //                                 what the batched loop's plies write into the ring: evaluateBoard (default, chessai.cpp:115) or the
@@ -37,7 +39,7 @@ int main(int argc, char** argv) {
     std::vector<int> hidden;
     bool derive = false, json = false, adam = false, legal = false;
     unsigned long long seed = 0;
-    double clip = 0.0, mirror = 0.0;
+    double clip = 0.0, mirror = 0.0, swap = 0.0;
     xq::Reward reward;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
@@ -82,6 +84,11 @@ int main(int argc, char** argv) {
             mirror = std::strtod(a.c_str() + 7, &end);
             if (end == a.c_str() + 7 || *end || !(mirror >= 0.0 && mirror <= 1.0)) { std::fprintf(stderr, "mirror=: expected a probability in [0, 1], got %s\n", a.c_str() + 7); return 2; }
         }
+        else if (a.rfind("swap=", 0) == 0) {
+            char* end = nullptr;
+            swap = std::strtod(a.c_str() + 5, &end);
+            if (end == a.c_str() + 5 || *end || !(swap >= 0.0 && swap <= 1.0)) { std::fprintf(stderr, "swap=: expected a probability in [0, 1], got %s\n", a.c_str() + 5); return 2; }
+        }
         else if (a == "--hidden") {
             for (const char* p = next(); *p;) { hidden.push_back(std::atoi(p)); while (*p && *p != ',') ++p; if (*p == ',') ++p; }
         } else if (a.rfind("--", 0) == 0) { std::fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
@@ -102,6 +109,7 @@ int main(int argc, char** argv) {
         if (adam) ai.setOptimizer(xq::Optimizer::adam());
         if (clip != 0.0) ai.setGradClip(clip);
         if (mirror != 0.0) ai.setMirror(mirror);
+        if (swap != 0.0) ai.setColourSwap(swap);
         if (legal) ai.setTdBootstrap(xq::TdBootstrap::legal());
         ai.setReward(reward);
         if (replay > 0) ai.setReplay(replay, minibatch);

@@ -404,6 +404,10 @@ public:
     // left-right with probability prob, in the staged batch only
     void setMirror(double prob) { check(xq_replay_set_mirror(h_, prob)); }
     double mirror() const { double p = 0; check(xq_replay_get_mirror(h_, &p, nullptr)); return p; }
+    // colour-swap augmentation of every TD step that takes its minibatch from this ring (xq_replay_set_colour_swap; 0 = off): each row's
+    // colours exchanged (row -> 9 - row, Red <-> Black) with probability prob, in the staged batch only
+    void setColourSwap(double prob) { check(xq_replay_set_colour_swap(h_, prob)); }
+    double colourSwap() const { double p = 0; check(xq_replay_get_colour_swap(h_, &p, nullptr)); return p; }
     int size() const { int s = 0; check(xq_replay_size(h_, &s, nullptr, nullptr)); return s; }
     int capacity() const { int c = 0; check(xq_replay_size(h_, nullptr, &c, nullptr)); return c; }
     xq_replay* handle() const { return h_; }
@@ -777,6 +781,7 @@ public:
                         uint64_t versus[4] = {0, 0, 0, 0};      // with an opponent: the learner's wins, draws, losses, games ended
                         int nStep = 1;                          // the n-step setting of the trainer's ring as the run ended (setNStep)
                         double mirror = 0;                      // ... and its mirror probability (setMirror)
+                        double colour_swap = 0;                 // ... and its colour-swap probability (setColourSwap)
                         Reward reward; };                       // the reward rule of the trainer's env as the run ended (setReward)
     TrainStats lastTrainStats() const { return stats_; }
     // data-parallel train(): this process is rank comm->rank() of comm->world(); its batched games take the id range
@@ -805,6 +810,12 @@ public:
         mirror_ = prob;
     }
     double mirror() const { return mirror_; }
+    // colour-swap augmentation of the batched train(): xq_trainer_set_colour_swap on the trainer (0 = off, the default); on-policy too
+    void setColourSwap(double prob) {
+        if (!(prob >= 0.0 && prob <= 1.0)) throw std::invalid_argument("setColourSwap: prob must be in [0, 1]");
+        colourSwap_ = prob;
+    }
+    double colourSwap() const { return colourSwap_; }
     // Reward of the batched train(): xq_trainer_set_reward on the trainer (Reward::evaluate() = the reference's, the default).  The
     // single-board loops (trainEpisode, trainStep, startSelfPlay, train with parallelGames == 1) stay the reference's and throw
     // std::invalid_argument when asked for Reward::delta.
@@ -871,6 +882,7 @@ private:
         check(xq_trainer_set_target_tau(t, dqn->targetTau()));
         if (nStep_ > 1) check(xq_trainer_set_n_step(t, nStep_));
         if (mirror_ > 0.0) check(xq_trainer_set_mirror(t, mirror_));
+        if (colourSwap_ > 0.0) check(xq_trainer_set_colour_swap(t, colourSwap_));
         if (reward_.kind != XQ_REWARD_EVALUATE) check(xq_trainer_set_reward(t, reward_.kind, reward_.scale, reward_.plyCost, reward_.bound));
         const TdLoss loss = dqn->tdLoss();
         check(xq_dqn_set_td_loss(td, loss.kind, loss.kappa));
@@ -919,6 +931,7 @@ private:
             check(xq_trainer_replay(t, &tr));
             check(xq_replay_get_n_step(tr, &stats_.nStep, nullptr));
             check(xq_replay_get_mirror(tr, &stats_.mirror, nullptr));
+            check(xq_replay_get_colour_swap(tr, &stats_.colour_swap, nullptr));
             check(xq_env_get_reward(te, &stats_.reward.kind, &stats_.reward.scale, &stats_.reward.plyCost, &stats_.reward.bound));
         }
         {
@@ -946,6 +959,7 @@ private:
     bool l0Derive_ = false;
     int nStep_ = 1;
     double mirror_ = 0.0;
+    double colourSwap_ = 0.0;
     Reward reward_;
     int prefillPlies_ = 0;
     std::unique_ptr<Player> opponent_;

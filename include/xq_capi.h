@@ -330,6 +330,30 @@ int xq_replay_get_n_step(const xq_replay* r, int* n_step /* optional */, int* st
  * load, a target update and xq_replay_set_n_step. */
 int xq_replay_set_mirror(xq_replay* r, double prob);
 int xq_replay_get_mirror(const xq_replay* r, double* prob /* optional */, uint64_t* calls /* optional: the `call` the next mirror-mode step will use */);
+/* Colour-swap augmentation (DESIGN.md §4 "Colour-swap augmentation") — build-defined, off by default; the mirror's sibling.  Xiangqi is
+ * also symmetric under exchanging the colours while turning the board top to bottom (row -> 9 - row): the same position with Red and
+ * Black exchanged is the same game for the other side, so (swap(s), swap(a), r, swap(s'), done, 1 - side) is as true as the transition
+ * that was played.  While prob > 0 every xq_dqn_td_grads_replay from this ring stages its minibatch in the handle's staging buffers and
+ * transforms the rows whose flag is set; the TD step it always ran then runs on the staged batch.  The ring is never written.
+ *   flag_b = (prob == 1) || philox4x32_10(ctr = {b, 0, call, 4}, key = ring seed).v[0] < floor(prob * 2^32), saturated (the threshold
+ *   rule of the env's epsilon).  Counter word 4 keeps the stream apart from the draw (1), the stratified draw (2) and the mirror (3).
+ *   `call` is a counter of its own: the colour-swap-mode TD steps queued from this ring since it was created (the first is 0; steps
+ *   taken while prob == 0 do not count; the mirror's counter is untouched).  The flag depends on the row index alone.
+ *   A flagged row: board'[(9 - r) * 9 + c] = sigma(board[r * 9 + c]) for s and s', with sigma(0) = 0, sigma(x) = x + 7 for 1..7 and
+ *   sigma(x) = x - 7 for 8..14 (nibbles 90..95 stay 0); action a' = a + 81 - 18 (a div 9) when 0 <= a < 90, any other value (-1: dead or
+ *   empty, 90..95) as it is; reward and done unchanged; under the legal-move bootstrap (xq_dqn_set_td_bootstrap) the staged side byte
+ *   becomes 1 - side, taken after the n-step and mirror rules have chosen which slot's byte it is.  Dead and empty rows follow the same
+ *   flag rule and still contribute nothing.  An unflagged row is the sampled transition bit for bit.
+ *   The step: identity slot source on the staged batch, the discount rules of the mirror and the n-step returns; a prioritized draw gets
+ *   its importance weights as always and the priorities of its live rows go back to the SAMPLED slots behind the step.  With n_step > 1
+ *   the n-step batch is assembled first and the flag applies to the assembled transition.  With the mirror on as well both apply, each by
+ *   its own flags; they commute (the mirror acts on columns, this on rows and codes), so the staged batch is defined without an order.
+ * prob == 0 is off: the kernels, launches and bits of a ring that was never asked (a ring with the mirror on keeps exactly the mirror's).
+ * NaN or a value outside [0, 1] is XQ_ERR_INVALID_ARGUMENT.  Takes effect at the next xq_dqn_td_grads_replay; xq_dqn_td_grads with raw
+ * pointers, the host entry points, xq_dqn_backpropagate, the arena and the single-board loops are never affected.  The setting lives on
+ * the ring: it survives xq_dqn_set_optimizer, set_params, a model load, a target update, xq_replay_set_n_step and xq_replay_set_mirror. */
+int xq_replay_set_colour_swap(xq_replay* r, double prob);
+int xq_replay_get_colour_swap(const xq_replay* r, double* prob /* optional */, uint64_t* calls /* optional: the `call` the next colour-swap-mode step will use */);
 
 /* ------------------------------------------------------------------------------------------------------------
  * xq_dqn — DQN (dqn.h:97-116) = qNetwork + targetNetwork (NeuralNetwork, dqn.h:42-95, dqn.cu), fp32 on MFMA.
@@ -596,6 +620,15 @@ int xq_dqn_last_n_step(xq_dqn* d, int n, float* reward, uint8_t* done, int32_t* 
  * slot.  All outputs are host pointers, any of which may be NULL.  XQ_ERR_RUNTIME when the last TD step was not a mirror-mode one,
  * XQ_ERR_INVALID_ARGUMENT for n beyond its rows. */
 int xq_dqn_last_mirror(xq_dqn* d, int n, uint8_t* flags, uint8_t* boards90, uint8_t* next_boards90, int32_t* action_to, int32_t* slot);
+/* The first n rows of the batch the last xq_dqn_td_grads_replay staged in colour-swap mode (xq_replay_set_colour_swap; tests / interop;
+ * synchronises): the row's flag (1 = swapped), the two staged boards as 90 piece codes per row, the staged action, the staged side to
+ * move in s' (next_player; only behind a step under the legal-move bootstrap, which is what stages it: asked for behind any other step
+ * it is XQ_ERR_INVALID_ARGUMENT) and the sampled slot.  All outputs are host pointers, any of which may be NULL.  XQ_ERR_RUNTIME when
+ * the last TD step was not a colour-swap-mode one, XQ_ERR_INVALID_ARGUMENT for n beyond its rows.  Behind a step with both symmetries on,
+ * this call and xq_dqn_last_mirror report the same final staged batch (boards, action, slot: both transforms applied), each with its
+ * own flags. */
+int xq_dqn_last_colour_swap(xq_dqn* d, int n, uint8_t* flags, uint8_t* boards90, uint8_t* next_boards90, int32_t* action_to,
+                            uint8_t* next_player /* optional */, int32_t* slot);
 /* What the TD target bootstraps from (no upstream analogue: chessai.cpp:126 takes the maximum over all outputs).  XQ_BOOTSTRAP_ALL
  * (default): y = done ? r : r + gamma * max_k Q_net(s')[k] over ALL outputs — the kernels, launches and bits of a handle that was never
  * asked.  XQ_BOOTSTRAP_LEGAL: the maximum over the moves that can be played in s',
@@ -611,7 +644,8 @@ int xq_dqn_last_mirror(xq_dqn* d, int n, uint8_t* flags, uint8_t* boards90, uint
  * The side to move in s' cannot be recovered from (s, a, s') and is an input: xq_dqn_td_grads_sided / xq_dqn_td_update_host_sided take
  * it per transition (0 = Red, 1 = Black), and a replay ring records it once xq_replay_track_next_player was called: xq_dqn_td_grads_replay
  * then reads the ring's column — the sampled slot's byte; for an n-step batch the byte of the slot whose next board was staged; for a
- * mirrored batch the sampled slot's (a reflection does not change the side); one small gather (legal_side_stage_kernel) stages them.
+ * mirrored batch the sampled slot's (a reflection does not change the side); one small gather (legal_side_stage_kernel) stages them; a
+ * colour-swapped batch (xq_replay_set_colour_swap) has them staged by its own kernel, 1 - side on the flagged rows.
  * While XQ_BOOTSTRAP_LEGAL is in force the step is XQ_ERR_INVALID_ARGUMENT through every entry that has no side — xq_dqn_td_grads,
  * xq_dqn_td_update_host, xq_dqn_td_grads_replay from a ring that does not track it — and on a bf16 precision (fp32 nets only).  An unknown kind, or XQ_BOOTSTRAP_LEGAL on a net with fewer than 96 outputs, is
  * XQ_ERR_INVALID_ARGUMENT.  The setting may change between any two steps and survives every other setter. */
@@ -847,6 +881,11 @@ int xq_trainer_set_n_step(xq_trainer* t, int n_step);
  * any n_step.  No window changes: the transform reads only what the step read anyway.  Call between iterations: XQ_ERR_RUNTIME while a
  * learn_grads waits for its learn_apply. */
 int xq_trainer_set_mirror(xq_trainer* t, double prob);
+/* xq_replay_set_colour_swap on the trainer's ring (DESIGN.md §4 "Colour-swap augmentation"): every learn_grads from then on exchanges
+ * the colours of a random part of its minibatch — uniform, prioritized and on-policy rings, any n_step, overlap_collect 0 and 1,
+ * self-play and versus, with or without the mirror and under both bootstraps.  No window changes.  Call between iterations:
+ * XQ_ERR_RUNTIME while a learn_grads waits for its learn_apply. */
+int xq_trainer_set_colour_swap(xq_trainer* t, double prob);
 /* xq_env_set_reward on the trainer's env (DESIGN.md §4 "Reward rule"): the next collect writes the new reward, slots already in the ring
  * keep theirs.  Uniform, prioritized and on-policy rings, overlap_collect 0 and 1, self-play and versus; n-step returns, the mirror,
  * prioritized replay and both bootstraps read the ring's reward column as before.  Call between iterations: XQ_ERR_RUNTIME while a
