@@ -196,6 +196,9 @@ PROTOTYPES = {
     "xq_env_set_reward": [_vp, _i, _d, _d, _d],
     "xq_env_get_reward": [_vp, _pi, _pd, _pd, _pd],
     "xq_trainer_set_reward": [_vp, _i, _d, _d, _d],
+    "xq_dqn_set_zero_sum": [_vp, _i],
+    "xq_dqn_get_zero_sum": [_vp, _pi],
+    "xq_trainer_set_zero_sum": [_vp, _i],
     "xq_dqn_kernel_stats": [_vp, _i, C.POINTER(KernelStat), _i, _pi],
     "xq_dqn_set_fused_apply": [_vp, _i],
     "xq_dqn_set_optimizer": [_vp, _i, _d, _d, _d],
@@ -278,8 +281,10 @@ LAZY_REWARD = frozenset(("xq_env_set_reward", "xq_env_get_reward", "xq_trainer_s
 # ... and those of the colour-swap augmentation
 LAZY_COLOUR_SWAP = frozenset(("xq_replay_set_colour_swap", "xq_replay_get_colour_swap", "xq_dqn_last_colour_swap",
                               "xq_trainer_set_colour_swap"))
+# ... and those of the zero-sum target
+LAZY_ZERO_SUM = frozenset(("xq_dqn_set_zero_sum", "xq_dqn_get_zero_sum", "xq_trainer_set_zero_sum"))
 _LAZY_ALL = (LAZY | LAZY_GRAD_CLIP | LAZY_TARGET_TAU | LAZY_TD_LOSS | LAZY_N_STEP | LAZY_MIRROR | LAZY_LEGAL | LAZY_REWARD
-             | LAZY_COLOUR_SWAP)
+             | LAZY_COLOUR_SWAP | LAZY_ZERO_SUM)
 _RESTYPES = {"xq_last_error": C.c_char_p, "xq_env_boards_dev": C.c_void_p, "xq_env_meta_dev": C.c_void_p}
 
 _lib = None

@@ -216,6 +216,9 @@ struct xq_dqn {
     xq::DevBuf<int> legal_nmoves;
     xq::DevBuf<uint8_t> hside, ns_side;         // side bytes of the host batch / of the staged (n-step, mirror) batch
     int legal_rows = 0;
+    // zero-sum (negamax) target (xq_dqn_set_zero_sum, DESIGN.md §4 "Zero-sum target"): the TD step's discount is -(float)gamma, the
+    // n-step discounts alternate in sign, and a side without a move under the legal bootstrap bootstraps from -inf (tanh: -1)
+    int zero_sum = 0;
     xq::Profiler prof;
     // fused launches of the TD step's tail (td_tail_kernel): while `tail_open`, the launch helpers of the small fp32 GEMMs, the
     // output-layer / layer-0 segmented sums and the bias column sums append their blocks to `tail` instead of launching.  Written by
@@ -2068,6 +2071,7 @@ static int qmax_legal(xq_dqn* d, const TdStep& s, bool gate_early) {
     if (s.dbl) { A.ev_slabs = d->z96_slabs + (size_t)want * slab_stride; A.ev_bias = d->bl(XQ_NET_TARGET, nl - 1); }
     A.slab_stride = slab_stride; A.nslabs = used[0];
     A.z96 = d->z96; A.zmax = d->zmax; A.zidx = d->zidx; A.n_moves = d->legal_nmoves;
+    A.no_move_zmax = d->zero_sum ? -__builtin_inff() : 0.f;      // zero-sum: a side that cannot move has lost, y = r + g
     // per row: the board, 6 B of fields, nets x nslabs x 96 slab values in, 96 values and 12 B out
     ProfScope ps(d, "legal_qmax", 0.0, (double)n * (48 + 6 + 384.0 * nets * used[0] + 384 + 12), true);
     hipExtLaunchKernelGGL(legal_qmax_kernel, dim3((n + 3) / 4), dim3(256), 0, d->cur, ps.start(), ps.stop(), 0, A, s.slots, n);
@@ -2170,7 +2174,9 @@ static int td_grads_impl(xq_dqn* d, const uint32_t* boards, const uint32_t* next
     TdStep s;
     s.action_to = action_to; s.reward = reward; s.done = done; s.slots = slots; s.per = per;
     s.next_boards = next_boards; s.next_player = next_player; s.legal = legal;
-    s.gamma = discount ? *discount : (float)d->gamma;
+    // zero-sum: the signed discount -g (r + (-g) t and r - g t are the same fp32 bits, contracted or not); an n-step batch's discount
+    // comes signed from td_grads_nstep
+    s.gamma = discount ? *discount : d->zero_sum ? -(float)d->gamma : (float)d->gamma;
     d->nstep_rows = 0;                               // (xq_dqn_td_grads_replay sets it behind an n-step batch)
     d->mirror_rows = 0;                              // (... and this one behind a mirror-mode batch)
     d->colour_swap_rows = 0;                         // (... and this one behind a colour-swap-mode batch)
@@ -2647,7 +2653,7 @@ static int td_grads_nstep(xq_dqn* d, xq_replay* r, SlotSrc src, int batch, int t
     else { A.first = r->size < cap ? 0 : r->write_pos; A.count = r->size; }
     r->read_count = -1;                              // a narrowed range holds for one step
     if (A.first < 0 || A.first >= cap || A.count > cap) return fail(XQ_ERR_INVALID_ARGUMENT, "n-step readable range (%d, %d) outside the ring", A.first, A.count);
-    const float gf = (float)d->gamma;
+    const float gf = d->zero_sum ? -(float)d->gamma : (float)d->gamma;      // zero-sum: disc_k = (-1)^k g^k, the chain's movers alternate
     float dk[kNStepMax + 1];                         // disc_k: float times float, one fp32 rounding per factor
     dk[0] = 1.f;
     for (int k = 1; k <= kNStepMax; ++k) dk[k] = dk[k - 1] * gf;
@@ -2833,6 +2839,18 @@ int xq_dqn_set_td_bootstrap(xq_dqn* d, int kind) {
 int xq_dqn_get_td_bootstrap(const xq_dqn* d, int* kind) {
     if (!d || !kind) return fail(XQ_ERR_INVALID_ARGUMENT, "null pointer");
     *kind = d->bootstrap;
+    return XQ_OK;
+}
+int xq_dqn_set_zero_sum(xq_dqn* d, int on) {
+    if (!d) return fail(XQ_ERR_INVALID_ARGUMENT, "null dqn");
+    if (on != 0 && on != 1) return fail(XQ_ERR_INVALID_ARGUMENT, "xq_dqn_set_zero_sum: on must be 0 or 1, got %d", on);
+    if (td_step_pending(d)) return fail(XQ_ERR_RUNTIME, "xq_dqn_set_zero_sum: a TD step is waiting for its apply_grads");
+    d->zero_sum = on;
+    return XQ_OK;
+}
+int xq_dqn_get_zero_sum(const xq_dqn* d, int* on) {
+    if (!d || !on) return fail(XQ_ERR_INVALID_ARGUMENT, "null pointer");
+    *on = d->zero_sum;
     return XQ_OK;
 }
 int xq_dqn_last_legal(xq_dqn* d, int n, int32_t* n_moves, int32_t* a_star, float* zmax, float* z96) {

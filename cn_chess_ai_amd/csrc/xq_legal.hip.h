@@ -19,8 +19,10 @@ struct LegalArgs {
     const float* ev_slabs; const float* ev_bias;
     long long slab_stride; int nslabs;
     // out, by minibatch row: z96 [n][96] the selecting net's pre-activations, zmax the bootstrap's pre-activation (0 where y = r: done,
-    // dead, no move), zidx the winning `to` (-1 there), n_moves the list length (-1 on done and dead rows)
+    // dead; no move: no_move_zmax), zidx the winning `to` (-1 there), n_moves the list length (-1 on done and dead rows)
     float* z96; float* zmax; int* zidx; int* n_moves;
+    // what zmax gets where the side to move in s' has no move: 0 (y = r), or -inf under the zero-sum target (tanh: -1, y = r + g)
+    float no_move_zmax;
 };
 
 // k-slabs summed in groups of four, (p0 + p1) + (p2 + p3), the groups in order, plus the bias — q_head_finish_kernel's association where
@@ -89,8 +91,8 @@ __global__ __launch_bounds__(256) void legal_qmax_kernel(LegalArgs A, SlotSrc sr
         if (lane < 32) qev[wid][64 + lane] = legal_head_sum(e1, A.nslabs, eb1);
     }
     wave_sync();
-    if (n_moves <= 0) {                                      // the side has no move in s': y = r
-        if (lane == 0) { A.zmax[b] = 0.f; A.zidx[b] = -1; A.n_moves[b] = 0; }
+    if (n_moves <= 0) {                                      // the side has no move in s': y = r (zero-sum: it has lost, y = r + g)
+        if (lane == 0) { A.zmax[b] = A.no_move_zmax; A.zidx[b] = -1; A.n_moves[b] = 0; }
         return;
     }
     const float NEG = -__builtin_inff();

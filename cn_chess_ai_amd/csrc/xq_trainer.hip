@@ -252,6 +252,18 @@ int xq_trainer_set_td_bootstrap(xq_trainer* t, int kind) {
     return xq_dqn_set_td_bootstrap(t->dqn, kind);
 }
 
+// The zero-sum (negamax) target on the trainer's Q-net.  It is for transitions whose s' has the other side to decide: a versus transition
+// runs from one learner decision to the next, so it and xq_trainer_set_opponent refuse each other.  No window changes: only the sign of
+// the discount and the no-move value of the legal bootstrap do
+int xq_trainer_set_zero_sum(xq_trainer* t, int on) {
+    if (!t) return fail(XQ_ERR_INVALID_ARGUMENT, "null trainer");
+    if (t->grads_queued) return fail(XQ_ERR_RUNTIME, "xq_trainer_set_zero_sum: call between iterations (after learn_apply)");
+    if (on == 1 && t->vs_on)
+        return fail(XQ_ERR_INVALID_ARGUMENT, "xq_trainer_set_zero_sum: an opponent is set (xq_trainer_set_opponent): a versus transition ends "
+                                             "with the learner to move again, which the zero-sum target is not for");
+    return xq_dqn_set_zero_sum(t->dqn, on);
+}
+
 // the reward rule of the trainer's env: the next collect writes it, slots already in the ring keep theirs
 int xq_trainer_set_reward(xq_trainer* t, int kind, double scale, double ply_cost, double bound) {
     if (!t) return fail(XQ_ERR_INVALID_ARGUMENT, "null trainer");
@@ -332,6 +344,11 @@ int xq_trainer_set_opponent(xq_trainer* t, const xq_arena_player* opp) {
     CheckedPlayer vs;
     XQ_TRY(make_player(opp, "xq_trainer_set_opponent: the opponent", &vs));
     if (vs.net && vs.net == t->dqn) return fail(XQ_ERR_INVALID_ARGUMENT, "xq_trainer_set_opponent: the opponent is the trainer's own network");
+    int zero_sum = 0;
+    XQ_TRY(xq_dqn_get_zero_sum(t->dqn, &zero_sum));
+    if (opp && zero_sum)
+        return fail(XQ_ERR_INVALID_ARGUMENT, "xq_trainer_set_opponent: the zero-sum target is on (xq_trainer_set_zero_sum): it is for self-play "
+                                             "transitions, whose s' has the other side to move");
     // the previous collects are finished and nothing of the next one is queued: the buffers below are free
     if (t->cstream) XQ_HIP(hipStreamSynchronize(t->cstream));
     XQ_HIP(hipStreamSynchronize(t->stream));

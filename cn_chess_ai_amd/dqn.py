@@ -115,7 +115,11 @@ class DQN:
         call("xq_dqn_load_model", self._h, str(filename).encode())
 
     def train(self, state, action, reward, next_state, done, mode=_capi.BACKPROP_REFERENCE):
-        """DQN::train (dqn.cpp:157-172): single transition, target network for max Q(s')."""
+        """DQN::train (dqn.cpp:157-172): single transition, target network for max Q(s').  The reference's rule only: under
+        set_zero_sum(True) it raises ValueError (the zero-sum target lives in the batched TD step)."""
+        if hasattr(_capi.load(), "xq_dqn_get_zero_sum") and self.zero_sum():
+            raise ValueError("DQN.train forms the reference's target r + gamma max Q(s') on the host; the zero-sum target "
+                             "(set_zero_sum) is the batched TD step's: use td_update / td_grads_replay / Trainer")
         q = self.getQValues(state)
         if done:
             q[action] = reward
@@ -505,6 +509,25 @@ def _last_legal(self, n, z96=True):
     return out
 
 
+def _set_zero_sum(self, on=True):
+    """The zero-sum (negamax) target of the batched TD step, for self-play (DESIGN.md §4 "Zero-sum target"): y = r - gamma tanh(zm)
+    in place of r + gamma tanh(zm), zm as the bootstrap, td_net and precision in force leave it; n-step discounts alternate in sign;
+    under set_td_bootstrap("legal") a side without a move in s' is worth -1 (y = r + gamma).  Off by default; DQN.train (the
+    single-board loop) refuses it."""
+    if not isinstance(on, (bool, np.bool_)):
+        raise ValueError(f"set_zero_sum: expected a bool, got {on!r}")
+    call("xq_dqn_set_zero_sum", self._h, 1 if on else 0)
+
+
+def _zero_sum(self):
+    """Whether the zero-sum target is in force."""
+    v = C.c_int32()
+    call("xq_dqn_get_zero_sum", self._h, C.byref(v))
+    return bool(v.value)
+
+
+DQN.set_zero_sum = _set_zero_sum
+DQN.zero_sum = _zero_sum
 DQN.set_td_bootstrap = _set_td_bootstrap
 DQN.td_bootstrap = _td_bootstrap
 DQN.last_legal = _last_legal
@@ -633,6 +656,13 @@ class Trainer:
         if kind not in _BOOTSTRAPS:
             raise ValueError(f"set_td_bootstrap: expected 'all' or 'legal', got {kind!r}")
         call("xq_trainer_set_td_bootstrap", self._h, _BOOTSTRAPS[kind])
+
+    def set_zero_sum(self, on=True):
+        """DQN.set_zero_sum on the trainer's net (DESIGN.md §4 "Zero-sum target"), for self-play: XqError with an opponent set, as
+        set_opponent is while it is on.  Uniform, prioritized and on-policy, any n_step.  Call between iterations."""
+        if not isinstance(on, (bool, np.bool_)):
+            raise ValueError(f"set_zero_sum: expected a bool, got {on!r}")
+        call("xq_trainer_set_zero_sum", self._h, 1 if on else 0)
 
     def set_reward(self, kind, scale=1e-3, ply_cost=0.0, bound=1.0):
         """VecEnv.set_reward on the trainer's env (DESIGN.md §4 "Reward rule"): "evaluate" (the reference's evaluateBoard, the default)

@@ -20,6 +20,9 @@
 //                                 Red <-> Black) with probability prob in [0, 1] (xq::ChessAI::setColourSwap; 0 = off)
 //   bootstrap=all|legal         target of the batched loop's TD step: the maximum over all outputs (default, chessai.cpp:126) or over the
 //                                 moves the side to move can play in s' (xq::ChessAI::setTdBootstrap)
+//   target=reference|zerosum      target of the batched loop's TD step in self-play: r + gamma max (default, chessai.cpp:126) or the zero-sum
+//                                 (negamax) one, r - gamma max: s' has the other side to move (xq::ChessAI::setZeroSum; the sequential
+//                                 loop, parallel_games = 1, refuses zerosum)
 //   reward=evaluate|delta[:scale[:cost[:bound]]]
 //                                 what the batched loop's plies write into the ring: evaluateBoard (default, chessai.cpp:115) or the
 //                                 transition's change of material balance, scaled (1e-3), less a cost per ply (0), clamped to +-bound (1)
@@ -37,7 +40,7 @@ int main(int argc, char** argv) {
     int episodes = 1000, parallel = 8192, replay = 0, minibatch = 0, save_every = 100, prefill = 0, npos = 0;
     const char* file = "model.bin";
     std::vector<int> hidden;
-    bool derive = false, json = false, adam = false, legal = false;
+    bool derive = false, json = false, adam = false, legal = false, zerosum = false;
     unsigned long long seed = 0;
     double clip = 0.0, mirror = 0.0, swap = 0.0;
     xq::Reward reward;
@@ -61,6 +64,11 @@ int main(int argc, char** argv) {
             const std::string v = a.substr(10);
             if (v != "all" && v != "legal") { std::fprintf(stderr, "bootstrap=: expected all or legal, got %s\n", v.c_str()); return 2; }
             legal = v == "legal";
+        }
+        else if (a.rfind("target=", 0) == 0) {
+            const std::string v = a.substr(7);
+            if (v != "reference" && v != "zerosum") { std::fprintf(stderr, "target=: expected reference or zerosum, got %s\n", v.c_str()); return 2; }
+            zerosum = v == "zerosum";
         }
         else if (a.rfind("reward=", 0) == 0) {
             // evaluate | delta[:scale[:cost[:bound]]]; the values are checked by ChessAI::setReward
@@ -111,6 +119,7 @@ int main(int argc, char** argv) {
         if (mirror != 0.0) ai.setMirror(mirror);
         if (swap != 0.0) ai.setColourSwap(swap);
         if (legal) ai.setTdBootstrap(xq::TdBootstrap::legal());
+        if (zerosum) ai.setZeroSum(true);
         ai.setReward(reward);
         if (replay > 0) ai.setReplay(replay, minibatch);
         ai.setSaveInterval(save_every);
@@ -139,6 +148,7 @@ int main(int argc, char** argv) {
         }
         std::printf("%d episodes in %.2f s (%.0f episodes/s), mean captured material red %.1f black %.1f, model -> %s\n", games, s,
                     games / s, games ? (double)red / games : 0.0, games ? (double)black / games : 0.0, file);
+        if (st.zero_sum) std::printf("target: zero-sum (y = r - gamma max)\n");
         if (st.seconds > 0)
             std::printf("batched loop: %llu plies + %llu updates in %.3f s = %.2f M env steps/s + %.0f updates/s\n",
                         (unsigned long long)st.envSteps, (unsigned long long)st.updates, st.seconds, st.envSteps / st.seconds / 1e6,

@@ -344,6 +344,13 @@ public:
     }
     // target of the batched TD step (xq_dqn_set_td_bootstrap): TdBootstrap::all() (default) or TdBootstrap::legal()
     void setTdBootstrap(const TdBootstrap& b) { check(xq_dqn_set_td_bootstrap(h_, b.kind)); }
+    // zero-sum (negamax) target of the batched TD step, for self-play (xq_dqn_set_zero_sum): y = r - gamma tanh(zm); off by default
+    void setZeroSum(bool on) { check(xq_dqn_set_zero_sum(h_, on ? 1 : 0)); }
+    bool zeroSum() const {
+        int on = 0;
+        check(xq_dqn_get_zero_sum(h_, &on));
+        return on != 0;
+    }
     TdBootstrap tdBootstrap() const {
         TdBootstrap b;
         check(xq_dqn_get_td_bootstrap(h_, &b.kind));
@@ -651,10 +658,14 @@ public:
 
 private:
     // the single-board loops are the reference's: they learn on evaluateBoard and never silently on another reward
+    // ... and on the reference's target r + gamma max Q(s'), never silently on the zero-sum one
     void parityLoopReward(const char* who) const {
         if (reward_.kind != XQ_REWARD_EVALUATE)
             throw std::invalid_argument(std::string("ChessAI::") + who + ": Reward::delta needs the batched loop (setParallelGames(n > 1)); "
                                         "the single-board loops keep the reference's evaluateBoard");
+        if (zeroSum_)
+            throw std::invalid_argument(std::string("ChessAI::") + who + ": setZeroSum needs the batched loop (setParallelGames(n > 1)); "
+                                        "the single-board loops keep the reference's target");
     }
     // trainLoop = true: ChessAI::train (local 200-ply cap, done includes moveCount+1 >= 200, :96/:119);
     // trainLoop = false: ChessAI::startSelfPlay (no local cap, done = checkGameOver(), :197/:227).
@@ -769,7 +780,11 @@ public:
     // Versus training (DESIGN.md §4 "Versus training"): the batched train() plays a fixed opponent instead of itself — Player::random(),
     // Player::search(depth, eps) or Player::net(dqn, eps) (a network that must outlive train()); the learner plays Black in every
     // other game.  clearOpponent() returns to self-play.  The sequential loop (parallelGames == 1) has no opponent: train() throws.
-    void setOpponent(const Player& p) { opponent_.reset(new Player(p)); }
+    // It and setZeroSum(true) refuse each other (std::invalid_argument): a versus transition ends with the learner to move again.
+    void setOpponent(const Player& p) {
+        if (zeroSum_) throw std::invalid_argument("setOpponent: the zero-sum target is on (setZeroSum): it is for self-play transitions");
+        opponent_.reset(new Player(p));
+    }
     void clearOpponent() { opponent_.reset(); }
     // what the last batched train() did: plies played by this process, updates, episodes finished, wall seconds of the loop
     // (from the first iteration queued to the last one finished, model saves included)
@@ -782,7 +797,8 @@ public:
                         int nStep = 1;                          // the n-step setting of the trainer's ring as the run ended (setNStep)
                         double mirror = 0;                      // ... and its mirror probability (setMirror)
                         double colour_swap = 0;                 // ... and its colour-swap probability (setColourSwap)
-                        Reward reward; };                       // the reward rule of the trainer's env as the run ended (setReward)
+                        Reward reward;                          // the reward rule of the trainer's env as the run ended (setReward)
+                        bool zero_sum = false; };               // whether the trainer's net formed the zero-sum target as the run ended (setZeroSum)
     TrainStats lastTrainStats() const { return stats_; }
     // data-parallel train(): this process is rank comm->rank() of comm->world(); its batched games take the id range
     // [rank * parallelGames, (rank + 1) * parallelGames) and every update all-reduces the gradients over RCCL (nullptr = off)
@@ -830,6 +846,14 @@ public:
     // Target of the batched train(), carried onto the trainer's network like the loss: TdBootstrap::legal() makes the trainer's ring
     // record the side to move in s' (xq_trainer_set_td_bootstrap, before the first collect).  fp32 nets; the sequential loop is unaffected.
     void setTdBootstrap(const TdBootstrap& b) { initializeDQN(); dqn->setTdBootstrap(b); }
+    // Zero-sum (negamax) target of the batched self-play train(): xq_trainer_set_zero_sum on the trainer train() creates (off by
+    // default).  std::invalid_argument with an opponent set (setOpponent), as setOpponent is while it is on; the single-board loops
+    // stay the reference's and throw std::invalid_argument under it, as they do for Reward::delta.
+    void setZeroSum(bool on) {
+        if (on && opponent_) throw std::invalid_argument("setZeroSum: an opponent is set (setOpponent): the zero-sum target is for self-play transitions");
+        zeroSum_ = on;
+    }
+    bool zeroSum() const { return zeroSum_; }
     DQN* network() { return dqn.get(); }
     std::vector<double> getStateRepresentation() {                           // chessai.cpp:268-289 (encoding only)
         std::vector<double> s(90 * 14, 0.0);
@@ -889,6 +913,7 @@ private:
         if (comm_) check(xq_trainer_set_comm(t, comm_->handle()));
         if (prefillPlies_ > 0) check(xq_trainer_random_plies(t, prefillPlies_));
         if (opponent_) check(xq_trainer_set_opponent(t, &opponent_->spec()));
+        if (zeroSum_) check(xq_trainer_set_zero_sum(t, 1));
         std::vector<xq_episode_record> rec(4096);
         // Every rank must run the same number of iterations (each carries a collective): the loop ends when the episodes
         // finished on ALL ranks together reach numEpisodes per rank; a rank reports at most its own numEpisodes.
@@ -933,6 +958,9 @@ private:
             check(xq_replay_get_mirror(tr, &stats_.mirror, nullptr));
             check(xq_replay_get_colour_swap(tr, &stats_.colour_swap, nullptr));
             check(xq_env_get_reward(te, &stats_.reward.kind, &stats_.reward.scale, &stats_.reward.plyCost, &stats_.reward.bound));
+            int zs = 0;
+            check(xq_dqn_get_zero_sum(td, &zs));
+            stats_.zero_sum = zs != 0;
         }
         {
             uint64_t q[4] = {0, 0, 0, 0}; int hold = 0;
@@ -961,6 +989,7 @@ private:
     double mirror_ = 0.0;
     double colourSwap_ = 0.0;
     Reward reward_;
+    bool zeroSum_ = false;
     int prefillPlies_ = 0;
     std::unique_ptr<Player> opponent_;
     TrainStats stats_;

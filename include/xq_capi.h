@@ -670,6 +670,26 @@ int xq_dqn_td_update_host_sided(xq_dqn* d, int n, const uint8_t* boards90, const
  * All outputs are host pointers, any of which may be NULL.  XQ_ERR_RUNTIME when the last TD step was not a legal one,
  * XQ_ERR_INVALID_ARGUMENT for n beyond its rows. */
 int xq_dqn_last_legal(xq_dqn* d, int n, int32_t* n_moves, int32_t* a_star, float* zmax, float* z96);
+/* The zero-sum (negamax) target for self-play (DESIGN.md §4 "Zero-sum target"; no upstream analogue).  on = 0 (default): every handle,
+ * launch and bit is what it is without this call.  on = 1: s' of a self-play transition has the OTHER side to move, so its best value
+ * counts against the mover of s.  With g = (float)gamma,
+ *   y = done ? r : r - g * tanh(zm)
+ * where zm is exactly what it is for the handle's bootstrap, td_net and precision (the screened or exact maximum over all outputs, or
+ * the legal-move maximum, Double DQN's evaluation on the target net).  The step's kernels are the same: they take the signed discount
+ * -g through the argument they have (r + (-g) t and r - g t are the same fp32 bits).  Loss, importance weights, priorities
+ * (|q - y| + eps)^alpha and xq_dqn_td_error_stats follow the new y and are otherwise unchanged.
+ * n-step batches (xq_replay_set_n_step): disc_0 = 1, disc_k = fl32(disc_{k-1} * (-g)) — today's magnitudes with the sign (-1)^k — and
+ * the step's discount is disc_n: in a self-play ring the chain's slots alternate movers, so this is the negamax n-step return.
+ * Under XQ_BOOTSTRAP_LEGAL a row whose side to move in s' has no move bootstraps from -inf (xq_dqn_last_legal: zmax = -inf, a_star = -1,
+ * n_moves = 0): tanh(-inf) = -1 is the lowest value the net can express, a side that cannot move has lost, y = r + g.  Done and dead
+ * rows keep zmax = 0.
+ * Applies to xq_dqn_td_grads, _sided, _replay (n-step, mirrored and colour-swapped batches too), xq_dqn_td_update_host and _sided; not
+ * to xq_dqn_backpropagate (the caller's targets).  on other than 0 or 1: XQ_ERR_INVALID_ARGUMENT; XQ_ERR_RUNTIME while a TD step waits
+ * for its apply_grads.  The setting survives every other setter, xq_dqn_set_params, xq_dqn_load_model and xq_dqn_update_target.
+ * The net still sees absolute colours and no side to move; a ring holding rows from before a switch gets the current sign on all of
+ * them. */
+int xq_dqn_set_zero_sum(xq_dqn* d, int on);
+int xq_dqn_get_zero_sum(const xq_dqn* d, int* on);
 /* The ring's side-to-move column (for XQ_BOOTSTRAP_LEGAL): one byte per slot, the side to move in the stored next board.  The column is
  * allocated by xq_replay_track_next_player, which must come while the ring is empty (XQ_ERR_RUNTIME otherwise; a second call is a
  * no-op); a ring that never tracked is the ring of before, array for array.  On a tracking ring every transition written by
@@ -896,6 +916,12 @@ int xq_trainer_set_reward(xq_trainer* t, int kind, double scale, double ply_cost
  * between iterations (XQ_ERR_RUNTIME while a learn_grads waits for its learn_apply); the column keeps being written.  Uniform,
  * prioritized and on-policy rings, overlap_collect 0 and 1, self-play and versus. */
 int xq_trainer_set_td_bootstrap(xq_trainer* t, int kind);
+/* xq_dqn_set_zero_sum on the trainer's Q-net (DESIGN.md §4 "Zero-sum target").  Uniform, prioritized and on-policy rings, any n_step,
+ * overlap_collect 0 and 1; no window changes.  The zero-sum target is for transitions whose s' has the other side to decide, and a
+ * versus transition runs from one learner decision to the next: on = 1 while an opponent is set is XQ_ERR_INVALID_ARGUMENT, and so is
+ * xq_trainer_set_opponent(non-NULL) while zero-sum is on.  Call between iterations: XQ_ERR_RUNTIME while a learn_grads waits for its
+ * learn_apply. */
+int xq_trainer_set_zero_sum(xq_trainer* t, int on);
 /* Versus training (DESIGN.md §4 "Versus training"): from the next collect on, the learner plays against a fixed opponent instead of
  * itself — uniform-random play, the material search (depth 1..3, eps) or a borrowed network (eps; layer_sizes[0] == 1260, >= 90
  * outputs, not the trainer's own).  The learner plays Black in game g iff (first_game_id + g) & 1.  A collect still writes one

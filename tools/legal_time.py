@@ -3,12 +3,15 @@
 
     python tools/legal_time.py [--steps 200] [--warmup 50] [--reps 4] [--td-net 0]
     python tools/legal_time.py --trainer [--steps 200] [--warmup 100] [--reps 3] [--ring 1048576]
+    python tools/legal_time.py --zero-sum [--steps 200] [--warmup 50] [--reps 4] [--td-net 0]
 
 One process, one handle, one batch of 8192 real self-play transitions held in HBM (boards after 40 random plies, the side to move in s'
 from the env's own record); DQN.set_td_bootstrap alternates "all", "legal", .. --reps times each.  The step is xq_dqn_td_grads(_sided) +
 xq_dqn_apply_grads on that batch with nothing beside it (no collect, no select chain).  Per leg one JSON line: wall ms/step of --steps
 steps and, from the kernel statistics of a further --steps steps, the time per launch of every bracketed kernel (legal_qmax and
 gemm_legal_head among them) and their sum.
+--zero-sum: the two legs are the legal step without and with the zero-sum target (DQN.set_zero_sum; the kernel then writes -inf in place of
+0 for a side without a move and the step's discount is negative: no launch changes).
 --trainer: the whole training step instead, through two Trainers of the headline configuration in one process (8192 games, ring of 1 M,
 overlapped collect) — one under "all", one under "legal" (the setting must precede a trainer's first collect) — timed alternately.
 profiles/NOTES.md ("Legal-move bootstrap") says what to set it against."""
@@ -78,6 +81,7 @@ def main():
     ap.add_argument("--reps", type=int, default=4)
     ap.add_argument("--td-net", type=int, default=0)
     ap.add_argument("--trainer", action="store_true")
+    ap.add_argument("--zero-sum", action="store_true")
     ap.add_argument("--ring", type=int, default=1 << 20)
     args = ap.parse_args()
     if args.trainer:
@@ -119,8 +123,9 @@ def main():
 
     steps(args.warmup, False)
     for rep in range(args.reps):
-        for kind in ("all", "legal"):
+        for kind, zero_sum in ((("legal", False), ("legal", True)) if args.zero_sum else (("all", False), ("legal", False))):
             d.set_td_bootstrap(kind)
+            d.set_zero_sum(zero_sum)
             legal = kind == "legal"
             steps(10, legal)
             t0 = time.perf_counter()
@@ -129,11 +134,12 @@ def main():
             d.kernel_stats(2)
             steps(args.steps, legal)
             st = {s["name"]: s for s in d.kernel_stats(0)}
-            out = dict(rep=rep, bootstrap=kind, td_net=args.td_net, ms_per_step=round(ms, 4),
+            out = dict(rep=rep, bootstrap=kind, zero_sum=zero_sum, td_net=args.td_net, ms_per_step=round(ms, 4),
                        step_kernel_sum_us=round(1e3 * sum(s["ms"] for s in st.values()) / args.steps, 2),
                        kernels_us={k: round(1e3 * s["ms"] / s["launches"], 2) for k, s in st.items()})
             if legal:
                 L = d.last_legal(n, z96=False)
+                out["rows_without_a_move"] = int((L["n_moves"] == 0).sum())
                 out["rows_with_moves"], out["mean_moves"] = int((L["n_moves"] > 0).sum()), round(float(L["n_moves"][L["n_moves"] > 0].mean()), 1)
             print(json.dumps(out), flush=True)
     d.close()
