@@ -6,8 +6,8 @@ libxqhip.so (include/xq_capi.h).  All compute is hand-written HIP for gfx950; th
 from . import _capi
 from ._capi import XqError
 from .vecenv import VecEnv, ReplayBuffer, StepResult, START_BOARD, eps_to_u32
-from .dqn import DQN, Trainer, TrainerConfig
+from .dqn import DQN, Trainer, TrainerConfig, view_boards
 from .arena import Arena, Search
 
 __all__ = ["VecEnv", "ReplayBuffer", "DQN", "Trainer", "TrainerConfig", "Arena", "Search", "XqError", "StepResult", "START_BOARD",
-           "eps_to_u32"]
+           "eps_to_u32", "view_boards"]

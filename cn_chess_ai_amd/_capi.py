@@ -22,6 +22,7 @@ QMAX_FULL, QMAX_SCREENED = 0, 1
 OPT_SGD, OPT_ADAM = 0, 1
 LOSS_SQUARED, LOSS_HUBER = 0, 1
 BOOTSTRAP_ALL, BOOTSTRAP_LEGAL = 0, 1
+VIEW_ABSOLUTE, VIEW_MOVER = 0, 1
 REWARD_EVALUATE, REWARD_DELTA = 0, 1
 MAX_N_STEP = 8
 ORDER_RING_CONTENTS, ORDER_RING_PRIORITIES, ORDER_RING_DRAW, ORDER_TRAINER_PARAMS, ORDER_ALL = 1, 2, 4, 8, 15
@@ -199,6 +200,17 @@ PROTOTYPES = {
     "xq_dqn_set_zero_sum": [_vp, _i],
     "xq_dqn_get_zero_sum": [_vp, _pi],
     "xq_trainer_set_zero_sum": [_vp, _i],
+    "xq_dqn_set_view": [_vp, _i],
+    "xq_dqn_get_view": [_vp, _pi],
+    "xq_view_boards_dev": [_vp, _vp, _i, _vp, _vp],
+    "xq_dqn_last_view": [_vp, _i, _pu8, _pu8, _pu8, _pu8, _pi, _pi],
+    "xq_replay_track_mover": [_vp],
+    "xq_replay_push_host_sides": [_vp, _i, _pu8, _pi, _pf, _pu8, _pu8, _pu8, _pu8],
+    "xq_replay_get_mover": [_vp, _i, _i, _pu8],
+    "xq_env_set_q_view": [_vp, _i],
+    "xq_env_get_q_view": [_vp, _pi],
+    "xq_trainer_set_view": [_vp, _i],
+    "xq_arena_ply_q_dev_view": [_vp, _vp, _i, _d, _d, _i, _i],
     "xq_dqn_kernel_stats": [_vp, _i, C.POINTER(KernelStat), _i, _pi],
     "xq_dqn_set_fused_apply": [_vp, _i],
     "xq_dqn_set_optimizer": [_vp, _i, _d, _d, _d],
@@ -283,8 +295,12 @@ LAZY_COLOUR_SWAP = frozenset(("xq_replay_set_colour_swap", "xq_replay_get_colour
                               "xq_trainer_set_colour_swap"))
 # ... and those of the zero-sum target
 LAZY_ZERO_SUM = frozenset(("xq_dqn_set_zero_sum", "xq_dqn_get_zero_sum", "xq_trainer_set_zero_sum"))
+# ... and those of the mover view
+LAZY_VIEW = frozenset(("xq_dqn_set_view", "xq_dqn_get_view", "xq_view_boards_dev", "xq_dqn_last_view", "xq_replay_track_mover",
+                       "xq_replay_push_host_sides", "xq_replay_get_mover", "xq_env_set_q_view", "xq_env_get_q_view", "xq_trainer_set_view",
+                       "xq_arena_ply_q_dev_view"))
 _LAZY_ALL = (LAZY | LAZY_GRAD_CLIP | LAZY_TARGET_TAU | LAZY_TD_LOSS | LAZY_N_STEP | LAZY_MIRROR | LAZY_LEGAL | LAZY_REWARD
-             | LAZY_COLOUR_SWAP | LAZY_ZERO_SUM)
+             | LAZY_COLOUR_SWAP | LAZY_ZERO_SUM | LAZY_VIEW)
 _RESTYPES = {"xq_last_error": C.c_char_p, "xq_env_boards_dev": C.c_void_p, "xq_env_meta_dev": C.c_void_p}
 
 _lib = None

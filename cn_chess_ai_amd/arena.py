@@ -96,11 +96,15 @@ class Arena:
     def reset(self, opening_plies=8):
         call("xq_arena_reset", self._h, int(opening_plies))
 
-    def ply_q_dev(self, q_dev, q_stride=96, eps_a=0.0, eps_b=0.0):
-        """One ply with caller Q rows: q_dev = device pointer (int) or a cuda torch tensor [2P][>= 90], None = random."""
+    def ply_q_dev(self, q_dev, q_stride=96, eps_a=0.0, eps_b=0.0, view_a=False, view_b=False):
+        """One ply with caller Q rows: q_dev = device pointer (int) or a cuda torch tensor [2P][>= 90], None = random.  view_a / view_b:
+        that player's rows are in the mover's view (computed on view_boards' boards)."""
         if hasattr(q_dev, "data_ptr"):
             q_stride = int(q_dev.stride(0))
             q_dev = q_dev.data_ptr()
+        if view_a or view_b:
+            call("xq_arena_ply_q_dev_view", self._h, q_dev, int(q_stride), float(eps_a), float(eps_b), int(bool(view_a)), int(bool(view_b)))
+            return
         call("xq_arena_ply_q_dev", self._h, q_dev, int(q_stride), float(eps_a), float(eps_b))
 
     def run(self, dqn_a, dqn_b, eps_a=0.0, eps_b=0.0, max_plies=0):

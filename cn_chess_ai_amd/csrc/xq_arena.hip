@@ -23,7 +23,8 @@ struct xq_arena {
     xq::PinnedBuf<int> live_host;
     xq::DevBuf<xq_step_result> results;     // [2 pairs] the last ply's step results
     xq::DevBuf<int16_t> pick;               // [2 pairs] the search players' move indices of the ply (xq_search.hip)
-    xq::Event ev_env, ev_q[2];
+    xq::DevBuf<uint32_t> view;              // [2 pairs][12] the boards as a mover-view net player reads them (allocated with the first one)
+    xq::Event ev_env, ev_q[2], ev_view[2];  // ev_view: behind the staging of a half's view boards
 };
 
 namespace xq {
@@ -48,6 +49,7 @@ int make_player(const xq_arena_player* in, const char* who, CheckedPlayer* out) 
         return fail(XQ_ERR_INVALID_ARGUMENT, "%s needs layer_sizes[0] == 1260 and >= 90 outputs (got %d -> %d)", who, nin, nout);
     out->net = x.dqn;
     out->n_out = std::min(nout, 96);
+    out->view = dqn_view(x.dqn) == XQ_VIEW_MOVER ? 1 : 0;
     return XQ_OK;
 }
 
@@ -83,16 +85,17 @@ int mover_of_half(const xq_arena* a, int h) { return ((a->ply & 1) ^ h) == 0 ? 0
 // one ply of players pl on the Q rows q of the halves a network player moves in (its own, or the caller's: xq_arena_ply_q_dev)
 int launch_ply(xq_arena* a, const float* q, int q_stride, const CheckedPlayer pl[2]) {
     uint32_t e[2];
-    int hq[2], pick_on[2];
+    int hq[2], pick_on[2], q_view[2];
     for (int h = 0; h < 2; ++h) {
         const CheckedPlayer& p = pl[mover_of_half(a, h)];
         e[h] = p.eps_u32;
         hq[h] = p.kind == XQ_PLAYER_NET ? 1 : 0;
+        q_view[h] = hq[h] && p.view;
         pick_on[h] = p.kind == XQ_PLAYER_SEARCH && a->ply >= a->opening ? 1 : 0;
         if (pick_on[h])      // the searching half's picks, on the arena's stream right ahead of the ply (frozen games are skipped)
             XQ_TRY(search_pick_launch(a->env, p.depth, h * a->pairs, a->pairs, a->pairs, false, e[h], a->pick, a->env->stream));
     }
-    XQ_TRY(env_arena_launch(a->env, q, q_stride, a->pairs, a->opening, e, hq, a->rec, a->live, a->results, a->pick, pick_on));
+    XQ_TRY(env_arena_launch(a->env, q, q_stride, a->pairs, a->opening, e, hq, a->rec, a->live, a->results, a->pick, pick_on, q_view));
     a->ply += 1;
     return XQ_OK;
 }
@@ -111,9 +114,16 @@ int run_players(xq_arena* a, const CheckedPlayer pl[2], int max_plies, int* plie
             for (int h = 0; h < 2; ++h) {
                 const CheckedPlayer& p = pl[mover_of_half(a, h)];
                 const size_t off = (size_t)h * a->pairs;
-                if (p.net)
-                    XQ_TRY(borrowed_forward(p.net, a->env->boards + off * kBoardWords, a->pairs, p.n_out, a->q + off * 96, a->env->stream,
-                                            a->ev_env, a->ev_q[h]));
+                if (!p.net) continue;
+                const uint32_t* boards = a->env->boards + off * kBoardWords;
+                if (p.view) {        // per half and ply the side is uniform; the general kernel reads it from the games' meta anyway
+                    XQ_TRY(a->view.reserve(2 * (size_t)a->pairs * kBoardWords));
+                    XQ_TRY(view_boards_launch(boards, nullptr, a->env->meta + off, a->pairs, a->view + off * kBoardWords, a->env->stream));
+                    boards = a->view + off * kBoardWords;
+                    if (dqn_stream(p.net) != a->env->stream) XQ_HIP(hipEventRecord(a->ev_view[h], a->env->stream));
+                }
+                XQ_TRY(borrowed_forward(p.net, boards, a->pairs, p.n_out, a->q + off * 96, a->env->stream,
+                                        p.view ? a->ev_view[h] : a->ev_env, a->ev_q[h]));
             }
         }
         XQ_TRY(launch_ply(a, a->q, 96, pl));
@@ -148,6 +158,7 @@ static int arena_init(xq_arena* a, int n_pairs, uint64_t seed, uint32_t first_ga
     XQ_TRY(a->live_host.alloc(1));
     XQ_TRY(a->ev_env.create(stream_event_flags()));
     for (auto& ev : a->ev_q) XQ_TRY(ev.create(stream_event_flags()));
+    for (auto& ev : a->ev_view) XQ_TRY(ev.create(stream_event_flags()));
     return xq_arena_reset(a, 8);
 }
 
@@ -182,7 +193,12 @@ int xq_arena_reset(xq_arena* a, int opening_plies) {
 }
 
 int xq_arena_ply_q_dev(xq_arena* a, const float* q_dev, int q_stride, double eps_a, double eps_b) {
+    return xq_arena_ply_q_dev_view(a, q_dev, q_stride, eps_a, eps_b, 0, 0);
+}
+
+int xq_arena_ply_q_dev_view(xq_arena* a, const float* q_dev, int q_stride, double eps_a, double eps_b, int view_a, int view_b) {
     if (!a) return fail(XQ_ERR_INVALID_ARGUMENT, "null arena");
+    if ((view_a != 0 && view_a != 1) || (view_b != 0 && view_b != 1)) return fail(XQ_ERR_INVALID_ARGUMENT, "xq_arena_ply_q_dev_view: a view flag is 0 or 1");
     if (q_dev && q_stride < 90) return fail(XQ_ERR_INVALID_ARGUMENT, "q_stride must be >= 90");
     if (!(eps_a >= 0.0 && eps_a <= 1.0 && eps_b >= 0.0 && eps_b <= 1.0)) return fail(XQ_ERR_INVALID_ARGUMENT, "epsilon must be in [0, 1]");
     int live = 0;
@@ -192,6 +208,7 @@ int xq_arena_ply_q_dev(xq_arena* a, const float* q_dev, int q_stride, double eps
     pl[0].kind = pl[1].kind = q_dev ? XQ_PLAYER_NET : XQ_PLAYER_RANDOM;
     pl[0].eps_u32 = eps_to_u32(eps_a);
     pl[1].eps_u32 = eps_to_u32(eps_b);
+    pl[0].view = view_a; pl[1].view = view_b;
     return launch_ply(a, q_dev, q_stride, pl);
 }
 

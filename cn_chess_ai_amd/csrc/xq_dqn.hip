@@ -219,6 +219,12 @@ struct xq_dqn {
     // zero-sum (negamax) target (xq_dqn_set_zero_sum, DESIGN.md §4 "Zero-sum target"): the TD step's discount is -(float)gamma, the
     // n-step discounts alternate in sign, and a side without a move under the legal bootstrap bootstraps from -inf (tanh: -1)
     int zero_sum = 0;
+    // mover view (xq_dqn_set_view, DESIGN.md §4 "Mover view"): a TD step from a ring stages view(s, mover) and view(s', next side) with
+    // mover_view_stage_kernel, the last staging transform; per row the two flags.  view_rows: rows of the last TD step if it was a
+    // view-mode one, else 0 (xq_dqn_last_view)
+    int view = XQ_VIEW_ABSOLUTE;
+    xq::DevBuf<uint8_t> ns_vflag, ns_vflag_next;
+    int view_rows = 0;
     xq::Profiler prof;
     // fused launches of the TD step's tail (td_tail_kernel): while `tail_open`, the launch helpers of the small fp32 GEMMs, the
     // output-layer / layer-0 segmented sums and the bias column sums append their blocks to `tail` instead of launching.  Written by
@@ -251,6 +257,7 @@ namespace xq {
 
 Profiler* dqn_profiler(xq_dqn* d) { return &d->prof; }
 int dqn_fused_apply(const xq_dqn* d) { return d->fused_apply ? 1 : 0; }
+int dqn_view(const xq_dqn* d) { return d->view; }
 xq_comm* dqn_comm(const xq_dqn* d) { return d->comm; }
 hipStream_t dqn_stream(xq_dqn* d) { return d->stream; }
 void dqn_shape(const xq_dqn* d, int* n_in, int* n_out) { *n_in = d->L[0]; *n_out = d->nout(); }
@@ -307,6 +314,7 @@ struct SmallTiles {
 #include "xq_nstep.hip.h"
 #include "xq_mirror.hip.h"
 #include "xq_colour_swap.hip.h"
+#include "xq_view.hip.h"
 #include "xq_legal.hip.h"
 
 namespace xq {
@@ -1223,6 +1231,16 @@ static int soft_target_whole(xq_dqn* d, double tau) {
     ProfScope ps(d, "soft_target", 2.0 * n, 12.0 * n + (tb ? 2.0 * d->nw : 0.0), true);
     hipExtLaunchKernelGGL(soft_target_kernel, dim3(blocks), dim3(256), 0, d->cur, ps.start(), ps.stop(), 0, p, t, tb, n, (long long)d->nw,
                           (float)tau, vec);
+    XQ_HIP(hipGetLastError());
+    return XQ_OK;
+}
+
+// view_boards_kernel on `stream` (xq_internal.h): the sides from side_dev or, with meta_dev, from bit 16 of meta[b].x
+int view_boards_launch(const uint32_t* boards_dev, const uint8_t* side_dev, const uint4* meta_dev, int n, uint32_t* out_dev,
+                       hipStream_t stream) {
+    if (!boards_dev || !out_dev || (!side_dev && !meta_dev) || n < 0) return fail(XQ_ERR_INVALID_ARGUMENT, "view_boards: bad argument");
+    if (!n) return XQ_OK;
+    hipLaunchKernelGGL(view_boards_kernel, dim3((n + 63) / 64), dim3(64), 0, stream, boards_dev, side_dev, meta_dev, n, out_dev);
     XQ_HIP(hipGetLastError());
     return XQ_OK;
 }
@@ -2180,6 +2198,7 @@ static int td_grads_impl(xq_dqn* d, const uint32_t* boards, const uint32_t* next
     d->nstep_rows = 0;                               // (xq_dqn_td_grads_replay sets it behind an n-step batch)
     d->mirror_rows = 0;                              // (... and this one behind a mirror-mode batch)
     d->colour_swap_rows = 0;                         // (... and this one behind a colour-swap-mode batch)
+    d->view_rows = 0;                                // (... and this one behind a view-mode batch)
     s.n = n; s.mode = mode; s.nl = nl; s.Hl = Hl; s.NO = NO; s.dbl = dbl; s.bf = bf; s.sel_net = td_net == XQ_TD_TARGET_NET ? XQ_NET_TARGET : XQ_NET_ONLINE;
     chain_views(d, d->acts, d->acts_bf, XQ_MAX_LAYERS, true, s.outs, s.outs_bf);
     chain_views(d, d->tacts, d->tacts_bf, 2, !bf, s.touts, s.touts_bf);
@@ -2578,10 +2597,64 @@ static int mirror_stage(xq_dqn* d, xq_replay* r, SlotSrc src, int batch, bool ga
 // A TD step on a mirror-augmented batch of one-step transitions (xq_replay_set_mirror on a ring with n_step == 1): one gather stages the
 // minibatch with its flagged rows reflected, the step then runs on that batch with the identity slot source and the handle's discount; a
 // prioritized draw's priorities go back to the sampled slots behind the step (the n-step arrangement)
+static int mover_view_stage(xq_dqn* d, xq_replay* r, SlotSrc src, int batch, bool gather, const int32_t* row_last);
 static int td_grads_mirror(xq_dqn* d, xq_replay* r, SlotSrc src, int batch, int td_net, int mode, const PerOpts* per) {
+    const bool viewed = d->view == XQ_VIEW_MOVER;
     XQ_TRY(mirror_stage(d, r, src, batch, true));
-    XQ_TRY(td_grads_staged(d, r, d->ns_first, batch, td_net, mode, per, nullptr));
+    if (viewed) XQ_TRY(mover_view_stage(d, r, src, batch, false, d->ns_first));
+    XQ_TRY(td_grads_staged(d, r, d->ns_first, batch, td_net, mode, per, nullptr, viewed));
     d->mirror_rows = batch;
+    if (viewed) d->view_rows = batch;
+    return XQ_OK;
+}
+
+// Mover view (xq_dqn_set_view): queues mover_view_stage_kernel for the next TD step from ring `r`, the last staging transform.  gather:
+// the minibatch from the ring (through `src`) into the handle's staging batch; otherwise the staging batch an n-step assembly and / or
+// a mirror gather just filled, in place, s flagged by the ring's mover column at ns_first[b] and s' by its next_player column at
+// row_last[b].  Under the legal-move bootstrap the kernel stages the side bytes too — 0 on every row, the view of s' has Red to move —
+// so td_grads_staged launches no legal_side_stage_kernel
+static int mover_view_stage(xq_dqn* d, xq_replay* r, SlotSrc src, int batch, bool gather, const int32_t* row_last) {
+    const size_t rows = (size_t)batch;
+    const bool sided = d->bootstrap == XQ_BOOTSTRAP_LEGAL;
+    if (gather) {
+        XQ_TRY(d->ns_boards.reserve(rows * kBoardWords));
+        XQ_TRY(d->ns_next.reserve(rows * kBoardWords));
+        for (DevBuf<int32_t>* b : {&d->ns_action, &d->ns_first}) XQ_TRY(b->reserve(rows));
+        XQ_TRY(d->ns_reward.reserve(rows));
+        XQ_TRY(d->ns_done.reserve(rows));
+    }
+    XQ_TRY(d->ns_vflag.reserve(rows));
+    XQ_TRY(d->ns_vflag_next.reserve(rows));
+    if (sided) XQ_TRY(d->ns_side.reserve(rows));
+    MoverViewArgs A; memset(&A, 0, sizeof A);
+    if (gather) {
+        A.boards = r->dev.boards; A.next_boards = r->dev.next_boards; A.action_to = r->dev.action_to; A.reward = r->dev.reward; A.done = r->dev.done;
+    } else {
+        A.boards = d->ns_boards; A.next_boards = d->ns_next; A.action_to = d->ns_action; A.reward = d->ns_reward; A.done = d->ns_done;
+        A.row_first = d->ns_first; A.row_last = row_last;
+    }
+    A.s_boards = d->ns_boards; A.s_next = d->ns_next; A.s_action = d->ns_action; A.s_reward = d->ns_reward; A.s_done = d->ns_done;
+    A.s_first = d->ns_first; A.s_flag = d->ns_vflag; A.s_flag_next = d->ns_vflag_next;
+    A.mover = r->dev.mover; A.next_player = r->dev.next_player;
+    if (sided) A.s_side = d->ns_side;
+    A.cap = r->dev.capacity;
+    A.gather = gather ? 1u : 0u;
+    {
+        // per row: the mirror's bytes (from the ring 215, in place 201) with a second flag out, the two side bytes in, in place the 8 B
+        // of the two slots they are read at; under the legal bootstrap the staged side byte out
+        ProfScope ps(d, "mover_view_stage", 0.0, (double)batch * ((gather ? 218.0 : 212.0) + (sided ? 1.0 : 0.0)), true);
+        hipExtLaunchKernelGGL(mover_view_stage_kernel, dim3((batch + 63) / 64), dim3(64), 0, d->cur, ps.start(), ps.stop(), 0, A, src, batch);
+        XQ_HIP(hipGetLastError());
+    }
+    return XQ_OK;
+}
+
+// A TD step under the mover view on one-step transitions with no other staging transform: one gather stages the minibatch in the view,
+// the step then runs as behind the mirror
+static int td_grads_view(xq_dqn* d, xq_replay* r, SlotSrc src, int batch, int td_net, int mode, const PerOpts* per) {
+    XQ_TRY(mover_view_stage(d, r, src, batch, true, nullptr));
+    XQ_TRY(td_grads_staged(d, r, d->ns_first, batch, td_net, mode, per, nullptr, true));
+    d->view_rows = batch;
     return XQ_OK;
 }
 
@@ -2677,8 +2750,11 @@ static int td_grads_nstep(xq_dqn* d, xq_replay* r, SlotSrc src, int batch, int t
     if (mirrored) XQ_TRY(mirror_stage(d, r, src, batch, false));
     const bool swapped = r->colour_swap_prob > 0.0;
     if (swapped) XQ_TRY(colour_swap_stage(d, r, src, batch, false, d->ns_last));
-    XQ_TRY(td_grads_staged(d, r, d->ns_last, batch, td_net, mode, per, &disc_n, swapped));
+    const bool viewed = d->view == XQ_VIEW_MOVER;      // (never with `swapped`: xq_dqn_td_grads_replay refuses the pair)
+    if (viewed) XQ_TRY(mover_view_stage(d, r, src, batch, false, d->ns_last));
+    XQ_TRY(td_grads_staged(d, r, d->ns_last, batch, td_net, mode, per, &disc_n, swapped || viewed));
     d->nstep_rows = batch;
+    if (viewed) d->view_rows = batch;
     if (mirrored) d->mirror_rows = batch;
     if (swapped) { d->colour_swap_rows = batch; d->colour_swap_sided = d->bootstrap == XQ_BOOTSTRAP_LEGAL; }
     return XQ_OK;
@@ -2743,6 +2819,27 @@ int xq_dqn_last_colour_swap(xq_dqn* d, int n, uint8_t* flags, uint8_t* boards90,
     return XQ_OK;
 }
 
+int xq_dqn_last_view(xq_dqn* d, int n, uint8_t* flag_s, uint8_t* flag_next, uint8_t* boards90, uint8_t* next_boards90, int32_t* action_to,
+                     int32_t* slot) {
+    if (!d) return fail(XQ_ERR_INVALID_ARGUMENT, "null dqn");
+    if (d->view_rows <= 0) return fail(XQ_ERR_RUNTIME, "xq_dqn_last_view: the last TD step was not a view-mode one");
+    if (n < 0 || n > d->view_rows) return fail(XQ_ERR_INVALID_ARGUMENT, "xq_dqn_last_view: n exceeds the last TD step's %d rows", d->view_rows);
+    XQ_HIP(hipStreamSynchronize(d->stream));
+    if (!n) return XQ_OK;
+    if (flag_s) XQ_HIP(hipMemcpy(flag_s, d->ns_vflag, (size_t)n, hipMemcpyDeviceToHost));
+    if (flag_next) XQ_HIP(hipMemcpy(flag_next, d->ns_vflag_next, (size_t)n, hipMemcpyDeviceToHost));
+    std::vector<uint32_t> w((size_t)n * kBoardWords);
+    const struct { uint8_t* out; const uint32_t* dev; } boards[2] = {{boards90, d->ns_boards}, {next_boards90, d->ns_next}};
+    for (const auto& bd : boards) {
+        if (!bd.out) continue;
+        XQ_HIP(hipMemcpy(w.data(), bd.dev, w.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        for (int i = 0; i < n; ++i) unpack_board(&w[(size_t)i * kBoardWords], bd.out + (size_t)i * 90);
+    }
+    if (action_to) XQ_HIP(hipMemcpy(action_to, d->ns_action, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (slot) XQ_HIP(hipMemcpy(slot, d->ns_first, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return XQ_OK;
+}
+
 int xq_dqn_td_grads_replay(xq_dqn* d, xq_replay* r, int batch, int td_net, int mode) {
     if (!d || !r) return fail(XQ_ERR_INVALID_ARGUMENT, "null handle");
     SlotSrc src = explicit_slots(nullptr);
@@ -2762,6 +2859,13 @@ int xq_dqn_td_grads_replay(xq_dqn* d, xq_replay* r, int batch, int td_net, int m
     if (batch <= 0) return fail(XQ_ERR_RUNTIME, "replay is empty");
     if (d->bootstrap == XQ_BOOTSTRAP_LEGAL && !r->dev.next_player)
         return fail(XQ_ERR_INVALID_ARGUMENT, "the legal-move bootstrap needs the side to move in s': this ring does not track it (xq_replay_track_next_player)");
+    const bool viewed = d->view == XQ_VIEW_MOVER;
+    if (viewed && (!r->dev.mover || !r->dev.next_player))
+        return fail(XQ_ERR_INVALID_ARGUMENT, "the mover view needs who moved and who moves next: this ring does not track both "
+                                             "(xq_replay_track_mover, xq_replay_track_next_player)");
+    if (viewed && r->colour_swap_prob > 0.0)
+        return fail(XQ_ERR_INVALID_ARGUMENT, "the mover view (xq_dqn_set_view) and colour-swap augmentation (xq_replay_set_colour_swap) are both "
+                                             "on: the view of a swapped transition is the view of the transition, switch one of them off");
     PerOpts per; memset(&per, 0, sizeof per);
     const bool prioritized = r->per.enabled && r->per.last_prioritized && !r->implicit && src.slots != nullptr;
     if (prioritized) {        // importance weights in, TD-error priorities out (xq_replay_sample_prioritized drew the slots)
@@ -2775,6 +2879,7 @@ int xq_dqn_td_grads_replay(xq_dqn* d, xq_replay* r, int batch, int td_net, int m
     if (r->n_step > 1) return td_grads_nstep(d, r, src, batch, td_net, mode, prioritized ? &per : nullptr);
     if (r->colour_swap_prob > 0.0) return td_grads_colour_swap(d, r, src, batch, td_net, mode, prioritized ? &per : nullptr);
     if (r->mirror_prob > 0.0) return td_grads_mirror(d, r, src, batch, td_net, mode, prioritized ? &per : nullptr);
+    if (viewed) return td_grads_view(d, r, src, batch, td_net, mode, prioritized ? &per : nullptr);
     return td_grads_impl(d, r->dev.boards, r->dev.next_boards, r->dev.action_to, r->dev.reward, r->dev.done, src, batch, td_net,
                          mode, prioritized ? &per : nullptr, nullptr, r->dev.next_player);
 }
@@ -2852,6 +2957,24 @@ int xq_dqn_get_zero_sum(const xq_dqn* d, int* on) {
     if (!d || !on) return fail(XQ_ERR_INVALID_ARGUMENT, "null pointer");
     *on = d->zero_sum;
     return XQ_OK;
+}
+int xq_dqn_set_view(xq_dqn* d, int view) {
+    if (!d) return fail(XQ_ERR_INVALID_ARGUMENT, "null dqn");
+    if (view != XQ_VIEW_ABSOLUTE && view != XQ_VIEW_MOVER) return fail(XQ_ERR_INVALID_ARGUMENT, "xq_dqn_set_view: unknown view %d", view);
+    if (td_step_pending(d)) return fail(XQ_ERR_RUNTIME, "xq_dqn_set_view: a TD step is waiting for its apply_grads");
+    d->view = view;
+    return XQ_OK;
+}
+int xq_dqn_get_view(const xq_dqn* d, int* view) {
+    if (!d || !view) return fail(XQ_ERR_INVALID_ARGUMENT, "null pointer");
+    *view = d->view;
+    return XQ_OK;
+}
+int xq_view_boards_dev(const void* boards_dev, const void* side_dev, int n, void* out_dev, void* hip_stream) {
+    if (!boards_dev || !side_dev || !out_dev || n < 0) return fail(XQ_ERR_INVALID_ARGUMENT, "xq_view_boards_dev: bad argument");
+    if (boards_dev == out_dev) return fail(XQ_ERR_INVALID_ARGUMENT, "xq_view_boards_dev: out_dev must not be boards_dev");
+    return view_boards_launch(static_cast<const uint32_t*>(boards_dev), static_cast<const uint8_t*>(side_dev), nullptr, n,
+                              static_cast<uint32_t*>(out_dev), static_cast<hipStream_t>(hip_stream));
 }
 int xq_dqn_last_legal(xq_dqn* d, int n, int32_t* n_moves, int32_t* a_star, float* zmax, float* z96) {
     if (!d) return fail(XQ_ERR_INVALID_ARGUMENT, "null dqn");

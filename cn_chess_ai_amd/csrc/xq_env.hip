@@ -64,6 +64,10 @@ struct EnvParams {
     // XQ_REWARD_DELTA = delta_reward() of the transition's change of material balance; xq_step_result.reward is evaluateBoard always
     int rw_kind;
     float rw_scale, rw_cost, rw_bound;
+    // mover view (xq_env_set_q_view, DESIGN.md §4 "Mover view"): the Q rows of this launch are in the mover's view, so with Black to move
+    // the value of the destination `to` is output swap(to) = to + 81 - 18 (to div 9).  Arena: per half, like arena_has_q
+    int q_view;
+    int arena_q_view[2];
 };
 
 __constant__ uint32_t c_start_words[kBoardWords];
@@ -250,9 +254,12 @@ __global__ __launch_bounds__(256) void env_kernel(EnvParams P) {
                 // argument, same bits as a tanh per output) is taken of the candidates' values only: one pass over the wave for the usual
                 // <= 64 moves instead of two passes over the 90 outputs (~40 vector instructions each)
                 const bool pre = P.q_slabs != nullptr;
-                if (lane < n_moves) { v0 = S.q[S.moves[lane] % 90]; if (pre) v0 = tanhf(v0); }
+                // mover view: Black reads its destinations through the colour swap's square map (wave-uniform: one game per wave)
+                const bool swap_to = (MODE == MODE_ARENA ? P.arena_q_view[arena_half] : P.q_view) != 0 && player == 1;
+                auto q_at = [&](int code) { const int t = code % 90; return swap_to ? t + 81 - 18 * (t / 9) : t; };
+                if (lane < n_moves) { v0 = S.q[q_at(S.moves[lane])]; if (pre) v0 = tanhf(v0); }
                 if (n_moves > 64) {                                            // (wave-uniform)
-                    if (lane + 64 < n_moves) { v1 = S.q[S.moves[lane + 64] % 90]; if (pre) v1 = tanhf(v1); }
+                    if (lane + 64 < n_moves) { v1 = S.q[q_at(S.moves[lane + 64])]; if (pre) v1 = tanhf(v1); }
                 }
                 if (!(v0 == v0)) v0 = NEG;                                     // NaN never wins `q > maxQ`
                 if (!(v1 == v1)) v1 = NEG;
@@ -370,6 +377,7 @@ __global__ __launch_bounds__(256) void env_kernel(EnvParams P) {
             P.rp.reward[slot] = P.rw_kind == XQ_REWARD_DELTA ? delta_reward(gain, P.rw_scale, P.rw_cost, P.rw_bound) : (float)reward;
             P.rp.done[slot] = done ? 1 : 0;
             if (P.rp.next_player != nullptr) P.rp.next_player[slot] = (uint8_t)(1 - mover);       // the side to move in s'
+            if (P.rp.mover != nullptr) P.rp.mover[slot] = (uint8_t)mover;                         // the side that moved in s
             // prioritized replay: a new transition enters with the largest priority assigned so far (an empty one never gets sampled)
             if (P.rp.prio != nullptr) P.rp.prio[slot] = have_action ? __uint_as_float(*P.rp.pmax_snap) : 0.f;
         }
@@ -400,6 +408,7 @@ __global__ __launch_bounds__(256) void env_kernel(EnvParams P) {
                 P.rp.reward[slot] = ph == 0 ? 0.f : rw_delta ? delta_reward(delta, P.rw_scale, P.rw_cost, P.rw_bound) : (float)reward;
                 P.rp.done[slot] = ph == 0 || done ? 1 : 0;
                 if (P.rp.next_player != nullptr) P.rp.next_player[slot] = (uint8_t)vs_learner;    // s' is the learner's to move
+                if (P.rp.mover != nullptr) P.rp.mover[slot] = (uint8_t)vs_learner;                // ... and s was
                 if (P.rp.prio != nullptr) P.rp.prio[slot] = learner_moved ? __uint_as_float(*P.rp.pmax_snap) : 0.f;
             }
         }
@@ -584,6 +593,7 @@ int env_selfplay_launch(xq_env* e, const float* q90_dev, int q_stride, uint32_t 
     XQ_TRY(set_q_source(P, q90_dev, q_stride, qs));
     P.eps_u32 = eps_u32;
     P.results = results_dev;
+    P.q_view = e->q_view;
     if (replay != nullptr) XQ_TRY(set_ring(P, replay));
     const int blocks = (e->n + 3) / 4;
     if (replay != nullptr) XQ_TRY(replay_writer_begin(replay, on ? on : e->stream));    // (costs nothing when the ring's users share this stream)
@@ -597,7 +607,8 @@ int env_selfplay_launch(xq_env* e, const float* q90_dev, int q_stride, uint32_t 
 // One arena ply (xq_arena.hip): q90_dev = [n][q_stride] rows of the halves whose has_q is set, pick_dev = [n] move indices of the halves
 // whose pick_on is set; nothing else of the env is touched
 int env_arena_launch(xq_env* e, const float* q90_dev, int q_stride, int pairs, int opening, const uint32_t eps_u32[2], const int has_q[2],
-                     xq_arena_game* records_dev, int* live_dev, xq_step_result* results_dev, const int16_t* pick_dev, const int pick_on[2]) {
+                     xq_arena_game* records_dev, int* live_dev, xq_step_result* results_dev, const int16_t* pick_dev, const int pick_on[2],
+                     const int q_view[2]) {
     EnvParams P = base_params(e);
     P.ep_ring = nullptr;                  // no episode records, no stats, no replay: an arena game ends once and stays as it ended
     P.q90 = q90_dev;
@@ -609,6 +620,7 @@ int env_arena_launch(xq_env* e, const float* q90_dev, int q_stride, int pairs, i
         P.arena_eps[h] = eps_u32[h];
         P.arena_pick_on[h] = pick_on[h] && pick_dev != nullptr;
         P.arena_has_q[h] = has_q[h] && q90_dev != nullptr && !P.arena_pick_on[h];
+        P.arena_q_view[h] = q_view != nullptr && q_view[h] != 0;
     }
     P.arena_pick = pick_dev;
     P.arena_rec = records_dev;
@@ -622,13 +634,14 @@ int env_arena_launch(xq_env* e, const float* q90_dev, int q_stride, int pairs, i
 // opponent's, on its search picks (pick_dev), its Q rows (q90_dev) or uniform-random (neither) with its eps_u32.  The transitions go to
 // the ring slots from replay->write_pos; the caller advances the ring once the collect's last phase is queued.
 int env_versus_launch(xq_env* e, int phase, const float* q90_dev, int q_stride, const QSource* qs, uint32_t eps_u32, const int16_t* pick_dev,
-                      uint4* counts_dev, xq_replay* replay, hipStream_t on) {
+                      uint4* counts_dev, xq_replay* replay, hipStream_t on, int opponent_view) {
     if (phase < 0 || phase > 2 || replay == nullptr || counts_dev == nullptr) return fail(XQ_ERR_INVALID_ARGUMENT, "env_versus_launch: bad argument");
     EnvParams P = base_params(e);
     XQ_TRY(set_ring(P, replay));
     XQ_TRY(set_q_source(P, q90_dev, q_stride, phase == 1 ? qs : nullptr));
     P.eps_u32 = eps_u32;
     P.vs_phase = phase;
+    P.q_view = phase == 1 ? e->q_view : opponent_view;
     P.vs_pick = phase == 1 ? nullptr : pick_dev;
     P.vs_counts = counts_dev;
     hipStream_t s = on ? on : e->stream;
@@ -908,6 +921,17 @@ int xq_env_selfplay_step_host(xq_env* e, const float* q90_host, uint32_t eps_u32
     return XQ_OK;
 }
 
+int xq_env_set_q_view(xq_env* e, int on) {
+    if (!e) return fail(XQ_ERR_INVALID_ARGUMENT, "null env");
+    if (on != 0 && on != 1) return fail(XQ_ERR_INVALID_ARGUMENT, "xq_env_set_q_view: on must be 0 or 1, got %d", on);
+    e->q_view = on;
+    return XQ_OK;
+}
+int xq_env_get_q_view(const xq_env* e, int* on) {
+    if (!e || !on) return fail(XQ_ERR_INVALID_ARGUMENT, "null pointer");
+    *on = e->q_view;
+    return XQ_OK;
+}
 int xq_env_set_reward(xq_env* e, int kind, double scale, double ply_cost, double bound) {
     if (!e) return fail(XQ_ERR_INVALID_ARGUMENT, "null env");
     if (kind != XQ_REWARD_EVALUATE && kind != XQ_REWARD_DELTA) return fail(XQ_ERR_INVALID_ARGUMENT, "xq_env_set_reward: unknown kind %d", kind);

@@ -187,6 +187,7 @@ struct ReplayDev {
     float* reward = nullptr;          // [capacity]
     uint8_t* done = nullptr;          // [capacity]
     uint8_t* next_player = nullptr;   // [capacity]   side to move in next_boards (0 Red, 1 Black); nullptr until xq_replay_track_next_player
+    uint8_t* mover = nullptr;         // [capacity]   side that moved in `boards` (the learner's colour in versus training); nullptr until xq_replay_track_mover
     int capacity = 0;
     // prioritized replay (xq_replay_enable_per; nullptr = uniform): priority of every slot = leaves of the sum tree, and the
     // largest priority assigned so far as it stood at the last rebuild (what a new transition enters with), as float bits
@@ -199,7 +200,7 @@ struct xq_replay {
     xq::DevBuf<uint32_t> boards, next_boards;     // what `dev` points into
     xq::DevBuf<int32_t> action_to;
     xq::DevBuf<float> reward, prio;
-    xq::DevBuf<uint8_t> done, next_player;
+    xq::DevBuf<uint8_t> done, next_player, mover;
     int size = 0;
     int write_pos = 0;
     uint64_t total = 0;
@@ -278,6 +279,8 @@ struct xq_env {
     // the reward the env kernel writes into a ring (xq_env_set_reward), as given; the launches carry the fp32 values
     int rw_kind = XQ_REWARD_EVALUATE;
     double rw_scale = 1e-3, rw_cost = 0.0, rw_bound = 1.0;
+    // the Q rows handed to the self-play and versus-learner launches are in the mover's view (xq_env_set_q_view)
+    int q_view = 0;
 };
 
 namespace xq {
@@ -389,6 +392,10 @@ struct QSource { const float* slabs; long long slab_stride; int nslabs; const fl
 // *q90_dev = nullptr) for the env kernel to finish; otherwise qs->slabs = nullptr and *q90_dev holds the finished values as always
 int dqn_q90_boards(xq_dqn* d, const uint32_t* boards_dev, int n, float** q90_dev, int* q_stride, hipStream_t on = nullptr, QSource* qs = nullptr);
 hipStream_t dqn_stream(xq_dqn* d);
+int dqn_view(const xq_dqn* d);              // current xq_dqn_set_view setting
+// view_boards_kernel (xq_view.hip.h) on `stream`: out[b] = view(boards[b], side of b), the side from side_dev[b] or, with meta_dev (an
+// env's boards), from bit 16 of meta_dev[b].x
+int view_boards_launch(const uint32_t* boards_dev, const uint8_t* side_dev, const uint4* meta_dev, int n, uint32_t* out_dev, hipStream_t stream);
 hipEvent_t dqn_qmax_event(xq_dqn* d);      // recorded behind the column-max GEMM of the last xq_dqn_td_grads*
 uint64_t dqn_params_version(const xq_dqn* d);   // counts the operations that rewrote parameters (either net, fp32 or the bf16 shadow)
 
@@ -415,13 +422,15 @@ int env_selfplay_launch(xq_env* env, const float* q90_dev, int q_stride, uint32_
                         hipEvent_t ev_stop = nullptr);      // ev_*: the kernel's own start / stop events (profiler, kernel-exact timing)
 int env_arena_launch(xq_env* env, const float* q90_dev, int q_stride, int pairs, int opening, const uint32_t eps_u32[2],
                      const int has_q[2], xq_arena_game* records_dev, int* live_dev, xq_step_result* results_dev,
-                     const int16_t* pick_dev, const int pick_on[2]);   // xq_arena.hip
+                     const int16_t* pick_dev, const int pick_on[2], const int q_view[2] = nullptr);   // xq_arena.hip; q_view: per half, the
+                                                                                                     // rows are in the mover's view
 void dqn_shape(const xq_dqn* d, int* n_in, int* n_out);    // layer_sizes[0], outputs
 constexpr uint32_t kMetaFrozen = 1u << 20;                  // meta.x flag of a finished arena game (xq_env.hip META_FROZEN)
 constexpr uint32_t kMetaVsDone = 1u << 21;                  // meta.x flag: the game's versus slot of this collect is written (META_VS_DONE)
 // versus training (xq_trainer_set_opponent): one phase of the collect, see env_versus_launch in xq_env.hip
 int env_versus_launch(xq_env* env, int phase, const float* q90_dev, int q_stride, const QSource* qs, uint32_t eps_u32,
-                      const int16_t* pick_dev, uint4* counts_dev, xq_replay* replay, hipStream_t on);
+                      const int16_t* pick_dev, uint4* counts_dev, xq_replay* replay, hipStream_t on, int opponent_view = 0);
+                      // (phase 1 reads the learner's rows by the env's q_view; opponent_view: phases 0 and 2, a net opponent's rows)
 // The search player's picks (xq_search.hip) of games [first, first + count) of env, on stream s: pick_dev[g] = an index into game g's
 // move list.  Arena: ties are broken on the stream of the pair (twin g - pairs).  seated (versus training, pairs = INT_MAX): only the
 // games where the learner's opponent is to move, ties on the game's own stream.
@@ -437,6 +446,7 @@ struct CheckedPlayer {
     int depth = 0;              // XQ_PLAYER_SEARCH: 1..3
     uint32_t eps_u32 = 0;       // (0 for random play: every move explores anyway)
     int n_out = 96;             // XQ_PLAYER_NET: the Q columns to compute, min(outputs, 96)
+    int view = 0;               // XQ_PLAYER_NET: the net reads the mover's view (its handle's xq_dqn_set_view when the player was made)
 };
 // in == nullptr: uniform-random play.  `who` opens the message of a rejected player ("xq_arena_run_players: player A")
 int make_player(const xq_arena_player* in, const char* who, CheckedPlayer* out);

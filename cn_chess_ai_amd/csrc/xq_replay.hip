@@ -351,10 +351,31 @@ int xq_replay_get_next_player(xq_replay* r, int first, int n, uint8_t* out) {
     if (n) XQ_HIP(hipMemcpy(out, r->dev.next_player + first, (size_t)n, hipMemcpyDeviceToHost));
     return XQ_OK;
 }
+// The who-moved column (the mover view, DESIGN.md §4 "Mover view"): next_player's sibling, by the same rules.  In versus training the
+// side that moved in s cannot be told from (s, a.to, s'), and a ring may mix modes, so it has a column of its own
+int xq_replay_track_mover(xq_replay* r) {
+    if (!r) return fail(XQ_ERR_INVALID_ARGUMENT, "null replay");
+    if (r->dev.mover) return XQ_OK;
+    if (r->size != 0 || r->total != 0) return fail(XQ_ERR_RUNTIME, "xq_replay_track_mover: the ring already holds transitions");
+    XQ_TRY(r->mover.alloc((size_t)r->dev.capacity));
+    XQ_HIP(hipMemsetAsync(r->mover, 0, (size_t)r->dev.capacity, r->stream));
+    XQ_HIP(hipStreamSynchronize(r->stream));
+    r->dev.mover = r->mover;
+    return XQ_OK;
+}
+int xq_replay_get_mover(xq_replay* r, int first, int n, uint8_t* out) {
+    if (!r || !out) return fail(XQ_ERR_INVALID_ARGUMENT, "null pointer");
+    if (!r->dev.mover) return fail(XQ_ERR_RUNTIME, "xq_replay_get_mover: the ring does not track who moved");
+    if (first < 0 || n < 0 || (long long)first + n > r->dev.capacity) return fail(XQ_ERR_INVALID_ARGUMENT, "slots [%d, %d + %d) outside the ring", first, first, n);
+    XQ_HIP(hipDeviceSynchronize());
+    if (n) XQ_HIP(hipMemcpy(out, r->dev.mover + first, (size_t)n, hipMemcpyDeviceToHost));
+    return XQ_OK;
+}
 static int push_host_impl(xq_replay* r, int n, const uint8_t* boards90, const int32_t* action_to, const float* reward,
-                          const uint8_t* done, const uint8_t* next_boards90, const uint8_t* next_player);
+                          const uint8_t* done, const uint8_t* next_boards90, const uint8_t* next_player, const uint8_t* mover = nullptr);
 int xq_replay_push_host(xq_replay* r, int n, const uint8_t* boards90, const int32_t* action_to, const float* reward,
                         const uint8_t* done, const uint8_t* next_boards90) {
+    if (r && r->dev.mover) return fail(XQ_ERR_INVALID_ARGUMENT, "xq_replay_push_host: this ring tracks who moved: use xq_replay_push_host_sides");
     if (r && r->dev.next_player)
         return fail(XQ_ERR_INVALID_ARGUMENT, "xq_replay_push_host: this ring tracks the side to move in s': use xq_replay_push_host_sided");
     return push_host_impl(r, n, boards90, action_to, reward, done, next_boards90, nullptr);
@@ -362,13 +383,26 @@ int xq_replay_push_host(xq_replay* r, int n, const uint8_t* boards90, const int3
 int xq_replay_push_host_sided(xq_replay* r, int n, const uint8_t* boards90, const int32_t* action_to, const float* reward,
                               const uint8_t* done, const uint8_t* next_boards90, const uint8_t* next_player) {
     if (!r || !next_player) return fail(XQ_ERR_INVALID_ARGUMENT, "xq_replay_push_host_sided: null pointer");
+    if (r->dev.mover) return fail(XQ_ERR_INVALID_ARGUMENT, "xq_replay_push_host_sided: this ring tracks who moved: use xq_replay_push_host_sides");
     if (!r->dev.next_player) return fail(XQ_ERR_INVALID_ARGUMENT, "xq_replay_push_host_sided: call xq_replay_track_next_player first");
     for (int i = 0; i < n; ++i)
         if (next_player[i] > 1) return fail(XQ_ERR_INVALID_ARGUMENT, "next_player[%d] = %d: 0 (Red) or 1 (Black)", i, (int)next_player[i]);
     return push_host_impl(r, n, boards90, action_to, reward, done, next_boards90, next_player);
 }
+int xq_replay_push_host_sides(xq_replay* r, int n, const uint8_t* boards90, const int32_t* action_to, const float* reward,
+                              const uint8_t* done, const uint8_t* next_boards90, const uint8_t* mover, const uint8_t* next_player) {
+    if (!r || !mover) return fail(XQ_ERR_INVALID_ARGUMENT, "xq_replay_push_host_sides: null pointer");
+    if (!r->dev.mover) return fail(XQ_ERR_INVALID_ARGUMENT, "xq_replay_push_host_sides: call xq_replay_track_mover first");
+    if ((next_player != nullptr) != (r->dev.next_player != nullptr))
+        return fail(XQ_ERR_INVALID_ARGUMENT, "xq_replay_push_host_sides: next_player goes with xq_replay_track_next_player, and only with it");
+    for (int i = 0; i < n; ++i) {
+        if (mover[i] > 1) return fail(XQ_ERR_INVALID_ARGUMENT, "mover[%d] = %d: 0 (Red) or 1 (Black)", i, (int)mover[i]);
+        if (next_player && next_player[i] > 1) return fail(XQ_ERR_INVALID_ARGUMENT, "next_player[%d] = %d: 0 (Red) or 1 (Black)", i, (int)next_player[i]);
+    }
+    return push_host_impl(r, n, boards90, action_to, reward, done, next_boards90, next_player, mover);
+}
 static int push_host_impl(xq_replay* r, int n, const uint8_t* boards90, const int32_t* action_to, const float* reward,
-                          const uint8_t* done, const uint8_t* next_boards90, const uint8_t* next_player) {
+                          const uint8_t* done, const uint8_t* next_boards90, const uint8_t* next_player, const uint8_t* mover) {
     if (!r || n < 0 || !boards90 || !action_to || !reward || !done || !next_boards90)
         return fail(XQ_ERR_INVALID_ARGUMENT, "xq_replay_push_host: null pointer");
     if (n > r->dev.capacity) return fail(XQ_ERR_INVALID_ARGUMENT, "push of %d exceeds capacity %d", n, r->dev.capacity);
@@ -388,6 +422,7 @@ static int push_host_impl(xq_replay* r, int n, const uint8_t* boards90, const in
         XQ_HIP(hipMemcpy(r->dev.reward + slot, reward + i, sizeof(float), hipMemcpyHostToDevice));
         XQ_HIP(hipMemcpy(r->dev.done + slot, done + i, 1, hipMemcpyHostToDevice));
         if (next_player) XQ_HIP(hipMemcpy(r->dev.next_player + slot, next_player + i, 1, hipMemcpyHostToDevice));
+        if (mover) XQ_HIP(hipMemcpy(r->dev.mover + slot, mover + i, 1, hipMemcpyHostToDevice));
         if (r->per.enabled) {       // a new transition enters with the largest priority assigned so far (0 for an empty one)
             hipLaunchKernelGGL(per_fill_kernel, dim3(1), dim3(64), 0, r->stream, r->dev.prio, slot, 1, r->dev.capacity,
                                action_to[i] >= 0 ? r->per.scalars + 0 : nullptr, 0.f);

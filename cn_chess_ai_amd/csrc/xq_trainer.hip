@@ -56,6 +56,10 @@ struct xq_trainer {
     xq::DevBuf<float> vs_q;
     xq::DevBuf<uint4> vs_counts;
     xq::Event vs_ev_env, vs_ev_q;
+    // mover view (xq_trainer_set_view): the env's boards as the net reads them, staged by view_boards_kernel on the collect's stream in
+    // front of every select chain — the learner's (view_sel) and a versus net opponent's with a view of its own (view_opp)
+    int view = XQ_VIEW_ABSOLUTE;
+    xq::DevBuf<uint32_t> view_sel, view_opp;
 };
 
 using namespace xq;
@@ -147,25 +151,45 @@ static int versus_opponent(xq_trainer* t, int phase, hipStream_t s) {
     const CheckedPlayer& o = t->vs;
     const int16_t* pick = nullptr;
     const float* q = nullptr;
+    int opp_view = 0;
     if (o.kind == XQ_PLAYER_SEARCH) {
         XQ_TRY(search_pick_launch(t->env, o.depth, 0, t->env->n, INT_MAX, true, o.eps_u32, t->vs_pick, s));
         pick = t->vs_pick;
     } else if (o.kind == XQ_PLAYER_NET) {
-        if (dqn_stream(o.net) != s) XQ_HIP(hipEventRecord(t->vs_ev_env, s));     // behind the env's last launch
-        XQ_TRY(borrowed_forward(o.net, t->env->boards, t->env->n, o.n_out, t->vs_q, s, t->vs_ev_env, t->vs_ev_q));
+        // the opponent reads the boards through ITS OWN handle's view
+        const uint32_t* boards = t->env->boards;
+        if (dqn_view(o.net) == XQ_VIEW_MOVER) {
+            XQ_TRY(t->view_opp.reserve((size_t)t->env->n * kBoardWords));
+            XQ_TRY(view_boards_launch(t->env->boards, nullptr, t->env->meta, t->env->n, t->view_opp, s));
+            boards = t->view_opp;
+            opp_view = 1;
+        }
+        if (dqn_stream(o.net) != s) XQ_HIP(hipEventRecord(t->vs_ev_env, s));     // behind the env's last launch (and the view's)
+        XQ_TRY(borrowed_forward(o.net, boards, t->env->n, o.n_out, t->vs_q, s, t->vs_ev_env, t->vs_ev_q));
         q = t->vs_q;
     }
-    return env_versus_launch(t->env, phase, q, 96, nullptr, o.eps_u32, pick, t->vs_counts, t->replay, s);
+    return env_versus_launch(t->env, phase, q, 96, nullptr, o.eps_u32, pick, t->vs_counts, t->replay, s, opp_view);
 }
 
 // A versus collect on stream s (`on`: the collect stream, if any): pre-move, select chain, learner half-ply, reply; one transition per
 // game, into the ring slots from write_pos, which moves once the last phase is queued
+// The boards the trainer's select chain reads: the env's or, under the mover view, their view in view_sel, staged on stream s now
+static int select_boards(xq_trainer* t, hipStream_t s, const uint32_t** boards) {
+    *boards = t->env->boards;
+    if (t->view != XQ_VIEW_MOVER) return XQ_OK;
+    XQ_TRY(view_boards_launch(t->env->boards, nullptr, t->env->meta, t->env->n, t->view_sel, s));
+    *boards = t->view_sel;
+    return XQ_OK;
+}
+
 static int versus_collect(xq_trainer* t, hipStream_t on, hipStream_t s) {
     float* q90 = nullptr;
     int stride = 0;
     QSource qs;
+    const uint32_t* boards = nullptr;
     XQ_TRY(versus_opponent(t, 0, s));
-    XQ_TRY(dqn_q90_boards(t->dqn, t->env->boards, t->env->n, &q90, &stride, on, &qs));
+    XQ_TRY(select_boards(t, s, &boards));
+    XQ_TRY(dqn_q90_boards(t->dqn, boards, t->env->n, &q90, &stride, on, &qs));
     XQ_TRY(env_versus_launch(t->env, 1, q90, stride, &qs, t->eps_u32, nullptr, t->vs_counts, t->replay, s));
     XQ_TRY(versus_opponent(t, 2, s));
     replay_advance(t->replay, t->env->n);
@@ -208,7 +232,9 @@ static int collect_impl(xq_trainer* t) {
         float* q90 = nullptr;
         int stride = 0;
         QSource qs;
-        XQ_TRY(dqn_q90_boards(t->dqn, t->env->boards, t->env->n, &q90, &stride, on, &qs));
+        const uint32_t* boards = nullptr;
+        XQ_TRY(select_boards(t, s, &boards));
+        XQ_TRY(dqn_q90_boards(t->dqn, boards, t->env->n, &q90, &stride, on, &qs));
         Profiler* p = dqn_profiler(t->dqn);
         const int h = p->begin("env_selfplay_step", s, true);       // one kernel: timed by its own start / stop events
         XQ_TRY(env_selfplay_launch(t->env, q90, stride, t->eps_u32, nullptr, t->replay, on, &qs, h >= 0 ? p->recs[h].a : nullptr,
@@ -262,6 +288,26 @@ int xq_trainer_set_zero_sum(xq_trainer* t, int on) {
         return fail(XQ_ERR_INVALID_ARGUMENT, "xq_trainer_set_zero_sum: an opponent is set (xq_trainer_set_opponent): a versus transition ends "
                                              "with the learner to move again, which the zero-sum target is not for");
     return xq_dqn_set_zero_sum(t->dqn, on);
+}
+
+// The mover view on the trainer's Q-net, env and ring (DESIGN.md §4 "Mover view"): before the first collect, because the ring's two side
+// columns can only be allocated while it is empty and a ring filled under one view is not a ring of the other.  The collects then stage
+// view(board, side to move) in front of the select chain and the env picks through the view's square map; learn_grads stages the
+// minibatch in the view (xq_dqn_td_grads_replay).  No window changes.
+int xq_trainer_set_view(xq_trainer* t, int view) {
+    if (!t) return fail(XQ_ERR_INVALID_ARGUMENT, "null trainer");
+    if (view != XQ_VIEW_ABSOLUTE && view != XQ_VIEW_MOVER) return fail(XQ_ERR_INVALID_ARGUMENT, "xq_trainer_set_view: unknown view %d", view);
+    if (t->env_steps != 0 || t->grads_queued || t->inflight > 0 || t->prepaid_collects > 0 || t->replay->total != 0)
+        return fail(XQ_ERR_RUNTIME, "xq_trainer_set_view: call before the first collect");
+    if (view == XQ_VIEW_MOVER) {
+        XQ_TRY(xq_replay_track_mover(t->replay));
+        XQ_TRY(xq_replay_track_next_player(t->replay));
+        XQ_TRY(t->view_sel.reserve((size_t)t->env->n * kBoardWords));
+    }
+    XQ_TRY(xq_dqn_set_view(t->dqn, view));
+    XQ_TRY(xq_env_set_q_view(t->env, view == XQ_VIEW_MOVER ? 1 : 0));
+    t->view = view;
+    return XQ_OK;
 }
 
 // the reward rule of the trainer's env: the next collect writes it, slots already in the ring keep theirs

@@ -117,6 +117,9 @@ class DQN:
     def train(self, state, action, reward, next_state, done, mode=_capi.BACKPROP_REFERENCE):
         """DQN::train (dqn.cpp:157-172): single transition, target network for max Q(s').  The reference's rule only: under
         set_zero_sum(True) it raises ValueError (the zero-sum target lives in the batched TD step)."""
+        if hasattr(_capi.load(), "xq_dqn_get_view") and self.view() == "mover":
+            raise ValueError("DQN.train reads absolute boards on the host; the mover view (set_view) is the batched paths': build the "
+                             "view with view_boards and use td_update, or td_grads_replay from a tracking ring")
         if hasattr(_capi.load(), "xq_dqn_get_zero_sum") and self.zero_sum():
             raise ValueError("DQN.train forms the reference's target r + gamma max Q(s') on the host; the zero-sum target "
                              "(set_zero_sum) is the batched TD step's: use td_update / td_grads_replay / Trainer")
@@ -231,6 +234,17 @@ class DQN:
         if next_player:
             out["next_player"] = p
         return out
+
+    def last_view(self, n):
+        """The first n rows of the batch the last td_grads_replay staged under set_view("mover"): dict of flag_s (1 = Black moved: s and
+        the action were swapped), flag_next (1 = Black moves next: s' was swapped), boards and next_boards ([n, 90] piece codes as
+        staged), action (as staged) and slot (the sampled slot).  Raises XqError when the last TD step was not a view-mode one."""
+        f, fn = np.zeros(n, np.uint8), np.zeros(n, np.uint8)
+        b, nb = np.zeros((n, 90), np.uint8), np.zeros((n, 90), np.uint8)
+        a, s = np.zeros(n, np.int32), np.zeros(n, np.int32)
+        call("xq_dqn_last_view", self._h, int(n), _ptr(f, C.c_uint8), _ptr(fn, C.c_uint8), _ptr(b, C.c_uint8), _ptr(nb, C.c_uint8),
+             _ptr(a, C.c_int32), _ptr(s, C.c_int32))
+        return dict(flag_s=f, flag_next=fn, boards=b, next_boards=nb, action=a, slot=s)
 
     def kernel_stats(self, enable=-1):
         """Returns the HIP-event timings collected so far; enable: 1 on, 0 off, 2 on + clear, -1 leave."""
@@ -528,6 +542,66 @@ def _zero_sum(self):
 
 DQN.set_zero_sum = _set_zero_sum
 DQN.zero_sum = _zero_sum
+
+
+# ---- mover view (build-defined, DESIGN.md §4 "Mover view") ----
+VIEWS = {"absolute": _capi.VIEW_ABSOLUTE, "mover": _capi.VIEW_MOVER}
+
+
+def _set_view(self, view="mover"):
+    """ "absolute" (the default: the net reads boards as they stand) or "mover": the net reads every position from the side to move —
+    view(board, side) is the board for Red and its colour swap (row -> 9 - row, Red <-> Black) for Black — and output k is the value
+    of moving to square k of the view.  td_grads_replay then stages view(s, mover), the action with it and view(s', next side) from a
+    ring with ReplayBuffer.track_mover() and track_next_player(); a VecEnv told set_q_view(True) picks through the same map.  The
+    host and raw-pointer entry points (td_update, q_boards, getQValues, ...) take boards as the net reads them: build them with
+    view_boards.  XqError while a TD step waits for its apply_grads; DQN.train refuses the mover view.  Not stored in the model
+    file."""
+    if view not in VIEWS:
+        raise ValueError(f"set_view: expected one of {sorted(VIEWS)}, got {view!r}")
+    call("xq_dqn_set_view", self._h, VIEWS[view])
+
+
+def _view(self):
+    """ "absolute" or "mover", as last set"""
+    v = C.c_int32()
+    call("xq_dqn_get_view", self._h, C.byref(v))
+    return {n: k for k, n in VIEWS.items()}[v.value]
+
+
+_NIBBLE_SHIFTS = (4 * np.arange(8)).astype(np.uint32)
+
+
+def view_boards_packed(words, side):
+    """view_boards on packed boards: [n, 12] uint32 words (square s = nibble s & 7 of word s >> 3) -> [n, 12] uint32"""
+    import torch
+    w = np.ascontiguousarray(words, dtype=np.uint32).reshape(-1, _capi.BOARD_WORDS)
+    n = len(w)
+    s = np.ascontiguousarray(side, dtype=np.uint8).reshape(n)
+    if n == 0:
+        return w.copy()
+    src = torch.from_numpy(w.view(np.int32)).cuda()
+    sd = torch.from_numpy(s).cuda()
+    out = torch.empty_like(src)
+    torch.cuda.synchronize()
+    call("xq_view_boards_dev", C.c_void_p(src.data_ptr()), C.c_void_p(sd.data_ptr()), n, C.c_void_p(out.data_ptr()), None)
+    call("xq_stream_synchronize", None)
+    return np.ascontiguousarray(out.cpu().numpy()).view(np.uint32)
+
+
+def view_boards(boards, side):
+    """view(board, side) of [n, 90] piece codes and [n] sides (0 = Red: the board, anything else: its colour swap) on the device
+    (view_boards_kernel) -> [n, 90] uint8.  What a caller of the host entry points (td_update, getQValues, ...) feeds a net with
+    set_view("mover")."""
+    b = np.ascontiguousarray(boards, dtype=np.uint8).reshape(-1, 90)
+    nib = np.zeros((len(b), 96), np.uint32)
+    nib[:, :90] = b & 15
+    words = (nib.reshape(-1, _capi.BOARD_WORDS, 8) << _NIBBLE_SHIFTS).sum(axis=2, dtype=np.uint32)
+    out = view_boards_packed(words, side)
+    return ((out[:, :, None] >> _NIBBLE_SHIFTS) & 15).reshape(-1, 96)[:, :90].astype(np.uint8)
+
+
+DQN.set_view = _set_view
+DQN.view = _view
 DQN.set_td_bootstrap = _set_td_bootstrap
 DQN.td_bootstrap = _td_bootstrap
 DQN.last_legal = _last_legal
@@ -656,6 +730,13 @@ class Trainer:
         if kind not in _BOOTSTRAPS:
             raise ValueError(f"set_td_bootstrap: expected 'all' or 'legal', got {kind!r}")
         call("xq_trainer_set_td_bootstrap", self._h, _BOOTSTRAPS[kind])
+
+    def set_view(self, view="mover"):
+        """DQN.set_view on the trainer's net, VecEnv.set_q_view on its env and both side columns on its ring (DESIGN.md §4 "Mover
+        view"): before the first collect (XqError afterwards).  Every collect then shows the net the boards from the side to move."""
+        if view not in VIEWS:
+            raise ValueError(f"set_view: expected one of {sorted(VIEWS)}, got {view!r}")
+        call("xq_trainer_set_view", self._h, VIEWS[view])
 
     def set_zero_sum(self, on=True):
         """DQN.set_zero_sum on the trainer's net (DESIGN.md §4 "Zero-sum target"), for self-play: XqError with an opponent set, as

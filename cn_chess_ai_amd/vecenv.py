@@ -103,13 +103,31 @@ class ReplayBuffer:
         call("xq_replay_get_next_player", self._h, int(first), int(n), _ptr(out, C.c_uint8))
         return out
 
-    def push(self, boards, action_to, reward, done, next_boards, next_player=None):
+    def track_mover(self):
+        """Make the ring record the side that moved in every stored board (what DQN.set_view("mover") reads, beside
+        track_next_player()).  While the ring is empty; afterwards push() needs mover."""
+        call("xq_replay_track_mover", self._h)
+
+    def mover(self, first=0, n=None):
+        """the who-moved bytes of slots [first, first + n) of a tracking ring (0 = Red, 1 = Black)"""
+        n = self.stats()[1] - first if n is None else n
+        out = np.zeros(n, dtype=np.uint8)
+        call("xq_replay_get_mover", self._h, int(first), int(n), _ptr(out, C.c_uint8))
+        return out
+
+    def push(self, boards, action_to, reward, done, next_boards, next_player=None, mover=None):
         boards = np.ascontiguousarray(boards, dtype=np.uint8).reshape(-1, 90)
         next_boards = np.ascontiguousarray(next_boards, dtype=np.uint8).reshape(-1, 90)
         n = len(boards)
         a = np.ascontiguousarray(action_to, dtype=np.int32).reshape(n)
         r = np.ascontiguousarray(reward, dtype=np.float32).reshape(n)
         d = np.ascontiguousarray(done, dtype=np.uint8).reshape(n)
+        if mover is not None:
+            m = np.ascontiguousarray(mover, dtype=np.uint8).reshape(n)
+            p = None if next_player is None else np.ascontiguousarray(next_player, dtype=np.uint8).reshape(n)
+            call("xq_replay_push_host_sides", self._h, n, _ptr(boards, C.c_uint8), _ptr(a, C.c_int32), _ptr(r, C.c_float),
+                 _ptr(d, C.c_uint8), _ptr(next_boards, C.c_uint8), _ptr(m, C.c_uint8), None if p is None else _ptr(p, C.c_uint8))
+            return
         if next_player is not None:
             p = np.ascontiguousarray(next_player, dtype=np.uint8).reshape(n)
             call("xq_replay_push_host_sided", self._h, n, _ptr(boards, C.c_uint8), _ptr(a, C.c_int32), _ptr(r, C.c_float),
@@ -336,6 +354,21 @@ class VecEnv:
         """Asynchronous, device pointers only (ints): the hot-loop form."""
         call("xq_env_selfplay_step", self._h, C.c_void_p(q90_dev) if q90_dev else None, int(q_stride), eps_to_u32(eps),
              C.c_void_p(results_dev) if results_dev else None, replay.handle if replay is not None else None)
+
+    # ---- mover view (build-defined, DESIGN.md §4 "Mover view") ----
+    def set_q_view(self, on=True):
+        """The Q rows handed to selfplay_step / selfplay_step_dev from now on are in the mover's view (DQN.set_view("mover"), built from
+        view_boards): with Black to move the greedy pick reads q[swap(to)] for the destination `to`.  Nothing else of the step
+        changes."""
+        if not isinstance(on, (bool, int)) or on not in (0, 1):
+            raise ValueError(f"set_q_view: expected a bool, got {on!r}")
+        call("xq_env_set_q_view", self._h, 1 if on else 0)
+
+    @property
+    def q_view(self):
+        v = C.c_int32()
+        call("xq_env_get_q_view", self._h, C.byref(v))
+        return bool(v.value)
 
     # ---- reward rule (build-defined, DESIGN.md §4 "Reward rule") ----
     def set_reward(self, kind, scale=1e-3, ply_cost=0.0, bound=1.0):

@@ -39,6 +39,8 @@ ROCPROF_NAMES = {
     "per_writeback": "per_writeback_kernel(",
     "mirror_stage": "mirror_stage_kernel(",
     "colour_swap_stage": "colour_swap_stage_kernel(",
+    "mover_view_stage": "mover_view_stage_kernel(",
+    "view_boards@select": "view_boards_kernel(",
     "legal_qmax": "legal_qmax_kernel(",
     "legal_side_stage": "legal_side_stage_kernel(",
     "gemm_legal_head": "gemm_f32_kernel<0, 0, 0, 1, 1, 0>(",
@@ -125,7 +127,7 @@ def pick_splits(M, N, K):
 
 def step_work(layers, minibatch, n_games, plies=1, bf16=False, bf16_bwd=False, td="online", screened=True, derive=True,
               prioritized=False, l0_mfma=True, optimizer="sgd", grad_clip=False, soft_target=False, n_step=1,
-              mirror=False, bootstrap="all", colour_swap=False):
+              mirror=False, bootstrap="all", colour_swap=False, view=False):
     """{bracket name: dict(flops, hbm_bytes, bound, peak, peak_unit, what)} for one training step of the given configuration.
     optimizer="adam" (xq_dqn_set_optimizer): adam_apply stands in place of sgd_apply; the default step knows no adam_apply.
     grad_clip=True (xq_dqn_set_grad_clip): grad_norm stands in front of the apply and takes the slab sums over from it; the default
@@ -141,7 +143,13 @@ def step_work(layers, minibatch, n_games, plies=1, bf16=False, bf16_bwd=False, t
     step knows none of them.
     colour_swap=True (xq_replay_set_colour_swap with prob > 0): colour_swap_stage stands in front of the step (behind nstep_assemble and
     mirror_stage when they are on) and, on a prioritized draw that nothing else stages, per_writeback behind it; under
-    bootstrap="legal" it stages the side bytes too and legal_side_stage is not launched; the default step knows no colour_swap_stage."""
+    bootstrap="legal" it stages the side bytes too and legal_side_stage is not launched; the default step knows no colour_swap_stage.
+    view=True (xq_trainer_set_view(XQ_VIEW_MOVER); not together with colour_swap): mover_view_stage stands in front of the step as the
+    last staging transform and, on a prioritized draw that nothing else stages, per_writeback behind it; under bootstrap="legal" it
+    stages the side bytes (0) and legal_side_stage is not launched; view_boards stands in front of the select chain; the default step
+    knows neither."""
+    if view and colour_swap:
+        raise ValueError("view and colour_swap exclude each other (xq_dqn_td_grads_replay refuses the pair)")
     if bootstrap not in ("all", "legal"):
         raise ValueError("bootstrap: 'all' or 'legal'")
     legal = bootstrap == "legal"
@@ -345,7 +353,15 @@ def step_work(layers, minibatch, n_games, plies=1, bf16=False, bf16_bwd=False, t
             "exchange of the colours (row -> 9 - row, Red <-> Black) of the flagged minibatch rows in the staging batch the TD step reads")
         if prioritized and first:
             put("per_writeback", 0.0, 20.0 * B, "hbm", "TD-error priorities of a prioritized colour-swapped draw back to the sampled slots")
-    if legal and (n_step > 1 or mirror) and not colour_swap:
+    if view:
+        # per row: the mirror's bytes with a second flag out, the ring's two side bytes in, in place the 8 B of the two slots they are read
+        # at; under the legal bootstrap the staged side byte out (legal_side_stage is then not launched)
+        first = n_step == 1 and not mirror
+        put("mover_view_stage", 0.0, B * ((218.0 if first else 212.0) + (1.0 if legal else 0.0)), "hbm",
+            "mover view of the minibatch in the staging batch the TD step reads: s and the action by who moved, s' by who moves next")
+        if prioritized and first:
+            put("per_writeback", 0.0, 20.0 * B, "hbm", "TD-error priorities of a prioritized view-mode draw back to the sampled slots")
+    if legal and (n_step > 1 or mirror) and not colour_swap and not view:
         # per staged row: the slot whose side it takes (4 B), the ring's byte, the staged byte
         put("legal_side_stage", 0.0, 6.0 * B, "hbm", "side to move in s' of every staged row, from the ring's column (legal-move bootstrap)")
     nw =STATE * H1 + sum(h[l] * h[l - 1] for l in range(1, k)) + Hl * NO
@@ -369,6 +385,8 @@ def step_work(layers, minibatch, n_games, plies=1, bf16=False, bf16_bwd=False, t
             "hidden products of the select chain" + ("; the last one carries the select head (Q[0..95] as k-slabs)" if ride else ""))
     if not ride:
         put("gemm_q90_select@select", 2.0 * n * Hl * 96, n * Hl * fa + 96 * Hl * fa + n * 96 * 4, "mfma", "select head Q(s)[0..95]")
+    if view:
+        put("view_boards@select", 0.0, (48.0 + 16.0 + 48.0) * n, "hbm", "view(board, side to move) of every game's board for the select chain")
     put("env_selfplay_step", 0.0, float(ENV_BYTES_PER_GAME) * n, "hbm",
         "fused self-play ply: legal moves, epsilon-greedy select, movePiece, reward, game over, auto-reset, transition -> ring")
     return w

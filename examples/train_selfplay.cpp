@@ -23,6 +23,9 @@
 //   target=reference|zerosum      target of the batched loop's TD step in self-play: r + gamma max (default, chessai.cpp:126) or the zero-sum
 //                                 (negamax) one, r - gamma max: s' has the other side to move (xq::ChessAI::setZeroSum; the sequential
 //                                 loop, parallel_games = 1, refuses zerosum)
+//   view=absolute|mover           how the batched loop's net reads a board: as it stands (default) or from the side to move — Black's
+//                                 positions colour-swapped, outputs indexed in that view (xq::ChessAI::setView; the sequential loop,
+//                                 parallel_games = 1, and getAIMove refuse mover; not together with swap=)
 //   reward=evaluate|delta[:scale[:cost[:bound]]]
 //                                 what the batched loop's plies write into the ring: evaluateBoard (default, chessai.cpp:115) or the
 //                                 transition's change of material balance, scaled (1e-3), less a cost per ply (0), clamped to +-bound (1)
@@ -40,7 +43,7 @@ int main(int argc, char** argv) {
     int episodes = 1000, parallel = 8192, replay = 0, minibatch = 0, save_every = 100, prefill = 0, npos = 0;
     const char* file = "model.bin";
     std::vector<int> hidden;
-    bool derive = false, json = false, adam = false, legal = false, zerosum = false;
+    bool derive = false, json = false, adam = false, legal = false, zerosum = false, mover_view = false;
     unsigned long long seed = 0;
     double clip = 0.0, mirror = 0.0, swap = 0.0;
     xq::Reward reward;
@@ -69,6 +72,11 @@ int main(int argc, char** argv) {
             const std::string v = a.substr(7);
             if (v != "reference" && v != "zerosum") { std::fprintf(stderr, "target=: expected reference or zerosum, got %s\n", v.c_str()); return 2; }
             zerosum = v == "zerosum";
+        }
+        else if (a.rfind("view=", 0) == 0) {
+            const std::string v = a.substr(5);
+            if (v != "absolute" && v != "mover") { std::fprintf(stderr, "view=: expected absolute or mover, got %s\n", v.c_str()); return 2; }
+            mover_view = v == "mover";
         }
         else if (a.rfind("reward=", 0) == 0) {
             // evaluate | delta[:scale[:cost[:bound]]]; the values are checked by ChessAI::setReward
@@ -120,6 +128,7 @@ int main(int argc, char** argv) {
         if (swap != 0.0) ai.setColourSwap(swap);
         if (legal) ai.setTdBootstrap(xq::TdBootstrap::legal());
         if (zerosum) ai.setZeroSum(true);
+        if (mover_view) ai.setView(xq::View::Mover);          // (after --hidden's setDQN: the view is the network's too)
         ai.setReward(reward);
         if (replay > 0) ai.setReplay(replay, minibatch);
         ai.setSaveInterval(save_every);
@@ -149,10 +158,12 @@ int main(int argc, char** argv) {
         std::printf("%d episodes in %.2f s (%.0f episodes/s), mean captured material red %.1f black %.1f, model -> %s\n", games, s,
                     games / s, games ? (double)red / games : 0.0, games ? (double)black / games : 0.0, file);
         if (st.zero_sum) std::printf("target: zero-sum (y = r - gamma max)\n");
+        if (st.view == xq::View::Mover) std::printf("view: mover (Black's positions colour-swapped)\n");
         if (st.seconds > 0)
             std::printf("batched loop: %llu plies + %llu updates in %.3f s = %.2f M env steps/s + %.0f updates/s\n",
                         (unsigned long long)st.envSteps, (unsigned long long)st.updates, st.seconds, st.envSteps / st.seconds / 1e6,
                         st.updates / st.seconds);
+        if (mover_view) return 0;                                // getAIMove reads the absolute board: it refuses the mover view
         const auto mv = ai.getAIMove(xq::PieceColor::Red);       // the GUI's "AI move" path, chessai.cpp:29-83
         std::printf("AI move for Red from the final position of the caller's board: (%d,%d) -> (%d,%d)\n", mv.first.first,
                     mv.first.second, mv.second.first, mv.second.second);

@@ -216,6 +216,11 @@ struct TdLoss {
 // What the batched TD step's target bootstraps from (xq_dqn_set_td_bootstrap; no upstream analogue): all() is the reference's maximum over
 // every output (chessai.cpp:126), legal() the maximum over the moves the side to move can play in s' (fp32 nets; the step then needs the
 // side to move per transition: xq_dqn_td_grads_sided / xq_dqn_td_update_host_sided, or a ring that tracks it — ChessAI::setTdBootstrap).
+// How the net reads a board (xq_dqn_set_view; no upstream analogue): Absolute as it stands (the reference's, the default), or Mover:
+// from the side to move — the board for Red, its colour swap (row -> 9 - row, Red <-> Black) for Black — with output k the value of moving
+// to square k of that view.  Not stored in the model file.
+enum class View { Absolute = XQ_VIEW_ABSOLUTE, Mover = XQ_VIEW_MOVER };
+
 struct TdBootstrap {
     int kind = XQ_BOOTSTRAP_ALL;
     static TdBootstrap all() { return TdBootstrap(); }
@@ -350,6 +355,14 @@ public:
         int on = 0;
         check(xq_dqn_get_zero_sum(h_, &on));
         return on != 0;
+    }
+    // the net's view of a board (xq_dqn_set_view): honoured by xq_dqn_td_grads_replay, the trainer, the arena and a versus net opponent;
+    // the host entry points of this class take states as the net reads them
+    void setView(View v) { check(xq_dqn_set_view(h_, (int)v)); }
+    View view() const {
+        int v = 0;
+        check(xq_dqn_get_view(h_, &v));
+        return (View)v;
     }
     TdBootstrap tdBootstrap() const {
         TdBootstrap b;
@@ -636,6 +649,9 @@ public:
 
     // chessai.cpp:29-83 — epsilon stays 0.1 at play time; 10 re-validated attempts, then a random valid action
     Move getAIMove(PieceColor color) {
+        if (view_ == View::Mover)
+            throw std::invalid_argument("ChessAI::getAIMove: setView(View::Mover) is the batched paths' (train with setParallelGames(n > 1), "
+                                        "evaluateAgainst); the single-board paths read the absolute board");
         const std::vector<double> state = getStateRepresentation();
         for (int attempt = 0; attempt < 10; ++attempt) {
             const std::vector<Action> validActions = getAllValidActions(color);
@@ -666,6 +682,9 @@ private:
         if (zeroSum_)
             throw std::invalid_argument(std::string("ChessAI::") + who + ": setZeroSum needs the batched loop (setParallelGames(n > 1)); "
                                         "the single-board loops keep the reference's target");
+        if (view_ == View::Mover)
+            throw std::invalid_argument(std::string("ChessAI::") + who + ": setView(View::Mover) needs the batched loop (setParallelGames(n > 1)); "
+                                        "the single-board loops read the absolute board");
     }
     // trainLoop = true: ChessAI::train (local 200-ply cap, done includes moveCount+1 >= 200, :96/:119);
     // trainLoop = false: ChessAI::startSelfPlay (no local cap, done = checkGameOver(), :197/:227).
@@ -798,13 +817,14 @@ public:
                         double mirror = 0;                      // ... and its mirror probability (setMirror)
                         double colour_swap = 0;                 // ... and its colour-swap probability (setColourSwap)
                         Reward reward;                          // the reward rule of the trainer's env as the run ended (setReward)
-                        bool zero_sum = false; };               // whether the trainer's net formed the zero-sum target as the run ended (setZeroSum)
+                        bool zero_sum = false;                  // whether the trainer's net formed the zero-sum target as the run ended (setZeroSum)
+                        View view = View::Absolute; };          // the view of the trainer's net as the run ended (setView)
     TrainStats lastTrainStats() const { return stats_; }
     // data-parallel train(): this process is rank comm->rank() of comm->world(); its batched games take the id range
     // [rank * parallelGames, (rank + 1) * parallelGames) and every update all-reduces the gradients over RCCL (nullptr = off)
     void setCommunicator(Comm* comm) { comm_ = comm; }
     void setBatchSeed(uint64_t seed) { batchSeed_ = seed; }                  // 0 (default): time-seeded like upstream
-    void setDQN(std::unique_ptr<DQN> d) { dqn = std::move(d); }
+    void setDQN(std::unique_ptr<DQN> d) { dqn = std::move(d); if (dqn && view_ != View::Absolute) dqn->setView(view_); }
     // Optimizer of the batched train(): forwarded to this agent's network (created now if need be), whose choice the batched loop takes
     // over.  The sequential loop (parallelGames == 1) is the reference's backpropagate(lr): plain SGD whatever is set here.
     void setOptimizer(const Optimizer& o) { initializeDQN(); dqn->setOptimizer(o); }
@@ -829,6 +849,8 @@ public:
     // colour-swap augmentation of the batched train(): xq_trainer_set_colour_swap on the trainer (0 = off, the default); on-policy too
     void setColourSwap(double prob) {
         if (!(prob >= 0.0 && prob <= 1.0)) throw std::invalid_argument("setColourSwap: prob must be in [0, 1]");
+        if (prob > 0.0 && view_ == View::Mover)
+            throw std::invalid_argument("setColourSwap: the mover view is on (setView): the view of a swapped transition is the view of the transition");
         colourSwap_ = prob;
     }
     double colourSwap() const { return colourSwap_; }
@@ -854,6 +876,20 @@ public:
         zeroSum_ = on;
     }
     bool zeroSum() const { return zeroSum_; }
+    // Mover view (DESIGN.md §4 "Mover view") of the batched train(): xq_trainer_set_view on the trainer train() creates, and on this agent's
+    // own network (created now if need be), through which evaluateAgainst's arena reads it.  std::invalid_argument together with
+    // setColourSwap(> 0); the single-board paths (trainEpisode, trainStep, startSelfPlay, getAIMove, train with parallelGames == 1) read
+    // the absolute board and throw std::invalid_argument under it.  A model file does not carry the view: an opponent loaded from one
+    // plays with the absolute view.
+    void setView(View v) {
+        if (v != View::Absolute && v != View::Mover) throw std::invalid_argument("setView: unknown view");
+        if (v == View::Mover && colourSwap_ > 0.0)
+            throw std::invalid_argument("setView: colour-swap augmentation is on (setColourSwap): the view of a swapped transition is the view of the transition");
+        initializeDQN();
+        dqn->setView(v);
+        view_ = v;
+    }
+    View view() const { return view_; }
     DQN* network() { return dqn.get(); }
     std::vector<double> getStateRepresentation() {                           // chessai.cpp:268-289 (encoding only)
         std::vector<double> s(90 * 14, 0.0);
@@ -894,6 +930,7 @@ private:
         xq_dqn* td = nullptr; xq_env* te = nullptr;
         check(xq_trainer_dqn(t, &td)); check(xq_trainer_env(t, &te));
         if (dqn->tdBootstrap().kind != XQ_BOOTSTRAP_ALL) check(xq_trainer_set_td_bootstrap(t, dqn->tdBootstrap().kind));   // (the ring is empty)
+        if (view_ != View::Absolute) check(xq_trainer_set_view(t, (int)view_));                                             // (... and no collect has run)
         std::vector<double> w, b;
         dqn->getParameters(w, b);                // continue from this agent's weights
         check(xq_dqn_set_params(td, XQ_NET_ONLINE, w.data(), b.data()));
@@ -961,6 +998,9 @@ private:
             int zs = 0;
             check(xq_dqn_get_zero_sum(td, &zs));
             stats_.zero_sum = zs != 0;
+            int vw = 0;
+            check(xq_dqn_get_view(td, &vw));
+            stats_.view = (View)vw;
         }
         {
             uint64_t q[4] = {0, 0, 0, 0}; int hold = 0;
@@ -990,6 +1030,7 @@ private:
     double colourSwap_ = 0.0;
     Reward reward_;
     bool zeroSum_ = false;
+    View view_ = View::Absolute;
     int prefillPlies_ = 0;
     std::unique_ptr<Player> opponent_;
     TrainStats stats_;

@@ -701,6 +701,54 @@ int xq_replay_track_next_player(xq_replay* r);
 int xq_replay_push_host_sided(xq_replay* r, int n, const uint8_t* boards90, const int32_t* action_to, const float* reward,
                               const uint8_t* done, const uint8_t* next_boards90, const uint8_t* next_player);
 int xq_replay_get_next_player(xq_replay* r, int first, int n, uint8_t* out);
+/* Mover view (DESIGN.md §4 "Mover view").  Write swap for the colour-swap map: board'[(9 - r) 9 + c] = sigma(board[r 9 + c]) and
+ * a' = a + 81 - 18 (a div 9) for 0 <= a < 90, any other value as it is.  view(board, side) is board when side == 0 (Red) and
+ * swap(board) when side == 1.  A net with XQ_VIEW_MOVER reads view(s, side to move in s), and its output k is the value of moving to
+ * square k OF THE VIEW: on an absolute board with Black to move the value of the destination `to` is output swap(to).  A transition
+ * (s, a, r, s', done) with mover m and next side p trains on (view(s, m), m ? swap(a) : a, r, view(s', p), done); in that batch the side
+ * to move in s' is always Red.  Reward, done, discounts, zero-sum, the loss, n-step, mirror and prioritized replay do not change; the ring
+ * keeps absolute boards and absolute action_to.
+ * The view is a property of the handle, XQ_VIEW_ABSOLUTE by default: unknown values are XQ_ERR_INVALID_ARGUMENT, a change while a TD step
+ * waits for its apply_grads is XQ_ERR_RUNTIME, and it survives every other setter, xq_dqn_set_params, xq_dqn_load_model and
+ * xq_dqn_update_target.  It is not stored in the model file.
+ * The paths that know the side honour it: xq_dqn_td_grads_replay (below) and an env told that its rows are in the view
+ * (xq_env_set_q_view).  The raw-pointer and host entry points — xq_dqn_td_grads, _sided, xq_dqn_td_update_host*, xq_dqn_forward*,
+ * xq_dqn_select_q_dev, xq_dqn_backpropagate — take boards AS THE NET READS THEM and transform nothing: a caller who wants the view
+ * builds it with xq_view_boards_dev.
+ * xq_dqn_td_grads_replay under XQ_VIEW_MOVER stages the minibatch with one more kernel, mover_view_stage_kernel, the last staging
+ * transform (n-step, then mirror, then view): s and the action by mover[first slot], s' by next_player[the slot whose s' was staged],
+ * and under XQ_BOOTSTRAP_LEGAL the staged side byte 0 on every row.  The step then runs on the staged batch unchanged, a prioritized
+ * draw's priorities go to the sampled slots.  XQ_ERR_INVALID_ARGUMENT from a ring that does not track both columns
+ * (xq_replay_track_mover, xq_replay_track_next_player), and from a ring with xq_replay_set_colour_swap(prob > 0): the view of a swapped
+ * transition is the view of the transition bit for bit, so the augmentation would only spend a launch. */
+enum { XQ_VIEW_ABSOLUTE = 0, XQ_VIEW_MOVER = 1 };
+int xq_dqn_set_view(xq_dqn* d, int view);
+int xq_dqn_get_view(const xq_dqn* d, int* view);
+/* out_dev[b] = view(boards_dev[b], side_dev[b]) for n packed boards (12 words each; side_dev: [n] u8, 0 = Red, anything else Black),
+ * queued on hip_stream (nullptr: the default stream).  out_dev must not be boards_dev.  Nibbles 90..95 of a swapped board come out 0. */
+int xq_view_boards_dev(const void* boards_dev, const void* side_dev, int n, void* out_dev, void* hip_stream);
+/* The first n rows of the batch the last xq_dqn_td_grads_replay staged under XQ_VIEW_MOVER (tests / interop; XQ_ERR_RUNTIME if the last
+ * TD step was not a view-mode one): the two flags per row, the staged boards (90 piece codes each), actions and sampled slots.  Every
+ * pointer is optional.  Synchronises the handle's stream. */
+int xq_dqn_last_view(xq_dqn* d, int n, uint8_t* flag_s, uint8_t* flag_next, uint8_t* boards90, uint8_t* next_boards90, int32_t* action_to,
+                     int32_t* slot);
+/* The ring's who-moved column (for XQ_VIEW_MOVER): one byte per slot, the side that moved in the stored board — in versus training the
+ * learner's colour, which (s, a.to, s') does not tell.  next_player's sibling, by the same rules: xq_replay_track_mover allocates it
+ * while the ring is empty (XQ_ERR_RUNTIME otherwise; a second call is a no-op); on a tracking ring every transition written by
+ * xq_env_selfplay_step carries its mover and every one written by versus training the learner's colour; xq_replay_push_host and
+ * xq_replay_push_host_sided are XQ_ERR_INVALID_ARGUMENT and xq_replay_push_host_sides pushes with mover[n] and, exactly if the ring
+ * tracks that column too, next_player[n] (else nullptr).  xq_replay_get_mover copies slots [first, first + n) to the host (tests;
+ * synchronises; XQ_ERR_RUNTIME on a ring that does not track).  The column belongs to XQ_ORDER_RING_CONTENTS. */
+int xq_replay_track_mover(xq_replay* r);
+int xq_replay_push_host_sides(xq_replay* r, int n, const uint8_t* boards90, const int32_t* action_to, const float* reward,
+                              const uint8_t* done, const uint8_t* next_boards90, const uint8_t* mover, const uint8_t* next_player);
+int xq_replay_get_mover(xq_replay* r, int first, int n, uint8_t* out);
+/* "The Q rows handed to xq_env_selfplay_step* are in the mover's view": where the greedy pick reads q[to] it reads q[swap(to)] when
+ * Black is to move.  Nothing else of the step changes; the ring's action_to stays absolute.  Exact ties may resolve to another move than
+ * on the absolute board with permuted rows would, only in that the scan order of the move list is not symmetric: the pick is the first
+ * maximum over the list in its own order either way.  on other than 0 or 1: XQ_ERR_INVALID_ARGUMENT. */
+int xq_env_set_q_view(xq_env* e, int on);
+int xq_env_get_q_view(const xq_env* e, int* on);
 /* Per-kernel HIP-event timing on the handle stream, for bench.py (name -> summed ms, launches, algorithmic flops/bytes).
  * enable: -1 leave, 0 off, 1 on, 2 on + clear, 3 on + clear but bracket only the TD step's dominant GEMM (gemm_qmax_rowmax /
  * gemm_qmax_screen) and env_selfplay_step, 4 = 3 with the GEMM bracketed on every 4th launch only (a pair of event records
@@ -810,6 +858,10 @@ int xq_arena_reset(xq_arena* a, int opening_plies);
  * device, ordered behind the arena's stream by the caller (NULL = both players random); eps_a / eps_b in [0, 1] are the players'
  * epsilons.  A's rows are read from the half where A is to move.  INVALID_ARGUMENT once no game is live. */
 int xq_arena_ply_q_dev(xq_arena* a, const float* q_dev, int q_stride, double eps_a, double eps_b);
+/* ... with a flag per player (0 or 1): that player's rows are in the mover's view (DESIGN.md §4 "Mover view"; the caller computed them on
+ * xq_view_boards_dev's boards), so where it moves as Black the pick reads q[swap(to)].  (0, 0) is xq_arena_ply_q_dev.  A network player
+ * of xq_arena_run / xq_arena_run_players is read through its own handle's view (xq_dqn_set_view) without further ado. */
+int xq_arena_ply_q_dev_view(xq_arena* a, const float* q_dev, int q_stride, double eps_a, double eps_b, int view_a, int view_b);
 /* Plays until no game is live or max_plies plies (<= 0: no limit) have been played by this call; *plies_played (optional) = how many.
  * dqn_a / dqn_b: a network with layer_sizes[0] == 1260 and >= 90 outputs, or NULL for uniform-random play; dqn_a == dqn_b is allowed,
  * and so are handles on different streams (ordered by events).  eps_a, eps_b in [0, 1]. */
@@ -922,6 +974,13 @@ int xq_trainer_set_td_bootstrap(xq_trainer* t, int kind);
  * xq_trainer_set_opponent(non-NULL) while zero-sum is on.  Call between iterations: XQ_ERR_RUNTIME while a learn_grads waits for its
  * learn_apply. */
 int xq_trainer_set_zero_sum(xq_trainer* t, int on);
+/* The mover view (DESIGN.md §4 "Mover view") on the trainer: xq_dqn_set_view on its Q-net, xq_env_set_q_view on its env, and both side
+ * columns on its ring (xq_replay_track_mover, xq_replay_track_next_player).  Before the first collect (XQ_ERR_RUNTIME afterwards: the
+ * columns need an empty ring).  Every collect then stages view(board, side to move) of the env's boards with view_boards_kernel on the
+ * collect's stream and hands that to the select chain; a versus NET opponent is read through ITS OWN handle's view.  Composes with
+ * zero-sum, both bootstraps, n-step, mirror, prioritized replay and overlap_collect 0 and 1; with xq_trainer_set_colour_swap(prob > 0)
+ * learn_grads is XQ_ERR_INVALID_ARGUMENT. */
+int xq_trainer_set_view(xq_trainer* t, int view);
 /* Versus training (DESIGN.md §4 "Versus training"): from the next collect on, the learner plays against a fixed opponent instead of
  * itself — uniform-random play, the material search (depth 1..3, eps) or a borrowed network (eps; layer_sizes[0] == 1260, >= 90
  * outputs, not the trainer's own).  The learner plays Black in game g iff (first_game_id + g) & 1.  A collect still writes one
