@@ -24,8 +24,8 @@
 // the one place that touches params_version, the screen's kept rows, the select chain's kept sums and tgt_rest_synced.
 // This file = the handle (struct xq_dqn) + host orchestration + the C ABI; the kernels live in xq_l0.hip.h (layer-0 gathers and
 // segmented sums), xq_tail.hip.h (TD delta, gradient sums, fused launches, SGD), xq_refine.hip.h (screening pass 2), xq_l0grad.hip.h
-// (layer-0 gradient on the matrix pipe), xq_gemm*.hip.h and xq_screen.hip.h (matrix-pipe products), xq_nstep.hip.h, xq_mirror.hip.h and
-// xq_colour_swap.hip.h (staging of n-step, mirrored and colour-swapped batches), xq_legal.hip.h (the legal-move bootstrap, on the rules engine of xq_rules.hip.h).
+// (layer-0 gradient on the matrix pipe), xq_gemm*.hip.h and xq_screen.hip.h (matrix-pipe products), xq_nstep.hip.h and
+// xq_stage.hip.h (staging of n-step, mirrored, colour-swapped and mover-view batches), xq_legal.hip.h (the legal-move bootstrap, on the rules engine of xq_rules.hip.h).
 #include "xq_internal.h"
 #include <hip/hip_ext.h>
 #include "xq_gemm.hip.h"
@@ -83,6 +83,31 @@ struct Screen {
     void guard_decide(const unsigned long long totals[2]);  int guard_tick(bool* screened);  int guard_queue(int n, hipStream_t s);
     int shadow_job(const xq_dqn* d, int sel_net, int parity, hipStream_t s, ShadowJob* shadow);
     int plan(xq_dqn* d, const TdStep& s, ScreenPlan* P);
+};
+// The staging batch of a TD step from a ring: what the staging kernels fill — nstep_assemble_kernel, mirror_stage_kernel,
+// colour_swap_stage_kernel, mover_view_stage_kernel, in that order, the first one on gathering from the ring and every later one working
+// in place — and the TD step then reads with the identity slot source
+struct StageIo;
+struct StagedBatch {
+    enum : unsigned { kAssemble = 1u, kMirror = 2u, kColourSwap = 4u, kView = 8u };
+    DevBuf<uint32_t> ns_boards, ns_next;
+    DevBuf<int32_t> ns_action, ns_first;        // ns_first: the sampled slot
+    DevBuf<float> ns_reward;                    // (behind the assembly: the n-step return)
+    DevBuf<uint8_t> ns_done;
+    DevBuf<int32_t> ns_m, ns_last;              // assembly: chain elements used, the slot whose next board was staged
+    DevBuf<uint8_t> ns_flag, ns_cflag;          // mirror / colour swap: the row's flag
+    DevBuf<uint8_t> ns_vflag, ns_vflag_next;    // view: the flags of s and of s'
+    DevBuf<uint8_t> ns_side;                    // legal-move bootstrap: the side to move in the staged s'
+    // the last TD step: its rows if it ran on this batch (else 0), the stages that filled it, whether a transform staged the side bytes
+    struct Last { int rows = 0; unsigned stages = 0; bool sided = false; } last;
+    int reserve(size_t rows) {                  // the columns every stage shares
+        XQ_TRY(ns_boards.reserve(rows * kBoardWords));
+        XQ_TRY(ns_next.reserve(rows * kBoardWords));
+        for (DevBuf<int32_t>* b : {&ns_action, &ns_first}) XQ_TRY(b->reserve(rows));
+        XQ_TRY(ns_reward.reserve(rows));
+        return ns_done.reserve(rows);
+    }
+    StageIo io(const ReplayDev* ring) const;    // gather from `ring`, or (nullptr) the batch in place; defined below the kernel headers
 };
 }  // namespace xq
 struct xq_dqn {
@@ -190,41 +215,22 @@ struct xq_dqn {
     xq::DevBuf<float> xdense, qfull, tfull;
     xq::DevBuf<uint32_t> hb;                    // host-batch staging: boards, next boards
     xq::DevBuf<int32_t> ha;  xq::DevBuf<float> hr;  xq::DevBuf<uint8_t> hd;
-    // n-step returns (xq_replay_set_n_step): the staging batch nstep_assemble_kernel fills and the TD step then reads with the identity
-    // slot source — boards, next boards, action, n-step reward, done — and per row the chain elements used, the sampled slot and the slot
-    // whose next board was staged.  nstep_rows: rows of the last TD step if it was an n-step one, else 0 (xq_dqn_last_n_step)
-    xq::DevBuf<uint32_t> ns_boards, ns_next;
-    xq::DevBuf<int32_t> ns_action, ns_m, ns_first, ns_last;
-    xq::DevBuf<float> ns_reward;
-    xq::DevBuf<uint8_t> ns_done;
-    int nstep_rows = 0;
-    // mirror augmentation (xq_replay_set_mirror): mirror_stage_kernel stages into the same buffers (ns_first: the sampled slot) or
-    // transforms an n-step batch there in place; per row the flag.  mirror_rows: rows of the last TD step if it was a mirror-mode one
-    xq::DevBuf<uint8_t> ns_flag;
-    int mirror_rows = 0;
-    // colour-swap augmentation (xq_replay_set_colour_swap): colour_swap_stage_kernel does the same, as the first staging transform or in
-    // place behind the n-step assembly and / or the mirror; per row its own flag.  colour_swap_rows: rows of the last TD step if it was a
-    // colour-swap-mode one; colour_swap_sided: that step staged the side bytes too (it ran under the legal-move bootstrap)
-    xq::DevBuf<uint8_t> ns_cflag;
-    int colour_swap_rows = 0;
-    bool colour_swap_sided = false;
+    // the staging batch of a TD step from a ring (n-step returns, mirror, colour swap, mover view: DESIGN.md §4 "Staging pipeline")
+    xq::StagedBatch staged;
     // legal-move bootstrap (xq_dqn_set_td_bootstrap): the k-slabs of the 96-row head product of s' (the selecting net's, then the target
     // net's of a Double-DQN step), the pre-activations legal_qmax_kernel leaves of them, the move count per row, the host batch's side
     // bytes.  legal_rows: rows of the last TD step if it was a legal one, else 0 (xq_dqn_last_legal)
     int bootstrap = XQ_BOOTSTRAP_ALL;
     xq::DevBuf<float> z96, z96_slabs;
     xq::DevBuf<int> legal_nmoves;
-    xq::DevBuf<uint8_t> hside, ns_side;         // side bytes of the host batch / of the staged (n-step, mirror) batch
+    xq::DevBuf<uint8_t> hside;                  // side bytes of the host batch (the staged batch's: staged.ns_side)
     int legal_rows = 0;
     // zero-sum (negamax) target (xq_dqn_set_zero_sum, DESIGN.md §4 "Zero-sum target"): the TD step's discount is -(float)gamma, the
     // n-step discounts alternate in sign, and a side without a move under the legal bootstrap bootstraps from -inf (tanh: -1)
     int zero_sum = 0;
     // mover view (xq_dqn_set_view, DESIGN.md §4 "Mover view"): a TD step from a ring stages view(s, mover) and view(s', next side) with
-    // mover_view_stage_kernel, the last staging transform; per row the two flags.  view_rows: rows of the last TD step if it was a
-    // view-mode one, else 0 (xq_dqn_last_view)
+    // mover_view_stage_kernel, the last staging transform
     int view = XQ_VIEW_ABSOLUTE;
-    xq::DevBuf<uint8_t> ns_vflag, ns_vflag_next;
-    int view_rows = 0;
     xq::Profiler prof;
     // fused launches of the TD step's tail (td_tail_kernel): while `tail_open`, the launch helpers of the small fp32 GEMMs, the
     // output-layer / layer-0 segmented sums and the bias column sums append their blocks to `tail` instead of launching.  Written by
@@ -312,9 +318,7 @@ struct SmallTiles {
 #include "xq_tail.hip.h"
 #include "xq_refine.hip.h"
 #include "xq_nstep.hip.h"
-#include "xq_mirror.hip.h"
-#include "xq_colour_swap.hip.h"
-#include "xq_view.hip.h"
+#include "xq_stage.hip.h"
 #include "xq_legal.hip.h"
 
 namespace xq {
@@ -2195,12 +2199,9 @@ static int td_grads_impl(xq_dqn* d, const uint32_t* boards, const uint32_t* next
     s.action_to = action_to; s.reward = reward; s.done = done; s.slots = slots; s.per = per;
     s.next_boards = next_boards; s.next_player = next_player; s.legal = legal;
     // zero-sum: the signed discount -g (r + (-g) t and r - g t are the same fp32 bits, contracted or not); an n-step batch's discount
-    // comes signed from td_grads_nstep
+    // comes signed from nstep_assemble
     s.gamma = discount ? *discount : d->zero_sum ? -(float)d->gamma : (float)d->gamma;
-    d->nstep_rows = 0;                               // (xq_dqn_td_grads_replay sets it behind an n-step batch)
-    d->mirror_rows = 0;                              // (... and this one behind a mirror-mode batch)
-    d->colour_swap_rows = 0;                         // (... and this one behind a colour-swap-mode batch)
-    d->view_rows = 0;                                // (... and this one behind a view-mode batch)
+    d->staged.last = {};                             // (td_grads_ring_staged sets it behind a step on the staging batch)
     s.n = n; s.mode = mode; s.nl = nl; s.Hl = Hl; s.NO = NO; s.dbl = dbl; s.bf = bf; s.sel_net = td_net == XQ_TD_TARGET_NET ? XQ_NET_TARGET : XQ_NET_ONLINE;
     chain_views(d, d->acts, d->acts_bf, XQ_MAX_LAYERS, true, s.outs, s.outs_bf);
     chain_views(d, d->tacts, d->tacts_bf, 2, !bf, s.touts, s.touts_bf);
@@ -2530,196 +2531,33 @@ int xq_dqn_grad_buffer(xq_dqn* d, float** grads_dev, size_t* n_floats) {
     return XQ_OK;
 }
 
-// The TD step on the handle's staging batch (what an n-step assembly or a mirror gather filled): identity slot source, the given discount
-// (nullptr: the handle's gamma).  A prioritized draw keeps its importance weights; the step gets no priority table, and
-// per_writeback_kernel behind it writes the live rows' priorities to the sampled slots recorded in ns_first
-// Under the legal-move bootstrap the staged rows' side bytes come from the ring's column at row_slot[b] (legal_side_stage_kernel) —
-// unless colour_swap_stage_kernel has staged them already (side_staged: it flips the flagged rows' bytes as it goes)
-static int td_grads_staged(xq_dqn* d, xq_replay* r, const int32_t* row_slot, int batch, int td_net, int mode, const PerOpts* per,
-                           const float* discount, bool side_staged = false) {
-    PerOpts step_per;
-    if (per) { step_per = *per; step_per.prio = nullptr; step_per.pmax_live = nullptr; }
-    const uint8_t* side = nullptr;
-    if (d->bootstrap == XQ_BOOTSTRAP_LEGAL && side_staged) {
-        side = d->ns_side;
-    } else if (d->bootstrap == XQ_BOOTSTRAP_LEGAL) {
-        XQ_TRY(d->ns_side.reserve((size_t)batch));
-        ProfScope ps(d, "legal_side_stage", 0.0, (double)batch * 6.0, true);
-        hipExtLaunchKernelGGL(legal_side_stage_kernel, dim3((batch + 255) / 256), dim3(256), 0, d->cur, ps.start(), ps.stop(), 0,
-                              r->dev.next_player, row_slot, d->ns_side.p, batch, r->dev.capacity);
-        XQ_HIP(hipGetLastError());
-        side = d->ns_side;
-    }
-    XQ_TRY(td_grads_impl(d, d->ns_boards, d->ns_next, d->ns_action, d->ns_reward, d->ns_done, explicit_slots(nullptr), batch, td_net, mode,
-                         per ? &step_per : nullptr, discount, side));
-    if (per) {
-        ProfScope ps(d, "per_writeback", 0.0, (double)batch * 20.0, true);
-        hipExtLaunchKernelGGL(per_writeback_kernel, dim3((batch + 255) / 256), dim3(256), 0, d->cur, ps.start(), ps.stop(), 0, batch,
-                              d->qsa.p, d->yv.p, d->act_mb.p, d->ns_first.p, per->prio, per->pmax_live, per->eps, per->alpha);
-        XQ_HIP(hipGetLastError());
-    }
-    return XQ_OK;
-}
-
-// Mirror augmentation (xq_replay_set_mirror): queues mirror_stage_kernel for the next TD step from ring `r` and counts it.  gather: the
-// minibatch from the ring (through `src`) into the handle's staging batch; otherwise the staging batch an n-step assembly just filled,
-// in place.  Whether row b is reflected is the ring's Philox stream at {b, 0, call, 3}
-static int mirror_stage(xq_dqn* d, xq_replay* r, SlotSrc src, int batch, bool gather) {
-    const size_t rows = (size_t)batch;
-    if (gather) {
-        XQ_TRY(d->ns_boards.reserve(rows * kBoardWords));
-        XQ_TRY(d->ns_next.reserve(rows * kBoardWords));
-        for (DevBuf<int32_t>* b : {&d->ns_action, &d->ns_first}) XQ_TRY(b->reserve(rows));
-        XQ_TRY(d->ns_reward.reserve(rows));
-        XQ_TRY(d->ns_done.reserve(rows));
-    }
-    XQ_TRY(d->ns_flag.reserve(rows));
-    MirrorArgs A; memset(&A, 0, sizeof A);
-    if (gather) {
-        A.boards = r->dev.boards; A.next_boards = r->dev.next_boards; A.action_to = r->dev.action_to; A.reward = r->dev.reward; A.done = r->dev.done;
+// ---- the staging pipeline of a TD step from a ring (DESIGN.md §4 "Staging pipeline") --------------------------------------------------
+StageIo StagedBatch::io(const ReplayDev* ring) const {
+    StageIo io; memset(&io, 0, sizeof io);
+    if (ring) {
+        io.boards = ring->boards; io.next_boards = ring->next_boards; io.action_to = ring->action_to; io.reward = ring->reward; io.done = ring->done;
+        io.gather = 1u;
     } else {
-        A.boards = d->ns_boards; A.next_boards = d->ns_next; A.action_to = d->ns_action; A.reward = d->ns_reward; A.done = d->ns_done;
+        io.boards = ns_boards; io.next_boards = ns_next; io.action_to = ns_action; io.reward = ns_reward; io.done = ns_done;
     }
-    A.s_boards = d->ns_boards; A.s_next = d->ns_next; A.s_action = d->ns_action; A.s_reward = d->ns_reward; A.s_done = d->ns_done;
-    A.s_first = d->ns_first; A.s_flag = d->ns_flag;
-    A.thresh = eps_to_u32(r->mirror_prob); A.all = r->mirror_prob >= 1.0 ? 1u : 0u;
-    A.gather = gather ? 1u : 0u;
-    A.call = (uint32_t)r->mirror_calls; A.seed_lo = (uint32_t)r->seed; A.seed_hi = (uint32_t)(r->seed >> 32);
-    r->mirror_calls += 1;
-    {
-        // per row, from the ring: two boards and 9 B in, two boards, 9 B, the slot and the flag out; in place: two boards and the action
-        // in, two boards, the action and the flag out
-        ProfScope ps(d, "mirror_stage", 0.0, (double)batch * (gather ? 215.0 : 201.0), true);
-        hipExtLaunchKernelGGL(mirror_stage_kernel, dim3((batch + 63) / 64), dim3(64), 0, d->cur, ps.start(), ps.stop(), 0, A, src, batch);
-        XQ_HIP(hipGetLastError());
-    }
-    return XQ_OK;
+    io.s_boards = ns_boards; io.s_next = ns_next; io.s_action = ns_action; io.s_reward = ns_reward; io.s_done = ns_done; io.s_first = ns_first;
+    return io;
 }
 
-// A TD step on a mirror-augmented batch of one-step transitions (xq_replay_set_mirror on a ring with n_step == 1): one gather stages the
-// minibatch with its flagged rows reflected, the step then runs on that batch with the identity slot source and the handle's discount; a
-// prioritized draw's priorities go back to the sampled slots behind the step (the n-step arrangement)
-static int mover_view_stage(xq_dqn* d, xq_replay* r, SlotSrc src, int batch, bool gather, const int32_t* row_last);
-static int td_grads_mirror(xq_dqn* d, xq_replay* r, SlotSrc src, int batch, int td_net, int mode, const PerOpts* per) {
-    const bool viewed = d->view == XQ_VIEW_MOVER;
-    XQ_TRY(mirror_stage(d, r, src, batch, true));
-    if (viewed) XQ_TRY(mover_view_stage(d, r, src, batch, false, d->ns_first));
-    XQ_TRY(td_grads_staged(d, r, d->ns_first, batch, td_net, mode, per, nullptr, viewed));
-    d->mirror_rows = batch;
-    if (viewed) d->view_rows = batch;
-    return XQ_OK;
+// The flag stream of a random transform's next launch, {b, 0, *calls, stream word} of the ring's Philox; counts the launch
+static StageDraw stage_draw(const xq_replay* r, double prob, uint64_t* calls) {
+    const StageDraw dr = {eps_to_u32(prob), prob >= 1.0 ? 1u : 0u, (uint32_t)*calls, (uint32_t)r->seed, (uint32_t)(r->seed >> 32)};
+    *calls += 1;
+    return dr;
 }
 
-// Mover view (xq_dqn_set_view): queues mover_view_stage_kernel for the next TD step from ring `r`, the last staging transform.  gather:
-// the minibatch from the ring (through `src`) into the handle's staging batch; otherwise the staging batch an n-step assembly and / or
-// a mirror gather just filled, in place, s flagged by the ring's mover column at ns_first[b] and s' by its next_player column at
-// row_last[b].  Under the legal-move bootstrap the kernel stages the side bytes too — 0 on every row, the view of s' has Red to move —
-// so td_grads_staged launches no legal_side_stage_kernel
-static int mover_view_stage(xq_dqn* d, xq_replay* r, SlotSrc src, int batch, bool gather, const int32_t* row_last) {
-    const size_t rows = (size_t)batch;
-    const bool sided = d->bootstrap == XQ_BOOTSTRAP_LEGAL;
-    if (gather) {
-        XQ_TRY(d->ns_boards.reserve(rows * kBoardWords));
-        XQ_TRY(d->ns_next.reserve(rows * kBoardWords));
-        for (DevBuf<int32_t>* b : {&d->ns_action, &d->ns_first}) XQ_TRY(b->reserve(rows));
-        XQ_TRY(d->ns_reward.reserve(rows));
-        XQ_TRY(d->ns_done.reserve(rows));
-    }
-    XQ_TRY(d->ns_vflag.reserve(rows));
-    XQ_TRY(d->ns_vflag_next.reserve(rows));
-    if (sided) XQ_TRY(d->ns_side.reserve(rows));
-    MoverViewArgs A; memset(&A, 0, sizeof A);
-    if (gather) {
-        A.boards = r->dev.boards; A.next_boards = r->dev.next_boards; A.action_to = r->dev.action_to; A.reward = r->dev.reward; A.done = r->dev.done;
-    } else {
-        A.boards = d->ns_boards; A.next_boards = d->ns_next; A.action_to = d->ns_action; A.reward = d->ns_reward; A.done = d->ns_done;
-        A.row_first = d->ns_first; A.row_last = row_last;
-    }
-    A.s_boards = d->ns_boards; A.s_next = d->ns_next; A.s_action = d->ns_action; A.s_reward = d->ns_reward; A.s_done = d->ns_done;
-    A.s_first = d->ns_first; A.s_flag = d->ns_vflag; A.s_flag_next = d->ns_vflag_next;
-    A.mover = r->dev.mover; A.next_player = r->dev.next_player;
-    if (sided) A.s_side = d->ns_side;
-    A.cap = r->dev.capacity;
-    A.gather = gather ? 1u : 0u;
-    {
-        // per row: the mirror's bytes (from the ring 215, in place 201) with a second flag out, the two side bytes in, in place the 8 B
-        // of the two slots they are read at; under the legal bootstrap the staged side byte out
-        ProfScope ps(d, "mover_view_stage", 0.0, (double)batch * ((gather ? 218.0 : 212.0) + (sided ? 1.0 : 0.0)), true);
-        hipExtLaunchKernelGGL(mover_view_stage_kernel, dim3((batch + 63) / 64), dim3(64), 0, d->cur, ps.start(), ps.stop(), 0, A, src, batch);
-        XQ_HIP(hipGetLastError());
-    }
-    return XQ_OK;
-}
+// Each stage below queues its kernel for the next TD step from ring `r`.  gather: the minibatch from the ring (through `src`) into the
+// staging batch; otherwise the staging batch that the stages before it filled, in place.  row_next: in place, the column of the slots
+// whose s' the rows hold
 
-// A TD step under the mover view on one-step transitions with no other staging transform: one gather stages the minibatch in the view,
-// the step then runs as behind the mirror
-static int td_grads_view(xq_dqn* d, xq_replay* r, SlotSrc src, int batch, int td_net, int mode, const PerOpts* per) {
-    XQ_TRY(mover_view_stage(d, r, src, batch, true, nullptr));
-    XQ_TRY(td_grads_staged(d, r, d->ns_first, batch, td_net, mode, per, nullptr, true));
-    d->view_rows = batch;
-    return XQ_OK;
-}
-
-// Colour-swap augmentation (xq_replay_set_colour_swap): queues colour_swap_stage_kernel for the next TD step from ring `r` and counts
-// it.  gather: the minibatch from the ring (through `src`) into the handle's staging batch; otherwise the staging batch an n-step
-// assembly and / or a mirror gather just filled, in place.  Whether row b is swapped is the ring's Philox stream at {b, 0, call, 4}.
-// Under the legal-move bootstrap the kernel also stages the side bytes, from the ring's column at row_slot[b] (gather: at the sampled
-// slot; row_slot is not read), flipped on the flagged rows: td_grads_staged then launches no legal_side_stage_kernel
-static int colour_swap_stage(xq_dqn* d, xq_replay* r, SlotSrc src, int batch, bool gather, const int32_t* row_slot) {
-    const size_t rows = (size_t)batch;
-    const bool sided = d->bootstrap == XQ_BOOTSTRAP_LEGAL;
-    if (gather) {
-        XQ_TRY(d->ns_boards.reserve(rows * kBoardWords));
-        XQ_TRY(d->ns_next.reserve(rows * kBoardWords));
-        for (DevBuf<int32_t>* b : {&d->ns_action, &d->ns_first}) XQ_TRY(b->reserve(rows));
-        XQ_TRY(d->ns_reward.reserve(rows));
-        XQ_TRY(d->ns_done.reserve(rows));
-    }
-    XQ_TRY(d->ns_cflag.reserve(rows));
-    if (sided) XQ_TRY(d->ns_side.reserve(rows));
-    ColourSwapArgs A; memset(&A, 0, sizeof A);
-    if (gather) {
-        A.boards = r->dev.boards; A.next_boards = r->dev.next_boards; A.action_to = r->dev.action_to; A.reward = r->dev.reward; A.done = r->dev.done;
-    } else {
-        A.boards = d->ns_boards; A.next_boards = d->ns_next; A.action_to = d->ns_action; A.reward = d->ns_reward; A.done = d->ns_done;
-    }
-    A.s_boards = d->ns_boards; A.s_next = d->ns_next; A.s_action = d->ns_action; A.s_reward = d->ns_reward; A.s_done = d->ns_done;
-    A.s_first = d->ns_first; A.s_flag = d->ns_cflag;
-    if (sided) { A.ring_side = r->dev.next_player; A.row_slot = gather ? nullptr : row_slot; A.s_side = d->ns_side; }
-    A.cap = r->dev.capacity;
-    A.thresh = eps_to_u32(r->colour_swap_prob); A.all = r->colour_swap_prob >= 1.0 ? 1u : 0u;
-    A.gather = gather ? 1u : 0u;
-    A.call = (uint32_t)r->colour_swap_calls; A.seed_lo = (uint32_t)r->seed; A.seed_hi = (uint32_t)(r->seed >> 32);
-    r->colour_swap_calls += 1;
-    {
-        // per row: the mirror's bytes (from the ring 215, in place 201); under the legal bootstrap the ring's side byte in and the staged
-        // one out, in place also the 4 B of the slot it is read at
-        const double side_bytes = sided ? (gather ? 2.0 : 6.0) : 0.0;
-        ProfScope ps(d, "colour_swap_stage", 0.0, (double)batch * ((gather ? 215.0 : 201.0) + side_bytes), true);
-        hipExtLaunchKernelGGL(colour_swap_stage_kernel, dim3((batch + 63) / 64), dim3(64), 0, d->cur, ps.start(), ps.stop(), 0, A, src, batch);
-        XQ_HIP(hipGetLastError());
-    }
-    return XQ_OK;
-}
-
-// A TD step on a colour-swapped batch of one-step transitions (xq_replay_set_colour_swap on a ring with n_step == 1), with or without
-// the mirror: the first transform on gathers the minibatch from the ring, the colour swap behind the mirror works in place (the two
-// commute: one acts on columns, the other on rows and codes); the step then runs as behind the mirror alone
-static int td_grads_colour_swap(xq_dqn* d, xq_replay* r, SlotSrc src, int batch, int td_net, int mode, const PerOpts* per) {
-    const bool mirrored = r->mirror_prob > 0.0;
-    if (mirrored) XQ_TRY(mirror_stage(d, r, src, batch, true));
-    XQ_TRY(colour_swap_stage(d, r, src, batch, !mirrored, d->ns_first));
-    XQ_TRY(td_grads_staged(d, r, d->ns_first, batch, td_net, mode, per, nullptr, true));
-    if (mirrored) d->mirror_rows = batch;
-    d->colour_swap_rows = batch;
-    d->colour_swap_sided = d->bootstrap == XQ_BOOTSTRAP_LEGAL;
-    return XQ_OK;
-}
-
-// A TD step on n-step transitions (xq_replay_set_n_step): one gather assembles them into the handle's staging batch, the step then runs
-// on that batch with the identity slot source and the discount gamma^n; a prioritized draw's priorities go back behind the step.  With
-// mirror and / or colour-swap augmentation on as well, the assembled batch is transformed in place before the step
-static int td_grads_nstep(xq_dqn* d, xq_replay* r, SlotSrc src, int batch, int td_net, int mode, const PerOpts* per) {
+// n-step returns (xq_replay_set_n_step): assembles the n-step transitions; *disc_n: the step's discount, gamma^n
+static int nstep_assemble(xq_dqn* d, xq_replay* r, SlotSrc src, int batch, float* disc_n) {
+    StagedBatch& sb = d->staged;
     const int cap = r->dev.capacity, n = r->n_step;
     NStepArgs A; memset(&A, 0, sizeof A);
     A.boards = r->dev.boards; A.next_boards = r->dev.next_boards; A.action_to = r->dev.action_to; A.reward = r->dev.reward; A.done = r->dev.done;
@@ -2733,113 +2571,205 @@ static int td_grads_nstep(xq_dqn* d, xq_replay* r, SlotSrc src, int batch, int t
     dk[0] = 1.f;
     for (int k = 1; k <= kNStepMax; ++k) dk[k] = dk[k - 1] * gf;
     for (int k = 0; k < kNStepMax; ++k) A.disc[k] = dk[k];
-    const float disc_n = dk[n];
-    const size_t rows = (size_t)batch;
-    XQ_TRY(d->ns_boards.reserve(rows * kBoardWords));
-    XQ_TRY(d->ns_next.reserve(rows * kBoardWords));
-    for (DevBuf<int32_t>* b : {&d->ns_action, &d->ns_m, &d->ns_first, &d->ns_last}) XQ_TRY(b->reserve(rows));
-    XQ_TRY(d->ns_reward.reserve(rows));
-    XQ_TRY(d->ns_done.reserve(rows));
-    A.s_boards = d->ns_boards; A.s_next = d->ns_next; A.s_action = d->ns_action; A.s_reward = d->ns_reward; A.s_done = d->ns_done;
-    A.s_m = d->ns_m; A.s_first = d->ns_first; A.s_last = d->ns_last;
-    {
-        // per row: n x 9 B of chain fields and two boards in, two boards and 21 B out
-        ProfScope ps(d, "nstep_assemble", 0.0, (double)batch * (9.0 * n + 4.0 * 48 + 21), true);
-        hipExtLaunchKernelGGL(nstep_assemble_kernel, dim3((batch + 63) / 64), dim3(64), 0, d->cur, ps.start(), ps.stop(), 0, A, src, batch);
+    *disc_n = dk[n];
+    XQ_TRY(sb.reserve((size_t)batch));
+    for (DevBuf<int32_t>* b : {&sb.ns_m, &sb.ns_last}) XQ_TRY(b->reserve((size_t)batch));
+    A.s_boards = sb.ns_boards; A.s_next = sb.ns_next; A.s_action = sb.ns_action; A.s_reward = sb.ns_reward; A.s_done = sb.ns_done;
+    A.s_m = sb.ns_m; A.s_first = sb.ns_first; A.s_last = sb.ns_last;
+    // per row: n x 9 B of chain fields and two boards in, two boards and 21 B out
+    ProfScope ps(d, "nstep_assemble", 0.0, (double)batch * (9.0 * n + 4.0 * 48 + 21), true);
+    hipExtLaunchKernelGGL(nstep_assemble_kernel, dim3((batch + 63) / 64), dim3(64), 0, d->cur, ps.start(), ps.stop(), 0, A, src, batch);
+    XQ_HIP(hipGetLastError());
+    return XQ_OK;
+}
+
+// Mirror augmentation (xq_replay_set_mirror): whether row b is reflected is the ring's Philox stream at {b, 0, call, 3}
+static int mirror_stage(xq_dqn* d, xq_replay* r, SlotSrc src, int batch, bool gather) {
+    StagedBatch& sb = d->staged;
+    if (gather) XQ_TRY(sb.reserve((size_t)batch));
+    XQ_TRY(sb.ns_flag.reserve((size_t)batch));
+    MirrorArgs A; memset(&A, 0, sizeof A);
+    A.io = sb.io(gather ? &r->dev : nullptr);
+    A.draw = stage_draw(r, r->mirror_prob, &r->mirror_calls);
+    A.s_flag = sb.ns_flag;
+    // per row, from the ring: two boards and 9 B in, two boards, 9 B, the slot and the flag out; in place: two boards and the action
+    // in, two boards, the action and the flag out
+    ProfScope ps(d, "mirror_stage", 0.0, (double)batch * (gather ? 215.0 : 201.0), true);
+    hipExtLaunchKernelGGL(mirror_stage_kernel, dim3((batch + 63) / 64), dim3(64), 0, d->cur, ps.start(), ps.stop(), 0, A, src, batch);
+    XQ_HIP(hipGetLastError());
+    return XQ_OK;
+}
+
+// Colour-swap augmentation (xq_replay_set_colour_swap): whether row b is swapped is the ring's Philox stream at {b, 0, call, 4}.  Under
+// the legal-move bootstrap the kernel also stages the side bytes, from the ring's column at row_next[b] (gather: at the sampled slot),
+// flipped on the flagged rows
+static int colour_swap_stage(xq_dqn* d, xq_replay* r, SlotSrc src, int batch, bool gather, const DevBuf<int32_t>& row_next) {
+    StagedBatch& sb = d->staged;
+    const bool sided = d->bootstrap == XQ_BOOTSTRAP_LEGAL;
+    if (gather) XQ_TRY(sb.reserve((size_t)batch));
+    XQ_TRY(sb.ns_cflag.reserve((size_t)batch));
+    if (sided) XQ_TRY(sb.ns_side.reserve((size_t)batch));
+    ColourSwapArgs A; memset(&A, 0, sizeof A);
+    A.io = sb.io(gather ? &r->dev : nullptr);
+    A.draw = stage_draw(r, r->colour_swap_prob, &r->colour_swap_calls);
+    A.s_flag = sb.ns_cflag;
+    if (sided) { A.ring_side = r->dev.next_player; A.row_slot = gather ? nullptr : row_next.p; A.s_side = sb.ns_side; }
+    A.cap = r->dev.capacity;
+    // per row: the mirror's bytes (from the ring 215, in place 201); under the legal bootstrap the ring's side byte in and the staged
+    // one out, in place also the 4 B of the slot it is read at
+    const double side_bytes = sided ? (gather ? 2.0 : 6.0) : 0.0;
+    ProfScope ps(d, "colour_swap_stage", 0.0, (double)batch * ((gather ? 215.0 : 201.0) + side_bytes), true);
+    hipExtLaunchKernelGGL(colour_swap_stage_kernel, dim3((batch + 63) / 64), dim3(64), 0, d->cur, ps.start(), ps.stop(), 0, A, src, batch);
+    XQ_HIP(hipGetLastError());
+    return XQ_OK;
+}
+
+// Mover view (xq_dqn_set_view): s flagged by the ring's mover column at the sampled slot (in place: ns_first[b]) and s' by its
+// next_player column at the slot of s' (in place: row_next[b]).  Under the legal-move bootstrap the kernel stages the side bytes too —
+// 0 on every row, the view of s' has Red to move
+static int mover_view_stage(xq_dqn* d, xq_replay* r, SlotSrc src, int batch, bool gather, const DevBuf<int32_t>& row_next) {
+    StagedBatch& sb = d->staged;
+    const bool sided = d->bootstrap == XQ_BOOTSTRAP_LEGAL;
+    if (gather) XQ_TRY(sb.reserve((size_t)batch));
+    XQ_TRY(sb.ns_vflag.reserve((size_t)batch));
+    XQ_TRY(sb.ns_vflag_next.reserve((size_t)batch));
+    if (sided) XQ_TRY(sb.ns_side.reserve((size_t)batch));
+    MoverViewArgs A; memset(&A, 0, sizeof A);
+    A.io = sb.io(gather ? &r->dev : nullptr);
+    if (!gather) { A.row_first = sb.ns_first; A.row_last = row_next.p; }
+    A.s_flag = sb.ns_vflag; A.s_flag_next = sb.ns_vflag_next;
+    A.mover = r->dev.mover; A.next_player = r->dev.next_player;
+    if (sided) A.s_side = sb.ns_side;
+    A.cap = r->dev.capacity;
+    // per row: the mirror's bytes (from the ring 215, in place 201) with a second flag out, the two side bytes in, in place the 8 B
+    // of the two slots they are read at; under the legal bootstrap the staged side byte out
+    ProfScope ps(d, "mover_view_stage", 0.0, (double)batch * ((gather ? 218.0 : 212.0) + (sided ? 1.0 : 0.0)), true);
+    hipExtLaunchKernelGGL(mover_view_stage_kernel, dim3((batch + 63) / 64), dim3(64), 0, d->cur, ps.start(), ps.stop(), 0, A, src, batch);
+    XQ_HIP(hipGetLastError());
+    return XQ_OK;
+}
+
+// The TD step on the staging batch: identity slot source, the given discount (nullptr: the handle's gamma).  A prioritized draw keeps its
+// importance weights; the step gets no priority table, and per_writeback_kernel behind it writes the live rows' priorities to the sampled
+// slots recorded in ns_first.  Under the legal-move bootstrap the staged rows' side bytes come from the ring's column at row_next[b]
+// (legal_side_stage_kernel) unless a transform has staged them already (side_staged)
+static int td_grads_staged(xq_dqn* d, xq_replay* r, const DevBuf<int32_t>& row_next, int batch, int td_net, int mode, const PerOpts* per,
+                           const float* discount, bool side_staged) {
+    StagedBatch& sb = d->staged;
+    PerOpts step_per;
+    if (per) { step_per = *per; step_per.prio = nullptr; step_per.pmax_live = nullptr; }
+    const bool legal = d->bootstrap == XQ_BOOTSTRAP_LEGAL;
+    if (legal && !side_staged) {
+        XQ_TRY(sb.ns_side.reserve((size_t)batch));
+        ProfScope ps(d, "legal_side_stage", 0.0, (double)batch * 6.0, true);
+        hipExtLaunchKernelGGL(legal_side_stage_kernel, dim3((batch + 255) / 256), dim3(256), 0, d->cur, ps.start(), ps.stop(), 0,
+                              r->dev.next_player, row_next.p, sb.ns_side.p, batch, r->dev.capacity);
         XQ_HIP(hipGetLastError());
     }
-    const bool mirrored = r->mirror_prob > 0.0;
-    if (mirrored) XQ_TRY(mirror_stage(d, r, src, batch, false));
-    const bool swapped = r->colour_swap_prob > 0.0;
-    if (swapped) XQ_TRY(colour_swap_stage(d, r, src, batch, false, d->ns_last));
-    const bool viewed = d->view == XQ_VIEW_MOVER;      // (never with `swapped`: xq_dqn_td_grads_replay refuses the pair)
-    if (viewed) XQ_TRY(mover_view_stage(d, r, src, batch, false, d->ns_last));
-    XQ_TRY(td_grads_staged(d, r, d->ns_last, batch, td_net, mode, per, &disc_n, swapped || viewed));
-    d->nstep_rows = batch;
-    if (viewed) d->view_rows = batch;
-    if (mirrored) d->mirror_rows = batch;
-    if (swapped) { d->colour_swap_rows = batch; d->colour_swap_sided = d->bootstrap == XQ_BOOTSTRAP_LEGAL; }
+    XQ_TRY(td_grads_impl(d, sb.ns_boards, sb.ns_next, sb.ns_action, sb.ns_reward, sb.ns_done, explicit_slots(nullptr), batch, td_net, mode,
+                         per ? &step_per : nullptr, discount, legal ? sb.ns_side.p : nullptr));
+    if (per) {
+        ProfScope ps(d, "per_writeback", 0.0, (double)batch * 20.0, true);
+        hipExtLaunchKernelGGL(per_writeback_kernel, dim3((batch + 255) / 256), dim3(256), 0, d->cur, ps.start(), ps.stop(), 0, batch,
+                              d->qsa.p, d->yv.p, d->act_mb.p, sb.ns_first.p, per->prio, per->pmax_live, per->eps, per->alpha);
+        XQ_HIP(hipGetLastError());
+    }
     return XQ_OK;
+}
+
+// A TD step from ring `r` with at least one staging stage on.  The stages run in one fixed order — assemble, mirror, colour swap, view
+// (the last two never together: xq_dqn_td_grads_replay refuses the pair; mirror and colour swap commute, one acts on columns, the
+// other on rows and codes) — the first of them gathers from the ring and every later one works in place.  The slots of s' are ns_last
+// behind the assembly and the sampled slots otherwise: the colour swap and the view read the ring's side there, and under the legal
+// bootstrap so does legal_side_stage_kernel when neither of them ran.  The step then runs on the batch with the n-step discount or the
+// handle's; a prioritized draw's priorities go back to the sampled slots behind it
+static int td_grads_ring_staged(xq_dqn* d, xq_replay* r, SlotSrc src, int batch, int td_net, int mode, const PerOpts* per) {
+    StagedBatch& sb = d->staged;
+    const bool assembled = r->n_step > 1;
+    const DevBuf<int32_t>& row_next = assembled ? sb.ns_last : sb.ns_first;
+    const bool legal = d->bootstrap == XQ_BOOTSTRAP_LEGAL;
+    unsigned stages = 0;                             // == 0: the batch is not filled yet, the next stage gathers
+    bool sided = false;
+    float disc_n = 0.f;
+    if (assembled) { XQ_TRY(nstep_assemble(d, r, src, batch, &disc_n)); stages |= StagedBatch::kAssemble; }
+    if (r->mirror_prob > 0.0) { XQ_TRY(mirror_stage(d, r, src, batch, stages == 0)); stages |= StagedBatch::kMirror; }
+    if (r->colour_swap_prob > 0.0) {
+        XQ_TRY(colour_swap_stage(d, r, src, batch, stages == 0, row_next));
+        stages |= StagedBatch::kColourSwap; sided = legal;
+    }
+    if (d->view == XQ_VIEW_MOVER) {
+        XQ_TRY(mover_view_stage(d, r, src, batch, stages == 0, row_next));
+        stages |= StagedBatch::kView; sided = legal;
+    }
+    XQ_TRY(td_grads_staged(d, r, row_next, batch, td_net, mode, per, assembled ? &disc_n : nullptr, sided));
+    sb.last = {batch, stages, sided};
+    return XQ_OK;
+}
+
+// ---- read-back of the last step's staging batch (xq_dqn_last_*) ------------------------------------------------------------------------
+// The checks they share: the handle, that `stage` ran in the last TD step (`what`: "a mirror-mode", ...), n within its rows
+static int last_staged_rows(const xq_dqn* d, unsigned stage, int n, const char* fn, const char* what) {
+    if (!d) return fail(XQ_ERR_INVALID_ARGUMENT, "null dqn");
+    const StagedBatch::Last& last = d->staged.last;
+    if (!(last.stages & stage)) return fail(XQ_ERR_RUNTIME, "%s: the last TD step was not %s one", fn, what);
+    if (n < 0 || n > last.rows) return fail(XQ_ERR_INVALID_ARGUMENT, "%s: n exceeds the last TD step's %d rows", fn, last.rows);
+    return XQ_OK;
+}
+
+static int staged_column(void* out, const void* col, int n, size_t elem = 1) {        // rows 0..n-1 of a column, if asked for
+    if (out && n) XQ_HIP(hipMemcpy(out, col, (size_t)n * elem, hipMemcpyDeviceToHost));
+    return XQ_OK;
+}
+
+// Waits for the step, then copies what every transform's read-back returns: both boards (unpacked), the action and the sampled slot
+static int last_staged_batch(xq_dqn* d, int n, uint8_t* boards90, uint8_t* next_boards90, int32_t* action_to, int32_t* slot) {
+    const StagedBatch& sb = d->staged;
+    XQ_HIP(hipStreamSynchronize(d->stream));
+    if (!n) return XQ_OK;
+    std::vector<uint32_t> w((size_t)n * kBoardWords);
+    const struct { uint8_t* out; const uint32_t* dev; } boards[2] = {{boards90, sb.ns_boards}, {next_boards90, sb.ns_next}};
+    for (const auto& bd : boards) {
+        if (!bd.out) continue;
+        XQ_HIP(hipMemcpy(w.data(), bd.dev, w.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        for (int i = 0; i < n; ++i) unpack_board(&w[(size_t)i * kBoardWords], bd.out + (size_t)i * 90);
+    }
+    XQ_TRY(staged_column(action_to, sb.ns_action, n, sizeof(int32_t)));
+    return staged_column(slot, sb.ns_first, n, sizeof(int32_t));
 }
 
 int xq_dqn_last_n_step(xq_dqn* d, int n, float* reward, uint8_t* done, int32_t* steps, int32_t* first_slot, int32_t* last_slot,
                        int32_t* action) {
-    if (!d) return fail(XQ_ERR_INVALID_ARGUMENT, "null dqn");
-    if (d->nstep_rows <= 0) return fail(XQ_ERR_RUNTIME, "xq_dqn_last_n_step: the last TD step was not an n-step one");
-    if (n < 0 || n > d->nstep_rows) return fail(XQ_ERR_INVALID_ARGUMENT, "xq_dqn_last_n_step: n exceeds the last TD step's %d rows", d->nstep_rows);
-    XQ_HIP(hipStreamSynchronize(d->stream));
-    if (!n) return XQ_OK;
-    if (reward) XQ_HIP(hipMemcpy(reward, d->ns_reward, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
-    if (done) XQ_HIP(hipMemcpy(done, d->ns_done, (size_t)n, hipMemcpyDeviceToHost));
-    if (steps) XQ_HIP(hipMemcpy(steps, d->ns_m, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (first_slot) XQ_HIP(hipMemcpy(first_slot, d->ns_first, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (last_slot) XQ_HIP(hipMemcpy(last_slot, d->ns_last, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (action) XQ_HIP(hipMemcpy(action, d->ns_action, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
-    return XQ_OK;
+    XQ_TRY(last_staged_rows(d, StagedBatch::kAssemble, n, "xq_dqn_last_n_step", "an n-step"));
+    XQ_TRY(last_staged_batch(d, n, nullptr, nullptr, action, first_slot));
+    const StagedBatch& sb = d->staged;
+    XQ_TRY(staged_column(reward, sb.ns_reward, n, sizeof(float)));
+    XQ_TRY(staged_column(done, sb.ns_done, n));
+    XQ_TRY(staged_column(steps, sb.ns_m, n, sizeof(int32_t)));
+    return staged_column(last_slot, sb.ns_last, n, sizeof(int32_t));
 }
 
 int xq_dqn_last_mirror(xq_dqn* d, int n, uint8_t* flags, uint8_t* boards90, uint8_t* next_boards90, int32_t* action_to, int32_t* slot) {
-    if (!d) return fail(XQ_ERR_INVALID_ARGUMENT, "null dqn");
-    if (d->mirror_rows <= 0) return fail(XQ_ERR_RUNTIME, "xq_dqn_last_mirror: the last TD step was not a mirror-mode one");
-    if (n < 0 || n > d->mirror_rows) return fail(XQ_ERR_INVALID_ARGUMENT, "xq_dqn_last_mirror: n exceeds the last TD step's %d rows", d->mirror_rows);
-    XQ_HIP(hipStreamSynchronize(d->stream));
-    if (!n) return XQ_OK;
-    if (flags) XQ_HIP(hipMemcpy(flags, d->ns_flag, (size_t)n, hipMemcpyDeviceToHost));
-    std::vector<uint32_t> w((size_t)n * kBoardWords);
-    const struct { uint8_t* out; const uint32_t* dev; } boards[2] = {{boards90, d->ns_boards}, {next_boards90, d->ns_next}};
-    for (const auto& bd : boards) {
-        if (!bd.out) continue;
-        XQ_HIP(hipMemcpy(w.data(), bd.dev, w.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-        for (int i = 0; i < n; ++i) unpack_board(&w[(size_t)i * kBoardWords], bd.out + (size_t)i * 90);
-    }
-    if (action_to) XQ_HIP(hipMemcpy(action_to, d->ns_action, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (slot) XQ_HIP(hipMemcpy(slot, d->ns_first, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
-    return XQ_OK;
+    XQ_TRY(last_staged_rows(d, StagedBatch::kMirror, n, "xq_dqn_last_mirror", "a mirror-mode"));
+    XQ_TRY(last_staged_batch(d, n, boards90, next_boards90, action_to, slot));
+    return staged_column(flags, d->staged.ns_flag, n);
 }
 
 int xq_dqn_last_colour_swap(xq_dqn* d, int n, uint8_t* flags, uint8_t* boards90, uint8_t* next_boards90, int32_t* action_to,
                             uint8_t* next_player, int32_t* slot) {
-    if (!d) return fail(XQ_ERR_INVALID_ARGUMENT, "null dqn");
-    if (d->colour_swap_rows <= 0) return fail(XQ_ERR_RUNTIME, "xq_dqn_last_colour_swap: the last TD step was not a colour-swap-mode one");
-    if (n < 0 || n > d->colour_swap_rows)
-        return fail(XQ_ERR_INVALID_ARGUMENT, "xq_dqn_last_colour_swap: n exceeds the last TD step's %d rows", d->colour_swap_rows);
-    if (next_player && !d->colour_swap_sided)
+    XQ_TRY(last_staged_rows(d, StagedBatch::kColourSwap, n, "xq_dqn_last_colour_swap", "a colour-swap-mode"));
+    if (next_player && !d->staged.last.sided)
         return fail(XQ_ERR_INVALID_ARGUMENT, "xq_dqn_last_colour_swap: next_player asked, but the last TD step was not under the legal-move bootstrap");
-    XQ_HIP(hipStreamSynchronize(d->stream));
-    if (!n) return XQ_OK;
-    if (flags) XQ_HIP(hipMemcpy(flags, d->ns_cflag, (size_t)n, hipMemcpyDeviceToHost));
-    std::vector<uint32_t> w((size_t)n * kBoardWords);
-    const struct { uint8_t* out; const uint32_t* dev; } boards[2] = {{boards90, d->ns_boards}, {next_boards90, d->ns_next}};
-    for (const auto& bd : boards) {
-        if (!bd.out) continue;
-        XQ_HIP(hipMemcpy(w.data(), bd.dev, w.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-        for (int i = 0; i < n; ++i) unpack_board(&w[(size_t)i * kBoardWords], bd.out + (size_t)i * 90);
-    }
-    if (action_to) XQ_HIP(hipMemcpy(action_to, d->ns_action, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (next_player) XQ_HIP(hipMemcpy(next_player, d->ns_side, (size_t)n, hipMemcpyDeviceToHost));
-    if (slot) XQ_HIP(hipMemcpy(slot, d->ns_first, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
-    return XQ_OK;
+    XQ_TRY(last_staged_batch(d, n, boards90, next_boards90, action_to, slot));
+    XQ_TRY(staged_column(flags, d->staged.ns_cflag, n));
+    return staged_column(next_player, d->staged.ns_side, n);
 }
 
 int xq_dqn_last_view(xq_dqn* d, int n, uint8_t* flag_s, uint8_t* flag_next, uint8_t* boards90, uint8_t* next_boards90, int32_t* action_to,
                      int32_t* slot) {
-    if (!d) return fail(XQ_ERR_INVALID_ARGUMENT, "null dqn");
-    if (d->view_rows <= 0) return fail(XQ_ERR_RUNTIME, "xq_dqn_last_view: the last TD step was not a view-mode one");
-    if (n < 0 || n > d->view_rows) return fail(XQ_ERR_INVALID_ARGUMENT, "xq_dqn_last_view: n exceeds the last TD step's %d rows", d->view_rows);
-    XQ_HIP(hipStreamSynchronize(d->stream));
-    if (!n) return XQ_OK;
-    if (flag_s) XQ_HIP(hipMemcpy(flag_s, d->ns_vflag, (size_t)n, hipMemcpyDeviceToHost));
-    if (flag_next) XQ_HIP(hipMemcpy(flag_next, d->ns_vflag_next, (size_t)n, hipMemcpyDeviceToHost));
-    std::vector<uint32_t> w((size_t)n * kBoardWords);
-    const struct { uint8_t* out; const uint32_t* dev; } boards[2] = {{boards90, d->ns_boards}, {next_boards90, d->ns_next}};
-    for (const auto& bd : boards) {
-        if (!bd.out) continue;
-        XQ_HIP(hipMemcpy(w.data(), bd.dev, w.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-        for (int i = 0; i < n; ++i) unpack_board(&w[(size_t)i * kBoardWords], bd.out + (size_t)i * 90);
-    }
-    if (action_to) XQ_HIP(hipMemcpy(action_to, d->ns_action, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (slot) XQ_HIP(hipMemcpy(slot, d->ns_first, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
-    return XQ_OK;
+    XQ_TRY(last_staged_rows(d, StagedBatch::kView, n, "xq_dqn_last_view", "a view-mode"));
+    XQ_TRY(last_staged_batch(d, n, boards90, next_boards90, action_to, slot));
+    XQ_TRY(staged_column(flag_s, d->staged.ns_vflag, n));
+    return staged_column(flag_next, d->staged.ns_vflag_next, n);
 }
 
 int xq_dqn_td_grads_replay(xq_dqn* d, xq_replay* r, int batch, int td_net, int mode) {
@@ -2878,10 +2808,8 @@ int xq_dqn_td_grads_replay(xq_dqn* d, xq_replay* r, int batch, int td_net, int m
     // ring, slot list and priorities may have been written on other streams (env steps, the draw, a rebuild): this step starts behind
     // them, and whatever touches them next — the next draw overwrites the list, the next env step the slots — behind this step
     XQ_TRY(replay_consumer_begin(r, d->stream, src.slots != nullptr, prioritized));
-    if (r->n_step > 1) return td_grads_nstep(d, r, src, batch, td_net, mode, prioritized ? &per : nullptr);
-    if (r->colour_swap_prob > 0.0) return td_grads_colour_swap(d, r, src, batch, td_net, mode, prioritized ? &per : nullptr);
-    if (r->mirror_prob > 0.0) return td_grads_mirror(d, r, src, batch, td_net, mode, prioritized ? &per : nullptr);
-    if (viewed) return td_grads_view(d, r, src, batch, td_net, mode, prioritized ? &per : nullptr);
+    if (r->n_step > 1 || r->mirror_prob > 0.0 || r->colour_swap_prob > 0.0 || viewed)
+        return td_grads_ring_staged(d, r, src, batch, td_net, mode, prioritized ? &per : nullptr);
     return td_grads_impl(d, r->dev.boards, r->dev.next_boards, r->dev.action_to, r->dev.reward, r->dev.done, src, batch, td_net,
                          mode, prioritized ? &per : nullptr, nullptr, r->dev.next_player);
 }

@@ -393,7 +393,7 @@ struct QSource { const float* slabs; long long slab_stride; int nslabs; const fl
 int dqn_q90_boards(xq_dqn* d, const uint32_t* boards_dev, int n, float** q90_dev, int* q_stride, hipStream_t on = nullptr, QSource* qs = nullptr);
 hipStream_t dqn_stream(xq_dqn* d);
 int dqn_view(const xq_dqn* d);              // current xq_dqn_set_view setting
-// view_boards_kernel (xq_view.hip.h) on `stream`: out[b] = view(boards[b], side of b), the side from side_dev[b] or, with meta_dev (an
+// view_boards_kernel (xq_stage.hip.h) on `stream`: out[b] = view(boards[b], side of b), the side from side_dev[b] or, with meta_dev (an
 // env's boards), from bit 16 of meta_dev[b].x
 int view_boards_launch(const uint32_t* boards_dev, const uint8_t* side_dev, const uint4* meta_dev, int n, uint32_t* out_dev, hipStream_t stream);
 hipEvent_t dqn_qmax_event(xq_dqn* d);      // recorded behind the column-max GEMM of the last xq_dqn_td_grads*

@@ -528,7 +528,7 @@ int xq_replay_get_n_step(const xq_replay* r, int* n_step, int* stride) {
     return XQ_OK;
 }
 
-// ---- mirror augmentation: C ABI (the kernel is the TD step's: xq_mirror.hip.h) -------------------------------------------------------
+// ---- mirror augmentation: C ABI (the kernel is the TD step's: xq_stage.hip.h) --------------------------------------------------------
 int xq_replay_set_mirror(xq_replay* r, double prob) {
     if (!r) return fail(XQ_ERR_INVALID_ARGUMENT, "null replay");
     if (!(prob >= 0.0 && prob <= 1.0)) return fail(XQ_ERR_INVALID_ARGUMENT, "xq_replay_set_mirror: prob must be in [0, 1]");     // (NaN too)
@@ -543,7 +543,7 @@ int xq_replay_get_mirror(const xq_replay* r, double* prob, uint64_t* calls) {
     return XQ_OK;
 }
 
-// ---- colour-swap augmentation: C ABI (the kernel is the TD step's: xq_colour_swap.hip.h) ---------------------------------------------
+// ---- colour-swap augmentation: C ABI (the kernel is the TD step's: xq_stage.hip.h) ---------------------------------------------------
 int xq_replay_set_colour_swap(xq_replay* r, double prob) {
     if (!r) return fail(XQ_ERR_INVALID_ARGUMENT, "null replay");
     if (!(prob >= 0.0 && prob <= 1.0)) return fail(XQ_ERR_INVALID_ARGUMENT, "xq_replay_set_colour_swap: prob must be in [0, 1]");     // (NaN too)

@@ -211,12 +211,9 @@ class DQN:
         """The first n rows of the batch the last td_grads_replay staged from a ring with ReplayBuffer.set_mirror(prob > 0): dict of
         flags (1 = the row was reflected), boards and next_boards ([n, 90] piece codes as staged), action (as staged) and slot (the
         sampled slot).  Raises XqError when the last TD step was not a mirror-mode one."""
-        f = np.zeros(n, np.uint8)
-        b, nb = np.zeros((n, 90), np.uint8), np.zeros((n, 90), np.uint8)
-        a, s = np.zeros(n, np.int32), np.zeros(n, np.int32)
-        call("xq_dqn_last_mirror", self._h, int(n), _ptr(f, C.c_uint8), _ptr(b, C.c_uint8), _ptr(nb, C.c_uint8), _ptr(a, C.c_int32),
-             _ptr(s, C.c_int32))
-        return dict(flags=f, boards=b, next_boards=nb, action=a, slot=s)
+        f, out, (b, nb, a, s) = np.zeros(n, np.uint8), *_staged_rows(n)
+        call("xq_dqn_last_mirror", self._h, int(n), _ptr(f, C.c_uint8), b, nb, a, s)
+        return dict(flags=f, **out)
 
     def last_colour_swap(self, n, next_player=False):
         """The first n rows of the batch the last td_grads_replay staged from a ring with ReplayBuffer.set_colour_swap(prob > 0): dict
@@ -224,13 +221,10 @@ class DQN:
         slot (the sampled slot); with next_player=True also next_player (the staged side bytes: only behind a step under the legal-move
         bootstrap).  With the mirror on as well this is the same staged batch last_mirror reports, with this transform's flags.  Raises
         XqError when the last TD step was not a colour-swap-mode one."""
-        f = np.zeros(n, np.uint8)
-        b, nb = np.zeros((n, 90), np.uint8), np.zeros((n, 90), np.uint8)
-        a, s = np.zeros(n, np.int32), np.zeros(n, np.int32)
+        f, out, (b, nb, a, s) = np.zeros(n, np.uint8), *_staged_rows(n)
         p = np.zeros(n, np.uint8) if next_player else None
-        call("xq_dqn_last_colour_swap", self._h, int(n), _ptr(f, C.c_uint8), _ptr(b, C.c_uint8), _ptr(nb, C.c_uint8), _ptr(a, C.c_int32),
-             _ptr(p, C.c_uint8) if next_player else None, _ptr(s, C.c_int32))
-        out = dict(flags=f, boards=b, next_boards=nb, action=a, slot=s)
+        call("xq_dqn_last_colour_swap", self._h, int(n), _ptr(f, C.c_uint8), b, nb, a, _ptr(p, C.c_uint8) if next_player else None, s)
+        out = dict(flags=f, **out)
         if next_player:
             out["next_player"] = p
         return out
@@ -239,12 +233,9 @@ class DQN:
         """The first n rows of the batch the last td_grads_replay staged under set_view("mover"): dict of flag_s (1 = Black moved: s and
         the action were swapped), flag_next (1 = Black moves next: s' was swapped), boards and next_boards ([n, 90] piece codes as
         staged), action (as staged) and slot (the sampled slot).  Raises XqError when the last TD step was not a view-mode one."""
-        f, fn = np.zeros(n, np.uint8), np.zeros(n, np.uint8)
-        b, nb = np.zeros((n, 90), np.uint8), np.zeros((n, 90), np.uint8)
-        a, s = np.zeros(n, np.int32), np.zeros(n, np.int32)
-        call("xq_dqn_last_view", self._h, int(n), _ptr(f, C.c_uint8), _ptr(fn, C.c_uint8), _ptr(b, C.c_uint8), _ptr(nb, C.c_uint8),
-             _ptr(a, C.c_int32), _ptr(s, C.c_int32))
-        return dict(flag_s=f, flag_next=fn, boards=b, next_boards=nb, action=a, slot=s)
+        f, fn, out, (b, nb, a, s) = np.zeros(n, np.uint8), np.zeros(n, np.uint8), *_staged_rows(n)
+        call("xq_dqn_last_view", self._h, int(n), _ptr(f, C.c_uint8), _ptr(fn, C.c_uint8), b, nb, a, s)
+        return dict(flag_s=f, flag_next=fn, **out)
 
     def kernel_stats(self, enable=-1):
         """Returns the HIP-event timings collected so far; enable: 1 on, 0 off, 2 on + clear, -1 leave."""
@@ -253,6 +244,15 @@ class DQN:
         call("xq_dqn_kernel_stats", self._h, int(enable), arr, 64, C.byref(n))
         return [dict(name=arr[i].name.decode(), ms=arr[i].ms, launches=arr[i].launches, flops=arr[i].flops,
                      bytes=arr[i].bytes, exact=arr[i].exact_launches) for i in range(n.value)]
+
+
+def _staged_rows(n):
+    """What every staging transform's read-back returns for n rows: (dict of boards, next_boards, action, slot; their pointers in the
+    C calls' order)"""
+    out = dict(boards=np.zeros((n, 90), np.uint8), next_boards=np.zeros((n, 90), np.uint8), action=np.zeros(n, np.int32),
+               slot=np.zeros(n, np.int32))
+    return out, (_ptr(out["boards"], C.c_uint8), _ptr(out["next_boards"], C.c_uint8), _ptr(out["action"], C.c_int32),
+                 _ptr(out["slot"], C.c_int32))
 
 
 def _kernel_filter(self, names=None):
