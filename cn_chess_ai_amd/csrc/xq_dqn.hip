@@ -23,8 +23,9 @@
 // (ScreenPlan in TdStep); qmax_screened is the launches.  What a write of the parameters makes stale is described once: params_written,
 // the one place that touches params_version, the screen's kept rows, the select chain's kept sums and tgt_rest_synced.
 // This file = the handle (struct xq_dqn) + host orchestration + the C ABI; the kernels live in xq_l0.hip.h (layer-0 gathers and
-// segmented sums), xq_tail.hip.h (TD delta, gradient sums, fused launches, SGD), xq_refine.hip.h (screening pass 2), xq_l0grad.hip.h
-// (layer-0 gradient on the matrix pipe), xq_gemm*.hip.h and xq_screen.hip.h (matrix-pipe products), xq_nstep.hip.h and
+// segmented sums), xq_td.hip.h (the TD rule: fold, target, delta, record, priority), xq_tail.hip.h (gradient sums, fused launches),
+// xq_apply.hip.h (slab sums, segment walk, optimizers, clipping, soft target), xq_refine.hip.h (screening pass 2), xq_l0grad.hip.h (layer-0
+// gradient on the matrix pipe), xq_gemm*.hip.h and xq_screen.hip.h (matrix-pipe products), xq_nstep.hip.h and
 // xq_stage.hip.h (staging of n-step, mirrored, colour-swapped and mover-view batches), xq_legal.hip.h (the legal-move bootstrap, on the rules engine of xq_rules.hip.h).
 #include "xq_internal.h"
 #include <hip/hip_ext.h>
@@ -315,7 +316,9 @@ struct SmallTiles {
 
 // kernels (each header opens namespace xq itself)
 #include "xq_l0.hip.h"
+#include "xq_td.hip.h"
 #include "xq_tail.hip.h"
+#include "xq_apply.hip.h"
 #include "xq_refine.hip.h"
 #include "xq_nstep.hip.h"
 #include "xq_stage.hip.h"
@@ -1991,19 +1994,14 @@ static int qmax_screened(xq_dqn* d, const TdStep& s, bool* td_fused) {
             }
             // whole groups: 2 = the popular ones through LDS when the launch has room for it, 1 = all of them four per round trip
             const int whole_mode = stage ? 2 : 1;
-            if (*td_fused && d->loss_kind == XQ_LOSS_HUBER) {
-                const auto kern = qmax_refine2_kernel<256, true, HuberLoss>;
-                XQ_TRY(ensure_max_dynamic_lds(kern, 152 * 1024));
+            const auto launch = [&](auto kern, auto loss) -> int {        // the one launch of the family; the loss is its last argument
+                XQ_TRY(ensure_max_dynamic_lds(kern, 152 * 1024));          // the staged pass asks for ~145 KB
                 hipExtLaunchKernelGGL(kern, grid, dim3(256), lds, d->cur, ps.start(), ps.stop(), 0, scr.R.p, ranges, gpr, scr.p1.p, scr.p2.p,
-                                      G, n, ldp, scr.na.p, a_last, Hl, W, bias, NO, scr.wmax.p, parity, d->zmax.p, scr.stats.p, T, whole_mode,
-                                      HuberLoss{d->loss_kappa32});
-            } else {
-                const auto kern = *td_fused ? qmax_refine2_kernel<256, true> : Hl == 256 ? qmax_refine2_kernel<256> : qmax_refine2_kernel<512>;
-                XQ_TRY(ensure_max_dynamic_lds(kern, 152 * 1024));     // the staged pass asks for ~145 KB
-                hipExtLaunchKernelGGL(kern, grid, dim3(256), lds, d->cur, ps.start(), ps.stop(), 0, scr.R.p, ranges, gpr, scr.p1.p, scr.p2.p,
-                                      G, n, ldp, scr.na.p, a_last, Hl, W, bias, NO, scr.wmax.p, parity, d->zmax.p, scr.stats.p, T, whole_mode,
-                                      SquaredLoss{});
-            }
+                                      G, n, ldp, scr.na.p, a_last, Hl, W, bias, NO, scr.wmax.p, parity, d->zmax.p, scr.stats.p, T, whole_mode, loss);
+                return XQ_OK;
+            };
+            if (*td_fused && d->loss_kind == XQ_LOSS_HUBER) XQ_TRY(launch(qmax_refine2_kernel<256, true, HuberLoss>, HuberLoss{d->loss_kappa32}));
+            else XQ_TRY(launch(*td_fused ? qmax_refine2_kernel<256, true> : Hl == 256 ? qmax_refine2_kernel<256> : qmax_refine2_kernel<512>, SquaredLoss{}));
         } else {
             const bool small = G <= 8 * 32;
             const auto kern = Hl == 256 ? (small ? qmax_refine_kernel<256, 32> : qmax_refine_kernel<256, 64>)
@@ -2123,15 +2121,13 @@ static int td_delta(xq_dqn* d, const TdStep& s, int zparts) {
         X.is_w = per->is_w; X.is_wmax = per->is_wmax; X.prio = per->prio; X.pmax_live = per->pmax_live;
         X.per_eps = per->eps; X.per_alpha = per->alpha;
     }
-    if (d->loss_kind == XQ_LOSS_HUBER)
-        hipLaunchKernelGGL(td_delta_huber_kernel, dim3((n + 3) / 4), dim3(256), 0, d->cur, n, s.slots, s.action_to, s.reward, s.done,
+    const auto launch = [&](auto kern, auto... loss) {                  // the one launch of the family; what the loss adds goes last
+        hipLaunchKernelGGL(kern, dim3((n + 3) / 4), dim3(256), 0, d->cur, n, s.slots, s.action_to, s.reward, s.done,
                            s.outs[lt], Hl, d->wl(XQ_NET_ONLINE, nl - 1), d->bl(XQ_NET_ONLINE, nl - 1), d->zmax, zparts,
-                           s.gamma, s.view, s.view_ld, s.view_kmax, d->deltas[lt], d->dsc, d->act_mb, d->qsa, d->yv, d->lossv, X,
-                           d->loss_kappa32);
-    else
-        hipLaunchKernelGGL(td_delta_kernel, dim3((n + 3) / 4), dim3(256), 0, d->cur, n, s.slots, s.action_to, s.reward, s.done,
-                           s.outs[lt], Hl, d->wl(XQ_NET_ONLINE, nl - 1), d->bl(XQ_NET_ONLINE, nl - 1), d->zmax, zparts,
-                           s.gamma, s.view, s.view_ld, s.view_kmax, d->deltas[lt], d->dsc, d->act_mb, d->qsa, d->yv, d->lossv, X);
+                           s.gamma, s.view, s.view_ld, s.view_kmax, d->deltas[lt], d->dsc, d->act_mb, d->qsa, d->yv, d->lossv, X, loss...);
+    };
+    if (d->loss_kind == XQ_LOSS_HUBER) launch(td_delta_huber_kernel, d->loss_kappa32);
+    else launch(td_delta_kernel);
     XQ_HIP(hipGetLastError());
     return XQ_OK;
 }

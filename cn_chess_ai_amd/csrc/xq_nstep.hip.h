@@ -82,17 +82,14 @@ __global__ __launch_bounds__(64) void nstep_assemble_kernel(NStepArgs A, SlotSrc
 }
 
 // Behind the TD step of a prioritized n-step draw: prio[first_slot[b]] = (|q - y| + eps)^alpha for the live rows, and the running maximum
-// by td_delta_kernel's test-then-atomicMax (positive floats order like their bit patterns; a maximum is order-independent)
+// by td_delta_kernel's test-then-atomicMax (per_priority_store, xq_td.hip.h)
 __global__ __launch_bounds__(256) void per_writeback_kernel(int n, const float* __restrict__ qsa, const float* __restrict__ yv,
                                                             const int32_t* __restrict__ act, const int32_t* __restrict__ first_slot,
                                                             float* __restrict__ prio, unsigned* pmax_live, float eps, float alpha) {
     const int b = (int)(blockIdx.x * blockDim.x + threadIdx.x);
     if (b >= n) return;
     if (act[b] < 0) return;
-    const float p = powf(fabsf(qsa[b] - yv[b]) + eps, alpha);
-    prio[first_slot[b]] = p;
-    if (__float_as_uint(p) > __hip_atomic_load(pmax_live, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
-        atomicMax(pmax_live, __float_as_uint(p));
+    per_priority_store(prio, pmax_live, first_slot[b], qsa[b], yv[b], eps, alpha);
 }
 
 }  // namespace xq

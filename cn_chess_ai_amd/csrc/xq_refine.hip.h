@@ -225,7 +225,7 @@ __host__ __device__ inline size_t refine_cand_words(int G) { const size_t w = (s
 // bytes of the whole-group list, and of the extra dynamic LDS of the staged pass (activation rows + the rows of two more groups), K = 256
 __host__ __device__ inline size_t refine_wlist_bytes(int G) { return ((size_t)G * 32 * sizeof(uint16_t) + 15) & ~(size_t)15; }
 __host__ __device__ inline size_t refine_stage_bytes() { return (size_t)3 * 32 * 256 * sizeof(float); }
-// Loss (TD only): the TD loss object of xq_tail.hip.h, the kernel's LAST argument — behind whole_mode it lies in what was padding in front
+// Loss (TD only): the TD loss object of xq_td.hip.h, the kernel's LAST argument — behind whole_mode it lies in what was padding in front
 // of the hidden arguments (an empty SquaredLoss, or HuberLoss's one float), so the argument block of every other instantiation stays as it was.
 // DBG (tools/refine_probe.hip only; 0 in the library): 1 = s_memtime stamps at the level boundaries into refine_dbg[block][16] (every stamp
 // drains the wave's loads first: read shares, not lengths), 2 = the second-largest values loaded beside the largest ones.  The stamp buffer and
@@ -588,20 +588,14 @@ __global__ __launch_bounds__(256) void qmax_refine2_kernel(const float* __restri
         float q = 0.f, y = 0.f, delta = 0.f;
         if (td_lane < 8) {
             const float zm = float_from_key(best[td_w * 8 + td_lane]);
-            const float r = td_r;
             const bool dn = td_dn != 0u;
             if (mine) {
                 q = td_q;
-                y = dn ? r : r + T.gamma * tanhf(zm);
-                delta = L.err(q - y) * td_dtanh(q) * 1.f;
+                y = td_target(td_r, dn, T.gamma, zm);
+                delta = td_output_delta(L, q, y, 1.f);
             }
             const int bb = b0 + td_w * 8 + td_lane;
-            if (bb < n) {
-                T.dsc[bb] = delta;
-                T.act[bb] = mine ? td_a : -1;
-                T.qsa[bb] = q; T.yv[bb] = y;
-                T.lossv[bb] = mine ? L.loss(q - y) : 0.f;
-            }
+            if (bb < n) td_record_store(L, T.dsc, T.act, T.qsa, T.yv, T.lossv, bb, mine, td_a, delta, q, y);
         }
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
@@ -609,14 +603,8 @@ __global__ __launch_bounds__(256) void qmax_refine2_kernel(const float* __restri
             const int a = __shfl(td_a, i, 64);
             const float dl = __shfl(delta, i, 64);
             const bool live = a >= 0 && a < 96;
-            if (bb < n) {                                         // wave-uniform
-                float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (live && a < T.view_kmax) {
-                    o.x = dl * tvv[i].x * (1.f - tav[i].x * tav[i].x); o.y = dl * tvv[i].y * (1.f - tav[i].y * tav[i].y);
-                    o.z = dl * tvv[i].z * (1.f - tav[i].z * tav[i].z); o.w = dl * tvv[i].w * (1.f - tav[i].w * tav[i].w);
-                }
-                *reinterpret_cast<float4*>(T.dtop + (long long)bb * 256 + td_lane * 4) = o;
-            }
+            if (bb < n)                                           // wave-uniform
+                *reinterpret_cast<float4*>(T.dtop + (long long)bb * 256 + td_lane * 4) = td_top_delta(live && a < T.view_kmax, dl, tvv[i], tav[i]);
         }
     }
     if (DBG & 1) {

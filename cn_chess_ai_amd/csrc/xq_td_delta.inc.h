@@ -1,8 +1,9 @@
-// xq_td_delta.inc.h — the text of td_delta_kernel, included by xq_tail.hip.h once per TD loss (inside namespace xq; see there).  The includer
+// xq_td_delta.inc.h — the text of td_delta_kernel, included by xq_td.hip.h once per TD loss (inside namespace xq; see there).  The includer
 // defines XQ_TD_DELTA_KERNEL (the kernel's name), XQ_TD_DELTA_LOSS_PARAM (what the loss adds behind the last parameter, or nothing) and
 // XQ_TD_DELTA_LOSS (the declaration of the loss object L).  A kernel per loss from ONE text, and not one inlined body under two kernels: the
 // squared kernel keeps its name (profiles and cn_chess_ai_amd/workmodel.py know it by that) and, being the same function as before, its
 // instructions — a body inlined into a wrapper compiles to other register assignments and another order of the argument loads.
+// The rule itself is xq_td.hip.h's; called here: td_fold_max, first_max_take, td_target, td_output_delta, td_top_delta, td_record_store, per_priority_store.
 __global__ __launch_bounds__(256) void XQ_TD_DELTA_KERNEL(int n, SlotSrc src,
                                                           const int32_t* __restrict__ action_to, const float* __restrict__ reward,
                                                           const uint8_t* __restrict__ done, const float* __restrict__ a_last, int H,
@@ -29,9 +30,7 @@ __global__ __launch_bounds__(256) void XQ_TD_DELTA_KERNEL(int n, SlotSrc src,
         const float4 wv = *reinterpret_cast<const float4*>(w_out + (long long)ac * 256 + lane * 4);
         const bool has_view = live && a < view_kmax;
         const float4 vv = has_view ? *reinterpret_cast<const float4*>(view + (long long)a * view_ld + lane * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
-        float zm = partial[b];                         // the (up to kReduceParts) maxima left per sample
-#pragma unroll
-        for (int t = 1; t < 4; ++t) zm = fmaxf(zm, partial[(long long)min(t, n_partial - 1) * n + b]);
+        const float zm = td_fold_max(partial, n, b, n_partial);
         const float bo = b_out[ac], r = reward[s];
         const bool dn = done[s] != 0;
         const float isw = X.is_w ? X.is_w[b] / X.is_wmax[0] : 1.f;
@@ -40,15 +39,10 @@ __global__ __launch_bounds__(256) void XQ_TD_DELTA_KERNEL(int n, SlotSrc src,
         for (int off = 32; off > 0; off >>= 1) z += __shfl_xor(z, off, 64);
         if (live) {
             q = tanhf(z + bo);
-            y = dn ? r : r + gamma * tanhf(zm);
-            delta = L.err(q - y) * td_dtanh(q) * isw;
+            y = td_target(r, dn, gamma, zm);
+            delta = td_output_delta(L, q, y, isw);
         }
-        float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (has_view) {
-            o.x = delta * vv.x * (1.f - av.x * av.x); o.y = delta * vv.y * (1.f - av.y * av.y);
-            o.z = delta * vv.z * (1.f - av.z * av.z); o.w = delta * vv.w * (1.f - av.w * av.w);
-        }
-        *reinterpret_cast<float4*>(dtop + (long long)b * 256 + lane * 4) = o;
+        *reinterpret_cast<float4*>(dtop + (long long)b * 256 + lane * 4) = td_top_delta(has_view, delta, vv, av);
     } else if (H == 512 && !X.wout_bf && !X.double_dqn && n_partial <= 4) {
         // fp32 net, 512-wide last hidden layer (BASELINE configs[3]): the 256-wide path with two 16-byte pieces per lane and row
         // (columns 4 lane + 256 v); per-lane partial = piece 0 + piece 1, then the same shuffle tree
@@ -61,9 +55,7 @@ __global__ __launch_bounds__(256) void XQ_TD_DELTA_KERNEL(int n, SlotSrc src,
             wv[v] = *reinterpret_cast<const float4*>(w_out + (long long)ac * 512 + v * 256 + lane * 4);
             vv[v] = has_view ? *reinterpret_cast<const float4*>(view + (long long)a * view_ld + v * 256 + lane * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
         }
-        float zm = partial[b];
-#pragma unroll
-        for (int t = 1; t < 4; ++t) zm = fmaxf(zm, partial[(long long)min(t, n_partial - 1) * n + b]);
+        const float zm = td_fold_max(partial, n, b, n_partial);
         const float bo = b_out[ac], r = reward[s];
         const bool dn = done[s] != 0;
         const float isw = X.is_w ? X.is_w[b] / X.is_wmax[0] : 1.f;
@@ -73,18 +65,12 @@ __global__ __launch_bounds__(256) void XQ_TD_DELTA_KERNEL(int n, SlotSrc src,
         for (int off = 32; off > 0; off >>= 1) z += __shfl_xor(z, off, 64);
         if (live) {
             q = tanhf(z + bo);
-            y = dn ? r : r + gamma * tanhf(zm);
-            delta = L.err(q - y) * td_dtanh(q) * isw;
+            y = td_target(r, dn, gamma, zm);
+            delta = td_output_delta(L, q, y, isw);
         }
 #pragma unroll
-        for (int v = 0; v < 2; ++v) {
-            float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (has_view) {
-                o.x = delta * vv[v].x * (1.f - av[v].x * av[v].x); o.y = delta * vv[v].y * (1.f - av[v].y * av[v].y);
-                o.z = delta * vv[v].z * (1.f - av[v].z * av[v].z); o.w = delta * vv[v].w * (1.f - av[v].w * av[v].w);
-            }
-            *reinterpret_cast<float4*>(dtop + (long long)b * 512 + v * 256 + lane * 4) = o;
-        }
+        for (int v = 0; v < 2; ++v)
+            *reinterpret_cast<float4*>(dtop + (long long)b * 512 + v * 256 + lane * 4) = td_top_delta(has_view, delta, vv[v], av[v]);
     } else if (H == 512 && X.wout_bf && n_partial <= 4 && (!X.double_dqn || X.wout_t_bf)) {
         // bf16 net, 512-wide last hidden layer (BASELINE configs[4]): the same idea — every load that depends only on (b, s, a) issued up
         // front, 8 columns per lane as 16-byte loads; Double DQN adds ONE dependent round trip (the target net's row of the arg-max)
@@ -115,7 +101,7 @@ __global__ __launch_bounds__(256) void XQ_TD_DELTA_KERNEL(int n, SlotSrc src,
         float zm = pm[0]; int zi = pi[0];
 #pragma unroll
         for (int t = 1; t < 4; ++t) {
-            if (X.double_dqn) { if (pm[t] > zm || (pm[t] == zm && pi[t] < zi)) { zm = pm[t]; zi = pi[t]; } }
+            if (X.double_dqn) first_max_take(zm, zi, pm[t], pi[t]);
             else zm = fmaxf(zm, pm[t]);
         }
         if (X.double_dqn) {          // value of the online net's greedy action on the TARGET net
@@ -129,23 +115,18 @@ __global__ __launch_bounds__(256) void XQ_TD_DELTA_KERNEL(int n, SlotSrc src,
         }
         if (live) {
             q = tanhf(z + bo);
-            y = dn ? r : r + gamma * tanhf(zm);
-            delta = L.err(q - y) * td_dtanh(q) * isw;
+            y = td_target(r, dn, gamma, zm);
+            delta = td_output_delta(L, q, y, isw);
         }
-        float o[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        if (has_view) {
-            o[0] = delta * vv0.x * (1.f - av0.x * av0.x); o[1] = delta * vv0.y * (1.f - av0.y * av0.y);
-            o[2] = delta * vv0.z * (1.f - av0.z * av0.z); o[3] = delta * vv0.w * (1.f - av0.w * av0.w);
-            o[4] = delta * vv1.x * (1.f - av1.x * av1.x); o[5] = delta * vv1.y * (1.f - av1.y * av1.y);
-            o[6] = delta * vv1.z * (1.f - av1.z * av1.z); o[7] = delta * vv1.w * (1.f - av1.w * av1.w);
-        }
+        float4 o0 = make_float4(0.f, 0.f, 0.f, 0.f), o1 = o0;
+        if (has_view) { o0 = td_top_delta(true, delta, vv0, av0); o1 = td_top_delta(true, delta, vv1, av1); }      // (one branch for both quads)
         float* dp = dtop + (long long)b * 512 + lane * 8;
-        *reinterpret_cast<float4*>(dp) = make_float4(o[0], o[1], o[2], o[3]);
-        *reinterpret_cast<float4*>(dp + 4) = make_float4(o[4], o[5], o[6], o[7]);
+        *reinterpret_cast<float4*>(dp) = o0;
+        *reinterpret_cast<float4*>(dp + 4) = o1;
         if (X.dtop_bf)
             *reinterpret_cast<uint4*>(X.dtop_bf + (long long)b * 512 + lane * 8) =
-                make_uint4((uint32_t)bf16_bits(o[0]) | ((uint32_t)bf16_bits(o[1]) << 16), (uint32_t)bf16_bits(o[2]) | ((uint32_t)bf16_bits(o[3]) << 16),
-                           (uint32_t)bf16_bits(o[4]) | ((uint32_t)bf16_bits(o[5]) << 16), (uint32_t)bf16_bits(o[6]) | ((uint32_t)bf16_bits(o[7]) << 16));
+                make_uint4((uint32_t)bf16_bits(o0.x) | ((uint32_t)bf16_bits(o0.y) << 16), (uint32_t)bf16_bits(o0.z) | ((uint32_t)bf16_bits(o0.w) << 16),
+                           (uint32_t)bf16_bits(o1.x) | ((uint32_t)bf16_bits(o1.y) << 16), (uint32_t)bf16_bits(o1.z) | ((uint32_t)bf16_bits(o1.w) << 16));
     } else {
     if (live) {
         float z = 0.f;
@@ -158,10 +139,8 @@ __global__ __launch_bounds__(256) void XQ_TD_DELTA_KERNEL(int n, SlotSrc src,
         int zi = X.double_dqn ? X.partial_idx[b] : 0;
         for (int t = 1; t < n_partial; ++t) {
             const float v = partial[(long long)t * n + b];
-            if (X.double_dqn) {
-                const int vi = X.partial_idx[(long long)t * n + b];
-                if (v > zm || (v == zm && vi < zi)) { zm = v; zi = vi; }
-            } else zm = fmaxf(zm, v);
+            if (X.double_dqn) first_max_take(zm, zi, v, X.partial_idx[(long long)t * n + b]);
+            else zm = fmaxf(zm, v);
         }
         if (X.double_dqn) {          // value of the online net's greedy action on the TARGET net
             const int astar = (zi >= 0 && zi < X.nout) ? zi : 0;
@@ -176,17 +155,14 @@ __global__ __launch_bounds__(256) void XQ_TD_DELTA_KERNEL(int n, SlotSrc src,
             zm = zt + X.bout_t[astar];
         }
         q = tanhf(z);
-        const float r = reward[s];
-        y = done[s] ? r : r + gamma * tanhf(zm);       // max_k tanh(z_k) = tanh(max_k z_k)
-        delta = L.err(q - y) * td_dtanh(q);          // (a - target) * (1 - tanh(z)^2), the error through the loss
-        if (X.is_w) delta *= X.is_w[b] / X.is_wmax[0];
+        y = td_target(reward[s], done[s] != 0, gamma, zm);
+        delta = td_output_delta(L, q, y, X.is_w ? X.is_w[b] / X.is_wmax[0] : 1.f);
     }
     float* drow = dtop + (long long)b * H;
     if (live && a < view_kmax) {
         const float* vr = view + (long long)a * view_ld;
         for (int i = lane; i < H; i += 64) {
-            const float h = ar[i];
-            const float v = delta * vr[i] * (1.f - h * h);
+            const float v = td_top_delta(delta, vr[i], ar[i]);
             drow[i] = v;
             if (X.dtop_bf) X.dtop_bf[(long long)b * H + i] = bf16_bits(v);
         }
@@ -195,17 +171,7 @@ __global__ __launch_bounds__(256) void XQ_TD_DELTA_KERNEL(int n, SlotSrc src,
     }
     }
     if (lane == 0) {
-        dsc[b] = delta;
-        act[b] = live ? a : -1;
-        qsa[b] = q; yv[b] = y;
-        lossv[b] = live ? L.loss(q - y) : 0.f;
-        if (X.prio && live) {
-            const float p = powf(fabsf(q - y) + X.per_eps, X.per_alpha);
-            X.prio[s] = p;
-            // the running maximum rarely moves once training is under way: test first, so that 16 K waves do not queue on one address
-            // (positive floats order like their bit patterns; a maximum is order-independent, hence still deterministic)
-            if (__float_as_uint(p) > __hip_atomic_load(X.pmax_live, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
-                atomicMax(X.pmax_live, __float_as_uint(p));
-        }
+        td_record_store(L, dsc, act, qsa, yv, lossv, b, live, a, delta, q, y);
+        if (X.prio && live) per_priority_store(X.prio, X.pmax_live, s, q, y, X.per_eps, X.per_alpha);
     }
 }

@@ -150,7 +150,7 @@ def forward(net, boards, next_boards, A, R, D, gamma, td_rule, precision=PRECISI
     assert (A < net.sizes[-1]).all()
     tnet = target if target is not None else net
     f = Forward()
-    f.live = A >= 0                                                     # action -1: an empty slot, no gradient (xq_tail.hip.h)
+    f.live = A >= 0                                                     # action -1: an empty slot, no gradient (xq_td.hip.h)
     A = np.maximum(A, 0)
     f.n, f.boards, f.A, f.R, f.D, f.td_rule, f.precision = n, boards, A, R, D, td_rule, precision
     f.acts = [np.empty((n, h)) for h in net.sizes[1:-1]]

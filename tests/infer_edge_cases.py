@@ -1,5 +1,5 @@
 """The table of small inference calls that sit on the kernel-selection boundaries of the Q-net's forward paths (xq_dqn.hip, xq_l0.hip.h,
-xq_tail.hip.h, xq_env.hip), shared by tests/test_infer_shape_edges_gpu.py (every case on the device against the fp64 rows of
+xq_apply.hip.h, xq_env.hip), shared by tests/test_infer_shape_edges_gpu.py (every case on the device against the fp64 rows of
 batch_ref.q_rows) and the CPU controls of tests/test_batch_ref_cpu.py (the same cases: a damaged result must leave the bar).  Test
 infrastructure only, in the style of tests/td_edge_cases.py.
 

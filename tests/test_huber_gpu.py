@@ -43,6 +43,10 @@ CASES = {
     "bf16_512": (CFG4_NET, 37, 0, 0, 1, False, False),
     "bf16_512_double": (CFG4_NET, 37, 2, 0, 1, False, False),
     "f32_256_fast_per": (CFG2_NET, 1024, 0, 0, 0, False, True),
+    # (prioritized replay on the other three bodies of td_delta_kernel: importance weight in the delta, priority written back)
+    "f32_512_per": (F32_512_NET, 37, 0, 0, 0, False, True),
+    "general_128_per": (REF_NET, 37, 0, 0, 0, False, True),
+    "bf16_512_per": (CFG4_NET, 37, 0, 0, 1, False, True),
 }
 BOTH_MODES = [(name, mode) for name in list(CASES)[:2] for mode in (0, 1)] + [(name, CASES[name][3]) for name in list(CASES)[2:]]
 

@@ -1,4 +1,4 @@
-"""The ordered sums of xq_tail.hip.h bit for bit against plain C++ loops — `pytest -m gpu`.
+"""The ordered sums of xq_apply.hip.h bit for bit against plain C++ loops — `pytest -m gpu`.
 
 tools/slab_sum_probe.hip includes the kernel header itself and runs reduce_slabs_kernel, sgd_segments_kernel (stepping and reduce_only),
 adam_segments_kernel and colsum_partial_kernel over the slab counts, lengths, strides and alignments at which a batch boundary, a

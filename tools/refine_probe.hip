@@ -18,9 +18,8 @@
 #include "../cn_chess_ai_amd/csrc/xq_gemm.hip.h"
 #include "../cn_chess_ai_amd/csrc/xq_screen.hip.h"
 #include "../cn_chess_ai_amd/csrc/xq_gemm_dma.hip.h"
-#include "../cn_chess_ai_amd/csrc/xq_l0grad.hip.h"
-#include "../cn_chess_ai_amd/csrc/xq_l0.hip.h"
-#include "../cn_chess_ai_amd/csrc/xq_tail.hip.h"
+#include "../cn_chess_ai_amd/csrc/xq_l0.hip.h"           // SlotSrc
+#include "../cn_chess_ai_amd/csrc/xq_td.hip.h"
 #define XQ_REFINE_PROBE 1          // the stamp buffer and the clock of DBG = 1
 #include "../cn_chess_ai_amd/csrc/xq_refine.hip.h"
 using namespace xq;

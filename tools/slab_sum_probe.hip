@@ -1,5 +1,5 @@
-// tools/slab_sum_probe.hip — the ordered sums of xq_tail.hip.h (slab_sum through reduce_slabs_kernel, sgd_segments_kernel stepping and
-// reduce_only, adam_segments_kernel; the same chains over rows in colsum_partial_kernel) bit for bit against host loops that spell the order in
+// tools/slab_sum_probe.hip — the ordered sums of xq_apply.hip.h (slab_sum through reduce_slabs_kernel, sgd_segments_kernel stepping and
+// reduce_only, adam_segments_kernel; the same chains over rows in colsum_partial_kernel of xq_tail.hip.h) bit for bit against host loops that spell the order in
 // plain C++: four chains z = j, j + 4, .., leftover terms into chain 0, then (s0 + s1) + (s2 + s3).  The kernels may load their terms
 // whenever they like; the bits may not move.
 //   slabs:    nslabs {1,2,3,4,5,7,8,9,15,16,17,31,32,33,63,64,65} x len {1,3,4,5,252,256,257,1028} x stride % 4 {0,1} x base {16-byte
@@ -28,7 +28,8 @@
 #include "../cn_chess_ai_amd/csrc/xq_gemm_dma.hip.h"
 #include "../cn_chess_ai_amd/csrc/xq_l0grad.hip.h"
 #include "../cn_chess_ai_amd/csrc/xq_l0.hip.h"
-#include "../cn_chess_ai_amd/csrc/xq_tail.hip.h"
+#include "../cn_chess_ai_amd/csrc/xq_tail.hip.h"        // colsum_partial_kernel (and what its fused launch needs, above)
+#include "../cn_chess_ai_amd/csrc/xq_apply.hip.h"
 using namespace xq;
 #define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { printf("HIP error %s at %d\n", hipGetErrorString(e_), __LINE__); exit(2); } } while (0)
 

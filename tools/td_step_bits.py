@@ -1,6 +1,6 @@
 """The bits and the launches of a TD step over a fixed seeded matrix, and whether another build of the library gives the same ones.
 
-    python tools/td_step_bits.py [--forward] [--parent OTHER/libxqhip.so]
+    python tools/td_step_bits.py [--forward | --rule] [--parent OTHER/libxqhip.so]
 
 Cells: net {1260-128-8100, 1260-256-256-8100, 1260-512-512-512-8100, 1260-127-129-132-8100 (textbook rule)} x minibatch {333: one
 layer-0 chunk, partial tiles; 1100: slabs everywhere, no epilogue planes; and, for the two nets of even 256 / 512 widths, 2048: whole
@@ -18,6 +18,15 @@ boards with l0_derive on: plain, kept and derived layer-0 sums; the Q rows and t
 collect, two plies per update, 2048 games so that the select head rides on the last hidden product, screened maximum, four iterations;
 the final parameters of both nets and the kernel list).  The select cells, the trainer cells and the screened / bf16 TD cells run once
 more with the profiler off and without the kernel list ("prof=0"): only then does the forward product take the fork event itself.
+--rule: a third matrix, over the options of the TD rule itself (xq_td.hip.h), every caller of the rule at its smallest shape: the fp32
+256-wide path (1260-256-8100, 37 samples: a last block of one wave), the refine-fused step (the same net, screened maximum and fused
+tail, 897 samples: the first batch at which the screen engages, its last refine block holds one sample), the fp32 512-wide path
+(1260-512-8100, 37), the general path (1260-132-8100, 37), the general path with the Double fold (1260-256-8100, Double, 37) and the bf16
+512-wide path with Double (1260-512-8100, BF16, 37) x loss {squared, Huber kappa 0.25} x zero_sum {0, 1} x source {the host batch, a ring
+of four plies drawn prioritized, the same with n_step = 3: per_writeback_kernel}.  A combination the library refuses is printed as
+refused and is no cell.  Two steps per cell; hashed: both nets' parameters, the gradient buffer, Q(s,a) and y, last_loss, the
+td_error_stats record, the ring's priorities and their maximum, the kernel list.  A Huber cell prints linear/live of its last step and
+counts only if 0 < linear < live, both branches of the clamp taken; otherwise the run fails.
 --parent LIB: the matrix again in a fresh child process on that library (XQ_LIBXQHIP); exit status 1 if any cell differs."""
 import argparse
 import hashlib
@@ -213,19 +222,133 @@ def forward_matrix():
     return out
 
 
+RULE_CALLERS = [   # name, net, batch, TD rule, precision (a _capi name), screened maximum + fused tail
+    ("f32_256", (1260, 256, 8100), 37, 0, "PRECISION_F32", False),
+    ("refine_fused", (1260, 256, 8100), 897, 0, "PRECISION_F32", True),
+    ("f32_512", (1260, 512, 8100), 37, 0, "PRECISION_F32", False),
+    ("general", (1260, 132, 8100), 37, 0, "PRECISION_F32", False),
+    ("general_double", (1260, 256, 8100), 37, 2, "PRECISION_F32", False),
+    ("bf16_512_double", (1260, 512, 8100), 37, 2, "PRECISION_BF16", False),
+]
+RULE_KAPPA = 0.25
+RULE_PLIES = 4                     # the ring: four consecutive plies of n games, so that a chain of three is a real one
+
+
+def ring_plies(xq, n, seed):
+    """RULE_PLIES consecutive self-play plies of n games as (S, A, R, D, S2) per ply, every seventh row of a ply terminal"""
+    import numpy as np
+    env = xq.VecEnv(n, seed=seed)
+    for _ in range(13):
+        env.selfplay_step(None)
+    plies = []
+    for _ in range(RULE_PLIES):
+        S, _ = env.get_state()
+        res = env.selfplay_step(None)
+        S2, _ = env.get_state()
+        D = res["done"].copy()
+        D[::7] = 1
+        plies.append((S, (res["action"] % 90).astype(np.int32), (res["reward"] / 100.0).astype(np.float32), D, S2))
+    env.close()
+    return plies
+
+
+def rule_cell(xq, sizes, n, td_net, precision, screened, huber, zero_sum, source, plies):
+    import numpy as np
+    import torch
+    from cn_chess_ai_amd import _capi, dist as xd
+    d = seeded_net(xq, sizes, precision)
+    rng = np.random.default_rng(sizes[1] + 7)                  # a target net of its own: the Double rule reads other weights
+    d.set_params(rng.uniform(-0.05, 0.05, size=d.n_weights), rng.uniform(-0.05, 0.05, size=d.n_biases), net=_capi.NET_TARGET)
+    rp = None
+    try:
+        d.set_qmax_mode(_capi.QMAX_SCREENED if screened else _capi.QMAX_FULL)
+        d.set_td_tail(screened)
+        if huber:
+            d.set_td_loss("huber", RULE_KAPPA)
+        d.set_zero_sum(bool(zero_sum))
+        if source != "host":
+            rp = xq.ReplayBuffer(RULE_PLIES * n, seed=0xFEED + n)
+            rp.enable_per(0.6, 0.4, 1e-3)
+            for p in plies:
+                rp.push(*p)
+            rp.set_priorities(np.random.default_rng(7).uniform(0.05, 2.0, size=RULE_PLIES * n).astype(np.float32))
+            if source == "per_n3":
+                rp.set_n_step(3, n)
+        h = hashlib.sha256()
+        d.kernel_stats(enable=2)
+        for _ in range(2):
+            if rp is None:
+                S, A, R, D, S2 = plies[0]
+                d.td_update(S, S2, A, R, D, td_net=td_net, mode=_capi.BACKPROP_REFERENCE, learning_rate=0.05, grad_scale=1.0 / n)
+            else:
+                rp.per_rebuild()
+                rp.sample_prioritized(n, host=False)
+                d.td_grads_replay(rp, n, td_net=td_net, mode=_capi.BACKPROP_REFERENCE)
+                d.apply_grads(0.05, 1.0 / n)
+            for x in d.last_td_values(n):
+                h.update(x.tobytes())
+            st = d.td_error_stats()
+            h.update(json.dumps([d.last_loss()] + [st[k] for k in ("live", "mean_abs", "max_abs", "mean_loss", "linear")]).encode())
+        kernel_list(d, h, 1)
+        for net in (_capi.NET_ONLINE, _capi.NET_TARGET):
+            for x in d.get_params(net=net):
+                h.update(np.ascontiguousarray(x).tobytes())
+        ptr, k = d.grad_buffer()
+        torch.cuda.synchronize()
+        h.update(xd.wrap_device_floats(ptr, k).cpu().numpy().tobytes())
+        if rp is not None:
+            rp.per_rebuild()
+            h.update(rp.get_priorities(0, RULE_PLIES * n).tobytes())
+            h.update(json.dumps(rp.per_stats()["max_priority"]).encode())
+        return h.hexdigest(), st["linear"], st["live"]
+    finally:
+        d.close()
+        if rp is not None:
+            rp.close()
+
+
+def rule_matrix():
+    import cn_chess_ai_amd as xq
+    from cn_chess_ai_amd import _capi
+    out, refused, one_sided = {}, 0, []
+    rings = {}
+    for (cname, sizes, n, td_net, prec, screened), huber, zero_sum, source in itertools.product(RULE_CALLERS, (0, 1), (0, 1), ("host", "per", "per_n3")):
+        if n not in rings:
+            rings[n] = ring_plies(xq, n, seed=83)
+        name = "rule %s %s n=%d loss=%s zero_sum=%d source=%s" % (cname, "-".join(map(str, sizes)), n, "huber" if huber else "squared", zero_sum, source)
+        try:
+            digest, linear, live = rule_cell(xq, sizes, n, td_net, getattr(_capi, prec), screened, huber, zero_sum, source, rings[n])
+        except xq.XqError as e:
+            refused += 1
+            print("refused", name, "--", str(e).splitlines()[0], flush=True)
+            continue
+        out[name] = digest
+        print(digest, name, ("linear/live %d/%d" % (linear, live)) if huber else "", flush=True)
+        if huber and not 0 < linear < live:
+            one_sided.append(name)
+    for name in one_sided:
+        print("ONE-SIDED CLAMP", name, flush=True)
+    print("%d cells run, %d refused, %d Huber cells with a one-sided clamp" % (len(out), refused, len(one_sided)), flush=True)
+    if one_sided:
+        sys.exit(2)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--parent")
     ap.add_argument("--forward", action="store_true", help="the forward-half matrix instead of the gradient-half one")
+    ap.add_argument("--rule", action="store_true", help="the matrix over the TD rule's options and callers instead")
     ap.add_argument("--json", action="store_true", help="(the child process of --parent) the cells as one JSON line at the end")
     args = ap.parse_args()
-    mine = forward_matrix() if args.forward else matrix()
+    which = ["--forward"] if args.forward else ["--rule"] if args.rule else []
+    mine = forward_matrix() if args.forward else rule_matrix() if args.rule else matrix()
     if args.json:
         print("CELLS " + json.dumps(mine), flush=True)
     if not args.parent:
         return 0
     env = dict(os.environ, XQ_LIBXQHIP=os.path.abspath(args.parent))
-    r = subprocess.run([sys.executable, os.path.abspath(__file__), "--json"] + (["--forward"] if args.forward else []), env=env,
+    r = subprocess.run([sys.executable, os.path.abspath(__file__), "--json"] + which, env=env,
                        stdout=subprocess.PIPE, text=True, timeout=900)
     if r.returncode != 0:
         print("the run on", args.parent, "ended with", r.returncode, flush=True)
