@@ -2558,10 +2558,10 @@ static int nstep_assemble(xq_dqn* d, xq_replay* r, SlotSrc src, int batch, float
     NStepArgs A; memset(&A, 0, sizeof A);
     A.boards = r->dev.boards; A.next_boards = r->dev.next_boards; A.action_to = r->dev.action_to; A.reward = r->dev.reward; A.done = r->dev.done;
     A.cap = cap; A.stride = r->n_stride; A.n = n;
-    if (r->read_count >= 0) { A.first = r->read_first; A.count = r->read_count; }
-    else { A.first = r->size < cap ? 0 : r->write_pos; A.count = r->size; }
+    const RingSpan range = r->read_count >= 0 ? RingSpan{r->read_first, r->read_count} : ring_filled(ring_state(r));
+    A.first = range.first; A.count = range.count;
     r->read_count = -1;                              // a narrowed range holds for one step
-    if (A.first < 0 || A.first >= cap || A.count > cap) return fail(XQ_ERR_INVALID_ARGUMENT, "n-step readable range (%d, %d) outside the ring", A.first, A.count);
+    if (!range.inside(cap)) return fail(XQ_ERR_INVALID_ARGUMENT, "n-step readable range (%d, %d) outside the ring", A.first, A.count);
     const float gf = d->zero_sum ? -(float)d->gamma : (float)d->gamma;      // zero-sum: disc_k = (-1)^k g^k, the chain's movers alternate
     float dk[kNStepMax + 1];                         // disc_k: float times float, one fp32 rounding per factor
     dk[0] = 1.f;

@@ -2,6 +2,7 @@
 #pragma once
 
 #include "xq_common.h"
+#include "xq_ring_window.h"
 
 #include <algorithm>
 #include <climits>
@@ -414,6 +415,7 @@ void replay_advance(xq_replay* r, int n);   // n transitions were written (or qu
 int replay_per_rebuild(xq_replay* r, int retire_start, int retire_count, hipStream_t on, int hold_start = 0, int hold_count = 0);
 // the readable range of the next n-step TD step from this ring: `count` slots in age order from slot `first` (count < 0: the default)
 void replay_set_readable(xq_replay* r, int first, int count);
+inline RingState ring_state(const xq_replay* r) { return {r->size, r->write_pos, r->dev.capacity}; }
 int replay_per_sample(xq_replay* r, int batch, hipStream_t on);
 
 // env-side launchers used by the trainer

@@ -502,10 +502,8 @@ int xq_replay_per_rebuild(xq_replay* r, int retire_start, int retire_count) {
 
 int xq_replay_per_rebuild_hold(xq_replay* r, int retire_start, int retire_count, int hold_start, int hold_count) {
     if (!r) return fail(XQ_ERR_INVALID_ARGUMENT, "null replay");
-    if (retire_count < 0 || retire_count > r->dev.capacity || retire_start < 0 || retire_start >= r->dev.capacity)
-        return fail(XQ_ERR_INVALID_ARGUMENT, "bad retire window");
-    if (hold_count < 0 || hold_count > r->dev.capacity || hold_start < 0 || hold_start >= r->dev.capacity)
-        return fail(XQ_ERR_INVALID_ARGUMENT, "bad hold window");
+    if (!RingSpan{retire_start, retire_count}.inside(r->dev.capacity)) return fail(XQ_ERR_INVALID_ARGUMENT, "bad retire window");
+    if (!RingSpan{hold_start, hold_count}.inside(r->dev.capacity)) return fail(XQ_ERR_INVALID_ARGUMENT, "bad hold window");
     return replay_per_rebuild(r, retire_start, retire_count, nullptr, hold_start, hold_count);
 }
 

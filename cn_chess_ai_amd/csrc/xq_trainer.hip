@@ -15,9 +15,8 @@
 // slots collect(t) is writing, learn_apply(t) joins both before theta_{t+1} is written.  Preferred call order there:
 // learn_grads, collect, learn_apply — collect then starts behind the column-max GEMM (which wants the chip to itself) and
 // runs beside the gradient chain, which is a string of small latency-bound kernels.  collect-first is also accepted.
+// Which ring slots an iteration samples, reads and retires is stated once, in xq_ring_window.h (plan_iteration, plan_rebuild).
 #include "xq_internal.h"
-
-#include <climits>
 
 struct xq_trainer {
     xq_trainer_config cfg;
@@ -40,10 +39,10 @@ struct xq_trainer {
     int excluded = 0;                       // ring slots the queued learn_grads left out of its minibatch (from write_pos - inflight)
     xq::LazyMark grads;                     // main: the queued learn_grads has finished reading the ring
     bool per_ready = false;                 // prioritized replay: the sum tree holds the ring as of the last learn_apply
-    // n-step returns (xq_trainer_set_n_step; 1 = off).  per_first / per_count: the readable range that goes with the tree of the last
-    // rebuild — the filled ring minus the slots retired there, in age order — of which the newest (n_step - 1) * n_games are held
+    // n-step returns (xq_trainer_set_n_step; 1 = off).  tree: the readable range that goes with the tree of the last rebuild
+    // (xq::RebuildPlan::tree), of which the newest (n_step - 1) * n_games are held
     int n_step = 1;
-    int per_first = 0, per_count = 0;
+    xq::RingSpan tree;
     bool early_collect = false;             // collects_per_update > 1: collects start behind the previous parameter update (see collect_impl)
     uint64_t params_version = 0;            // dqn_params_version() when `params` was last recorded: anything that rewrote parameters on the
                                             // handle's stream since (set_params on a bf16 net, an apply_grads of the caller's own) lies
@@ -72,6 +71,17 @@ static int trainer_init(xq_trainer* t, const xq_trainer_config* cfg, void* hip_s
 static int record_params(xq_trainer* t) {
     XQ_TRY(t->params.record());
     t->params_version = dqn_params_version(t->dqn);
+    return XQ_OK;
+}
+
+static int plies_of(const xq_trainer* t) { return t->cfg.collects_per_update > 1 ? t->cfg.collects_per_update : 1; }
+
+// The setters' refusal of a null handle and of a call inside an iteration: a queued learn_grads, also collects in flight, also collects played ahead
+enum Busy { BUSY_GRADS, BUSY_COLLECTS, BUSY_PREPAID };
+static int between_iterations(const xq_trainer* t, const char* fn, Busy b = BUSY_GRADS) {
+    if (!t) return fail(XQ_ERR_INVALID_ARGUMENT, "null trainer");
+    if (t->grads_queued || (b >= BUSY_COLLECTS && t->inflight > 0) || (b >= BUSY_PREPAID && t->prepaid_collects > 0))
+        return fail(XQ_ERR_RUNTIME, "%s: call between iterations (after learn_apply)", fn);
     return XQ_OK;
 }
 
@@ -117,13 +127,13 @@ static int trainer_init(xq_trainer* t, const xq_trainer_config* cfg, void* hip_s
         // Several plies per update: the plies ARE the critical path (each waits for the move of the one before, bench --config 4:
         // 4 x 155 us alone, 375 + 314 us for the two that share the chip with the TD step) => most urgent: 1.096 -> 1.054 ms per step
         // (one ply per update with the select chain most urgent: no difference on the headline bench, -0.5 % on bench --config 5)
-        const int prio = cfg->collects_per_update > 1 ? hi : lo;
+        const int prio = plies_of(t) > 1 ? hi : lo;
         XQ_TRY(t->cstream.open_owned(hipStreamNonBlocking, prio));
         XQ_TRY(t->params.open(t->stream));
         XQ_TRY(t->collects.open(t->cstream));
         XQ_TRY(t->grads.open(t->stream));
         XQ_TRY(record_params(t));                             // orders the first collect after the handles' initialisation
-        t->early_collect = cfg->collects_per_update > 1;
+        t->early_collect = plies_of(t) > 1;
     }
     return XQ_OK;
 }
@@ -171,26 +181,25 @@ static int versus_opponent(xq_trainer* t, int phase, hipStream_t s) {
     return env_versus_launch(t->env, phase, q, 96, nullptr, o.eps_u32, pick, t->vs_counts, t->replay, s, opp_view);
 }
 
-// A versus collect on stream s (`on`: the collect stream, if any): pre-move, select chain, learner half-ply, reply; one transition per
-// game, into the ring slots from write_pos, which moves once the last phase is queued
-// The boards the trainer's select chain reads: the env's or, under the mover view, their view in view_sel, staged on stream s now
-static int select_boards(xq_trainer* t, hipStream_t s, const uint32_t** boards) {
-    *boards = t->env->boards;
-    if (t->view != XQ_VIEW_MOVER) return XQ_OK;
-    XQ_TRY(view_boards_launch(t->env->boards, nullptr, t->env->meta, t->env->n, t->view_sel, s));
-    *boards = t->view_sel;
-    return XQ_OK;
+// The learner's select chain on stream s (`on`: the collect stream, if any): Q(s)[0..89] of every game, from the env's boards or, under
+// the mover view, from their view in view_sel, staged on s in front of it
+struct SelectQ { float* q90 = nullptr; int stride = 0; QSource qs; };
+static int select_chain(xq_trainer* t, hipStream_t on, hipStream_t s, SelectQ* q) {
+    const uint32_t* boards = t->env->boards;
+    if (t->view == XQ_VIEW_MOVER) {
+        XQ_TRY(view_boards_launch(t->env->boards, nullptr, t->env->meta, t->env->n, t->view_sel, s));
+        boards = t->view_sel;
+    }
+    return dqn_q90_boards(t->dqn, boards, t->env->n, &q->q90, &q->stride, on, &q->qs);
 }
 
+// A versus collect on stream s: pre-move, select chain, learner half-ply, reply; one transition per game, into the ring slots from
+// write_pos, which moves once the last phase is queued
 static int versus_collect(xq_trainer* t, hipStream_t on, hipStream_t s) {
-    float* q90 = nullptr;
-    int stride = 0;
-    QSource qs;
-    const uint32_t* boards = nullptr;
+    SelectQ q;
     XQ_TRY(versus_opponent(t, 0, s));
-    XQ_TRY(select_boards(t, s, &boards));
-    XQ_TRY(dqn_q90_boards(t->dqn, boards, t->env->n, &q90, &stride, on, &qs));
-    XQ_TRY(env_versus_launch(t->env, 1, q90, stride, &qs, t->eps_u32, nullptr, t->vs_counts, t->replay, s));
+    XQ_TRY(select_chain(t, on, s, &q));
+    XQ_TRY(env_versus_launch(t->env, 1, q.q90, q.stride, &q.qs, t->eps_u32, nullptr, t->vs_counts, t->replay, s));
     XQ_TRY(versus_opponent(t, 2, s));
     replay_advance(t->replay, t->env->n);
     return XQ_OK;
@@ -222,22 +231,15 @@ static int collect_impl(xq_trainer* t) {
         if (t->grads_queued && t->inflight + t->env->n > t->excluded) XQ_TRY(t->grads.wait(on));
     }
     hipStream_t s = on ? on : t->stream;
-    if (t->cfg.replay_capacity == 0) {           // on-policy: the ring is exactly one batch, refilled every ply
-        t->replay->write_pos = 0;
-        t->replay->size = 0;
-    }
+    if (t->cfg.replay_capacity == 0) t->replay->write_pos = t->replay->size = 0;     // on-policy: the ring is exactly one batch, refilled every ply
     if (t->vs_on) {
         XQ_TRY(versus_collect(t, on, s));
     } else {
-        float* q90 = nullptr;
-        int stride = 0;
-        QSource qs;
-        const uint32_t* boards = nullptr;
-        XQ_TRY(select_boards(t, s, &boards));
-        XQ_TRY(dqn_q90_boards(t->dqn, boards, t->env->n, &q90, &stride, on, &qs));
+        SelectQ q;
+        XQ_TRY(select_chain(t, on, s, &q));
         Profiler* p = dqn_profiler(t->dqn);
         const int h = p->begin("env_selfplay_step", s, true);       // one kernel: timed by its own start / stop events
-        XQ_TRY(env_selfplay_launch(t->env, q90, stride, t->eps_u32, nullptr, t->replay, on, &qs, h >= 0 ? p->recs[h].a : nullptr,
+        XQ_TRY(env_selfplay_launch(t->env, q.q90, q.stride, t->eps_u32, nullptr, t->replay, on, &q.qs, h >= 0 ? p->recs[h].a : nullptr,
                                    h >= 0 ? p->recs[h].b : nullptr));
         // algorithmic HBM bytes per game and ply: board+meta in/out (2*(48+16)), Q row 360, transition 48+48+4+4+1
         p->end(h, s, 0.0, (double)t->env->n * (2.0 * (48 + 16) + 360 + 105));
@@ -257,14 +259,12 @@ int xq_trainer_collect(xq_trainer* t) {
 }
 
 int xq_trainer_set_comm(xq_trainer* t, xq_comm* comm) {
-    if (!t) return fail(XQ_ERR_INVALID_ARGUMENT, "null trainer");
-    if (t->grads_queued) return fail(XQ_ERR_RUNTIME, "xq_trainer_set_comm: call between iterations (after learn_apply)");
+    XQ_TRY(between_iterations(t, "xq_trainer_set_comm"));
     return xq_dqn_set_comm(t->dqn, comm);
 }
 
 int xq_trainer_set_target_tau(xq_trainer* t, double tau) {
-    if (!t) return fail(XQ_ERR_INVALID_ARGUMENT, "null trainer");
-    if (t->grads_queued) return fail(XQ_ERR_RUNTIME, "xq_trainer_set_target_tau: call between iterations (after learn_apply)");
+    XQ_TRY(between_iterations(t, "xq_trainer_set_target_tau"));
     return xq_dqn_set_target_tau(t->dqn, tau);
 }
 
@@ -272,8 +272,7 @@ int xq_trainer_set_target_tau(xq_trainer* t, double tau) {
 // The legal-move bootstrap on the trainer's Q-net; `legal` first makes the trainer's ring record the side to move in s' (possible only
 // while the ring is empty: XQ_ERR_RUNTIME once it holds a transition, unless it tracks already).  Back to `all` the column stays written.
 int xq_trainer_set_td_bootstrap(xq_trainer* t, int kind) {
-    if (!t) return fail(XQ_ERR_INVALID_ARGUMENT, "null trainer");
-    if (t->grads_queued) return fail(XQ_ERR_RUNTIME, "xq_trainer_set_td_bootstrap: call between iterations (after learn_apply)");
+    XQ_TRY(between_iterations(t, "xq_trainer_set_td_bootstrap"));
     if (kind == XQ_BOOTSTRAP_LEGAL) XQ_TRY(xq_replay_track_next_player(t->replay));
     return xq_dqn_set_td_bootstrap(t->dqn, kind);
 }
@@ -282,8 +281,7 @@ int xq_trainer_set_td_bootstrap(xq_trainer* t, int kind) {
 // runs from one learner decision to the next, so it and xq_trainer_set_opponent refuse each other.  No window changes: only the sign of
 // the discount and the no-move value of the legal bootstrap do
 int xq_trainer_set_zero_sum(xq_trainer* t, int on) {
-    if (!t) return fail(XQ_ERR_INVALID_ARGUMENT, "null trainer");
-    if (t->grads_queued) return fail(XQ_ERR_RUNTIME, "xq_trainer_set_zero_sum: call between iterations (after learn_apply)");
+    XQ_TRY(between_iterations(t, "xq_trainer_set_zero_sum"));
     if (on == 1 && t->vs_on)
         return fail(XQ_ERR_INVALID_ARGUMENT, "xq_trainer_set_zero_sum: an opponent is set (xq_trainer_set_opponent): a versus transition ends "
                                              "with the learner to move again, which the zero-sum target is not for");
@@ -312,58 +310,32 @@ int xq_trainer_set_view(xq_trainer* t, int view) {
 
 // the reward rule of the trainer's env: the next collect writes it, slots already in the ring keep theirs
 int xq_trainer_set_reward(xq_trainer* t, int kind, double scale, double ply_cost, double bound) {
-    if (!t) return fail(XQ_ERR_INVALID_ARGUMENT, "null trainer");
-    if (t->grads_queued) return fail(XQ_ERR_RUNTIME, "xq_trainer_set_reward: call between iterations (after learn_apply)");
+    XQ_TRY(between_iterations(t, "xq_trainer_set_reward"));
     return xq_env_set_reward(t->env, kind, scale, ply_cost, bound);
 }
 
 int xq_trainer_set_mirror(xq_trainer* t, double prob) {
-    if (!t) return fail(XQ_ERR_INVALID_ARGUMENT, "null trainer");
-    if (t->grads_queued) return fail(XQ_ERR_RUNTIME, "xq_trainer_set_mirror: call between iterations (after learn_apply)");
+    XQ_TRY(between_iterations(t, "xq_trainer_set_mirror"));
     return xq_replay_set_mirror(t->replay, prob);
 }
 
 // ... and so does the colour swap (the side byte it flips is read at the slot the step reads it at anyway)
 int xq_trainer_set_colour_swap(xq_trainer* t, double prob) {
-    if (!t) return fail(XQ_ERR_INVALID_ARGUMENT, "null trainer");
-    if (t->grads_queued) return fail(XQ_ERR_RUNTIME, "xq_trainer_set_colour_swap: call between iterations (after learn_apply)");
+    XQ_TRY(between_iterations(t, "xq_trainer_set_colour_swap"));
     return xq_replay_set_colour_swap(t->replay, prob);
 }
 
-// The newest (n_step - 1) * n_games slots of the tree's readable range — unless that is all of it (the first iterations of a run): then
-// nothing is held, as the uniform window is sampled uncut, and the rows that reach past the range are dead
-static int held_slots(const xq_trainer* t) {
-    const int h = (t->n_step - 1) * t->cfg.n_games;
-    return t->per_count - h > 0 ? h : 0;
-}
-// the rebuild itself, for the range noted last: `retire_count` slots from write_pos out for good, the held ones out of this tree only
-static int rebuild_held(xq_trainer* t, int retire_count) {
-    xq_replay* r = t->replay;
-    const int hold = held_slots(t);
-    const int hold_start = hold > 0 ? (int)(((long long)t->per_first + t->per_count - hold) % r->dev.capacity) : 0;
-    return replay_per_rebuild(r, r->write_pos, retire_count, t->stream, hold_start, hold);
-}
-
-// Prioritized replay: rebuilds the tree with `retire_count` slots from write_pos retired, notes the readable range that goes with it
-// (what is filled and not retired, in age order) and holds that range's newest (n_step - 1) * n_games slots, whose chains are incomplete
-static int rebuild_tree(xq_trainer* t, int retire_count) {
-    xq_replay* r = t->replay;
-    const int cap = r->dev.capacity;
-    if (retire_count > 0) {          // (only once the ring is full up to the retired window: the rest of it is the whole readable range)
-        t->per_first = (r->write_pos + retire_count) % cap;
-        t->per_count = cap - retire_count;
-    } else {
-        t->per_first = r->size < cap ? 0 : r->write_pos;
-        t->per_count = r->size;
-    }
-    return rebuild_held(t, retire_count);
+// Prioritized replay: rebuilds the tree for the ring as it stands and the next `plies` collects (xq::plan_rebuild): the slots they
+// overwrite retired, the readable range that goes with the tree noted, its newest slots (incomplete chains) held out of this tree
+static int rebuild_tree(xq_trainer* t, int plies) {
+    const RebuildPlan p = plan_rebuild(ring_state(t->replay), t->cfg.n_games, plies, t->n_step);
+    t->tree = p.tree;
+    return replay_per_rebuild(t->replay, p.retire.first, p.retire.count, t->stream, p.hold.first, p.hold.count);
 }
 
 int xq_trainer_set_n_step(xq_trainer* t, int n_step) {
-    if (!t) return fail(XQ_ERR_INVALID_ARGUMENT, "null trainer");
-    if (t->grads_queued || t->inflight > 0 || t->prepaid_collects > 0)
-        return fail(XQ_ERR_RUNTIME, "xq_trainer_set_n_step: call between iterations (after learn_apply)");
-    const int plies = t->cfg.collects_per_update > 1 ? t->cfg.collects_per_update : 1;
+    XQ_TRY(between_iterations(t, "xq_trainer_set_n_step", BUSY_PREPAID));
+    const int plies = plies_of(t);
     if (n_step > 1 && t->cfg.replay_capacity == 0)
         return fail(XQ_ERR_INVALID_ARGUMENT, "xq_trainer_set_n_step: n-step returns need a replay ring (on-policy keeps one ply)");
     if (n_step > 1 && n_step <= XQ_MAX_N_STEP && (long long)t->cfg.replay_capacity <= (long long)(n_step - 1 + plies) * t->cfg.n_games)
@@ -372,21 +344,22 @@ int xq_trainer_set_n_step(xq_trainer* t, int n_step) {
     XQ_TRY(xq_replay_set_n_step(t->replay, n_step, t->cfg.n_games));
     t->n_step = n_step;
     // the tree of the last learn_apply was built for the previous hold: the same tree again (its retired slots are already 0), held anew
-    if (t->cfg.prioritized && t->per_ready) XQ_TRY(rebuild_held(t, 0));
+    if (t->cfg.prioritized && t->per_ready) {
+        const RingSpan hold = span_held(t->tree, (long long)(n_step - 1) * t->cfg.n_games, t->replay->dev.capacity);
+        XQ_TRY(replay_per_rebuild(t->replay, 0, 0, t->stream, hold.first, hold.count));
+    }
     return XQ_OK;
 }
 
 int xq_trainer_set_td_net(xq_trainer* t, int td_net) {
     if (!t || (td_net != XQ_TD_ONLINE_NET && td_net != XQ_TD_TARGET_NET && td_net != XQ_TD_DOUBLE)) return fail(XQ_ERR_INVALID_ARGUMENT, "bad td_net");
-    if (t->grads_queued) return fail(XQ_ERR_RUNTIME, "xq_trainer_set_td_net: call between iterations (after learn_apply)");
+    XQ_TRY(between_iterations(t, "xq_trainer_set_td_net"));
     t->cfg.td_net = td_net;
     return XQ_OK;
 }
 
 int xq_trainer_set_opponent(xq_trainer* t, const xq_arena_player* opp) {
-    if (!t) return fail(XQ_ERR_INVALID_ARGUMENT, "null trainer");
-    if (t->grads_queued || t->inflight > 0 || t->prepaid_collects > 0)
-        return fail(XQ_ERR_RUNTIME, "xq_trainer_set_opponent: call between iterations (after learn_apply)");
+    XQ_TRY(between_iterations(t, "xq_trainer_set_opponent", BUSY_PREPAID));
     CheckedPlayer vs;
     XQ_TRY(make_player(opp, "xq_trainer_set_opponent: the opponent", &vs));
     if (vs.net && vs.net == t->dqn) return fail(XQ_ERR_INVALID_ARGUMENT, "xq_trainer_set_opponent: the opponent is the trainer's own network");
@@ -426,81 +399,37 @@ int xq_trainer_versus_results(xq_trainer* t, uint64_t out[4]) {
 
 int xq_trainer_random_plies(xq_trainer* t, int n_plies) {
     if (!t || n_plies < 0) return fail(XQ_ERR_INVALID_ARGUMENT, "bad argument");
-    if (t->inflight > 0 || t->grads_queued) return fail(XQ_ERR_RUNTIME, "xq_trainer_random_plies: call between iterations (after learn_apply)");
+    XQ_TRY(between_iterations(t, "xq_trainer_random_plies", BUSY_COLLECTS));
     for (int i = 0; i < n_plies; ++i) XQ_TRY(env_selfplay_launch(t->env, nullptr, 0, 0u, nullptr, nullptr, t->stream));
     t->params.touched();                         // the next collect (own stream) starts behind these plies
     return XQ_OK;
 }
 
-// Prioritized replay: the minibatch comes from the sum tree as of the last learn_apply — it holds every transition collected
-// before this iteration except the slots this iteration's collects overwrite (retired there), in both call orders and with or
-// without overlap_collect.  An empty tree (first iteration) is filled by playing this iteration's plies first.
-static int learn_grads_prioritized(xq_trainer* t) {
-    const int plies = t->cfg.collects_per_update > 1 ? t->cfg.collects_per_update : 1;
-    if (!t->per_ready) {
-        if (t->inflight == 0 && t->replay->size == 0) {
+// The minibatch of iteration t (xq::plan_iteration).  Uniform with overlap_collect: drawn from the ring minus the slots collect(t) writes.
+// Prioritized: from the sum tree as of the last learn_apply — every transition collected before this iteration except the slots its
+// collects overwrite (retired there), in both call orders.  Nothing older than this iteration's plies, or no tree yet (the first
+// iteration): the plies come first, played here if need be, and the step learns on them.
+int xq_trainer_learn_grads(xq_trainer* t) {
+    if (!t) return fail(XQ_ERR_INVALID_ARGUMENT, "null trainer");
+    const int batch = t->cfg.replay_capacity > 0 ? t->cfg.minibatch : 0;     // (on-policy: the ply just played, all of it)
+    if (batch > 0) {
+        const int plies = plies_of(t);
+        const IterationPlan p = plan_iteration({ring_state(t->replay), t->cfg.n_games, plies, t->inflight, t->n_step, (bool)t->cstream,
+                                                t->cfg.prioritized != 0, t->per_ready, t->tree});
+        if (p.play_first) {
             for (int c = 0; c < plies; ++c) XQ_TRY(collect_impl(t));
             t->prepaid_collects = plies;
         }
-        if (t->cstream) { XQ_TRY(wait_collects(t)); t->inflight = 0; }
-        if (t->replay->size == 0) return fail(XQ_ERR_RUNTIME, "replay is empty");
-        XQ_TRY(rebuild_tree(t, 0));
-        t->per_ready = true;
-        t->excluded = 0;
-    } else {
-        t->excluded = plies * t->cfg.n_games;       // retired at the last learn_apply: the collects may run beside this step
-    }
-    XQ_TRY(replay_per_sample(t->replay, t->cfg.minibatch, t->stream));
-    if (t->n_step > 1) replay_set_readable(t->replay, t->per_first, t->per_count);
-    XQ_TRY(xq_dqn_td_grads_replay(t->dqn, t->replay, t->cfg.minibatch, t->cfg.td_net, t->cfg.backprop_mode));
-    t->grads.touched();
-    t->grads_queued = true;
-    return XQ_OK;
-}
-
-int xq_trainer_learn_grads(xq_trainer* t) {
-    if (!t) return fail(XQ_ERR_INVALID_ARGUMENT, "null trainer");
-    if (t->cfg.prioritized) return learn_grads_prioritized(t);
-    int batch = 0;
-    if (t->cfg.replay_capacity > 0) {
-        batch = t->cfg.minibatch;
-        int start = 0, count = -1;
-        if (t->cstream) {
-            // the ring minus the window the collects of this iteration write: [write_pos - inflight, write_pos) when they are
-            // already queued, else the next `plies * n_games` slots from write_pos (they will be queued behind the GEMM)
-            const xq_replay* r = t->replay;
-            const int cap = r->dev.capacity;
-            const int plies = t->cfg.collects_per_update > 1 ? t->cfg.collects_per_update : 1;
-            const int m = t->inflight > 0 ? t->inflight : plies * t->cfg.n_games;
-            const int size_after = t->inflight > 0 ? r->size : std::min(cap, r->size + m);
-            const int wpos_after = t->inflight > 0 ? r->write_pos : (r->write_pos + m) % cap;
-            if (size_after < cap) { start = 0; count = size_after - m; }
-            else { start = wpos_after; count = cap - m; }
-            if (count <= 0 || m > cap) {
-                // nothing older than this iteration's plies (first iteration): play them now, wait, learn on those
-                if (t->inflight == 0) {
-                    for (int c = 0; c < plies; ++c) XQ_TRY(collect_impl(t));
-                    t->prepaid_collects = plies;
-                }
-                XQ_TRY(wait_collects(t));
-                t->inflight = 0;
-                start = 0; count = -1;
-                t->excluded = 0;
-            } else {
-                t->excluded = m;
-            }
+        if (p.join_first && t->cstream) { XQ_TRY(wait_collects(t)); t->inflight = 0; }
+        if (p.join_first && t->cfg.prioritized) {
+            if (t->replay->size == 0) return fail(XQ_ERR_RUNTIME, "replay is empty");
+            XQ_TRY(rebuild_tree(t, 0));
+            t->per_ready = true;
         }
-        if (t->n_step > 1) {
-            // n-step returns: the window in age order (what the chains may read), sampled without its newest (n_step - 1) * n_games
-            // slots, whose chains are not complete — unless that leaves nothing (the first iterations): then the window as it is, and
-            // the rows that reach past it are dead
-            const xq_replay* r = t->replay;
-            if (count < 0) { start = r->size < r->dev.capacity ? 0 : r->write_pos; count = r->size; }
-            replay_set_readable(t->replay, start, count);
-            const int cut = (t->n_step - 1) * t->cfg.n_games;
-            if (count - cut > 0) count -= cut;
-        }
-        XQ_TRY(replay_sample_implicit(t->replay, batch, start, count));     // no sampling kernel: the consumers recompute the slots
+        t->excluded = p.excluded;
+        if (p.readable.count >= 0) replay_set_readable(t->replay, p.readable.first, p.readable.count);
+        if (t->cfg.prioritized) XQ_TRY(replay_per_sample(t->replay, batch, t->stream));
+        else XQ_TRY(replay_sample_implicit(t->replay, batch, p.sample.first, p.sample.count));  // no sampling kernel: the consumers recompute the slots
     }
     XQ_TRY(xq_dqn_td_grads_replay(t->dqn, t->replay, batch, t->cfg.td_net, t->cfg.backprop_mode));
     t->grads.touched();
@@ -518,13 +447,8 @@ int xq_trainer_learn_apply(xq_trainer* t, int world_size) {
     if (t->cfg.target_sync_interval > 0 && t->updates % (uint64_t)t->cfg.target_sync_interval == 0)
         XQ_TRY(xq_dqn_update_target(t->dqn));
     if (t->cfg.prioritized) {
-        // the tree of the next iteration: this iteration's TD-error priorities and new transitions in, the slots the next
-        // collects will overwrite out (only once the ring is full — before that they are fresh slots with priority 0)
-        const int plies = t->cfg.collects_per_update > 1 ? t->cfg.collects_per_update : 1;
-        const int m = plies * t->cfg.n_games;
-        const xq_replay* r = t->replay;
-        const bool full = r->size + m > r->dev.capacity;
-        XQ_TRY(rebuild_tree(t, full ? std::min(m, r->dev.capacity) : 0));
+        // the tree of the next iteration: this iteration's TD-error priorities and new transitions in, the next collects' slots out
+        XQ_TRY(rebuild_tree(t, plies_of(t)));
         t->per_ready = true;
     }
     t->params.touched();
@@ -536,7 +460,7 @@ int xq_trainer_learn_apply(xq_trainer* t, int world_size) {
 
 int xq_trainer_step(xq_trainer* t, int n_iterations) {
     if (!t || n_iterations < 0) return fail(XQ_ERR_INVALID_ARGUMENT, "bad argument");
-    const int plies = t->cfg.collects_per_update > 1 ? t->cfg.collects_per_update : 1;
+    const int plies = plies_of(t);
     if (plies > 1 && t->cfg.replay_capacity == 0)
         return fail(XQ_ERR_INVALID_ARGUMENT, "collects_per_update > 1 needs a replay ring (on-policy keeps one ply)");
     const int world = dqn_comm(t->dqn) ? comm_world(dqn_comm(t->dqn)) : 1;     // data-parallel when a communicator is attached
@@ -544,13 +468,9 @@ int xq_trainer_step(xq_trainer* t, int n_iterations) {
     XQ_TRY(xq_dqn_set_fused_apply(t->dqn, 1));      // single-GPU loop: nothing reads the gradient buffer between grads and apply
     int rc = XQ_OK;
     for (int i = 0; i < n_iterations && rc == XQ_OK; ++i) {
-        if (t->cstream) {
-            rc = xq_trainer_learn_grads(t);
-            for (int c = 0; c < plies && rc == XQ_OK; ++c) rc = xq_trainer_collect(t);
-        } else {
-            for (int c = 0; c < plies && rc == XQ_OK; ++c) rc = xq_trainer_collect(t);
-            if (rc == XQ_OK) rc = xq_trainer_learn_grads(t);
-        }
+        if (t->cstream) rc = xq_trainer_learn_grads(t);         // overlapped: the collects start behind its big GEMM
+        for (int c = 0; c < plies && rc == XQ_OK; ++c) rc = xq_trainer_collect(t);
+        if (!t->cstream && rc == XQ_OK) rc = xq_trainer_learn_grads(t);
         if (rc == XQ_OK) rc = xq_trainer_learn_apply(t, world);
     }
     const int rc_off = xq_dqn_set_fused_apply(t->dqn, fused_before);     // also after a failed iteration

@@ -367,7 +367,7 @@ def test_one_rank_communicator_has_the_same_bits(xq):
 def test_overlapped_trainer_with_huber_equals_its_sequential_definition(xq):
     """tests/test_trainer_gpu.py's composition with Huber on, 8 steps: bit for bit."""
     import torch
-    from test_trainer_gpu import overlap_window
+    from ring_window_ref import overlap_window
     n, cap, minibatch, iters, sizes, kappa = 64, 256, 48, 8, CFG2_NET, 0.05
     seed, first = 99, 7
     cfg = xq.TrainerConfig(n_games=n, layer_sizes=sizes, learning_rate=0.01, gamma=0.99, epsilon=0.2, replay_capacity=cap,

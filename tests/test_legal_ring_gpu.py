@@ -12,7 +12,7 @@ import pytest
 import xqoracle as xo
 from test_dqn_gpu import CFG2_NET
 from test_legal_gpu import GAMMA, SMALL_NET, bits, legal_net
-from test_trainer_gpu import overlap_window
+from ring_window_ref import overlap_window
 
 pytestmark = pytest.mark.gpu
 

@@ -12,7 +12,7 @@ import nstep_ref as nr
 import per_ref as pr
 import xqoracle as xo
 from test_dqn_gpu import CFG2_NET, make_net
-from test_trainer_gpu import overlap_window
+from ring_window_ref import default_range, overlap_window, tree_range
 
 pytestmark = pytest.mark.gpu
 
@@ -262,10 +262,6 @@ def ring_arrays(rp, cap):
     return A, R, D
 
 
-def default_range(size, total, cap):
-    return (0 if size < cap else total % cap), size
-
-
 @pytest.mark.parametrize("overlap,plies,versus", [(0, 1, False), (1, 1, False), (0, 2, False), (1, 2, True), (0, 1, True)])
 def test_trainer_assembles_complete_chains(xq, overlap, plies, versus):
     """64 games, a ring that is no multiple of 64 and wraps several times, n_step = 3: after each learn_grads the assembled batch is
@@ -371,13 +367,6 @@ def test_overlapped_n_step_trainer_equals_its_sequential_definition(xq):
         assert np.array_equal(q[0], tq[0]) and np.array_equal(q[1], tq[1])
     finally:
         t.close(); env.close(); d.close(); rp.close()
-
-
-def tree_range(size, total, cap, G):
-    """the readable range that goes with the tree learn_apply builds: the filled ring minus the next collect's slots once they wrap"""
-    if size + G > cap:
-        return (total % cap + G) % cap, cap - G
-    return default_range(size, total, cap)
 
 
 @pytest.mark.parametrize("warm", [0, 4])

@@ -477,7 +477,7 @@ def test_overlapped_trainer_with_tau_equals_its_sequential_definition(xq, n, cap
     communicator give bit-identical online and target parameters."""
     import torch
     from cn_chess_ai_amd import dist as xd
-    from test_trainer_gpu import overlap_window
+    from ring_window_ref import overlap_window
     seed, first, iters, tau, sizes = 99, 7, 12, 0.01, CFG2_NET
     mk = lambda: xq.TrainerConfig(n_games=n, layer_sizes=sizes, learning_rate=0.01, gamma=0.99, epsilon=0.2, replay_capacity=cap,
                                   minibatch=minibatch, td_net=1, backprop_mode=0, target_sync_interval=0, mean_gradient=1, seed=seed,

@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 import xqoracle as xo
+from ring_window_ref import overlap_window
 from test_dqn_gpu import oracle_td_update, REF_NET, CFG2_NET
 
 pytestmark = pytest.mark.gpu
@@ -136,20 +137,13 @@ def test_collects_per_update(xq):
     t.close(); bad.close()
 
 
-def overlap_window(size, total, cap, m):
-    """Eligible ring slots while a collect of m transitions is in flight: (start, count) from the pre-collect state."""
-    w = total % cap
-    if size + m < cap:
-        return 0, size
-    return (w + m) % cap, cap - m
-
-
 CFG4_NET = (1260, 512, 512, 512, 8100)          # BASELINE configs[3]: (512,512,512) hidden layers, 4 plies per update
 
 
 @pytest.mark.parametrize("n,cap,minibatch,plies,iters,sizes", [
     (64, 256, 48, 1, 9, CFG2_NET), (32, 200, 64, 2, 8, CFG2_NET), (2048, 1 << 15, 2048, 1, 6, CFG2_NET),
-    (256, 4096, 512, 4, 5, CFG4_NET)])           # configs[3] topology and cadence at a size the composition finishes quickly
+    (256, 4096, 512, 4, 5, CFG4_NET),            # configs[3] topology and cadence at a size the composition finishes quickly
+    (64, 100, 48, 2, 6, CFG2_NET)])              # plies x games = 128 exceeds the ring of 100: every iteration plays its plies first
 def test_overlapped_trainer_equals_its_sequential_definition(xq, n, cap, minibatch, plies, iters, sizes):
     """Iteration t: minibatch drawn from the ring minus the slots collect(t) writes, gradients with theta_t; collect(t) acts with
     theta_t; then apply.  First iteration (nothing older in the ring): collect, then learn on what was just played."""

@@ -18,6 +18,7 @@ import pytest
 
 import versus_ref as vr
 import xqoracle as xo
+from ring_window_ref import overlap_window
 from test_dqn_gpu import oracle_td_update, REF_NET, CFG2_NET, PTOL
 
 pytestmark = pytest.mark.gpu
@@ -179,13 +180,6 @@ def test_the_borrowed_opponent_is_left_as_it_was(xq):
         t.close(); net.close(); twin.close(); probe2.close()
     assert np.array_equal(runs[0][0], runs[1][0]) and np.array_equal(runs[0][1], runs[1][1])
     probe.close()
-
-
-def overlap_window(size, total, cap, m):
-    w = total % cap
-    if size + m < cap:
-        return 0, size
-    return (w + m) % cap, cap - m
 
 
 @pytest.mark.parametrize("n,cap,mb,plies,iters,kind", [(1024, 1 << 14, 1024, 1, 8, "search1"), (256, 4096, 512, 4, 5, "net")])

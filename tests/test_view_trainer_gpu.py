@@ -6,7 +6,7 @@ import pytest
 
 import view_ref as vr
 from test_legal_ring_gpu import ring_rows
-from test_trainer_gpu import overlap_window
+from ring_window_ref import overlap_window
 
 pytestmark = pytest.mark.gpu
 
