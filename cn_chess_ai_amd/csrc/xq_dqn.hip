@@ -201,6 +201,10 @@ struct xq_dqn {
     // layer-0 gradient on the bf16 matrix pipe (xq_l0grad.hip.h): delta_0 as three bf16 planes, transposed [plane][column][sample]
     xq::DevBuf<uint16_t> l0_planes;
     xq::DevBuf<uint16_t> l0_sel;                // selector half-words of the minibatch's boards (xq_l0grad.hip.h)
+    xq::DevBuf<uint16_t> l0_hot;                // the hot-row table (xq_l0hot.h), as built on the host
+    xq::DevBuf<uint16_t> l0_cold_list;          // cold occurrences of the minibatch's boards, per 64 samples, and their counts
+    xq::DevBuf<int> l0_cold_cnt;
+    const xq::L0HotTable* hot() const { return reinterpret_cast<const xq::L0HotTable*>(l0_hot.p); }
     bool l0_split_done = false;                 // this step's layer-0 delta product wrote the planes in its epilogue
     bool l0_sel_done = false;                   // this step's selector words rode in an earlier fused launch
     bool l0_mfma = true;                        // xq_dqn_set_l0_grad_mode (default since round 5: xq_l0grad.hip.h)
@@ -836,6 +840,14 @@ static int l0_chunk_of(int n) { return n >= 16384 ? 2048 : 1024; }
 static int ensure_l0_mfma(xq_dqn* d, int n) {
     const int H = d->L[1], chunk = l0_chunk_of(n), kpad = (n + chunk - 1) / chunk * chunk;
     XQ_TRY(reserve_zeroed(d->l0_planes, l0m_plane_elems(H, kpad), d->cur));     // (the slack behind the planes is read, never used)
+    if (!d->l0_hot.p) {                          // once per handle: the process's table, copied as it stands
+        const L0HotTable& t = l0_hot_table();
+        if (!t.ok) return fail(XQ_ERR_RUNTIME, "hot-row table: the reachable rows do not fit %d groups of %d", kL0HotGroups, kL0HotGroupRows);
+        XQ_TRY(d->l0_hot.reserve(sizeof(L0HotTable) / sizeof(uint16_t)));
+        XQ_HIP(hipMemcpyAsync(d->l0_hot.p, &t, sizeof t, hipMemcpyHostToDevice, d->cur));
+    }
+    XQ_TRY(d->l0_cold_list.reserve(l0cold_elems(kpad)));
+    XQ_TRY(d->l0_cold_cnt.reserve((size_t)kpad / 64));
     return reserve_zeroed(d->l0_sel, l0sel_elems(kpad), d->cur);
 }
 
@@ -1035,7 +1047,8 @@ static int l0_gradient(xq_dqn* d, int n, float* dst, xq_dqn::PendingSlab* defer)
             LaunchNow now(d);                        // launches of their own, in front of the fused launch that is being assembled
             if (!d->l0_sel_done) {                   // (fused TD step of a net with >= 2 hidden layers: rode in the launch before this one)
                 ProfScope ps(d, "l0_sel_words", 0.0, (double)n * 48 + 2.0 * need_sel);
-                hipLaunchKernelGGL(l0_sel_kernel, dim3(kpad / 64), dim3(256), 0, d->cur, d->gboards, n, kpad, d->l0_sel);
+                hipLaunchKernelGGL(l0_sel_kernel, dim3(kpad / 64), dim3(256), 0, d->cur, d->gboards, n, kpad, d->l0_sel, d->hot(), d->l0_cold_list.p,
+                                   d->l0_cold_cnt.p);
             }
             if (!d->l0_split_done) {                 // (whole tiles: the delta product's epilogue wrote the planes)
                 ProfScope ps(d, "l0_delta_split", 8.0 * n * H, (double)n * H * 4 + 6.0 * H * kpad);
@@ -1044,13 +1057,18 @@ static int l0_gradient(xq_dqn* d, int n, float* dst, xq_dqn::PendingSlab* defer)
             d->l0_sel_done = d->l0_split_done = false;
         }
         XQ_HIP(hipGetLastError());
-        const size_t shmem = l0m_lds_bytes();
-        const double fl = 2.0 * 80 * 16 * (double)H * kpad * 3, by = 6.0 * H * kpad + 2.0 * need_sel + 4.0 * nchunks * len;
+        // fused launch: the packed hot rows on the matrix pipe (48 tiles of 16 rows), the cold rows from their lists; alone: all 80 tiles
+        const bool hot = d->tail_open;
+        const size_t shmem = hot ? l0m_lds_bytes<true>() : l0m_lds_bytes<false>();
+        const double fl = 2.0 * (hot ? kL0HotGroups * kL0HotGroupRows : 80 * 16) * (double)H * kpad * 3,
+                     by = 6.0 * H * kpad + 2.0 * need_sel + 4.0 * nchunks * len;
         if (d->tail_open) {
             TailArgs& T = *d->tail;
             T.l0_n = n; T.l0_H = H; T.l0_chunk = chunk; T.l0_nch = nchunks; T.l0_partial = out;
             T.l0_sel = d->l0_sel; T.l0_planes = d->l0_planes; T.l0_plane_stride = plane_stride; T.l0_kpad = kpad; T.l0_ncb = H / kL0mCols;
-            T.n_l0 = 4 * (H / kL0mCols) * nchunks;
+            T.n_l0 = kL0HotGroups * (H / kL0mCols) * nchunks;
+            T.l0_hot = d->hot(); T.l0_cold_list = d->l0_cold_list; T.l0_cold_cnt = d->l0_cold_cnt; T.l0_delta = d->deltas[0];
+            T.n_l0cold = kL0ColdParts * nchunks;
             d->tail_flops += fl; d->tail_bytes += by;
             d->tail_lds = std::max(d->tail_lds, shmem);
         } else {
@@ -1715,7 +1733,7 @@ struct TailGrid {
     int launch(bool last, const char* name) {
         d->tail_open = false;
         const TailArgs& T = *d->tail;
-        const long long total = (long long)T.n_l0 + T.n_grad + T.n_delta + T.n_out + T.n_colsum + T.n_sel;
+        const long long total = (long long)T.n_l0 + T.n_grad + T.n_delta + T.n_out + T.n_colsum + T.n_sel + T.n_l0cold;
         if (total <= 0) return XQ_OK;
         ProfScope ps(d, name, d->tail_flops, d->tail_bytes, true);      // one launch: timed by its own start / stop events
         const auto kern = last ? (T.l0_planes != nullptr ? td_tail_kernel<TAIL_L0 | TAIL_GRAD | TAIL_OUT | TAIL_COLSUM, true>
@@ -1773,6 +1791,7 @@ static int tail_launches(xq_dqn* d, int n, float* const* outs, float* G, int mod
             TailArgs& T = *d->tail;
             const int chunk0 = l0_chunk_of(n), kpad = (n + chunk0 - 1) / chunk0 * chunk0;
             T.sel_boards = d->gboards; T.sel_n = n; T.sel_kpad = kpad; T.sel_out = d->l0_sel; T.n_sel = kpad / 64;
+            T.l0_hot = d->hot(); T.sel_cold_list = d->l0_cold_list; T.sel_cold_cnt = d->l0_cold_cnt;
             d->tail_bytes += (double)n * 48 + 2.0 * l0sel_elems(kpad);
             d->tail_lds = std::max(d->tail_lds, (size_t)64 * 13 * sizeof(uint32_t));
             d->l0_sel_done = true;

@@ -194,15 +194,18 @@ __global__ __launch_bounds__(256) void colsum_final_kernel(ColsumJobs J) {   // 
 // kernel, so the results are bitwise those of the two-stream path (tests/test_dqn_gpu.py).
 enum { TAIL_DELTA = 1, TAIL_GRAD = 2, TAIL_OUT = 4, TAIL_COLSUM = 8, TAIL_L0 = 16, TAIL_SEL = 32 };
 struct TailArgs {
-    // grid order: [l0][grad][delta][out][colsum][sel]; n_* = blocks of each part (0 = absent)
-    int n_l0, n_grad, n_delta, n_out, n_colsum, n_sel;
+    // grid order: [l0][l0 cold rows][grad][delta][out][colsum][sel]; n_* = blocks of each part (0 = absent)
+    int n_l0, n_grad, n_delta, n_out, n_colsum, n_sel, n_l0cold;
     GemmArgs grad;  int grad_gx, grad_gy;          // 64x64 tiles: grid (gx, gy, splits)
     GemmArgs delta; int delta_gx;                  // grid (gx, gy, 1)
     const int32_t* og_act; const float* og_dsc; const float* og_alast; int og_n, og_H, og_chunk; float* og_partial;   // grid (24, chunks)
     const uint32_t* l0_boards; const float* l0_delta; int l0_n, l0_H, l0_HS, l0_chunk, l0_nsets, l0_nch; float* l0_partial;   // (90, nch, H / HS)
-    const uint16_t* l0_planes; long long l0_plane_stride; int l0_kpad, l0_ncb;      // != nullptr: the matrix-pipe form, grid (4, H / 32, nch)
-    const uint16_t* l0_sel;                        // ... and its selector half-words (xq_l0grad.hip.h)
+    const uint16_t* l0_planes; long long l0_plane_stride; int l0_kpad, l0_ncb;      // != nullptr: the matrix-pipe form on the packed hot rows,
+    const uint16_t* l0_sel;                        // grid (3, H / 32, nch) ... and its selector half-words (xq_l0grad.hip.h)
+    const L0HotTable* l0_hot;                      // hot / cold rows (xq_l0hot.h); the cold rows: (kL0ColdParts, nch) blocks behind the hot ones
+    const uint16_t* l0_cold_list; const int* l0_cold_cnt;
     const uint32_t* sel_boards; int sel_n, sel_kpad; uint16_t* sel_out;             // TAIL_SEL: those half-words being made, 64 samples per block
+    uint16_t* sel_cold_list; int* sel_cold_cnt;    // ... with the cold-occurrence lists
     ColsumJobs cj; int cj_gx, cj_gy;               // grid (gx, R, njobs)
 };
 // L0MFMA: the layer-0 blocks are the matrix-pipe form (xq_dqn_set_l0_grad_mode(1)) — an instantiation of its own: that body needs 180
@@ -222,10 +225,10 @@ __global__ __launch_bounds__(256) void td_tail_kernel(const TailArgs a) {
                 // ... unless the chunks themselves go round the XCDs (8 | chunks): the CHUNK is then the fastest index, XCD x keeps to the planes
                 // AND the selector words of its own chunks (1.6 + 0.4 MB of 12.6 + 3.1), nothing is read by two XCDs — with the column block
                 // fastest every XCD read all the selector words (25 MB per launch instead of 3.1)
-                int rest = b / a.l0_ncb, cb = b % a.l0_ncb, sqg = rest & 3, ch = rest >> 2;
+                int rest = b / a.l0_ncb, cb = b % a.l0_ncb, sqg = rest % kL0HotGroups, ch = rest / kL0HotGroups;
                 if ((a.l0_nch & 7) == 0) { ch = b % a.l0_nch; rest = b / a.l0_nch; cb = rest % a.l0_ncb; sqg = rest / a.l0_ncb; }
-                l0_grad_mfma_block<0>(a.l0_sel, a.l0_planes, a.l0_plane_stride, a.l0_kpad, a.l0_H, a.l0_chunk, a.l0_partial, sqg, cb, ch,
-                                       reinterpret_cast<unsigned char*>(tail_smem));
+                l0_grad_mfma_block<0, true>(a.l0_sel, a.l0_planes, a.l0_plane_stride, a.l0_kpad, a.l0_H, a.l0_chunk, a.l0_partial, sqg, cb, ch,
+                                             reinterpret_cast<unsigned char*>(tail_smem), a.l0_hot);
                 return;
             }
             const int per = kSquares * a.l0_nch;
@@ -233,6 +236,14 @@ __global__ __launch_bounds__(256) void td_tail_kernel(const TailArgs a) {
             return;
         }
         b -= a.n_l0;
+        if (L0MFMA) {                             // the rows the matrix-pipe blocks above leave out: short blocks (stores of zeros, in play)
+            if (b < a.n_l0cold) {
+                l0_cold_block(a.l0_hot, a.l0_cold_list, a.l0_cold_cnt, a.l0_delta, a.l0_H, a.l0_chunk, a.l0_partial, b / kL0ColdParts,
+                              b % kL0ColdParts, kL0ColdParts);
+                return;
+            }
+            b -= a.n_l0cold;
+        }
     }
     if (KINDS & TAIL_GRAD) {
         if (b < a.n_grad) {
@@ -267,7 +278,11 @@ __global__ __launch_bounds__(256) void td_tail_kernel(const TailArgs a) {
         b -= a.n_colsum;
     }
     if (KINDS & TAIL_SEL) {
-        if (b < a.n_sel) l0_sel_block(a.sel_boards, a.sel_n, a.sel_kpad, a.sel_out, b, reinterpret_cast<uint32_t*>(tail_smem));
+        if (b < a.n_sel) {
+            l0_sel_block(a.sel_boards, a.sel_n, a.sel_kpad, a.sel_out, b, reinterpret_cast<uint32_t*>(tail_smem), a.l0_hot, a.sel_cold_list,
+                         a.sel_cold_cnt);
+            return;
+        }
     }
 }
 

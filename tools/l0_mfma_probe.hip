@@ -40,7 +40,7 @@ int main(int argc, char** argv) {
     auto grant = [&](auto kern) { CK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024)); };
     grant(l0_grad_mfma_kernel<0>); grant(l0_grad_mfma_kernel<1>); grant(l0_grad_mfma_kernel<2>); grant(l0_grad_mfma_kernel<3>);
     grant(l0_grad_mfma_kernel<4>); grant(l0_grad_mfma_kernel<6>);
-    auto selk = [&] { hipLaunchKernelGGL(l0_sel_kernel, dim3(kpad / 64), dim3(256), 0, 0, dB, n, kpad, dS); };
+    auto selk = [&] { hipLaunchKernelGGL(l0_sel_kernel, dim3(kpad / 64), dim3(256), 0, 0, dB, n, kpad, dS, nullptr, nullptr, nullptr); };
     auto split = [&] { hipLaunchKernelGGL(delta_split_kernel, dim3(kpad / 64, H / 64), dim3(256), 0, 0, dD, n, H, dP, plane_stride, kpad); };
     auto mfma = [&] { hipLaunchKernelGGL(l0_grad_mfma_kernel<0>, dim3(H / kL0mCols, 4, nch), dim3(256), lds, 0, dS, dP, plane_stride, kpad, H, chunk, dOut); };
     selk(); split(); mfma(); CK(hipDeviceSynchronize());
