@@ -24,6 +24,7 @@ LOSS_SQUARED, LOSS_HUBER = 0, 1
 BOOTSTRAP_ALL, BOOTSTRAP_LEGAL = 0, 1
 VIEW_ABSOLUTE, VIEW_MOVER = 0, 1
 REWARD_EVALUATE, REWARD_DELTA = 0, 1
+POLICY_GREEDY, POLICY_BOLTZMANN = 0, 1
 MAX_N_STEP = 8
 ORDER_RING_CONTENTS, ORDER_RING_PRIORITIES, ORDER_RING_DRAW, ORDER_TRAINER_PARAMS, ORDER_ALL = 1, 2, 4, 8, 15
 
@@ -267,6 +268,13 @@ PROTOTYPES = {
     "xq_arena_live": [_vp, _pi],
     "xq_arena_env": [_vp, _pvp],
     "xq_arena_last_step": [_vp, C.POINTER(StepResult)],
+    "xq_env_set_policy": [_vp, _i, _d],
+    "xq_env_get_policy": [_vp, _pi, _pd],
+    "xq_trainer_set_policy": [_vp, _i, _d],
+    "xq_trainer_set_epsilon": [_vp, _d],
+    "xq_trainer_get_epsilon": [_vp, _pd],
+    "xq_arena_set_temperature": [_vp, _d, _d],
+    "xq_arena_get_temperature": [_vp, _pd, _pd],
 }
 # bound when the loaded library has them: an older build given through XQ_LIBXQHIP (same-box A/B) still imports, and a call
 # of one of these on it raises XqError instead
@@ -299,8 +307,11 @@ LAZY_ZERO_SUM = frozenset(("xq_dqn_set_zero_sum", "xq_dqn_get_zero_sum", "xq_tra
 LAZY_VIEW = frozenset(("xq_dqn_set_view", "xq_dqn_get_view", "xq_view_boards_dev", "xq_dqn_last_view", "xq_replay_track_mover",
                        "xq_replay_push_host_sides", "xq_replay_get_mover", "xq_env_set_q_view", "xq_env_get_q_view", "xq_trainer_set_view",
                        "xq_arena_ply_q_dev_view"))
+# ... and those of the exploration policy
+LAZY_POLICY = frozenset(("xq_env_set_policy", "xq_env_get_policy", "xq_trainer_set_policy", "xq_trainer_set_epsilon",
+                         "xq_trainer_get_epsilon", "xq_arena_set_temperature", "xq_arena_get_temperature"))
 _LAZY_ALL = (LAZY | LAZY_GRAD_CLIP | LAZY_TARGET_TAU | LAZY_TD_LOSS | LAZY_N_STEP | LAZY_MIRROR | LAZY_LEGAL | LAZY_REWARD
-             | LAZY_COLOUR_SWAP | LAZY_ZERO_SUM | LAZY_VIEW)
+             | LAZY_COLOUR_SWAP | LAZY_ZERO_SUM | LAZY_VIEW | LAZY_POLICY)
 _RESTYPES = {"xq_last_error": C.c_char_p, "xq_env_boards_dev": C.c_void_p, "xq_env_meta_dev": C.c_void_p}
 
 _lib = None

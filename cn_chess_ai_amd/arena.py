@@ -96,6 +96,17 @@ class Arena:
     def reset(self, opening_plies=8):
         call("xq_arena_reset", self._h, int(opening_plies))
 
+    def set_temperature(self, temp_a=0.0, temp_b=0.0):
+        """A Boltzmann temperature per player (DESIGN.md §4 "Exploration policy"), 0 = greedy, else in [1e-3, 1e3]: network players and
+        caller-supplied rows draw their non-epsilon plies from the softmax of the legal moves' values; random and search players and
+        the opening are untouched.  Survives reset()."""
+        call("xq_arena_set_temperature", self._h, float(temp_a), float(temp_b))
+
+    def temperature(self):
+        a, b = C.c_double(), C.c_double()
+        call("xq_arena_get_temperature", self._h, C.byref(a), C.byref(b))
+        return a.value, b.value
+
     def ply_q_dev(self, q_dev, q_stride=96, eps_a=0.0, eps_b=0.0, view_a=False, view_b=False):
         """One ply with caller Q rows: q_dev = device pointer (int) or a cuda torch tensor [2P][>= 90], None = random.  view_a / view_b:
         that player's rows are in the mover's view (computed on view_boards' boards)."""

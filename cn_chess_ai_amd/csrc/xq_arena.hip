@@ -25,6 +25,7 @@ struct xq_arena {
     xq::DevBuf<int16_t> pick;               // [2 pairs] the search players' move indices of the ply (xq_search.hip)
     xq::DevBuf<uint32_t> view;              // [2 pairs][12] the boards as a mover-view net player reads them (allocated with the first one)
     xq::Event ev_env, ev_q[2], ev_view[2];  // ev_view: behind the staging of a half's view boards
+    double temp[2] = {0.0, 0.0};            // Boltzmann temperature of A and B (xq_arena_set_temperature; 0 = greedy), kept over a reset
 };
 
 namespace xq {
@@ -86,16 +87,19 @@ int mover_of_half(const xq_arena* a, int h) { return ((a->ply & 1) ^ h) == 0 ? 0
 int launch_ply(xq_arena* a, const float* q, int q_stride, const CheckedPlayer pl[2]) {
     uint32_t e[2];
     int hq[2], pick_on[2], q_view[2];
+    float it[2];
     for (int h = 0; h < 2; ++h) {
         const CheckedPlayer& p = pl[mover_of_half(a, h)];
         e[h] = p.eps_u32;
         hq[h] = p.kind == XQ_PLAYER_NET ? 1 : 0;
         q_view[h] = hq[h] && p.view;
+        const double temp = a->temp[mover_of_half(a, h)];
+        it[h] = hq[h] && temp != 0.0 ? temperature_to_inv(temp) : 0.f;
         pick_on[h] = p.kind == XQ_PLAYER_SEARCH && a->ply >= a->opening ? 1 : 0;
         if (pick_on[h])      // the searching half's picks, on the arena's stream right ahead of the ply (frozen games are skipped)
             XQ_TRY(search_pick_launch(a->env, p.depth, h * a->pairs, a->pairs, a->pairs, false, e[h], a->pick, a->env->stream));
     }
-    XQ_TRY(env_arena_launch(a->env, q, q_stride, a->pairs, a->opening, e, hq, a->rec, a->live, a->results, a->pick, pick_on, q_view));
+    XQ_TRY(env_arena_launch(a->env, q, q_stride, a->pairs, a->opening, e, hq, a->rec, a->live, a->results, a->pick, pick_on, q_view, it));
     a->ply += 1;
     return XQ_OK;
 }
@@ -210,6 +214,21 @@ int xq_arena_ply_q_dev_view(xq_arena* a, const float* q_dev, int q_stride, doubl
     pl[1].eps_u32 = eps_to_u32(eps_b);
     pl[0].view = view_a; pl[1].view = view_b;
     return launch_ply(a, q_dev, q_stride, pl);
+}
+
+int xq_arena_set_temperature(xq_arena* a, double temp_a, double temp_b) {
+    if (!a) return fail(XQ_ERR_INVALID_ARGUMENT, "null arena");
+    if (!(temp_a == 0.0 || temperature_ok(temp_a)) || !(temp_b == 0.0 || temperature_ok(temp_b)))
+        return fail(XQ_ERR_INVALID_ARGUMENT, "xq_arena_set_temperature: a temperature is 0 (greedy) or in [1e-3, 1e3] as fp32");
+    a->temp[0] = temp_a;
+    a->temp[1] = temp_b;
+    return XQ_OK;
+}
+int xq_arena_get_temperature(const xq_arena* a, double* temp_a, double* temp_b) {
+    if (!a) return fail(XQ_ERR_INVALID_ARGUMENT, "null arena");
+    if (temp_a) *temp_a = a->temp[0];
+    if (temp_b) *temp_b = a->temp[1];
+    return XQ_OK;
 }
 
 int xq_arena_run_players(xq_arena* a, const xq_arena_player* pa, const xq_arena_player* pb, int max_plies, int* plies_played) {

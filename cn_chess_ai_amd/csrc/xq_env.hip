@@ -68,6 +68,10 @@ struct EnvParams {
     // the value of the destination `to` is output swap(to) = to + 81 - 18 (to div 9).  Arena: per half, like arena_has_q
     int q_view;
     int arena_q_view[2];
+    // Boltzmann policy (xq_env_set_policy, DESIGN.md §4 "Exploration policy"): (float)(1 / T) for the plies that read Q rows and did not
+    // take the epsilon branch, 0 = first maximum.  Versus: the learner's phase only.  Arena: per half, like arena_eps
+    float inv_temp;
+    float arena_inv_temp[2];
 };
 
 __constant__ uint32_t c_start_words[kBoardWords];
@@ -94,8 +98,10 @@ __device__ __forceinline__ float delta_reward(int delta, float scale, float cost
     return fminf(fmaxf(r, -bound), bound);
 }
 
-template <int MODE>
-__global__ __launch_bounds__(256) void env_kernel(EnvParams P) {
+// The wave program of both kernels below.  BOLTZ: with the Boltzmann draw in its pick — env_kernel_boltzmann, launched only when a launch
+// carries an inverse temperature; env_kernel, the never-asked kernel, holds no instruction of it and keeps its name in a trace
+template <int MODE, bool BOLTZ>
+__device__ __forceinline__ void env_wave(const EnvParams P) {
     __shared__ WaveSlab slabs[4];
     // everything per game is wave-uniform: keeping the wave index, the game index and the meta record in SGPRs lets the compiler
     // run the bookkeeping and all ten Philox rounds on the scalar unit instead of on 64 identical lanes
@@ -193,6 +199,7 @@ __global__ __launch_bounds__(256) void env_kernel(EnvParams P) {
     // ---- choose the action ---------------------------------------------------------------------------------
     int from = 0, to = 0, n_moves = 0, action_code = -1;
     bool have_action = false, valid = false, explored = false;
+    bool boltzmann_moved = false;                                   // a Boltzmann draw picked another move than the first maximum
     const int mover = player;
 
     if (MODE == MODE_SELFPLAY || MODE == MODE_ARENA || MODE == MODE_VERSUS) {
@@ -270,6 +277,32 @@ __global__ __launch_bounds__(256) void env_kernel(EnvParams P) {
                 } else {
                     const unsigned long long b = __ballot(lane < n_moves && v0 == ma);
                     idx = b ? (__ffsll((long long)b) - 1) : 0;                 // all -inf: validActions[0] (dqn.cpp:40)
+                }
+                // Boltzmann draw (xq_env_set_policy, DESIGN.md §4 "Exploration policy", tests/boltzmann_ref.py): w = exp((v - max) / T) over
+                // the list, the first move whose running sum passes u * total on word 2 of the ply's Philox block (no other draw reads it).
+                // A maximum that is not finite leaves the first-maximum pick above.  (v - max) * it is a difference and a product rounded
+                // once each: this file is built with -ffp-contract=off
+                const float inv_temp = !BOLTZ ? 0.f : MODE == MODE_ARENA ? P.arena_inv_temp[arena_half] : P.inv_temp;
+                const float mx = fmaxf(ma, mb);
+                if (BOLTZ && inv_temp > 0.f && fabsf(mx) < __builtin_inff()) { // (wave-uniform)
+                    const float w0 = v0 == NEG ? 0.f : expf((v0 - mx) * inv_temp);
+                    const float c0 = wave_inclusive_scan_f32(w0);
+                    float total = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(c0), 63));
+                    float w1 = 0.f, c1 = 0.f;
+                    if (n_moves > 64) {                                        // (wave-uniform) moves 64..127 continue the first total
+                        w1 = v1 == NEG ? 0.f : expf((v1 - mx) * inv_temp);
+                        c1 = wave_inclusive_scan_f32(w1) + total;
+                        total = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(c1), 63));
+                    }
+                    const float thr = (float)(r.v[2] >> 8) * 0x1p-24f * total;
+                    const unsigned long long h0 = __ballot(w0 > 0.f && c0 > thr), h1 = __ballot(w1 > 0.f && c1 > thr);
+                    const unsigned long long p0 = __ballot(w0 > 0.f), p1 = __ballot(w1 > 0.f);
+                    int pick;
+                    if (h0) pick = __ffsll((long long)h0) - 1;
+                    else if (h1) pick = 64 + __ffsll((long long)h1) - 1;
+                    else pick = p1 ? 127 - __clzll((long long)p1) : 63 - __clzll((long long)p0);   // rounding left none: the last w > 0
+                    boltzmann_moved = pick != idx;
+                    idx = pick;
                 }
             }
             action_code = __builtin_amdgcn_readfirstlane((int)S.moves[idx]);
@@ -357,7 +390,7 @@ __global__ __launch_bounds__(256) void env_kernel(EnvParams P) {
         r.done = done ? 1 : 0;
         r.terminated = terminated ? 1 : 0;
         r.winner = (uint8_t)winner;
-        r.explored = explored ? 1 : 0;
+        r.explored = explored ? 1 : boltzmann_moved ? 2 : 0;
         r.move_count = (uint16_t)move_count;
         r.red_score = (int16_t)red;
         r.black_score = (int16_t)black;
@@ -480,6 +513,11 @@ __global__ __launch_bounds__(256) void env_kernel(EnvParams P) {
                                plies, episodes);
 }
 
+template <int MODE>
+__global__ __launch_bounds__(256) void env_kernel(EnvParams P) { env_wave<MODE, false>(P); }
+template <int MODE>
+__global__ __launch_bounds__(256) void env_kernel_boltzmann(EnvParams P) { env_wave<MODE, true>(P); }
+
 // isValidMove for all 90x90 pairs of one game (parity tests of E4-E11 through the validator path)
 __global__ __launch_bounds__(256) void valid_matrix_kernel(const uint32_t* boards, int g, uint8_t* out) {
     __shared__ uint8_t sq[96];
@@ -567,6 +605,9 @@ static EnvParams base_params(xq_env* e) {
     return P;
 }
 
+// the env's policy as the kernel takes it: (float)(1 / T) formed in double, 0 = greedy
+static float env_inv_temp(const xq_env* e) { return e->policy_kind == XQ_POLICY_BOLTZMANN ? temperature_to_inv(e->temperature) : 0.f; }
+
 // The Q values of a launch: finished rows q90_dev, or the k-slabs of the select head (qs && qs->slabs) for the kernel to finish
 static int set_q_source(EnvParams& P, const float* q90_dev, int q_stride, const QSource* qs) {
     P.q90 = q90_dev;
@@ -594,11 +635,13 @@ int env_selfplay_launch(xq_env* e, const float* q90_dev, int q_stride, uint32_t 
     P.eps_u32 = eps_u32;
     P.results = results_dev;
     P.q_view = e->q_view;
+    P.inv_temp = env_inv_temp(e);
     if (replay != nullptr) XQ_TRY(set_ring(P, replay));
     const int blocks = (e->n + 3) / 4;
     if (replay != nullptr) XQ_TRY(replay_writer_begin(replay, on ? on : e->stream));    // (costs nothing when the ring's users share this stream)
-    if (ev_start || ev_stop) hipExtLaunchKernelGGL(env_kernel<MODE_SELFPLAY>, dim3(blocks), dim3(256), 0, on ? on : e->stream, ev_start, ev_stop, 0, P);
-    else hipLaunchKernelGGL(env_kernel<MODE_SELFPLAY>, dim3(blocks), dim3(256), 0, on ? on : e->stream, P);
+    const auto kernel = P.inv_temp > 0.f ? env_kernel_boltzmann<MODE_SELFPLAY> : env_kernel<MODE_SELFPLAY>;
+    if (ev_start || ev_stop) hipExtLaunchKernelGGL(kernel, dim3(blocks), dim3(256), 0, on ? on : e->stream, ev_start, ev_stop, 0, P);
+    else hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), 0, on ? on : e->stream, P);
     XQ_HIP(hipGetLastError());
     if (replay != nullptr) replay_advance(replay, e->n);
     return XQ_OK;
@@ -608,7 +651,7 @@ int env_selfplay_launch(xq_env* e, const float* q90_dev, int q_stride, uint32_t 
 // whose pick_on is set; nothing else of the env is touched
 int env_arena_launch(xq_env* e, const float* q90_dev, int q_stride, int pairs, int opening, const uint32_t eps_u32[2], const int has_q[2],
                      xq_arena_game* records_dev, int* live_dev, xq_step_result* results_dev, const int16_t* pick_dev, const int pick_on[2],
-                     const int q_view[2]) {
+                     const int q_view[2], const float inv_temp[2]) {
     EnvParams P = base_params(e);
     P.ep_ring = nullptr;                  // no episode records, no stats, no replay: an arena game ends once and stays as it ended
     P.q90 = q90_dev;
@@ -621,11 +664,13 @@ int env_arena_launch(xq_env* e, const float* q90_dev, int q_stride, int pairs, i
         P.arena_pick_on[h] = pick_on[h] && pick_dev != nullptr;
         P.arena_has_q[h] = has_q[h] && q90_dev != nullptr && !P.arena_pick_on[h];
         P.arena_q_view[h] = q_view != nullptr && q_view[h] != 0;
+        P.arena_inv_temp[h] = inv_temp != nullptr && P.arena_has_q[h] ? inv_temp[h] : 0.f;
     }
     P.arena_pick = pick_dev;
     P.arena_rec = records_dev;
     P.arena_live = live_dev;
-    hipLaunchKernelGGL(env_kernel<MODE_ARENA>, dim3((e->n + 3) / 4), dim3(256), 0, e->stream, P);
+    const auto kernel = P.arena_inv_temp[0] > 0.f || P.arena_inv_temp[1] > 0.f ? env_kernel_boltzmann<MODE_ARENA> : env_kernel<MODE_ARENA>;
+    hipLaunchKernelGGL(kernel, dim3((e->n + 3) / 4), dim3(256), 0, e->stream, P);
     XQ_HIP(hipGetLastError());
     return XQ_OK;
 }
@@ -642,11 +687,13 @@ int env_versus_launch(xq_env* e, int phase, const float* q90_dev, int q_stride, 
     P.eps_u32 = eps_u32;
     P.vs_phase = phase;
     P.q_view = phase == 1 ? e->q_view : opponent_view;
+    P.inv_temp = phase == 1 ? env_inv_temp(e) : 0.f;       // the opponent's plies stay epsilon-greedy
     P.vs_pick = phase == 1 ? nullptr : pick_dev;
     P.vs_counts = counts_dev;
     hipStream_t s = on ? on : e->stream;
     if (phase == 0) XQ_TRY(replay_writer_begin(replay, s));
-    hipLaunchKernelGGL(env_kernel<MODE_VERSUS>, dim3((e->n + 3) / 4), dim3(256), 0, s, P);
+    const auto kernel = P.inv_temp > 0.f ? env_kernel_boltzmann<MODE_VERSUS> : env_kernel<MODE_VERSUS>;
+    hipLaunchKernelGGL(kernel, dim3((e->n + 3) / 4), dim3(256), 0, s, P);
     XQ_HIP(hipGetLastError());
     return XQ_OK;
 }
@@ -930,6 +977,20 @@ int xq_env_set_q_view(xq_env* e, int on) {
 int xq_env_get_q_view(const xq_env* e, int* on) {
     if (!e || !on) return fail(XQ_ERR_INVALID_ARGUMENT, "null pointer");
     *on = e->q_view;
+    return XQ_OK;
+}
+int xq_env_set_policy(xq_env* e, int kind, double temperature) {
+    if (!e) return fail(XQ_ERR_INVALID_ARGUMENT, "null env");
+    if (kind != XQ_POLICY_GREEDY && kind != XQ_POLICY_BOLTZMANN) return fail(XQ_ERR_INVALID_ARGUMENT, "xq_env_set_policy: unknown kind %d", kind);
+    if (!temperature_ok(temperature)) return fail(XQ_ERR_INVALID_ARGUMENT, "xq_env_set_policy: temperature must be in [1e-3, 1e3] as fp32");
+    e->policy_kind = kind;
+    e->temperature = temperature;
+    return XQ_OK;
+}
+int xq_env_get_policy(const xq_env* e, int* kind, double* temperature) {
+    if (!e) return fail(XQ_ERR_INVALID_ARGUMENT, "null env");
+    if (kind) *kind = e->policy_kind;
+    if (temperature) *temperature = e->temperature;
     return XQ_OK;
 }
 int xq_env_set_reward(xq_env* e, int kind, double scale, double ply_cost, double bound) {

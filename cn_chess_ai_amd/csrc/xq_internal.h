@@ -282,6 +282,9 @@ struct xq_env {
     double rw_scale = 1e-3, rw_cost = 0.0, rw_bound = 1.0;
     // the Q rows handed to the self-play and versus-learner launches are in the mover's view (xq_env_set_q_view)
     int q_view = 0;
+    // how a ply that reads Q rows and did not explore picks its move (xq_env_set_policy); GREEDY keeps the last temperature unused
+    int policy_kind = XQ_POLICY_GREEDY;
+    double temperature = 1.0;
 };
 
 namespace xq {
@@ -424,8 +427,9 @@ int env_selfplay_launch(xq_env* env, const float* q90_dev, int q_stride, uint32_
                         hipEvent_t ev_stop = nullptr);      // ev_*: the kernel's own start / stop events (profiler, kernel-exact timing)
 int env_arena_launch(xq_env* env, const float* q90_dev, int q_stride, int pairs, int opening, const uint32_t eps_u32[2],
                      const int has_q[2], xq_arena_game* records_dev, int* live_dev, xq_step_result* results_dev,
-                     const int16_t* pick_dev, const int pick_on[2], const int q_view[2] = nullptr);   // xq_arena.hip; q_view: per half, the
-                                                                                                     // rows are in the mover's view
+                     const int16_t* pick_dev, const int pick_on[2], const int q_view[2] = nullptr,    // xq_arena.hip; q_view: per half, the
+                     const float inv_temp[2] = nullptr);                                              // rows are in the mover's view;
+                                                                                                     // inv_temp: per half, 0 = greedy
 void dqn_shape(const xq_dqn* d, int* n_in, int* n_out);    // layer_sizes[0], outputs
 constexpr uint32_t kMetaFrozen = 1u << 20;                  // meta.x flag of a finished arena game (xq_env.hip META_FROZEN)
 constexpr uint32_t kMetaVsDone = 1u << 21;                  // meta.x flag: the game's versus slot of this collect is written (META_VS_DONE)
@@ -442,6 +446,10 @@ int search_pick_launch(xq_env* env, int depth, int first, int count, int pairs, 
 // ---- a player that moves on an env: the arena's two sides and the trainer's opponent (defined in xq_arena.hip) ----------------------
 // floor(eps * 2^32), saturated: the threshold the env kernel holds a Philox word against (vecenv.eps_to_u32 is the Python mirror)
 inline uint32_t eps_to_u32(double eps) { return (uint32_t)std::min(std::max(eps, 0.0) * 4294967296.0, 4294967295.0); }
+// A Boltzmann temperature (xq_env_set_policy, xq_arena_set_temperature) is held on its fp32 value: finite and in [1e-3, 1e3]; every
+// comparison is false for a NaN.  The kernel takes (float)(1 / T), formed in double
+inline bool temperature_ok(double t) { const float f = (float)t; return f >= 1e-3f && f <= 1e3f; }
+inline float temperature_to_inv(double t) { return (float)(1.0 / t); }
 struct CheckedPlayer {
     int kind = XQ_PLAYER_RANDOM;
     xq_dqn* net = nullptr;      // XQ_PLAYER_NET: borrowed

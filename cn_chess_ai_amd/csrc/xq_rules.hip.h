@@ -102,6 +102,18 @@ __device__ __forceinline__ int wave_inclusive_scan(int v) {           // inclusi
     v += dpp_int<0x143, 0xc>(0, v);      // row_bcast:31 into rows 2 and 3
     return v;
 }
+// The same network on floats (+0.0 is the identity: a lane without a source adds it exactly).  Lane i's sum is associated as the network
+// associates it, not left to right: the Boltzmann pick's band (DESIGN.md §4 "Exploration policy") covers the difference.
+__device__ __forceinline__ float wave_inclusive_scan_f32(float v) {
+    auto step = [&](int t) { v = v + __int_as_float(t); };
+    step(dpp_int<0x111, 0xf>(0, __float_as_int(v)));
+    step(dpp_int<0x112, 0xf>(0, __float_as_int(v)));
+    step(dpp_int<0x114, 0xf>(0, __float_as_int(v)));
+    step(dpp_int<0x118, 0xf>(0, __float_as_int(v)));
+    step(dpp_int<0x142, 0xa>(0, __float_as_int(v)));
+    step(dpp_int<0x143, 0xc>(0, __float_as_int(v)));
+    return v;
+}
 __device__ __forceinline__ int wave_sum(int v) {                      // total, wave-uniform (lane 63 of the scan)
     return __builtin_amdgcn_readlane(wave_inclusive_scan(v), 63);
 }

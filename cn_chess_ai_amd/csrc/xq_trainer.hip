@@ -314,6 +314,25 @@ int xq_trainer_set_reward(xq_trainer* t, int kind, double scale, double ply_cost
     return xq_env_set_reward(t->env, kind, scale, ply_cost, bound);
 }
 
+// The policy and the epsilon of the collects.  A launch carries both by value, so either may change between any two collects, with a
+// collect of the overlap stream still in flight too: that one keeps what it was queued with
+int xq_trainer_set_policy(xq_trainer* t, int kind, double temperature) {
+    if (!t) return fail(XQ_ERR_INVALID_ARGUMENT, "null trainer");
+    return xq_env_set_policy(t->env, kind, temperature);
+}
+int xq_trainer_set_epsilon(xq_trainer* t, double eps) {
+    if (!t) return fail(XQ_ERR_INVALID_ARGUMENT, "null trainer");
+    if (!(eps >= 0.0 && eps <= 1.0)) return fail(XQ_ERR_INVALID_ARGUMENT, "xq_trainer_set_epsilon: eps must be in [0, 1]");
+    t->cfg.epsilon = eps;
+    t->eps_u32 = eps_to_u32(eps);
+    return XQ_OK;
+}
+int xq_trainer_get_epsilon(const xq_trainer* t, double* eps) {
+    if (!t || !eps) return fail(XQ_ERR_INVALID_ARGUMENT, "null pointer");
+    *eps = t->cfg.epsilon;
+    return XQ_OK;
+}
+
 int xq_trainer_set_mirror(xq_trainer* t, double prob) {
     XQ_TRY(between_iterations(t, "xq_trainer_set_mirror"));
     return xq_replay_set_mirror(t->replay, prob);

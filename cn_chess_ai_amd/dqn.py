@@ -9,7 +9,7 @@ import numpy as np
 
 from . import _capi
 from ._capi import call, KernelStat, KernelSpan, TrainerConfig as _CConfig
-from .vecenv import VecEnv, ReplayBuffer, _ptr, reward_kind
+from .vecenv import VecEnv, ReplayBuffer, _ptr, reward_kind, policy_kind
 from .arena import Search, player
 
 REFERENCE_LAYERS = (1260, 128, 8100)     # ChessAI::initializeDQN, chessai.cpp:395-404
@@ -750,6 +750,24 @@ class Trainer:
         or "delta" (the transition's change of material balance, scaled, less ply_cost, clamped to +-bound).  The next collect writes
         it; slots already in the ring keep theirs.  Call between iterations."""
         call("xq_trainer_set_reward", self._h, reward_kind(kind), float(scale), float(ply_cost), float(bound))
+
+    def set_policy(self, kind, temperature=1.0):
+        """VecEnv.set_policy on the trainer's env (DESIGN.md §4 "Exploration policy"): "greedy" (the default) or "boltzmann" at
+        `temperature`.  The next collect picks by it; versus training: the learner only."""
+        call("xq_trainer_set_policy", self._h, policy_kind(kind), float(temperature))
+
+    def set_epsilon(self, eps):
+        """The exploration rate of the collects from the next one queued on (TrainerConfig.epsilon), 0 <= eps <= 1; legal between any
+        two collects.  Versus training: the learner's epsilon."""
+        eps = float(eps)
+        if not 0.0 <= eps <= 1.0:
+            raise ValueError(f"set_epsilon: eps must lie in [0, 1], got {eps!r}")
+        call("xq_trainer_set_epsilon", self._h, eps)
+
+    def epsilon(self):
+        v = C.c_double()
+        call("xq_trainer_get_epsilon", self._h, C.byref(v))
+        return v.value
 
     def set_opponent(self, opponent):
         """Train against a fixed opponent from the next collect on (DESIGN.md §4 "Versus training"): None = self-play (the default),

@@ -51,6 +51,18 @@ def reward_kind(kind):
     return int(kind)
 
 
+POLICY_KINDS = {"greedy": _capi.POLICY_GREEDY, "boltzmann": _capi.POLICY_BOLTZMANN}
+
+
+def policy_kind(kind):
+    """"greedy" / "boltzmann" -> XQ_POLICY_*; an int passes as it is (the library refuses an unknown one)."""
+    if isinstance(kind, str):
+        if kind not in POLICY_KINDS:
+            raise ValueError(f"set_policy: expected 'greedy' or 'boltzmann', got {kind!r}")
+        return POLICY_KINDS[kind]
+    return int(kind)
+
+
 class ReplayBuffer:
     """ReplayBuffer{capacity; push(s,a,r,s',done); sample(B)} — element = the 5-tuple of DQN::train (dqn.cpp:157)."""
 
@@ -385,6 +397,20 @@ class VecEnv:
         call("xq_env_get_reward", self._h, C.byref(k), C.byref(s), C.byref(c), C.byref(b))
         names = {v: n for n, v in REWARD_KINDS.items()}
         return names[k.value], s.value, c.value, b.value
+
+    # ---- exploration policy (build-defined, DESIGN.md §4 "Exploration policy") ----
+    def set_policy(self, kind, temperature=1.0):
+        """How a ply that reads Q rows and did not take the epsilon branch picks: "greedy" = the first maximum (the default), or
+        "boltzmann" = a softmax draw over the legal moves' values at `temperature` in [1e-3, 1e3] (tests/boltzmann_ref.py is the rule).
+        Takes effect at the next selfplay_step*; a step result's `explored` is 2 where the draw left the first maximum."""
+        call("xq_env_set_policy", self._h, policy_kind(kind), float(temperature))
+
+    def policy(self):
+        """(kind, temperature) as last set; ("greedy", 1.0) on an env that was never asked."""
+        k, t = C.c_int32(), C.c_double()
+        call("xq_env_get_policy", self._h, C.byref(k), C.byref(t))
+        names = {v: n for n, v in POLICY_KINDS.items()}
+        return names[k.value], t.value
 
     def drain_episodes(self, max_records=65536):
         rec = np.zeros(max_records, dtype=EPISODE_DTYPE)

@@ -12,6 +12,8 @@
 //   --seed S        Philox key of the games (default 1)
 //   --opening K     uniform-random opening plies, shared by the two games of a pair (default 8)
 //   --eps-a E, --eps-b E   exploration of each player (default 0: greedy)
+//   --temp-a T, --temp-b T Boltzmann temperature of each player in [1e-3, 1e3] (default 0: greedy; model players only, DESIGN.md §4
+//                   "Exploration policy")
 //   --json          one JSON line instead of the text summary
 #include <cstdio>
 #include <cstdlib>
@@ -65,7 +67,7 @@ int main(int argc, char** argv) {
     std::vector<std::string> pos;
     unsigned long long seed = 1;
     int opening = 8;
-    double eps_a = 0.0, eps_b = 0.0;
+    double eps_a = 0.0, eps_b = 0.0, temp_a = 0.0, temp_b = 0.0;
     bool json = false;
     for (int i = 1; i < argc; ++i) {
         const bool more = i + 1 < argc;
@@ -73,11 +75,13 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--opening") && more) opening = std::atoi(argv[++i]);
         else if (!std::strcmp(argv[i], "--eps-a") && more) eps_a = std::atof(argv[++i]);
         else if (!std::strcmp(argv[i], "--eps-b") && more) eps_b = std::atof(argv[++i]);
+        else if (!std::strcmp(argv[i], "--temp-a") && more) temp_a = std::atof(argv[++i]);
+        else if (!std::strcmp(argv[i], "--temp-b") && more) temp_b = std::atof(argv[++i]);
         else if (!std::strcmp(argv[i], "--json")) json = true;
         else pos.push_back(argv[i]);
     }
     if (pos.size() < 2) {
-        std::fprintf(stderr, "usage: %s MODEL_A|random|searchD MODEL_B|random|searchD [pairs] [--seed S] [--opening K] [--eps-a E] [--eps-b E] [--json]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s MODEL_A|random|searchD MODEL_B|random|searchD [pairs] [--seed S] [--opening K] [--eps-a E] [--eps-b E] [--temp-a T] [--temp-b T] [--json]\n", argv[0]);
         return 2;
     }
     const int pairs = pos.size() > 2 ? std::atoi(pos[2].c_str()) : 1024;
@@ -85,6 +89,7 @@ int main(int argc, char** argv) {
         auto a = load_player(pos[0]);
         auto b = load_player(pos[1]);
         xq::Arena arena(pairs, seed, 0, opening);
+        arena.setTemperature(temp_a, temp_b);
         const auto t0 = std::chrono::steady_clock::now();
         const int plies = arena.run(as_player(pos[0], a.get(), eps_a), as_player(pos[1], b.get(), eps_b));
         const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();

@@ -30,6 +30,10 @@
 //                                 what the batched loop's plies write into the ring: evaluateBoard (default, chessai.cpp:115) or the
 //                                 transition's change of material balance, scaled (1e-3), less a cost per ply (0), clamped to +-bound (1)
 //                                 (xq::ChessAI::setReward; the sequential loop, parallel_games = 1, refuses delta)
+//   policy=greedy|boltzmann:T     how the batched loop's non-epsilon plies pick: the first maximum (default, dqn.cpp:39-51) or a softmax draw
+//                                 over the legal moves' values at temperature T in [1e-3, 1e3] (xq::ChessAI::setPolicy; the sequential
+//                                 loop, parallel_games = 1, and getAIMove refuse boltzmann)
+//   eps=E                         exploration rate of the batched loop in [0, 1] (default 0.1, chessai.cpp:106; xq::ChessAI::setEpsilon)
 //   --json                        one JSON line with the loop's counters (bench.py's `facade` leg reads it)
 #include <chrono>
 #include <cstdio>
@@ -47,6 +51,8 @@ int main(int argc, char** argv) {
     unsigned long long seed = 0;
     double clip = 0.0, mirror = 0.0, swap = 0.0;
     xq::Reward reward;
+    xq::Policy policy;
+    double eps = 0.1;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         auto next = [&]() -> const char* { if (i + 1 >= argc) { std::fprintf(stderr, "%s needs a value\n", a.c_str()); std::exit(2); } return argv[++i]; };
@@ -95,6 +101,22 @@ int main(int argc, char** argv) {
                 reward = xq::Reward::delta(p[0], p[1], p[2]);
             } else { std::fprintf(stderr, "reward=: expected evaluate or delta[:scale[:cost[:bound]]], got %s\n", v.c_str()); return 2; }
         }
+        else if (a.rfind("policy=", 0) == 0) {
+            // greedy | boltzmann:T; the range of T is checked by ChessAI::setPolicy
+            const std::string v = a.substr(7);
+            if (v == "greedy") policy = xq::Policy::greedy();
+            else if (v.rfind("boltzmann:", 0) == 0) {
+                char* end = nullptr;
+                const double t = std::strtod(v.c_str() + 10, &end);
+                if (end == v.c_str() + 10 || *end) { std::fprintf(stderr, "policy=: expected a temperature after 'boltzmann:', got %s\n", v.c_str() + 10); return 2; }
+                policy = xq::Policy::boltzmann(t);
+            } else { std::fprintf(stderr, "policy=: expected greedy or boltzmann:T, got %s\n", v.c_str()); return 2; }
+        }
+        else if (a.rfind("eps=", 0) == 0) {
+            char* end = nullptr;
+            eps = std::strtod(a.c_str() + 4, &end);
+            if (end == a.c_str() + 4 || *end || !(eps >= 0.0 && eps <= 1.0)) { std::fprintf(stderr, "eps=: expected a probability in [0, 1], got %s\n", a.c_str() + 4); return 2; }
+        }
         else if (a.rfind("mirror=", 0) == 0) {
             char* end = nullptr;
             mirror = std::strtod(a.c_str() + 7, &end);
@@ -130,6 +152,8 @@ int main(int argc, char** argv) {
         if (zerosum) ai.setZeroSum(true);
         if (mover_view) ai.setView(xq::View::Mover);          // (after --hidden's setDQN: the view is the network's too)
         ai.setReward(reward);
+        ai.setPolicy(policy);
+        ai.setEpsilon(eps);
         if (replay > 0) ai.setReplay(replay, minibatch);
         ai.setSaveInterval(save_every);
         ai.setLayer0Derive(derive);
@@ -149,10 +173,12 @@ int main(int argc, char** argv) {
             std::printf("{\"entry_point\": \"xq::ChessAI::train(%d)\", \"parallel_games\": %d, \"replay_capacity\": %d, \"minibatch\": %d, "
                         "\"episodes_reported\": %d, \"episodes_finished\": %llu, \"env_steps\": %llu, \"updates\": %llu, "
                         "\"loop_seconds\": %.6f, \"train_call_seconds\": %.6f, \"env_steps_per_s\": %.1f, \"updates_per_s\": %.1f, "
-                        "\"screened_steps\": %llu, \"guard_fallbacks\": %llu, \"candidate_groups_per_sample\": %.3f, \"whole_groups_per_sample\": %.3f}\n",
+                        "\"screened_steps\": %llu, \"guard_fallbacks\": %llu, \"candidate_groups_per_sample\": %.3f, \"whole_groups_per_sample\": %.3f, "
+                        "\"policy\": \"%s\", \"temperature\": %.9g, \"epsilon\": %.9g, \"explored_plies\": %llu}\n",
                         episodes, parallel, replay, minibatch, games, (unsigned long long)st.episodes, (unsigned long long)st.envSteps,
                         (unsigned long long)st.updates, st.seconds, s, st.seconds > 0 ? st.envSteps / st.seconds : 0.0,
-                        st.seconds > 0 ? st.updates / st.seconds : 0.0, (unsigned long long)st.screenedSteps, (unsigned long long)st.guardFallbacks, st.candidateGroupsPerSample, st.wholeGroupsPerSample);
+                        st.seconds > 0 ? st.updates / st.seconds : 0.0, (unsigned long long)st.screenedSteps, (unsigned long long)st.guardFallbacks, st.candidateGroupsPerSample, st.wholeGroupsPerSample,
+                        st.policy.kind == XQ_POLICY_BOLTZMANN ? "boltzmann" : "greedy", st.policy.temperature, st.epsilon, (unsigned long long)st.exploredPlies);
             return 0;
         }
         std::printf("%d episodes in %.2f s (%.0f episodes/s), mean captured material red %.1f black %.1f, model -> %s\n", games, s,
@@ -163,7 +189,8 @@ int main(int argc, char** argv) {
             std::printf("batched loop: %llu plies + %llu updates in %.3f s = %.2f M env steps/s + %.0f updates/s\n",
                         (unsigned long long)st.envSteps, (unsigned long long)st.updates, st.seconds, st.envSteps / st.seconds / 1e6,
                         st.updates / st.seconds);
-        if (mover_view) return 0;                                // getAIMove reads the absolute board: it refuses the mover view
+        if (st.policy.kind == XQ_POLICY_BOLTZMANN) std::printf("policy: boltzmann, temperature %g\n", st.policy.temperature);
+        if (mover_view || policy.kind != XQ_POLICY_GREEDY) return 0;   // getAIMove reads the absolute board and picks as the reference: it refuses both
         const auto mv = ai.getAIMove(xq::PieceColor::Red);       // the GUI's "AI move" path, chessai.cpp:29-83
         std::printf("AI move for Red from the final position of the caller's board: (%d,%d) -> (%d,%d)\n", mv.first.first,
                     mv.first.second, mv.second.first, mv.second.second);

@@ -243,6 +243,20 @@ struct Reward {
     }
 };
 
+// How a ply that reads Q rows and did not take the epsilon branch picks its move (xq_env_set_policy, DESIGN.md §4 "Exploration policy"; no
+// upstream analogue): greedy() is the reference's first maximum; boltzmann(T) a softmax draw over the legal moves' values at temperature
+// T, as fp32 finite and in [1e-3, 1e3].
+struct Policy {
+    int kind = XQ_POLICY_GREEDY;
+    double temperature = 1.0;
+    static Policy greedy() { return Policy(); }
+    static Policy boltzmann(double temperature = 1.0) {
+        Policy p; p.kind = XQ_POLICY_BOLTZMANN; p.temperature = temperature;
+        return p;
+    }
+};
+inline bool temperatureOk(double t) { const float f = (float)t; return f >= 1e-3f && f <= 1e3f; }
+
 // ---- DQN, dqn.h:97-116 ----------------------------------------------------------------------------------------------
 class DQN {
 public:
@@ -572,6 +586,13 @@ public:
     Arena& operator=(const Arena&) = delete;
 
     void reset(int openingPlies = 8) { check(xq_arena_reset(h_, openingPlies)); }
+    // A Boltzmann temperature per player (xq_arena_set_temperature): 0 = greedy, else in [1e-3, 1e3].  Network players only; kept over reset()
+    void setTemperature(double tempA, double tempB) { check(xq_arena_set_temperature(h_, tempA, tempB)); }
+    std::pair<double, double> temperature() const {
+        double a = 0, b = 0;
+        check(xq_arena_get_temperature(h_, &a, &b));
+        return {a, b};
+    }
     // a / b: borrowed networks (nullptr = uniform-random play); plays every game to its end.  Returns the plies played.
     int run(const DQN* a, const DQN* b, double epsA = 0.0, double epsB = 0.0, int maxPlies = 0) {
         int n = 0;
@@ -625,9 +646,10 @@ public:
     }
 
     // Playing strength (build's own): this AI's network as player A against the model in opponentModelFile (same topology; "random" =
-    // uniform-random play) over `pairs` pairs of games on the GPU, greedy unless epsilons are given.  Returns A's summary.
+    // uniform-random play) over `pairs` pairs of games on the GPU, greedy unless epsilons or Boltzmann temperatures (Arena::setTemperature;
+    // 0 = greedy) are given.  Returns A's summary.
     ArenaSummary evaluateAgainst(const std::string& opponentModelFile, int pairs, uint64_t seed = 1, int openingPlies = 8,
-                                 double epsSelf = 0.0, double epsOpponent = 0.0) {
+                                 double epsSelf = 0.0, double epsOpponent = 0.0, double tempSelf = 0.0, double tempOpponent = 0.0) {
         if (!dqn) throw std::invalid_argument("DQN is not initialized. Cannot evaluate.");
         std::unique_ptr<DQN> opponent;
         if (opponentModelFile != "random") {
@@ -635,14 +657,16 @@ public:
             opponent->loadModel(opponentModelFile);
         }
         Arena arena(pairs, seed, 0, openingPlies);
+        arena.setTemperature(tempSelf, tempOpponent);
         arena.run(dqn.get(), opponent.get(), epsSelf, epsOpponent);
         return arena.summary();
     }
     // ... against the fixed material search of depth 1..3 (Player::search), a reference whose strength does not move between runs
     ArenaSummary evaluateAgainst(int searchDepth, int pairs, uint64_t seed = 1, int openingPlies = 8, double epsSelf = 0.0,
-                                 double epsOpponent = 0.0) {
+                                 double epsOpponent = 0.0, double tempSelf = 0.0) {
         if (!dqn) throw std::invalid_argument("DQN is not initialized. Cannot evaluate.");
         Arena arena(pairs, seed, 0, openingPlies);
+        arena.setTemperature(tempSelf, 0.0);
         arena.run(Player::net(*dqn, epsSelf), Player::search(searchDepth, epsOpponent));
         return arena.summary();
     }
@@ -652,6 +676,9 @@ public:
         if (view_ == View::Mover)
             throw std::invalid_argument("ChessAI::getAIMove: setView(View::Mover) is the batched paths' (train with setParallelGames(n > 1), "
                                         "evaluateAgainst); the single-board paths read the absolute board");
+        if (policy_.kind != XQ_POLICY_GREEDY)
+            throw std::invalid_argument("ChessAI::getAIMove: Policy::boltzmann is the batched paths' (train with setParallelGames(n > 1)); "
+                                        "the single-board paths keep the reference's selectAction");
         const std::vector<double> state = getStateRepresentation();
         for (int attempt = 0; attempt < 10; ++attempt) {
             const std::vector<Action> validActions = getAllValidActions(color);
@@ -674,8 +701,11 @@ public:
 
 private:
     // the single-board loops are the reference's: they learn on evaluateBoard and never silently on another reward
-    // ... and on the reference's target r + gamma max Q(s'), never silently on the zero-sum one
+    // ... and on the reference's target r + gamma max Q(s'), never silently on the zero-sum one; and they pick by the reference's selectAction
     void parityLoopReward(const char* who) const {
+        if (policy_.kind != XQ_POLICY_GREEDY)
+            throw std::invalid_argument(std::string("ChessAI::") + who + ": Policy::boltzmann needs the batched loop (setParallelGames(n > 1)); "
+                                        "the single-board loops keep the reference's selectAction");
         if (reward_.kind != XQ_REWARD_EVALUATE)
             throw std::invalid_argument(std::string("ChessAI::") + who + ": Reward::delta needs the batched loop (setParallelGames(n > 1)); "
                                         "the single-board loops keep the reference's evaluateBoard");
@@ -818,7 +848,10 @@ public:
                         double colour_swap = 0;                 // ... and its colour-swap probability (setColourSwap)
                         Reward reward;                          // the reward rule of the trainer's env as the run ended (setReward)
                         bool zero_sum = false;                  // whether the trainer's net formed the zero-sum target as the run ended (setZeroSum)
-                        View view = View::Absolute; };          // the view of the trainer's net as the run ended (setView)
+                        View view = View::Absolute;             // the view of the trainer's net as the run ended (setView)
+                        Policy policy;                          // the policy of the trainer's env as the run ended (setPolicy)
+                        double epsilon = 0.1;                   // ... and the trainer's epsilon (setEpsilon)
+                        uint64_t exploredPlies = 0; };          // epsilon plies of the run (xq_env_counters[5])
     TrainStats lastTrainStats() const { return stats_; }
     // data-parallel train(): this process is rank comm->rank() of comm->world(); its batched games take the id range
     // [rank * parallelGames, (rank + 1) * parallelGames) and every update all-reduces the gradients over RCCL (nullptr = off)
@@ -865,6 +898,21 @@ public:
         reward_ = r;
     }
     Reward reward() const { return reward_; }
+    // Exploration of the batched train() (DESIGN.md §4 "Exploration policy"): xq_trainer_set_policy / xq_trainer_set_epsilon on the trainer
+    // train() creates (Policy::greedy() and 0.1 = the reference's, the defaults).  With an opponent set both are the learner's.  The
+    // single-board paths (trainEpisode, trainStep, startSelfPlay, getAIMove, train with parallelGames == 1) keep the reference's
+    // selectAction at its literal epsilon 0.1 and throw std::invalid_argument when asked for Policy::boltzmann.
+    void setPolicy(const Policy& p) {
+        if (p.kind != XQ_POLICY_GREEDY && p.kind != XQ_POLICY_BOLTZMANN) throw std::invalid_argument("setPolicy: unknown kind");
+        if (!temperatureOk(p.temperature)) throw std::invalid_argument("setPolicy: temperature must be in [1e-3, 1e3]");
+        policy_ = p;
+    }
+    Policy policy() const { return policy_; }
+    void setEpsilon(double eps) {
+        if (!(eps >= 0.0 && eps <= 1.0)) throw std::invalid_argument("setEpsilon: eps must be in [0, 1]");
+        epsilon_ = eps;
+    }
+    double epsilon() const { return epsilon_; }
     // Target of the batched train(), carried onto the trainer's network like the loss: TdBootstrap::legal() makes the trainer's ring
     // record the side to move in s' (xq_trainer_set_td_bootstrap, before the first collect).  fp32 nets; the sequential loop is unaffected.
     void setTdBootstrap(const TdBootstrap& b) { initializeDQN(); dqn->setTdBootstrap(b); }
@@ -909,7 +957,7 @@ private:
         const auto& ls = dqn->layerSizes();
         cfg.n_sizes = (int)ls.size();
         for (size_t i = 0; i < ls.size(); ++i) cfg.layer_sizes[i] = ls[i];
-        cfg.learning_rate = learningRate; cfg.gamma = gamma; cfg.epsilon = 0.1;
+        cfg.learning_rate = learningRate; cfg.gamma = gamma; cfg.epsilon = epsilon_;
         const bool ring = replayCapacity_ > 0;
         if (ring) {                              // setReplay(): the throughput schedule
             cfg.replay_capacity = replayCapacity_ > cfg.n_games ? replayCapacity_ : cfg.n_games;
@@ -945,6 +993,7 @@ private:
         if (mirror_ > 0.0) check(xq_trainer_set_mirror(t, mirror_));
         if (colourSwap_ > 0.0) check(xq_trainer_set_colour_swap(t, colourSwap_));
         if (reward_.kind != XQ_REWARD_EVALUATE) check(xq_trainer_set_reward(t, reward_.kind, reward_.scale, reward_.plyCost, reward_.bound));
+        if (policy_.kind != XQ_POLICY_GREEDY) check(xq_trainer_set_policy(t, policy_.kind, policy_.temperature));
         const TdLoss loss = dqn->tdLoss();
         check(xq_dqn_set_td_loss(td, loss.kind, loss.kappa));
         if (comm_) check(xq_trainer_set_comm(t, comm_->handle()));
@@ -1001,6 +1050,11 @@ private:
             int vw = 0;
             check(xq_dqn_get_view(td, &vw));
             stats_.view = (View)vw;
+            check(xq_env_get_policy(te, &stats_.policy.kind, &stats_.policy.temperature));
+            check(xq_trainer_get_epsilon(t, &stats_.epsilon));
+            uint64_t c6[6] = {0, 0, 0, 0, 0, 0};
+            check(xq_env_counters(te, c6));
+            stats_.exploredPlies = c6[5];
         }
         {
             uint64_t q[4] = {0, 0, 0, 0}; int hold = 0;
@@ -1031,6 +1085,8 @@ private:
     Reward reward_;
     bool zeroSum_ = false;
     View view_ = View::Absolute;
+    Policy policy_;
+    double epsilon_ = 0.1;
     int prefillPlies_ = 0;
     std::unique_ptr<Player> opponent_;
     TrainStats stats_;

@@ -171,7 +171,8 @@ typedef struct {
     uint8_t done;        /* checkGameOver() || moveCount+1 >= 200 (chessai.cpp:119) */
     uint8_t terminated;  /* episode ended: checkGameOver() (chessboard.cpp:286-309) or no action; board was auto-reset */
     uint8_t winner;      /* getWinner() (chessboard.cpp:312-320) when terminated, else 2 */
-    uint8_t explored;    /* epsilon branch taken (dqn.cpp:31-34) */
+    uint8_t explored;    /* 1: epsilon branch taken (dqn.cpp:31-34); 2: a Boltzmann draw (xq_env_set_policy) played another move than
+                          * the first maximum; else 0 */
     uint16_t move_count; /* getMoveCount() after the move (before auto-reset) */
     int16_t red_score, black_score; /* getRedScore()/getBlackScore() after the move (before auto-reset) */
 } xq_step_result;
@@ -215,6 +216,28 @@ int xq_env_selfplay_step_host(xq_env* env, const float* q90_host, uint32_t eps_u
 enum { XQ_REWARD_EVALUATE = 0, XQ_REWARD_DELTA = 1 };
 int xq_env_set_reward(xq_env* env, int kind, double scale, double ply_cost, double bound);
 int xq_env_get_reward(const xq_env* env, int* kind, double* scale, double* ply_cost, double* bound);
+
+/* How a ply that reads Q rows and did NOT take the epsilon branch picks its move (DESIGN.md §4 "Exploration policy") — build-defined; the
+ * default is the reference's.
+ *   XQ_POLICY_GREEDY    : the first maximum of q[action.to] over the legal list (dqn.cpp:39-51).  Same launches and bits as an env that
+ *                         was never asked; the temperature is checked, kept and not used.
+ *   XQ_POLICY_BOLTZMANN : a softmax draw over the values v_i the greedy pick compares (q[to_i]; q[swap(to_i)] for Black under
+ *                         xq_env_set_q_view; NaN counts as -inf), list order i = 0..n-1.  m = max v_i; if m is not finite (every
+ *                         candidate -inf or NaN, or a +inf present) the pick is the first maximum.  Otherwise, in fp32 with one rounding
+ *                         per operation, x_i = fl(fl(v_i - m) * it), it = (float)(1.0 / temperature), w_i = expf(x_i) (0 where v_i =
+ *                         -inf), u = (r2 >> 8) * 2^-24 on word 2 of the ply's Philox block (r0: epsilon, r1: the uniform index),
+ *                         t = u * sum w: the first i whose inclusive running sum exceeds t, or the last i with w_i > 0 if rounding
+ *                         leaves none.  tests/boltzmann_ref.py is the definition, with the band inside which the device's expf and
+ *                         summation order may resolve a draw either way.
+ * The epsilon branch (r0 < eps_u32: move r1 % n), a ply without Q rows, the search players' picks and the arena's opening are untouched.
+ * xq_step_result.explored is 2 where the draw played another move than the first maximum; xq_env_counters[5] counts epsilon plies only.
+ * temperature as fp32 must be finite and in [1e-3, 1e3]; anything else, NaN included, or an unknown kind: XQ_ERR_INVALID_ARGUMENT and
+ * nothing changes.  Takes effect at the next xq_env_selfplay_step* or trainer collect on the env; versus training: the learner's
+ * half-ply only, the opponent stays epsilon-greedy.  xq_env_get_policy: the values as last given — on an env that was never asked
+ * XQ_POLICY_GREEDY, 1.  Outputs may be NULL. */
+enum { XQ_POLICY_GREEDY = 0, XQ_POLICY_BOLTZMANN = 1 };
+int xq_env_set_policy(xq_env* env, int kind, double temperature);
+int xq_env_get_policy(const xq_env* env, int* kind, double* temperature);
 
 /* Episode reporting — the gameCompleted(game, redScore, blackScore) signal (chessai.h:35, chessai.cpp:162). */
 typedef struct {
@@ -865,6 +888,13 @@ int xq_arena_ply_q_dev(xq_arena* a, const float* q_dev, int q_stride, double eps
  * xq_view_boards_dev's boards), so where it moves as Black the pick reads q[swap(to)].  (0, 0) is xq_arena_ply_q_dev.  A network player
  * of xq_arena_run / xq_arena_run_players is read through its own handle's view (xq_dqn_set_view) without further ado. */
 int xq_arena_ply_q_dev_view(xq_arena* a, const float* q_dev, int q_stride, double eps_a, double eps_b, int view_a, int view_b);
+/* A Boltzmann temperature per player (xq_env_set_policy's rule on that player's non-epsilon plies), 0 = greedy, else as fp32 finite and
+ * in [1e-3, 1e3]; anything else is XQ_ERR_INVALID_ARGUMENT and nothing changes.  Honoured for XQ_PLAYER_NET players and for
+ * caller-supplied rows (xq_arena_ply_q_dev*, xq_arena_run, xq_arena_run_players) from the next ply on; ignored for random and search
+ * players and in the opening.  Survives xq_arena_reset.  After the opening twins draw on their own game ids, as the epsilon draws do.
+ * xq_arena_get_temperature: the values as last given, (0, 0) on an arena that was never asked.  Outputs may be NULL. */
+int xq_arena_set_temperature(xq_arena* a, double temp_a, double temp_b);
+int xq_arena_get_temperature(const xq_arena* a, double* temp_a, double* temp_b);
 /* Plays until no game is live or max_plies plies (<= 0: no limit) have been played by this call; *plies_played (optional) = how many.
  * dqn_a / dqn_b: a network with layer_sizes[0] == 1260 and >= 90 outputs, or NULL for uniform-random play; dqn_a == dqn_b is allowed,
  * and so are handles on different streams (ordered by events).  eps_a, eps_b in [0, 1]. */
@@ -966,6 +996,14 @@ int xq_trainer_set_colour_swap(xq_trainer* t, double prob);
  * prioritized replay and both bootstraps read the ring's reward column as before.  Call between iterations: XQ_ERR_RUNTIME while a
  * learn_grads waits for its learn_apply. */
 int xq_trainer_set_reward(xq_trainer* t, int kind, double scale, double ply_cost, double bound);
+/* xq_env_set_policy on the trainer's env (DESIGN.md §4 "Exploration policy"): the next collect queued picks by it.  Self-play and the
+ * learner of versus training (the opponent stays epsilon-greedy), uniform, prioritized and on-policy rings, overlap_collect 0 and 1. */
+int xq_trainer_set_policy(xq_trainer* t, int kind, double temperature);
+/* The exploration rate of the collects (xq_trainer_config.epsilon), 0 <= eps <= 1; a NaN or a value outside: XQ_ERR_INVALID_ARGUMENT and
+ * nothing changes.  Legal between any two collects, with overlap_collect too: the next collect queued reads the new value, one already
+ * queued keeps the value it was launched with.  Versus training: the learner's epsilon; the opponent's stays its own. */
+int xq_trainer_set_epsilon(xq_trainer* t, double eps);
+int xq_trainer_get_epsilon(const xq_trainer* t, double* eps);
 /* xq_dqn_set_td_bootstrap on the trainer's Q-net.  XQ_BOOTSTRAP_LEGAL first turns tracking on for the trainer's ring, so call it before
  * the first collect: XQ_ERR_RUNTIME once the ring holds a transition (unless it tracks already).  Back to XQ_BOOTSTRAP_ALL is allowed
  * between iterations (XQ_ERR_RUNTIME while a learn_grads waits for its learn_apply); the column keeps being written.  Uniform,
